@@ -8,6 +8,12 @@ processes, BEFORE anything touches a GPU, and exits with their code.
 One "step" = one complete RM2 job over the ML-25M-shaped synthetic ratings, which are resident in HBM when the timed
 region starts: COO -> CSR/CSC, statistics, (all-gather), per-cluster co-rating matrix, scoring, top-N.
 Rank 0 prints ONE JSON line.  `value` = top-N recommendation rows produced by all ranks per second.
+A plain run sets up, warms up, times the K steps and prints the line (plus the figures derived from the timed steps' own
+statistics: phases, roofline).  `--full` adds everything else, each leg timed in runs of its own: the warm job, the
+reference's regime, the item-item similarity build, the factorisation, the PCIe-inclusive run and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step returned to its caller (the recommendation rows and the side outputs
+userSum / itemColl) as DIR/<name>.npy, float32 / float64; the inputs are identical from run to run, so two builds can be
+compared output for output.
 """
 import argparse
 import hashlib
@@ -44,7 +50,49 @@ def parse():
     ap.add_argument("--no-factorization", action="store_true", help="skip the PPC factorisation + cluster assignment leg")
     ap.add_argument("--no-regime", action="store_true", help="skip the reference-regime legs (50 clusters; top-1000)")
     ap.add_argument("--cpu-users", type=int, default=0, help="users in the CPU sample cluster (0 = auto)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline (warm job, reference regime, item "
+                    "similarity, factorisation, PCIe-inclusive run, CPU baselines); the --no-* options select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_MAX_ROWS = 1 << 21        # recommendation rows written by --dump-outputs: 16 B each (four float32 columns), 32 MiB at most
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, rec, n_users, top_n, prefix=""):
+    """What a caller of the timed path receives from its last step, as float32 / float64 .npy files under out_dir:
+    rec_{user,item,score,cluster} (Recommendations.rows(), in the order returned) and user_id / user_sum / item_id / item_coll /
+    total_sum (Recommendations.sums()).  When the lists of all users would exceed DUMP_MAX_ROWS rows, the rows of a fixed, seeded
+    sample of the user ids 1..n_users are written (chosen from the inputs alone, so every build writes the same users)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows, sums = rec.rows(), rec.sums()
+    if n_users * top_n > DUMP_MAX_ROWS:
+        rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        sample = np.sort(rng.choice(np.arange(1, n_users + 1, dtype=np.int32), size=DUMP_MAX_ROWS // top_n, replace=False))
+        sel = np.flatnonzero(np.isin(rows["user"], sample))
+    else:
+        sel = np.arange(len(rows["user"]))
+
+    def ids(x):            # int32 ids as floats: exact in float32 below 2^24
+        return x.astype(np.float32 if (len(x) == 0 or int(np.abs(x).max()) < (1 << 24)) else np.float64)
+
+    arrays = {"rec_user": ids(rows["user"][sel]), "rec_item": ids(rows["item"][sel]),
+              "rec_score": rows["score"][sel].astype(np.float32), "rec_cluster": ids(rows["cluster"][sel]),
+              "rec_count": np.array([rec.size], dtype=np.float64),
+              "user_id": sums["user_id"].astype(np.float64), "user_sum": sums["user_sum"].astype(np.float64),
+              "item_id": sums["item_id"].astype(np.float64), "item_coll": sums["item_coll"].astype(np.float64),
+              "total_sum": np.array([sums["total_sum"]], dtype=np.float64)}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes would exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), v)
 
 
 def launch_ranks(n):
@@ -205,8 +253,9 @@ def main():
             else:
                 dist.all_reduce(t, op=op)
 
-    def time_job(K, n_rec, steps, warmup, cache=False):
+    def time_job(K, n_rec, steps, warmup, cache=False, keep_last=False):
         """W untimed + K timed complete jobs between fences; returns (per-step stats, elapsed seconds = max over ranks, totals).
+        keep_last: the result of the last timed job is returned open (5th element; the caller closes it), not freed in the timed region.
         cache=False: every job is COLD (FY_RM2_NO_CACHE: the ratings are sorted into CSR / CSC and the row kernel's tables are built
         inside the timed step, nothing is kept) -- what the headline value is measured on.  cache=True: the jobs after the first
         find those structures on the resident ratings object (same clustering): the WARM job, reported beside the headline."""
@@ -221,17 +270,22 @@ def main():
         conf.setInt("numberOfRecommendations", n_rec)
         job = P.RM2Job(conf, ctx)
 
-        def step():
+        def step(keep=False):
             rec = job.run(ratings, clustering=clustering, rank=rank, world=world, exchange=exchange, collectives=collectives, cache=cache)
             st = rec.stats
+            if keep:
+                return st, rec
             rec.close()
-            return st
+            return st, None
 
         for _ in range(warmup):
             step()
         fence()
         t0 = time.perf_counter()
-        stats = [step() for _ in range(steps)]
+        stats, last = [], None
+        for i in range(steps):
+            st, last = step(keep_last and i == steps - 1)
+            stats.append(st)
         fence()
         elapsed = time.perf_counter() - t0
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -239,11 +293,15 @@ def main():
                            dtype=torch.float64, device=dev)
         reduce_(tt, dist.ReduceOp.MAX)
         reduce_(tot, dist.ReduceOp.SUM)
-        return stats, float(tt.item()), [float(x) for x in tot.tolist()], (job, clustering)
+        return stats, float(tt.item()), [float(x) for x in tot.tolist()], (job, clustering), last
 
     K = a.clusters
-    stats, elapsed, (total_recs, total_terms, total_users), (job, clustering) = time_job(K, top_n, a.steps, a.warmup)
+    stats, elapsed, (total_recs, total_terms, total_users), (job, clustering), last = \
+        time_job(K, top_n, a.steps, a.warmup, keep_last=a.dump_outputs is not None)
     ms_per_step = 1e3 * elapsed / a.steps
+    if last is not None:
+        dump_outputs(a.dump_outputs, last, facts["n_users"], top_n, prefix="" if world == 1 else "rank%d_" % rank)
+        last.close()
 
     # ---- roofline of the dominant kernel, from HIP events the library records on ITS stream around every launch.
     # Candidates: the co-rating row kernel (k_cooc_rm2, builds M) and the scoring kernels (k_score*, one family).
@@ -340,14 +398,14 @@ def main():
                                % (a.shape, facts["n_users"], facts["n_items"], facts["nnz"], top_n, a.lam, K, world),
                    "shape": a.shape, "top_n": top_n, "clusters": K, "lambda": a.lam, "nnz": facts["nnz"],
                    "headline": "one neighbourhood (numberOfClusters 1) is the hardest case and one the reference cannot run "
-                               "(its dense cache would need 77 TB); the reference's own regime is in reference_regime"},
-        "cold_or_warm": "cold: every timed job sorts the resident COO ratings into CSR / CSC and builds its tables (FY_RM2_NO_CACHE); see `warm`",
+                               "(its dense cache would need 77 TB); the reference's own regime is in reference_regime (--full)"},
+        "cold_or_warm": "cold: every timed job sorts the resident COO ratings into CSR / CSC and builds its tables (FY_RM2_NO_CACHE); see `warm` (--full)",
         "lists_per_s": total_users / (elapsed / a.steps), "log_terms_per_step": total_terms,
         "phase_ms_rank0": phases, "datagen_s": gen_s,
         "job_stats_rank0": {k: int(st[k]) for k in ("n_clusters_nonempty", "cooc_launches", "score_launches", "panel_clusters", "blocks_total",
                                                      "blocks_survived", "stray_blocks", "bound_repairs", "prune_fallbacks", "topn_select_users", "rows_refined")},
         "roofline": roofline, "roofline_other_kernel": other, "roofline_phases": roofline_phases,
-        "kernel_source_rev": rev,
+        "kernel_source_rev": rev, "full": a.full,
     }
 
     if world > 1:
@@ -360,9 +418,9 @@ def main():
         out["cpu_baseline_note"] = "timed on rank 0 of the N = 1 run only (see that line)"
         # the reference's own regime on N ranks: 50 clusters, WHOLE clusters per rank (no Gram is built twice, only the item statistics
         # are exchanged: RM2Job.java:251 runs one reduce group per cluster) -- the case SURVEY.md 8e expects to scale best
-        if not a.no_regime and a.shape == "ml25m" and K == 1:
+        if a.full and not a.no_regime and a.shape == "ml25m" and K == 1:
             try:
-                s50, el50, (r50, t50, u50), _ = time_job(50, top_n, 2, 1)
+                s50, el50, (r50, t50, u50), _, _ = time_job(50, top_n, 2, 1)
                 out["multi_gpu"]["clusters_50_top_%d" % top_n] = {
                     "value": r50 / (el50 / 2), "unit": "recs/s", "ms_per_step": 1e3 * el50 / 2,
                     "phase_ms_rank0": {k: float(np.mean([x[k] for x in s50])) for k in ("ms_prepare", "ms_tables", "ms_cooc", "ms_mirror", "ms_score", "ms_topn", "ms_total")},
@@ -373,9 +431,9 @@ def main():
 
     # ---- the warm job: same ratings object, same clustering -- the CSR / CSC, the per-item statistics and the row kernel's tables
     # of the previous job are found on the ratings object (fy_stats.prepared_from_cache); never the headline value
-    if world == 1:
+    if world == 1 and a.full:
         try:
-            sw, elw, (rw, _, _), _ = time_job(K, top_n, max(3, min(a.steps, 10)), 2, cache=True)
+            sw, elw, (rw, _, _), _, _ = time_job(K, top_n, max(3, min(a.steps, 10)), 2, cache=True)
             nw = len(sw)
             out["warm"] = {"value": rw / (elw / nw), "unit": "recs/s", "ms_per_step": 1e3 * elw / nw,
                            "prepared_from_cache": int(sw[-1]["prepared_from_cache"]), "tables_from_cache": int(sw[-1]["tables_from_cache"]),
@@ -386,11 +444,11 @@ def main():
 
     # ---- the reference's own operating regime, beside the headline: many clusters (numberOfClusters is a required option,
     # 50 in T/rmrecommender/TestRMRecommenderJob.java:49) and the default list length 1000 (RMRecommenderDriver.java:95)
-    if world == 1 and not a.no_regime and a.shape == "ml25m" and K == 1:
+    if world == 1 and a.full and not a.no_regime and a.shape == "ml25m" and K == 1:
         reg = {}
         for name, kk, nn in (("clusters_50_top_50", 50, top_n), ("clusters_50_top_1000", 50, 1000), ("clusters_1_top_1000", 1, 1000)):
             try:
-                s2, el2, (r2, t2, u2), _ = time_job(kk, nn, 2, 1)
+                s2, el2, (r2, t2, u2), _, _ = time_job(kk, nn, 2, 1)
                 reg[name] = {"value": r2 / (el2 / 2), "unit": "recs/s", "ms_per_step": 1e3 * el2 / 2, "lists_per_s": u2 / (el2 / 2),
                              "log_terms_per_s": t2 / (el2 / 2),
                              "phase_ms": {k: float(np.mean([x[k] for x in s2])) for k in ("ms_prepare", "ms_tables", "ms_cooc", "ms_mirror", "ms_score", "ms_topn", "ms_total")},
@@ -409,7 +467,7 @@ def main():
         out["reference_regime"] = reg
 
     # ---- item-item similarity build on the same ratings (second headline unit: pairs/s)
-    if not a.no_itemsim:
+    if a.full and not a.no_itemsim:
         try:
             sim_job = P.RowSimilarityJob(ctx)
             sim_job.run(ratings, maxSimilaritiesPerRow=100, rank=rank, world=world).close()
@@ -445,7 +503,7 @@ def main():
     # ---- the stage in front of the hot path: PPC factorisation (k = 50) + cluster assignment on the same
     # ratings.  Algorithmic bytes per iteration: both SpMMs read 12 B per rating and gather one k-row of the dense factor
     # (8 k B) per rating; the updates stream H, W, X once.
-    if world == 1 and not a.no_factorization:
+    if world == 1 and a.full and not a.no_factorization:
         try:
             kf, iters = 50, 4
             rng = np.random.Generator(np.random.PCG64(11))
@@ -485,7 +543,7 @@ def main():
         except RuntimeError as e:
             out["factorization"] = {"error": str(e)}
 
-    if world == 1:
+    if world == 1 and a.full:
         # the boundary also takes host buffers (fy_ratings_create FY_HOST + result download): PCIe-inclusive rate, reported
         # beside the headline value, never as it
         hu, hi_, hs = user.cpu().numpy(), item.cpu().numpy(), score.cpu().numpy()
@@ -496,7 +554,7 @@ def main():
         rec.close()
         out["pcie_inclusive"] = {"value": n_rows / dt, "unit": "recs/s", "ms": 1e3 * dt,
                                  "note": "host COO -> HBM -> job -> rows back in host memory, one run"}
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         n_cpu = a.cpu_users or {"ml25m": 270, "netflix": 200, "ml1m": 800, "ml100k": 943}.get(a.shape, 200)
         out.update(cpu_legs(S, a.shape, facts, a.lam, top_n, n_cpu, np))
         bl = importlib.import_module("tools.cpu_baselines") if os.path.exists(os.path.join(ROOT, "tools", "cpu_baselines.py")) else None

@@ -98,3 +98,43 @@ def test_ranks_refuse_an_output_directory_that_holds_any_part_file(tmp_path):
     # an EMPTY shared directory is fine for several ranks (rank 0 may have created it), an existing one is not for a single rank
     with pytest.raises(RuntimeError, match="RM2 failed!: output directory .* already exists"):
         P.RM2Job(conf).run_from_files()
+
+
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files only, at most 64 MiB, and above the row budget the rows of a seeded sample of
+    the user ids -- chosen from the inputs alone, so two builds (two runs) write the rows of the same users."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n_users, top_n = 60000, 50
+    user = np.repeat(np.arange(1, n_users + 1, dtype=np.int32), top_n)
+    rng = np.random.Generator(np.random.PCG64(3))
+
+    class Rec:      # the two accessors of host.Recommendations the dump reads
+        size = len(user)
+
+        def rows(self):
+            return {"user": user, "item": rng.integers(1, 5000, len(user)).astype(np.int32),
+                    "score": rng.random(len(user)).astype(np.float32), "cluster": np.zeros(len(user), np.int32)}
+
+        def sums(self):
+            return {"user_id": np.arange(1, n_users + 1, dtype=np.int32), "user_sum": rng.random(n_users),
+                    "item_id": np.arange(1, 5000, dtype=np.int32), "item_coll": rng.random(4999), "total_sum": 2.5}
+
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        bench.dump_outputs(str(d), Rec(), n_users, top_n)
+    names = sorted(os.listdir(str(dirs[0])))
+    assert names == sorted(n + ".npy" for n in ("rec_user", "rec_item", "rec_score", "rec_cluster", "rec_count", "user_id", "user_sum",
+                                                "item_id", "item_coll", "total_sum"))
+    arrays = {n: np.load(str(dirs[0] / n)) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    users = arrays["rec_user.npy"]
+    assert 0 < len(users) <= bench.DUMP_MAX_ROWS < len(user)
+    assert len(np.unique(users)) == bench.DUMP_MAX_ROWS // top_n                  # every row of each sampled user
+    assert np.array_equal(users, np.load(str(dirs[1] / "rec_user.npy")))          # the same users in a second run
+    assert arrays["rec_count.npy"][0] == len(user)

@@ -63,7 +63,7 @@ out = {"source_rev": sys.argv[2] if len(sys.argv) > 2 else source_rev(),
        "k_cooc_rm2": family("k_cooc_rm2<true, unsigned long long"), "k_mirror": merge(family("k_mirror"), family("k_colmax_upper"), family("k_flag_surviving")), "k_score": family("k_score"),
        "itemsim_walk": family("k_cooc_rm2<true, unsigned int"), "k_isim_sweep": family("k_isim_sweep"), "k_isim_finish": family("k_isim_finish"),
        "note": "FETCH_SIZE (KB) doubled per MI355X_MICROARCH.md; summed over the launches of the profiled jobs and divided by "
-               "their number; config: ml25m shape, numberOfClusters 1, top-50 (python3 bench.py --steps 1 --warmup 1 --no-cpu)"}
+               "their number; config: ml25m shape, numberOfClusters 1, top-50 (python3 bench.py --full --steps 1 --warmup 1 --no-cpu)"}
 # CU-side bytes of the scoring family: L1 -> L2 read requests (TCP_TCC_READ_REQ_sum).  The counter's unit is not documented for gfx950 in
 # MI355X_MICROARCH.md, so it is calibrated on the SAME run: k_colmax_upper streams whole 768-byte row segments of known count
 # (sum_{B >= seed blocks} (tiles behind B) x 256 rows x 768 B: 26 335 tiles = 5.178 GB at ML-25M shape with a one-block seed) -- round 4

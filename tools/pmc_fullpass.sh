@@ -7,7 +7,7 @@ TAG=$1; shift
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/pmc_fullpass_$TAG
 mkdir -p $OUT
-ARGS="--steps 1 --warmup 0 --no-cpu --no-regime --no-itemsim --no-factorization $*"
+ARGS="--full --steps 1 --warmup 0 --no-cpu --no-regime --no-itemsim --no-factorization $*"
 PER=${PMC_PASS_TIMEOUT:-55}
 ONLY=${PMC_PASSES:-}      # e.g. PMC_PASSES="fetch write": only these passes
 pass() {   # name, counters...

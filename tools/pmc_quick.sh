@@ -5,7 +5,7 @@ TAG=$1; shift
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p $OUT
-ARGS="--steps 1 --warmup 0 --no-cpu --no-itemsim $*"
+ARGS="--full --steps 1 --warmup 0 --no-cpu --no-itemsim $*"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t --output-format csv -- python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/trace.err || exit 1
 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o p --output-format csv -- python3 bench.py $ARGS > /dev/null 2> $OUT/fetch.err || exit 2
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum -d $OUT/tcc -o p --output-format csv -- python3 bench.py $ARGS > /dev/null 2> $OUT/tcc.err || exit 4

@@ -33,7 +33,7 @@ timeout -k 10 420 python3 -m pytest tests/test_rm2_gpu.py tests/test_pruned_coop
 tail -6 $OUT/tests_quick.log; [ $rc = 0 ] || fail "tests with the patches (rc $rc): no bench"
 
 step "bench with the patches"
-timeout -k 10 150 python3 bench.py > $OUT/bench_patched.json 2> $OUT/bench_patched.err || fail "bench with the patches"
+timeout -k 10 150 python3 bench.py --full > $OUT/bench_patched.json 2> $OUT/bench_patched.err || fail "bench with the patches"
 python3 - "$OUT/bench_patched.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
