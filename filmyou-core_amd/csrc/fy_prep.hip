@@ -17,6 +17,7 @@
 
 #include <hip/hip_fp16.h>
 
+#include "fy_partition.hpp"
 #include "fy_prep.hpp"
 
 namespace fy {
@@ -605,9 +606,15 @@ __global__ void k_shard_cluster_weights(int32_t n_raw_users, const int32_t* __re
 }
 
 // own[u] = 1: raw user u belongs to one of this rank's clusters
-__global__ void k_shard_owned(int32_t n_raw_users, const int32_t* __restrict__ cl_of_raw, const int32_t* __restrict__ owner, int32_t rank,
+// (the table holds the map's entry of EVERY raw id, also of users without a kept rating, whose cluster nobody has range-checked -- an
+// unrated user routed to -1 or K is legal input, k_shard_cluster_weights / k_lookup_cluster_table only look at rated users: such a user
+// is nobody's)
+__global__ void k_shard_owned(int32_t n_raw_users, const int32_t* __restrict__ cl_of_raw, const int32_t* __restrict__ owner, int32_t K, int32_t rank,
                               uint8_t* __restrict__ own) {
-    for (int32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < n_raw_users; u += gridDim.x * blockDim.x) own[u] = owner[cl_of_raw[u]] == rank ? 1 : 0;
+    for (int32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < n_raw_users; u += gridDim.x * blockDim.x) {
+        const int32_t c = cl_of_raw[u];
+        own[u] = (c >= 0 && c < K && owner[c] == rank) ? 1 : 0;
+    }
 }
 
 // The owned ratings, compacted in input order without a flag per rating: a wave's 64 keep-bits as one mask and one count (pass 1), an
@@ -635,33 +642,6 @@ __global__ void k_shard_compact(int64_t n, const unsigned long long* __restrict_
             os[p] = score[t];
         }
     }
-}
-
-// cuts `w` (one weight per position, in order) into `parts` contiguous runs with the smallest possible largest run (binary search on the
-// cap, greedy fill); returns the first position of every run (parts + 1 entries; trailing runs may be empty)
-static std::vector<int> linear_partition(const std::vector<int64_t>& w, int parts) {
-    const int n = (int)w.size();
-    auto runs_needed = [&](int64_t cap, std::vector<int>* first) -> int {
-        int runs = 1;
-        int64_t in_run = 0;
-        if (first) { first->clear(); first->push_back(0); }
-        for (int k = 0; k < n; k++) {
-            if (w[(size_t)k] > cap) return parts + 1;
-            if (in_run + w[(size_t)k] > cap && in_run > 0) { runs++; in_run = 0; if (first) first->push_back(k); }
-            in_run += w[(size_t)k];
-        }
-        return runs;
-    };
-    int64_t lo = 0, hi = 0;
-    for (int64_t x : w) hi += x;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (runs_needed(mid, nullptr) <= parts) hi = mid; else lo = mid + 1;
-    }
-    std::vector<int> first;
-    runs_needed(hi, &first);
-    while ((int)first.size() < parts + 1) first.push_back(n);
-    return first;
 }
 
 bool shard_ratings_by_cluster(Context* ctx, const fy_ratings* R, int32_t K, int64_t n_map, const int32_t* map_user, const int32_t* map_cluster,
@@ -729,7 +709,7 @@ bool shard_ratings_by_cluster(Context* ctx, const fy_ratings* R, int32_t K, int6
     DevBuf<int32_t> d_owner(ctx, (size_t)K);
     h2d(ctx, d_owner.get(), owner.data(), (size_t)K);
     DevBuf<uint8_t> own(ctx, (size_t)nRU);
-    k_shard_owned<<<grid_for(nRU), 256, 0, st>>>((int32_t)nRU, d_cl.get(), d_owner.get(), rank, own.get());
+    k_shard_owned<<<grid_for(nRU), 256, 0, st>>>((int32_t)nRU, d_cl.get(), d_owner.get(), K, rank, own.get());
     FY_KERNEL_CHECK();
     const int64_t n_waves = ceil_div(R->nnz, 64);
     DevBuf<unsigned long long> mask(ctx, (size_t)n_waves);

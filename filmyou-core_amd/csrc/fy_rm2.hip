@@ -1949,6 +1949,38 @@ void fy::rm2_set_global_stats(fy_rm2_job* J, const double* gathered, int32_t wor
     J->have_global = true;
 }
 
+// Sharded prep: the result's side outputs are the GLOBAL statistics (jobs RM2-1 / RM2-2 write one userSum and one itemColl for all clusters),
+// compacted out of the summed raw-id exchange buffer -- on every rank, whatever it prepared or scored (include/filmyou.h).
+static void sharded_side_outputs(fy_rm2_job* J, fy_result* R, const double* d_total) {
+    Context* ctx = J->ctx;
+    hipStream_t st = ctx->stream;
+    const RM2Static& S = *J->S;
+    const double* raw_items = J->stats_raw.get();
+    const double* raw_users = J->stats_raw.get() + S.n_raw_items + 1;
+    DevBuf<uint32_t> fi(ctx, (size_t)S.n_raw_items), pi(ctx, (size_t)S.n_raw_items), fu(ctx, (size_t)S.n_raw_users), pu(ctx, (size_t)S.n_raw_users);
+    k_flag_positive<<<grid_for(S.n_raw_items), 256, 0, st>>>(S.n_raw_items, raw_items, fi.get());
+    FY_KERNEL_CHECK();
+    k_flag_positive<<<grid_for(S.n_raw_users), 256, 0, st>>>(S.n_raw_users, raw_users, fu.get());
+    FY_KERNEL_CHECK();
+    inclusive_scan_u32(ctx, fi.get(), pi.get(), (size_t)S.n_raw_items);
+    inclusive_scan_u32(ctx, fu.get(), pu.get(), (size_t)S.n_raw_users);
+    uint32_t n_items_all = 0, n_users_all = 0;
+    d2h(ctx, &n_items_all, pi.get() + (S.n_raw_items - 1), 1);
+    d2h(ctx, &n_users_all, pu.get() + (S.n_raw_users - 1), 1);
+    sync(ctx);
+    R->d_item_id.alloc(ctx, n_items_all);
+    R->d_icoll.alloc(ctx, n_items_all);
+    R->d_user_id.alloc(ctx, n_users_all);
+    R->d_user_sum.alloc(ctx, n_users_all);
+    k_compact_positive<<<grid_for(S.n_raw_items), 256, 0, st>>>(S.n_raw_items, raw_items, pi.get(), d_total, R->d_item_id.get(), R->d_icoll.get());
+    FY_KERNEL_CHECK();
+    k_compact_positive<<<grid_for(S.n_raw_users), 256, 0, st>>>(S.n_raw_users, raw_users, pu.get(), nullptr, R->d_user_id.get(), R->d_user_sum.get());
+    FY_KERNEL_CHECK();
+    R->st.n_users = n_users_all;
+    R->st.n_items = n_items_all;
+    sync(ctx);      // (the flags and positions are released here)
+}
+
 fy_result* fy::rm2_score(fy_rm2_job* J) {
     Context* ctx = J->ctx;
     Prepared& P = J->P;
@@ -1976,6 +2008,14 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
     const size_t span_total = t_total.begin();
     size_t span_tables = t_tables.begin();
     if (P.nnz == 0) {
+        if (J->S->sharded) {      // nothing to score here, but the side outputs are everybody's
+            DevBuf<double> d_total(ctx, 1);
+            k_item_coll<<<1, 64, 0, st>>>(0, J->stats.get(), nullptr, d_total.get());
+            FY_KERNEL_CHECK();
+            sharded_side_outputs(J, R.get(), d_total.get());
+            d2h(ctx, &R->total_sum, d_total.get(), 1);
+            sync(ctx);
+        }
         t_total.end(span_total);
         sync(ctx);
         return R.release();
@@ -3280,32 +3320,7 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
     }
     // rm2/userSum and rm2/itemColl stay in HBM until somebody asks for them
     if (J->S->sharded) {
-        // the GLOBAL statistics (jobs RM2-1 / RM2-2 write one userSum and one itemColl for all clusters): out of the summed raw-id buffer
-        const RM2Static& S = *J->S;
-        const double* raw_items = J->stats_raw.get();
-        const double* raw_users = J->stats_raw.get() + S.n_raw_items + 1;
-        DevBuf<uint32_t> fi(ctx, (size_t)S.n_raw_items), pi(ctx, (size_t)S.n_raw_items), fu(ctx, (size_t)S.n_raw_users), pu(ctx, (size_t)S.n_raw_users);
-        k_flag_positive<<<grid_for(S.n_raw_items), 256, 0, st>>>(S.n_raw_items, raw_items, fi.get());
-        FY_KERNEL_CHECK();
-        k_flag_positive<<<grid_for(S.n_raw_users), 256, 0, st>>>(S.n_raw_users, raw_users, fu.get());
-        FY_KERNEL_CHECK();
-        inclusive_scan_u32(ctx, fi.get(), pi.get(), (size_t)S.n_raw_items);
-        inclusive_scan_u32(ctx, fu.get(), pu.get(), (size_t)S.n_raw_users);
-        uint32_t n_items_all = 0, n_users_all = 0;
-        d2h(ctx, &n_items_all, pi.get() + (S.n_raw_items - 1), 1);
-        d2h(ctx, &n_users_all, pu.get() + (S.n_raw_users - 1), 1);
-        sync(ctx);
-        R->d_item_id.alloc(ctx, n_items_all);
-        R->d_icoll.alloc(ctx, n_items_all);
-        R->d_user_id.alloc(ctx, n_users_all);
-        R->d_user_sum.alloc(ctx, n_users_all);
-        k_compact_positive<<<grid_for(S.n_raw_items), 256, 0, st>>>(S.n_raw_items, raw_items, pi.get(), d_total.get(), R->d_item_id.get(), R->d_icoll.get());
-        FY_KERNEL_CHECK();
-        k_compact_positive<<<grid_for(S.n_raw_users), 256, 0, st>>>(S.n_raw_users, raw_users, pu.get(), nullptr, R->d_user_id.get(), R->d_user_sum.get());
-        FY_KERNEL_CHECK();
-        R->st.n_users = n_users_all;
-        R->st.n_items = n_items_all;
-        sync(ctx);      // (the flags and positions are released here)
+        sharded_side_outputs(J, R.get(), d_total.get());
     } else {
         R->d_user_id.alloc(ctx, nU);
         R->d_user_sum.alloc(ctx, nU);

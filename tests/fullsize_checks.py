@@ -57,6 +57,72 @@ def run_rm2(data, top_n, lam, env=None, clusters=1):
     return rows, sums, st
 
 
+def run_rm2_thread_ranks(data, top_n, lam, world, clusters=1):
+    """The same job by `world` ranks on ONE card: threads of this process, one fy context each, meeting in parallel.ThreadCollectives
+    (serialised: one rank computes at a time, the others wait at the collective -- tools/coop_rehearsal.py), the ratings handed over as the
+    device tensors of `data`.  Default tuning: what a real multi-rank job takes.  Returns ([(rows, sums, stats) per rank], [collectives
+    per rank]).  A rank that dies aborts the barrier; a rank that is still alive after the join is a failure, not a timeout to sit out."""
+    import importlib
+    import threading
+    P = pkg()
+    par = importlib.import_module("filmyou-core_amd.parallel")
+    conf = P.Configuration()
+    conf.set("lambda", repr(lam))
+    conf.setInt("numberOfItems", data["facts"]["n_items"])
+    conf.setInt("numberOfClusters", clusters)
+    conf.setInt("numberOfRecommendations", top_n)
+    clustering = clustering_of(data, clusters)
+    group = par.ThreadGroup(world, serialize=True)
+    comms = [par.ThreadCollectives(group, k, 0) for k in range(world)]
+    out, err = [None] * world, [None] * world
+
+    def body(rank):
+        try:
+            ctx = P.Context(0)
+            ratings = P.Ratings(ctx, *data["dev"])
+            comms[rank].enter()
+            rec = P.RM2Job(conf, ctx).run(ratings, clustering=clustering, rank=rank, world=world, collectives=comms[rank])
+            ctx.synchronize()
+            comms[rank].leave("tail")
+            out[rank] = (rec.rows(), rec.sums(), dict(rec.stats))
+            rec.close()
+            ratings.close()
+            ctx.close()
+        except BaseException as e:      # a dead rank must not leave the others at the barrier (or in front of the lock)
+            err[rank] = e
+            group.barrier.abort()
+            try:
+                group.lock.release()
+            except RuntimeError:
+                pass
+
+    threads = [threading.Thread(target=body, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(600)
+    assert not any(t.is_alive() for t in threads), "a rank is stuck"
+    for e in err:
+        if e is not None and not isinstance(e, threading.BrokenBarrierError):
+            raise e
+    assert all(o is not None for o in out), err
+    return out, comms
+
+
+def union_by_user(parts):
+    """rows of several ranks (or one job) as one table in ascending user id, list order kept (a stable sort: the ranks' rows arrive in
+    another user order than the one-rank job's)"""
+    rows = {k: np.concatenate([r[k] for r in parts]) for k in ("user", "item", "score", "cluster")}
+    o = np.argsort(rows["user"], kind="stable")
+    return {k: v[o] for k, v in rows.items()}
+
+
+def disjoint_owners(parts, n_users):
+    """ranks own disjoint users and together all of them"""
+    owned = [np.unique(r["user"]) for r in parts]
+    assert sum(len(o) for o in owned) == len(np.unique(np.concatenate(owned))) == n_users
+
+
 def check_rm2(data, rows, sums, st, top_n, lam, n_picks=10):
     R, uu, iu = data["R"], data["uu"], data["iu"]
     U, I = R.shape

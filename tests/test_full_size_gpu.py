@@ -4,8 +4,10 @@ See tests/fullsize_checks.py for what is checked: exact statistics (quirk Q1 on 
 list, spot checks against the fp64 definition, and -- all 8.1 M rows -- the pruned job against the plain full pass."""
 import pytest
 
-from fullsize_checks import (all_rows_against_fp64_definition, assert_same_lists, check_itemsim, compare_itemsim_builds, check_rm2, load_shape,
-                             run_rm2, whole_clusters_against_the_gram_oracle)
+import numpy as np
+
+from fullsize_checks import (all_rows_against_fp64_definition, assert_same_lists, check_itemsim, compare_itemsim_builds, check_rm2, disjoint_owners,
+                             load_shape, run_rm2, run_rm2_thread_ranks, union_by_user, whole_clusters_against_the_gram_oracle)
 
 pytestmark = pytest.mark.gpu
 LAM, TOPN = 0.1, 50
@@ -78,6 +80,57 @@ def test_rm2_panel_mode_50_clusters_equals_full_pass_all_rows(data, panel50):
     print("panel mode vs full pass, 50 clusters: %d rows, %d differ (ties at a cut-off), worst score difference %.2e, %d strays"
           % (len(rows["user"]), n_diff, worst, st["stray_blocks"]))
     assert n_diff <= 1e-5 * len(rows["user"])
+
+
+def test_rm2_cooperative_8_ranks_all_rows_against_the_fp64_definition(data, pruned):
+    """The cooperative path -- ONE neighbourhood scored by all ranks, every rank building an eighth of the matrix rows, default tuning -- at
+    full size: 8 thread ranks on one card, the union of their rows (all 8.1 M) against the fp64 DEFINITION, pure relative 1e-5, and against
+    the single-GPU job's lists.  This path has no fp64 refinement pass (fy_rm2.hip: refine = ... && !p.coop) and sums its partial scores
+    over ranks in fp32: the least precise path of the library.  Measured: 4.39e-6 against the definition (99.99th percentile 5.4e-7; the worst
+    row is again the user with 11 ratings whose score is -0.83, which the single-GPU job re-scores in fp64 and this path does not), the same
+    4.39e-6 against the single-GPU rows, no list differs."""
+    world = 8
+    rows1, sums1, st1 = pruned
+    out, comms = run_rm2_thread_ranks(data, TOPN, LAM, world)
+    # the cooperative path really ran: per cooperative cluster the seed + bounds (+ survivors) reduce-scatters; every rank scored its share
+    assert all(c.calls["reduce_scatter_f32"] >= 2 for c in comms), [c.calls for c in comms]
+    assert sum(o[2]["users_scored"] for o in out) == st1["users_scored"] == 162541
+    disjoint_owners([o[0] for o in out], 162541)
+    for _, sums, _ in out:          # every rank returns the global side outputs: the single-GPU job's, exactly
+        for k in ("user_id", "user_sum", "item_id", "item_coll", "total_sum"):
+            np.testing.assert_array_equal(sums[k], sums1[k])
+    rows = union_by_user([o[0] for o in out])
+    all_rows_against_fp64_definition(data, rows, LAM, 1, "ML-25M shape, one cluster, 8 cooperative ranks")
+    n_diff, worst = assert_same_lists(rows, union_by_user([rows1]), score_rtol=1e-5, tie_rtol=1e-5)
+    print("8 cooperative ranks vs the single-GPU job: %d rows, %d differ (ties at a cut-off), worst relative score difference %.2e" % (len(rows["user"]), n_diff, worst))
+    assert n_diff <= 1e-5 * len(rows["user"])
+
+
+def test_rm2_50_clusters_on_8_ranks_equals_single_gpu_all_rows(data, panel50):
+    """Whole clusters per rank at full size: 50 clusters on 8 thread ranks, sharded prep (every rank preps the ratings of its own
+    clusters alone), the library's own all-gather of the raw-id statistics.  Half-star data: the statistics are bit-identical, so the
+    union of the rows is the single-GPU job's in (user, item) bit for bit and within 1e-6 in score."""
+    world = 8
+    rows1, sums1, st1 = panel50
+    out, comms = run_rm2_thread_ranks(data, TOPN, LAM, world, clusters=50)
+    # sharded: each rank prepared a strict part of the ratings, the parts add up
+    nnz = [o[2]["nnz"] for o in out]
+    assert all(0 < x < st1["nnz"] for x in nnz) and sum(nnz) == st1["nnz"], nnz
+    assert all(c.calls["all_gather"] >= 1 for c in comms)
+    assert sum(o[2]["users_scored"] for o in out) == st1["users_scored"]
+    disjoint_owners([o[0] for o in out], 162541)
+    held = [set(np.unique(o[0]["cluster"]).tolist()) for o in out]
+    assert all(held) and sum(len(h) for h in held) == len(set().union(*held)) == 50, held       # whole clusters, every rank has some
+    for _, sums, _ in out:
+        for k in ("user_id", "user_sum", "item_id", "item_coll", "total_sum"):
+            np.testing.assert_array_equal(sums[k], sums1[k])
+    a, b = union_by_user([o[0] for o in out]), union_by_user([rows1])
+    for k in ("user", "item", "cluster"):
+        np.testing.assert_array_equal(a[k], b[k])
+    x, y = a["score"].astype(np.float64), b["score"].astype(np.float64)
+    worst = float(np.max(np.abs(x - y) / np.abs(y)))
+    print("50 clusters on 8 ranks vs the single-GPU job: %d rows, worst relative score difference %.2e" % (len(x), worst))
+    assert worst < 1e-6
 
 
 @pytest.mark.parametrize("clusters", [1, 50])

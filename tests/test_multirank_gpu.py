@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import oracle
-from util import assert_topn_matches, pkg, synth
+from util import assert_topn_matches, pkg, skewed_clustering, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +28,56 @@ def device_doubles(ptr, n):
 @pytest.mark.parametrize("shape,K,world", [("tiny", 1, 2), ("tiny", 5, 3), ("ml100k", 1, 4), ("ml100k", 12, 8), ("ml100k", 8, 8), ("ml100k", 50, 4)])
 def test_sharded_equals_single(ctx, shape, K, world):
     sharded_equals_single(ctx, shape, K, world)
+
+
+@pytest.mark.parametrize("K,world,big_at", [(K, world, at) for K in (6, 12) for world in (4, 8) for at in ("first", "middle", "last")]
+                         + [(4, 4, "middle"), (8, 8, "first")])
+def test_skewed_clusters(ctx, K, world, big_at):
+    """Cluster sizes as uneven as the PPC stage makes them, and more: ~70 % of the users in ONE cluster (at id 0, in the middle, at K - 1:
+    the partition is over ascending ids), the rest spread over the other K - 1.  The big cluster alone outweighs all the others, so the
+    min-cap partition needs fewer runs than there are ranks; every rank must still own a cluster (K >= world: whole clusters per rank,
+    sharded prep; (4, 4) and (8, 8): exactly as many non-empty clusters as ranks), the rank with the big cluster owns nothing else, and
+    every rank returns the global side outputs.  (6, 8): fewer clusters than ranks, the users are split by slot range instead.)"""
+    big = {"first": 0, "middle": K // 2, "last": K - 1}[big_at]
+    sharded_equals_single(ctx, "ml100k", K, world, clustering=lambda uu: (uu, skewed_clustering(uu, K, big)), big_cluster=big)
+
+
+def test_thread_ranks_with_skewed_clusters():
+    """A skewed case with the ranks as threads and the library's own all-gather (parallel.ThreadCollectives), default tuning: the ranks
+    with next to nothing to score pass the collective and return -- with the global side outputs -- instead of leaving the others
+    waiting (run_threads fails when a rank is still alive after the join)."""
+    from test_pruned_coop_gpu import run_threads
+    P, S = pkg(), synth()
+    K, world, big = 12, 8, 11
+    u, i, s, facts = S.generate("ml100k")
+    u, i, s = u.numpy(), i.numpy(), s.numpy()
+    uu = np.unique(u)
+    clustering = (uu, skewed_clustering(uu, K, big))
+    conf = P.Configuration()
+    conf.set("lambda", "0.1")
+    conf.setInt("numberOfItems", facts["n_items"])
+    conf.setInt("numberOfClusters", K)
+    conf.setInt("numberOfRecommendations", 20)
+    c = P.Context(0)
+    single = P.RM2Job(conf, c).run((u, i, s), clustering=clustering)
+    rows1, sums1, st1 = single.rows(), single.sums(), dict(single.stats)
+    c.close()
+    out, comms = run_threads(world, (u, i, s), clustering, conf)
+    assert all(x.calls["all_gather"] == 1 and x.calls["reduce_scatter_f32"] == 0 for x in comms), [x.calls for x in comms]
+    rows = {k: np.concatenate([o[0][k] for o in out]) for k in ("user", "item", "score", "cluster")}
+    assert_topn_matches(rows, oracle_of("ml100k", K, clustering, (u, i, s), facts), 20)
+    o_, o1 = np.lexsort((rows["item"], rows["user"])), np.lexsort((rows1["item"], rows1["user"]))
+    for k in ("user", "item", "cluster"):
+        np.testing.assert_array_equal(rows[k][o_], rows1[k][o1])
+    a, b = rows["score"][o_].astype(np.float64), rows1["score"][o1].astype(np.float64)
+    assert np.max(np.abs(a - b) / np.abs(b)) < 1e-6
+    held = [set(np.unique(o[0]["cluster"]).tolist()) for o in out]
+    assert all(held) and sum(len(h) for h in held) == len(set().union(*held)) == K, held
+    assert [h for h in held if big in h] == [{big}], held
+    assert sum(o[1]["users_scored"] for o in out) == st1["users_scored"]
+    for o in out:
+        for k in ("user_id", "user_sum", "item_id", "item_coll", "total_sum"):
+            np.testing.assert_array_equal(o[2][k], sums1[k])
 
 
 def test_whole_clusters_with_the_replicated_prep(monkeypatch):
@@ -78,7 +128,25 @@ def test_sharded_prep_with_ragged_input(ctx):
     """Sharded prep on input that is not tidy: users the clustering map does not name (cluster 0, quirk Q2), map entries of users who
     rated nothing, a repeated map entry (the later one wins), clusters nobody is routed to, ratings <= 0 (dropped), scores that are no
     halves (the prep's general mode) -- the ranks' rows together are the one-rank rows, bit for bit, and the clusteringCount is checked
-    by the rank that owns the cluster."""
+    by the rank that owns the cluster.
+    Map entries of users WITHOUT a kept rating whose id lies below the largest user id -- one whose every rating is 0, one whose every
+    rating is negative, one id that does not occur in the ratings -- routed to -1, K and K + 1000: legal (nobody routes a rating by
+    them; the one-rank job accepts them), and the sharded prep's ownership table is indexed by the cluster of EVERY raw id.  A user WITH
+    a kept rating routed to K is FY_ERR_CLUSTER_RANGE on every rank, as in the one-rank job."""
+    ragged_input(ctx, sharded=True)
+
+
+def test_replicated_prep_with_ragged_input(monkeypatch):
+    """The same input with FY_SHARD_PREP=0: the replicated prep is held to the same behaviour."""
+    monkeypatch.setenv("FY_SHARD_PREP", "0")
+    c = pkg().Context(0)
+    try:
+        ragged_input(c, sharded=False)
+    finally:
+        c.close()
+
+
+def ragged_input(ctx, sharded):
     P, S = pkg(), synth()
     u, i, s, facts = S.generate("ml100k", seed_offset=3)
     u, i, s = u.numpy().copy(), i.numpy().copy(), s.numpy().copy()
@@ -87,12 +155,18 @@ def test_sharded_prep_with_ragged_input(ctx):
     s[3] = np.float32(2.7)
     uu = np.unique(u)
     K, world = 11, 4
+    # users below the largest id without a kept rating: every rating 0, every rating negative, an id that does not occur
+    all_zero, all_negative, absent = int(uu[10]), int(uu[len(uu) // 2]), 0
+    s[u == all_zero] = 0.0
+    s[u == all_negative] = -2.0
+    assert absent not in set(uu.tolist()) and max(all_zero, all_negative, absent) < int(uu.max())
+    assert not (s[(u == all_zero) | (u == all_negative)] > 0).any()
     named = uu[uu % 5 != 0]                                  # a fifth of the users is not in the map
     cl = S.hash_clustering(named, K)
     cl[cl == 7] = 2                                          # nobody in cluster 7
     cl[cl == 9] = 3                                          # nor in 9
-    map_user = np.concatenate([named, [int(uu.max()) + 50, int(uu.max()) + 51], named[:3]]).astype(np.int32)
-    map_cluster = np.concatenate([cl, [7, 4], [(int(cl[0]) + 1) % 7, int(cl[1]), int(cl[2])]]).astype(np.int32)
+    map_user = np.concatenate([named, [int(uu.max()) + 50, int(uu.max()) + 51], named[:3], [all_zero, all_negative, absent]]).astype(np.int32)
+    map_cluster = np.concatenate([cl, [7, 4], [(int(cl[0]) + 1) % 7, int(cl[1]), int(cl[2])], [-1, K, K + 1000]]).astype(np.int32)
     clustering = (map_user, map_cluster)
     conf = P.Configuration()
     conf.set("lambda", "0.2")
@@ -112,7 +186,7 @@ def test_sharded_prep_with_ragged_input(ctx):
         count[route.get(usr, 0)] += 1
     assert count[7] == 0 and count[9] == 0 and (count > 0).sum() >= world
     prepared = [job.prepare(ratings, clustering=clustering, clustering_count=count, rank=r, world=world) for r in range(world)]
-    assert all(pr.stats_layout()[1] > 0 for pr in prepared)      # sharded
+    assert all((pr.stats_layout()[1] > 0) == sharded for pr in prepared)
     parts = []
     for pr in prepared:
         ptr, n = pr.partial_stats()
@@ -134,28 +208,40 @@ def test_sharded_prep_with_ragged_input(ctx):
     # test_sharded_equals_single)
     a_, b_ = rows["score"][order].astype(np.float64), rows1["score"][order1].astype(np.float64)
     assert np.max(np.abs(a_ - b_) / np.abs(b_)) < 1e-6
-    for r in results:
-        if r.size:
-            for k2 in ("user_id", "item_id"):
-                np.testing.assert_array_equal(r.sums()[k2], single.sums()[k2])
-            for k2 in ("user_sum", "item_coll", "total_sum"):
-                np.testing.assert_allclose(r.sums()[k2], single.sums()[k2], rtol=1e-14, atol=0)
-    # a clusteringCount that is wrong for ONE cluster: only its owner can see it, every rank fails with FY_ERR_CLUSTER_COUNT
+    for r in results:       # every rank, whatever it scored
+        for k2 in ("user_id", "item_id"):
+            np.testing.assert_array_equal(r.sums()[k2], single.sums()[k2])
+        for k2 in ("user_sum", "item_coll", "total_sum"):
+            np.testing.assert_allclose(r.sums()[k2], single.sums()[k2], rtol=1e-14, atol=0)
+    # a clusteringCount that is wrong for ONE cluster
     bad = count.copy()
     bad[int(np.flatnonzero(count)[-1])] += 1
-    prepared = [job.prepare(ratings, clustering=clustering, clustering_count=bad, rank=r, world=world, cache=False) for r in range(world)]
-    parts = []
-    for pr in prepared:
-        ptr, n = pr.partial_stats()
-        parts.append(device_doubles(ptr, n).clone())
-    torch.cuda.synchronize()
-    assert sorted(float(p[-1]) for p in parts) == [0.0] * (world - 1) + [6.0]
-    gathered = torch.cat(parts).contiguous()
-    for pr in prepared:
-        with pytest.raises(P.FilmYouError) as e:
-            pr.set_global_stats(gathered.data_ptr())
-        assert e.value.code == -6
-        pr.close()
+    if sharded:     # only its owner can see it, every rank fails with FY_ERR_CLUSTER_COUNT
+        prepared = [job.prepare(ratings, clustering=clustering, clustering_count=bad, rank=r, world=world, cache=False) for r in range(world)]
+        parts = []
+        for pr in prepared:
+            ptr, n = pr.partial_stats()
+            parts.append(device_doubles(ptr, n).clone())
+        torch.cuda.synchronize()
+        assert sorted(float(p[-1]) for p in parts) == [0.0] * (world - 1) + [6.0]
+        gathered = torch.cat(parts).contiguous()
+        for pr in prepared:
+            with pytest.raises(P.FilmYouError) as e:
+                pr.set_global_stats(gathered.data_ptr())
+            assert e.value.code == -6
+            pr.close()
+    else:           # every rank preps every cluster and sees it itself
+        for r in range(world):
+            with pytest.raises(RuntimeError, match="RM2 failed!") as e:
+                job.prepare(ratings, clustering=clustering, clustering_count=bad, rank=r, world=world, cache=False)
+            assert e.value.__cause__.code == -6
+    # the mirror of the stray entries: a user WITH a kept rating routed to K -- FY_ERR_CLUSTER_RANGE from prepare, one rank or several
+    rated = int(np.unique(u[s > 0])[7])
+    out_of_range = (np.append(map_user, rated).astype(np.int32), np.append(map_cluster, K).astype(np.int32))
+    for r, w in [(0, 1)] + [(r, world) for r in range(world)]:
+        with pytest.raises(RuntimeError, match="RM2 failed!") as e:
+            job.prepare(ratings, clustering=out_of_range, rank=r, world=w, cache=False)
+        assert e.value.__cause__.code == -5
     ratings.close()
 
 
@@ -169,12 +255,26 @@ def test_sharded_panel_mode(ctx, monkeypatch):
     assert all(x["panel_clusters"] > 0 for x in st)
 
 
-def sharded_equals_single(ctx, shape, K, world):
+ORACLE_CACHE = {}
+
+
+def oracle_of(shape, K, clustering, triples, facts):
+    """the brute-force oracle's full ranking at lambda 0.1 (the same job on another number of ranks: one oracle run)"""
+    key = (shape, K, clustering[0].tobytes(), clustering[1].tobytes())
+    if key not in ORACLE_CACHE:
+        ORACLE_CACHE[key] = oracle.rm2(*triples, lam=0.1, number_of_items=facts["n_items"], number_of_recommendations=1 << 30,
+                                       number_of_clusters=K, map_user=clustering[0], map_cluster=clustering[1], n_threads=16)
+    return ORACLE_CACHE[key]
+
+
+def sharded_equals_single(ctx, shape, K, world, clustering=None, big_cluster=None):
+    """clustering: None = users hashed to K equal clusters, or a function of the user ids; big_cluster: a cluster that outweighs all the
+    others together (its rank must hold nothing else)"""
     P, S = pkg(), synth()
     u, i, s, facts = S.generate(shape)
     u, i, s = u.numpy(), i.numpy(), s.numpy()
     uu = np.unique(u)
-    clustering = (uu, S.hash_clustering(uu, K))
+    clustering = clustering(uu) if clustering else (uu, S.hash_clustering(uu, K))
     conf = P.Configuration()
     conf.set("lambda", "0.1")
     conf.setInt("numberOfItems", facts["n_items"])
@@ -219,17 +319,14 @@ def sharded_equals_single(ctx, shape, K, world):
         pr.set_global_stats(gathered.data_ptr())
         results.append(pr.score())
         pr.close()
-    for r in results:       # every rank returns the GLOBAL side outputs (rm2/userSum, rm2/itemColl), whatever it prepared
-        if r.size:
-            for k2 in ("user_id", "user_sum", "item_id", "item_coll", "total_sum"):
-                np.testing.assert_array_equal(r.sums()[k2], sums[k2])
+    for r in results:       # every rank returns the GLOBAL side outputs (rm2/userSum, rm2/itemColl), whatever it prepared or scored
+        for k2 in ("user_id", "user_sum", "item_id", "item_coll", "total_sum"):
+            np.testing.assert_array_equal(r.sums()[k2], sums[k2])
     rows = {k: np.concatenate([r.rows()[k] for r in results]) for k in ("user", "item", "score", "cluster")}
     # ranks own disjoint users, together all of them
     owners = [set(r.rows()["user"].tolist()) for r in results]
     assert sum(len(o) for o in owners) == len(set().union(*owners)) == len(np.unique(single.rows()["user"]))
-    ref = oracle.rm2(u, i, s, lam=0.1, number_of_items=facts["n_items"], number_of_recommendations=1 << 30,
-                     number_of_clusters=K, map_user=clustering[0], map_cluster=clustering[1], n_threads=8)
-    assert_topn_matches(rows, ref, 20)
+    assert_topn_matches(rows, oracle_of(shape, K, clustering, (u, i, s), facts), 20)
     # and the shards agree with the one-GPU run row for row (same kernels, same statistics)
     key = lambda r: sorted(zip(r["user"].tolist(), r["item"].tolist()))
     assert key(rows) == key(single.rows())
@@ -242,6 +339,10 @@ def sharded_equals_single(ctx, shape, K, world):
     if n_nonempty >= world:
         held = [set(np.unique(r.rows()["cluster"]).tolist()) for r in results]
         assert sum(len(h) for h in held) == len(set().union(*held)) == n_nonempty, held
+        if n_user_slots:        # sharded prep: the clusters are cut by weight, and no rank is left without one
+            assert all(held), held
+            if big_cluster is not None:
+                assert [h for h in held if big_cluster in h] == [{big_cluster}], held
     st = [r.stats for r in results]
     assert sum(x["users_scored"] for x in st) == single.stats["users_scored"]
     assert sum(x["log_terms"] for x in st) == single.stats["log_terms"]

@@ -97,7 +97,7 @@ def run_threads(world, data, clustering, conf):
             ctx = P.Context(0)
             comms[rank] = par.ThreadCollectives(group, rank, 0)
             rec = P.RM2Job(conf, ctx).run(data, clustering=clustering, rank=rank, world=world, collectives=comms[rank])
-            out[rank] = (rec.rows(), dict(rec.stats))
+            out[rank] = (rec.rows(), dict(rec.stats), rec.sums())
             rec.close()
             ctx.close()
         except BaseException as e:      # a dead rank must not leave the others at the barrier
@@ -109,6 +109,7 @@ def run_threads(world, data, clustering, conf):
         t.start()
     for t in threads:
         t.join(600)
+    assert not any(t.is_alive() for t in threads), "a rank is stuck (in a collective the others never entered?)"
     for e in err:
         if e is not None and not isinstance(e, threading.BrokenBarrierError):
             raise e
