@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_itemsim.hip", "fy_itemcf.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_coop.hpp"]  # fy_itemcf.hip uses fy_prep.hpp / fy_rm2.hpp
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_itemsim.hip", "fy_itemcf.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_coop.hpp", "fy_refine.hpp"]  # fy_itemcf.hip uses fy_prep.hpp / fy_rm2.hpp
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -27,6 +27,10 @@ SYMBOLS = [
     "fy_result_item_id", "fy_result_item_coll", "fy_result_total_sum", "fy_result_free", "fy_result_stats",
     "fy_seqfile_read_int_int", "fy_seqfile_read_int_double", "fy_seqfile_read_intpair_float", "fy_seqfile_write_int_int",
     "fy_seqfile_write_int_double", "fy_seqfile_write_intpair_float", "fy_mapfile_write_int_double", "fy_buffer_free",
+    "fy_submap_create", "fy_submap_n_users", "fy_submap_n_items", "fy_submap_nnz", "fy_submap_counts", "fy_submap_users",
+    "fy_submap_items", "fy_submap_matrix", "fy_submap_destroy", "fy_cluster_refine", "fy_refined_n_users", "fy_refined_n_counts",
+    "fy_refined_clustering", "fy_refined_layout", "fy_refined_h_size", "fy_refined_w_size", "fy_refined_factors",
+    "fy_refined_stats", "fy_refined_free",
 ]
 
 
@@ -120,6 +124,21 @@ class Collectives(C.Structure):
 class NMFParams(C.Structure):
     _fields_ = [("number_of_users", C.c_int32), ("number_of_items", C.c_int32), ("number_of_clusters", C.c_int32),
                 ("number_of_iterations", C.c_int32), ("ppc", C.c_int32), ("normalization_frequency", C.c_int32)]
+
+
+class RefineParams(C.Structure):
+    _fields_ = [("number_of_users", C.c_int32), ("number_of_clusters", C.c_int32), ("users_per_sub_cluster", C.c_int32),
+                ("number_of_iterations", C.c_int32), ("ppc", C.c_int32), ("normalization_frequency", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class RefineStats(C.Structure):
+    _fields_ = [("ms_mappings", C.c_double), ("ms_iterations", C.c_double), ("ms_assign", C.c_double), ("ms_total", C.c_double),
+                ("launches", C.c_int64), ("sum_users", C.c_int64), ("sum_items", C.c_int64), ("sum_k", C.c_int64),
+                ("nnz", C.c_int64), ("collisions", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ItemSimParams(C.Structure):
@@ -230,5 +249,23 @@ def load():
     L.fy_mapfile_write_int_double.argtypes = [cp, i64, vp, vp]
     L.fy_buffer_free.argtypes = [vp]
     L.fy_buffer_free.restype = None
+    L.fy_submap_create.argtypes = [vp, vp, i32, i64, vp, vp, pvp]
+    for name in ("fy_submap_n_users", "fy_submap_n_items", "fy_submap_nnz", "fy_refined_n_users", "fy_refined_n_counts",
+                 "fy_refined_h_size", "fy_refined_w_size"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = i64
+    L.fy_submap_counts.argtypes = [vp, vp, vp]
+    L.fy_submap_users.argtypes = [vp, vp, vp, vp]
+    L.fy_submap_items.argtypes = [vp, vp, vp, vp]
+    L.fy_submap_matrix.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.fy_submap_destroy.argtypes = [vp]
+    L.fy_submap_destroy.restype = None
+    L.fy_cluster_refine.argtypes = [vp, C.POINTER(RefineParams), vp, i64, vp, vp, vp, vp, pvp]
+    L.fy_refined_clustering.argtypes = [vp, vp, vp, vp]
+    L.fy_refined_layout.argtypes = [vp, vp, vp, vp]
+    L.fy_refined_factors.argtypes = [vp, vp, vp]
+    L.fy_refined_stats.argtypes = [vp, C.POINTER(RefineStats)]
+    L.fy_refined_free.argtypes = [vp]
+    L.fy_refined_free.restype = None
     _lib = L
     return L

@@ -675,3 +675,221 @@ class NMFDriver:
             if own:
                 r.close()
         return H, W
+
+
+class SubClusterMappings:
+    """What SubClusterMappingJob leaves behind (the reference's `mapping/<cluster>` and `subClustering{User,Item}/clusteringCount`
+    files), as arrays.  Users and items come cluster after cluster, inside a cluster by ascending raw id; `*_new_id` counts from 1
+    inside the cluster.  ``csr`` / ``csc``: the kept ratings over these rows, ``(rowptr, col, value)`` with ``col`` a row of the
+    other side."""
+
+    def __init__(self, lib, h, n_clusters):
+        i32 = np.int32
+        nu, ni, nnz = lib.fy_submap_n_users(h), lib.fy_submap_n_items(h), lib.fy_submap_nnz(h)
+        self.users_in_cluster, self.items_in_cluster = np.zeros(n_clusters, i32), np.zeros(n_clusters, i32)
+        _check(lib.fy_submap_counts(h, self.users_in_cluster.ctypes.data, self.items_in_cluster.ctypes.data))
+        self.user, self.user_cluster, self.user_new_id = np.zeros(nu, i32), np.zeros(nu, i32), np.zeros(nu, i32)
+        _check(lib.fy_submap_users(h, self.user.ctypes.data, self.user_cluster.ctypes.data, self.user_new_id.ctypes.data))
+        self.item, self.item_cluster, self.item_new_id = np.zeros(ni, i32), np.zeros(ni, i32), np.zeros(ni, i32)
+        _check(lib.fy_submap_items(h, self.item.ctypes.data, self.item_cluster.ctypes.data, self.item_new_id.ctypes.data))
+        self.nnz = nnz
+        self.csr = (np.zeros(nu + 1, i32), np.zeros(nnz, i32), np.zeros(nnz, np.float32))
+        self.csc = (np.zeros(ni + 1, i32), np.zeros(nnz, i32), np.zeros(nnz, np.float32))
+        for by_item, (p, c, v) in ((0, self.csr), (1, self.csc)):
+            _check(lib.fy_submap_matrix(h, by_item, p.ctypes.data, c.ctypes.data, v.ctypes.data))
+
+
+def _clustering_arrays(clustering):
+    mu, mc = (_i32(clustering[0]), _i32(clustering[1])) if clustering is not None else (_i32(None), _i32(None))
+    if len(mu) != len(mc):
+        raise ValueError("clustering users / clusters differ in length")
+    return mu, mc
+
+
+class SubClusterMappingJob:
+    """New user and item ids per parent cluster (M/nmf/clustering/SubClusterMappingJob.java with User / ItemMappingReducer),
+    for all parent clusters in one pass on the GPU.  Configuration key: numberOfClusters.  The order of the new ids, which the
+    reference leaves to the shuffle, is ascending raw id."""
+
+    JOB_NAME = "SubClusterMappingJob"
+
+    def __init__(self, conf, context):
+        self._conf, self._ctx = conf, context
+        self._lib = _native.load()
+
+    def run(self, ratings, clustering):
+        """ratings: a ``Ratings`` or a (user, item, score) triple; clustering: (users, clusters) of the parent clustering."""
+        K = self._conf.getInt("numberOfClusters", -1)
+        if K is None or K <= 0:
+            raise ValueError("Invalid number of clusters (%s)" % K)      # RMRecommenderDriver.java:302-305
+        mu, mc = _clustering_arrays(clustering)
+        own = not isinstance(ratings, Ratings)
+        r = Ratings(self._ctx, *ratings) if own else ratings
+        h = C.c_void_p()
+        try:
+            try:
+                _check(self._lib.fy_submap_create(self._ctx._h, r._h, K, len(mu), mu.ctypes.data, mc.ctypes.data, C.byref(h)))
+                return SubClusterMappings(self._lib, h, K)
+            except FilmYouError as e:
+                raise RuntimeError("%s failed!: %s" % (self.JOB_NAME, e.message)) from e
+        finally:
+            if h:
+                self._lib.fy_submap_destroy(h)
+            if own:
+                r.close()
+
+
+class ClusterRefinementJob:
+    """Cluster refinement (RMRecommenderDriver.clusterRefinement, M/rmrecommender/RMRecommenderDriver.java:217-266): the
+    mappings, one PPC (``ppc=True``, what the reference runs) or NMF factorisation per parent cluster with
+    ceil(usersInCluster / usersPerSubCluster) sub-clusters, and ClusterAssignmentJob(true) -- all parent clusters in one batched
+    pass on the GPU (fy_cluster_refine).  Configuration keys: numberOfUsers (only the id stride
+    ceil(numberOfUsers / numberOfClusters)), numberOfClusters, usersPerSubCluster, numberOfIterations, normalizationFrequency
+    (unset = -1, like NMFDriver).  ``run`` returns ``(users, clusters, counts)`` like ``ClusterAssignmentJob.run_sub``;
+    afterwards ``stats`` (fy_refine_stats), ``users_in_cluster`` / ``items_in_cluster`` / ``sub_clusters`` per parent and, with
+    ``keep_factors=True``, ``factors`` = [(H_c, W_c), ...] per parent are set."""
+
+    JOB_NAME = "ClusterRefinement"
+
+    def __init__(self, conf, context, ppc=True):
+        self._conf, self._ctx, self._ppc = conf, context, bool(ppc)
+        self._lib = _native.load()
+        self.stats = self.factors = self.users_in_cluster = self.items_in_cluster = self.sub_clusters = None
+
+    def run(self, ratings, clustering, H0=None, W0=None, seed=0, keep_factors=False):
+        """H0 / W0: the initial matrices, either a list with one (n_c x k_c) / (m_c x k_c) array per parent cluster (rows in
+        new-id order = ascending raw id) or the concatenated flat array; None: the device draws them from ``seed``
+        (include/filmyou.h gives the formula)."""
+        conf = self._conf
+        K, ups = conf.getInt("numberOfClusters", -1), conf.getInt("usersPerSubCluster", -1)
+        n_users = conf.getInt("numberOfUsers", -1)
+        if K is None or K <= 0:
+            raise ValueError("Invalid number of clusters (%s)" % K)
+        if ups is None or ups <= 0:
+            raise ValueError("usersPerSubCluster must be > 0 (%s)" % ups)
+        if n_users is None or n_users <= 0:
+            raise ValueError("numberOfUsers is required")
+        if (H0 is None) != (W0 is None):
+            raise ValueError("H0 and W0 must be given together")
+        mu, mc = _clustering_arrays(clustering)
+
+        def flat(M):
+            if isinstance(M, (list, tuple)):
+                M = np.concatenate([np.asarray(m, dtype=np.float64).ravel() for m in M]) if len(M) else np.zeros(0)
+            return np.ascontiguousarray(M, dtype=np.float64).ravel()
+        p = _native.RefineParams(n_users, K, ups, conf.getInt("numberOfIterations", 1), 1 if self._ppc else 0,
+                                 conf.getInt("normalizationFrequency", -1), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        own = not isinstance(ratings, Ratings)
+        r = Ratings(self._ctx, *ratings) if own else ratings
+        h = C.c_void_p()
+        lib = self._lib
+        try:
+            h0, w0 = (flat(H0), flat(W0)) if H0 is not None else (None, None)
+            if h0 is not None:
+                # the sizes are known only after the mappings: the library reads sum n_c k_c / sum m_c k_c doubles, so check first
+                m = SubClusterMappingJob(conf, self._ctx).run(r, (mu, mc))
+                kc = -(-m.users_in_cluster.astype(np.int64) // ups)
+                if len(h0) != int((m.users_in_cluster * kc).sum()) or len(w0) != int((m.items_in_cluster * kc).sum()):
+                    raise ValueError("H0 / W0 must hold usersInCluster x subClusters and itemsInCluster x subClusters values per parent cluster")
+            try:
+                _check(lib.fy_cluster_refine(self._ctx._h, C.byref(p), r._h, len(mu), mu.ctypes.data, mc.ctypes.data,
+                                             h0.ctypes.data if h0 is not None else None, w0.ctypes.data if w0 is not None else None,
+                                             C.byref(h)))
+            except FilmYouError as e:
+                raise RuntimeError("%s failed!: %s" % (self.JOB_NAME, e.message)) from e
+            n, nc = lib.fy_refined_n_users(h), lib.fy_refined_n_counts(h)
+            users, clusters, counts = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(nc, np.int32)
+            _check(lib.fy_refined_clustering(h, users.ctypes.data, clusters.ctypes.data, counts.ctypes.data))
+            nu, ni, kc = np.zeros(K, np.int32), np.zeros(K, np.int32), np.zeros(K, np.int32)
+            _check(lib.fy_refined_layout(h, nu.ctypes.data, ni.ctypes.data, kc.ctypes.data))
+            self.users_in_cluster, self.items_in_cluster, self.sub_clusters = nu, ni, kc
+            st = _native.RefineStats()
+            _check(lib.fy_refined_stats(h, C.byref(st)))
+            self.stats = st.as_dict()
+            self.factors = None
+            if keep_factors:
+                H, W = np.zeros(lib.fy_refined_h_size(h)), np.zeros(lib.fy_refined_w_size(h))
+                _check(lib.fy_refined_factors(h, H.ctypes.data, W.ctypes.data))
+                ho = np.r_[0, np.cumsum(nu.astype(np.int64) * kc)]
+                wo = np.r_[0, np.cumsum(ni.astype(np.int64) * kc)]
+                self.factors = [(H[ho[c]:ho[c + 1]].reshape(nu[c], kc[c]), W[wo[c]:wo[c + 1]].reshape(ni[c], kc[c])) for c in range(K)]
+            return users, clusters, counts
+        finally:
+            if h:
+                lib.fy_refined_free(h)
+            if own:
+                r.close()
+
+
+class RMRecommenderDriver:
+    """The reference's production entry point in one call (M/rmrecommender/RMRecommenderDriver.java:164-206):
+
+      numberOfIterations > 0      PPC factorisation -> cluster assignment -> cluster refinement if usersPerSubCluster > 0 -> counts
+      numberOfIterations <= 0     the caller's ``clustering`` (and ``clustering_count``) are used
+      numberOfRecommendations > 0 the RM2 job runs on the result
+
+    Configuration keys: numberOfUsers, numberOfItems, numberOfClusters (required, :90-92) and the driver's own defaults
+    (:93-119) for usersPerSubCluster (-1), numberOfIterations (10), numberOfRecommendations (1000), normalizationFrequency (12),
+    lambda, filterUsers.  One ``Ratings`` object serves every stage.  ``run`` returns ``(recommendations, (users, clusters,
+    counts))``: the ``Recommendations`` of ``RM2Job.run`` (None when numberOfRecommendations <= 0) and the clustering the RM2 job
+    was -- or would have been -- given.  After refinement the cluster ids are parent * ceil(numberOfUsers / numberOfClusters) +
+    sub-cluster, sparse in a long ``counts``; the RM2 job then runs with numberOfClusters = len(counts) (the reference sets the
+    NUMBER of sub-clusters there, :262, which its own ids exceed)."""
+
+    DEFAULTS = {"usersPerSubCluster": -1, "numberOfIterations": 10, "numberOfRecommendations": 1000, "normalizationFrequency": 12}
+
+    def __init__(self, conf, ctx=None):
+        self.conf = conf
+        self.ctx = ctx
+        self.stats = {}
+
+    def _stage_conf(self, **over):
+        c = Configuration(self.conf)
+        for k, v in self.DEFAULTS.items():
+            if k not in c:
+                c.setInt(k, v)
+        for k, v in over.items():
+            c.setInt(k, v)
+        return c
+
+    def run(self, ratings, H=None, W=None, clustering=None, clustering_count=None, seed=0):
+        """H / W: the initial matrices of the top-level PPC run (numberOfUsers x numberOfClusters, numberOfItems x
+        numberOfClusters); None = uniform in (0, 1] from ``seed`` (the reference draws unpinned random matrices).  ``seed`` also
+        seeds the sub-runs' matrices."""
+        conf = self._stage_conf()
+        n_users, n_items, K = (conf.getInt(k, -1) for k in ("numberOfUsers", "numberOfItems", "numberOfClusters"))
+        if min(n_users, n_items, K) <= 0:
+            raise ValueError("numberOfUsers, numberOfItems and numberOfClusters are required")
+        iterations = conf.getInt("numberOfIterations", 10)
+        if iterations <= 0 and clustering is None:
+            raise ValueError("numberOfIterations <= 0 needs the caller's clustering")
+        ctx = self.ctx or Context(0)
+        self.ctx = ctx
+        own = not isinstance(ratings, Ratings)
+        r = Ratings(ctx, *ratings) if own else ratings
+        self.stats = {}
+        try:
+            if iterations > 0:
+                rng = np.random.default_rng(seed)
+                H = 1.0 - rng.random((n_users, K)) if H is None else H
+                W = 1.0 - rng.random((n_items, K)) if W is None else W
+                ppc = NMFDriver(conf, ctx, ppc=True)
+                H, W = ppc.run(r, H, W)
+                self.stats["ppc"] = ppc.stats
+                users, clusters, counts = ClusterAssignmentJob(ctx).run(H, first_user=1)
+                if conf.getInt("usersPerSubCluster", -1) > 0:
+                    refine = ClusterRefinementJob(conf, ctx, ppc=True)
+                    users, clusters, counts = refine.run(r, (users, clusters), seed=seed)
+                    self.stats["refine"] = refine.stats
+            else:
+                users, clusters = _clustering_arrays(clustering)
+                counts = None if clustering_count is None else _i32(clustering_count)
+            rec = None
+            if conf.getInt("numberOfRecommendations", 1000) > 0:
+                n_ids = len(counts) if counts is not None else K
+                rec = RM2Job(self._stage_conf(numberOfClusters=n_ids), ctx).run(r, clustering=(users, clusters), clustering_count=counts)
+                self.stats["rm2"] = rec.stats
+            return rec, (users, clusters, counts)
+        finally:
+            if own:
+                r.close()

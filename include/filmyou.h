@@ -301,6 +301,95 @@ typedef struct {
  * HBM), ms_total = everything including the host transfers of H and W in both directions. */
 int fy_nmf_factorize(fy_context*, const fy_nmf_params*, const fy_ratings*, double* H_inout, double* W_inout, fy_stats* stats_or_null);
 
+/* ------------------------------------------------------------------ cluster refinement (--usersPerSubCluster / -k2)
+ * Replaces RMRecommenderDriver.clusterRefinement / doMappings (M/rmrecommender/RMRecommenderDriver.java:217-266, 298-345):
+ * SubClusterMappingJob with its User / ItemMappingReducer, the Mappings mappers and reducers, one PPCDriver run per parent
+ * cluster and ClusterAssignmentJob(true) -- for ALL parent clusters in one batched pass on the GPU (csrc/fy_refine.hip).
+ *
+ * Mappings.  Input: the resident ratings and a parent clustering (map_user / map_cluster, HOST arrays, clusters in
+ * [0, number_of_clusters); a later entry of one user replaces the earlier; a member of a cluster outside that range fails with
+ * FY_ERR_CLUSTER_RANGE).
+ *   users of cluster c : the map's entries (InverseMapper over the `clustering` file): a mapped user without a kept rating is
+ *                        still a member;
+ *   items of cluster c : the distinct items with score > 0 rated by a user whose getCluster is c
+ *                        (ItemByClusterHDFSMapper.java:38-43); a user the map does not name has cluster 0 (Trove's no-entry
+ *                        value, AbstractByClusterMapper.java:77-79): its items join cluster 0's items, the user joins no user map;
+ *   new ids            : 1 .. n_c (users) and 1 .. m_c (items).  The reference leaves their order to the shuffle; here it is
+ *                        ASCENDING RAW ID inside every cluster;
+ *   kept ratings       : score > 0, the user has a new id in its cluster and the item one too
+ *                        (VectorByItemHDFSMapper.java:48-52, ItemScoreByUserHDFSMapper.java:46-49).
+ * Accessors copy to HOST arrays of the caller.  Users / items come cluster after cluster, ascending raw id inside a cluster
+ * ("row order": row = position in these arrays).  fy_submap_matrix: the kept ratings as CSR over user rows (by_item = 0: rowptr
+ * of n_users + 1, col = item ROW, ascending) or as CSC over item rows (by_item = 1: rowptr of n_items + 1, col = user ROW). */
+typedef struct fy_submap fy_submap;
+int fy_submap_create(fy_context*, const fy_ratings*, int32_t number_of_clusters, int64_t n_map, const int32_t* map_user,
+                     const int32_t* map_cluster, fy_submap** out);
+int64_t fy_submap_n_users(const fy_submap*);      /* sum of usersInCluster */
+int64_t fy_submap_n_items(const fy_submap*);      /* sum of itemsInCluster */
+int64_t fy_submap_nnz(const fy_submap*);          /* kept ratings */
+int fy_submap_counts(const fy_submap*, int32_t* users_in_cluster, int32_t* items_in_cluster);   /* number_of_clusters ints each */
+int fy_submap_users(fy_submap*, int32_t* raw_user, int32_t* cluster, int32_t* new_id);          /* n_users ints each */
+int fy_submap_items(fy_submap*, int32_t* raw_item, int32_t* cluster, int32_t* new_id);          /* n_items ints each */
+int fy_submap_matrix(fy_submap*, int by_item, int32_t* rowptr, int32_t* col, float* value);
+void fy_submap_destroy(fy_submap*);
+
+/* Refinement.  Parent cluster c gets k_c = ceil(n_c / users_per_sub_cluster) sub-clusters (RMRecommenderDriver.java:239) and
+ * its own n_c x k_c H and m_c x k_c W; all parents advance together through number_of_iterations multiplicative updates with
+ * the arithmetic of fy_nmf_factorize (fp64, eps 1e-12, H2 and W2 from the old pair, PPC's diagonal terms and L1 normalisation
+ * when iteration % normalization_frequency == 0).  Summation orders are fixed: two runs give the same bits.  H and W stay in
+ * HBM; what leaves the device is the refined clustering
+ *     user    = raw id
+ *     cluster = parent * ceil(number_of_users / number_of_clusters) + first index of the row's largest value
+ *               (FindSubClusterMapper.java:53, 76; number_of_users is the CONFIGURATION value, not the number of map entries)
+ *     count   = users per cluster id, n_counts entries (number_of_clusters x that stride, or more -- see below): long and
+ *               sparse in ids, exactly the (map_user, map_cluster, cluster_count) arguments of fy_rm2_prepare with
+ *               fy_rm2_params::number_of_clusters = n_counts.
+ * REFERENCE QUIRK, reproduced: when some k_c exceeds the stride, ids of neighbouring parents collide (a user of parent c with
+ * argmax >= stride lands in the id range of parent c + 1; for the last parent the count array grows beyond K x stride).
+ * fy_refine_stats::collisions counts the users with argmax >= stride; nothing is renumbered.
+ * Initial matrices: H0 / W0 (HOST, both or neither) hold the per-cluster matrices one after the other in cluster order, rows in
+ * new-id order, row-major (sum n_c k_c and sum m_c k_c doubles).  When NULL the device fills them from `seed` (the
+ * reference's sub-runs start from unpinned random matrices, AbstractNMFDriver.java:103-109): element (row, col), both from 0,
+ * of matrix `which` (0 = H, 1 = W) of parent cluster c is
+ *     mix(x) : x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
+ *     z = mix(seed ^ mix(((c << 32) | which) ^ mix((row << 32) | col)))            (64-bit, wrapping: splitmix64's finaliser)
+ *     value = ((z >> 11) + 1) * 2^-53                                              in (0, 1]
+ * Failures: k_c > 256 (the limit of fy_nmf_factorize) is FY_ERR_UNSUPPORTED and names the parent cluster; a member user
+ * without a kept rating fails like the reference's sub-run, "User %d has not rated any item (parent cluster %d)", an item
+ * likewise with "Item %d has not been rated by anybody (parent cluster %d)" -- both with the RAW id (only when
+ * number_of_iterations > 0; the items of a parent cluster without users are passed over). */
+typedef struct {
+    int32_t number_of_users;           /* "numberOfUsers": only the id stride ceil(numberOfUsers / numberOfClusters) */
+    int32_t number_of_clusters;        /* "numberOfClusters": parent clusters */
+    int32_t users_per_sub_cluster;     /* "usersPerSubCluster" (> 0) */
+    int32_t number_of_iterations;      /* "numberOfIterations" */
+    int32_t ppc;                       /* 0 = NMFDriver, 1 = PPCDriver (what the reference runs) */
+    int32_t normalization_frequency;   /* as in fy_nmf_params */
+    uint64_t seed;                     /* initial matrices when H0 / W0 are NULL */
+} fy_refine_params;
+typedef struct {
+    double ms_mappings;        /* HIP-event milliseconds: mappings, remapped CSR / CSC, launch tables */
+    double ms_iterations;      /* the multiplicative updates alone */
+    double ms_assign;          /* argmax, counts and the copy of the clustering to the host */
+    double ms_total;
+    int64_t launches;          /* kernel and rocPRIM launches of the whole call */
+    int64_t sum_users, sum_items, sum_k;   /* sum over the parents of n_c, m_c, k_c */
+    int64_t nnz;               /* kept ratings */
+    int64_t collisions;        /* users whose argmax >= stride (see above) */
+} fy_refine_stats;
+typedef struct fy_refined fy_refined;
+int fy_cluster_refine(fy_context*, const fy_refine_params*, const fy_ratings*, int64_t n_map, const int32_t* map_user,
+                      const int32_t* map_cluster, const double* H0, const double* W0, fy_refined** out);
+int64_t fy_refined_n_users(const fy_refined*);
+int64_t fy_refined_n_counts(const fy_refined*);
+int fy_refined_clustering(const fy_refined*, int32_t* user, int32_t* cluster, int32_t* count);   /* n_users, n_users, n_counts ints */
+int fy_refined_layout(const fy_refined*, int32_t* users_in_cluster, int32_t* items_in_cluster, int32_t* sub_clusters);   /* n_c, m_c, k_c */
+int64_t fy_refined_h_size(const fy_refined*);     /* sum n_c k_c */
+int64_t fy_refined_w_size(const fy_refined*);     /* sum m_c k_c */
+int fy_refined_factors(fy_refined*, double* H, double* W);   /* downloads the final factors (tests, diagnostics), layout of H0 / W0 */
+int fy_refined_stats(const fy_refined*, fy_refine_stats* out);
+void fy_refined_free(fy_refined*);
+
 /* ------------------------------------------------------------------ the Hadoop files on either side of the RM2 job
  * (csrc/fy_seqfile.cpp).  Hadoop 1.2.1 SequenceFile, version 6, uncompressed record format, as the
  * reference's jobs and fixture writers produce it (M/util/DataInitialization.java:155-222, M/rm/RM2HDFSReducer.java:44-50,
