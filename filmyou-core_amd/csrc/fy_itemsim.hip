@@ -6,7 +6,10 @@
 // restated here is Mahout's published one (see oracle/itemsim_oracle.c for the statement both sides implement):
 //   cosine        sim(i, j) = sum_u (r_ui / |r_.i|) (r_uj / |r_.j|)      (rows L2-normalised, then dot products)
 //   co-occurrence sim(i, j) = #users who rated both
-// over co-rated pairs only, j != i when excludeSelfSimilarity, sim >= threshold (no threshold: sim > 0), the
+// and the five other measures of Mahout 0.8's RowSimilarityJob (include/filmyou.h has the table): each is a dot product d of
+// per-item transformed columns, then a scalar function of (d, a_i, a_j, number of users) -- the isim_finish_* functions below,
+// fp64, shared by every kernel that turns an accumulator into a similarity.
+// Over co-rated pairs only, j != i when excludeSelfSimilarity, sim >= threshold (no threshold: sim > 0), the
 // maxSimilaritiesPerRow best per item (ties, unspecified in Mahout, by ascending item id).
 // Two builds:
 //  * symmetric (round 3; cosine on positive fp16-exact ratings, one rank, the benchmark sizes): the product is symmetric, so
@@ -36,47 +39,120 @@ static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
 // shuffles, the four waves' partials in order), and -- round 4 -- the column's rating sum and largest rating in the same pass (the
 // bounds of the fixed-point scale of the symmetric build; k_isim_gram_prep walked the columns a second time for them).  A wave per
 // item made both passes wait for the heaviest column: 81 k entries on one wave = 1 270 dependent trips, 0.6 ms each pass.
+// sumsq (optional): sum r^2 before the root (Euclidean distance).  PEARSON: a second walk of the column in the same fixed order
+// for the centred norm -- centre[p] = (sum |r|) / n, cnorm[p] = || r - centre ||_2 over the item's raters; no atomics anywhere,
+// two runs give the same bits.
+template <bool PEARSON>
 __global__ __launch_bounds__(256) void k_item_norms(int32_t nP, const int32_t* __restrict__ pair_start, const float* __restrict__ csc_r,
-                                                    double* __restrict__ norm, float* __restrict__ colsum, float* __restrict__ colmax) {
+                                                    double* __restrict__ norm, float* __restrict__ colsum, float* __restrict__ colmax,
+                                                    double* __restrict__ sumsq, double* __restrict__ centre, double* __restrict__ cnorm) {
     __shared__ double sh_s[4];
+    __shared__ double sh_a[4], sh_centre;
     __shared__ float sh_sum[4], sh_max[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int32_t p = blockIdx.x; p < nP; p += gridDim.x) {
-        double s = 0.0;
+        double s = 0.0, sa = 0.0;
         float sum = 0.0f, mx = 0.0f;
         for (int32_t q = pair_start[p] + threadIdx.x; q < pair_start[p + 1]; q += 256) {
             const float r = csc_r[q];
             s += (double)r * (double)r;
             sum += r;
             mx = fmaxf(mx, r);
+            if constexpr (PEARSON) sa += fabs((double)r);
         }
         for (int o = 32; o > 0; o >>= 1) {
             s += __shfl_down(s, o, 64);
             sum += __shfl_down(sum, o, 64);
             mx = fmaxf(mx, __shfl_down(mx, o, 64));
+            if constexpr (PEARSON) sa += __shfl_down(sa, o, 64);
         }
-        if (lane == 0) { sh_s[wave] = s; sh_sum[wave] = sum; sh_max[wave] = mx; }
+        if (lane == 0) { sh_s[wave] = s; sh_sum[wave] = sum; sh_max[wave] = mx; if constexpr (PEARSON) sh_a[wave] = sa; }
         __syncthreads();
         if (threadIdx.x == 0) {
-            norm[p] = sqrt(((sh_s[0] + sh_s[1]) + sh_s[2]) + sh_s[3]);
+            const double ss = ((sh_s[0] + sh_s[1]) + sh_s[2]) + sh_s[3];
+            norm[p] = sqrt(ss);
+            if (sumsq) sumsq[p] = ss;
             if (colsum) colsum[p] = ((sh_sum[0] + sh_sum[1]) + sh_sum[2]) + sh_sum[3];
             if (colmax) colmax[p] = fmaxf(fmaxf(sh_max[0], sh_max[1]), fmaxf(sh_max[2], sh_max[3]));
+            if constexpr (PEARSON) sh_centre = (((sh_a[0] + sh_a[1]) + sh_a[2]) + sh_a[3]) / (double)(pair_start[p + 1] - pair_start[p]);
         }
         __syncthreads();
+        if constexpr (PEARSON) {
+            const double c = sh_centre;
+            double s2 = 0.0;
+            for (int32_t q = pair_start[p] + threadIdx.x; q < pair_start[p + 1]; q += 256) {
+                const double x = (double)csc_r[q] - c;
+                s2 += x * x;
+            }
+            for (int o = 32; o > 0; o >>= 1) s2 += __shfl_down(s2, o, 64);
+            __syncthreads();      // everybody has read sh_centre; sh_s is free again
+            if (lane == 0) sh_s[wave] = s2;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                centre[p] = c;
+                cnorm[p] = sqrt(((sh_s[0] + sh_s[1]) + sh_s[2]) + sh_s[3]);
+            }
+            __syncthreads();
+        }
     }
 }
 
+// ---- the measures (include/filmyou.h): weight of a preference, and similarity from the dot product d of two weighted columns
+// cosine and Euclidean distance multiply the ratings themselves, the count measures ones
+__host__ __device__ inline bool isim_weight_is_rating(int measure) { return measure == FY_SIMILARITY_COSINE || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE; }
+// weight where nothing is applied in the epilogue.  norm: cosine ||r_.i||, Pearson ||c_.i||; centre: Pearson (sum |r|) / n (else unused)
+__device__ __forceinline__ float isim_weight(int measure, float r, double norm, double centre) {
+    switch (measure) {
+        case FY_SIMILARITY_COSINE: return (float)((double)r / norm);
+        case FY_SIMILARITY_EUCLIDEAN_DISTANCE: return r;
+        case FY_SIMILARITY_PEARSON_CORRELATION: return (float)(((double)r - centre) / norm);       // 0 / 0 = NaN for a constant item: its pairs drop out
+        default: return 1.0f;
+    }
+}
 __global__ void k_csc_weights(int64_t nnz, const int32_t* __restrict__ csc_pair, const float* __restrict__ csc_r,
-                              const double* __restrict__ norm, int cosine, float* __restrict__ csc_w) {
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x)
-        csc_w[q] = cosine ? (float)((double)csc_r[q] / norm[csc_pair[q]]) : 1.0f;
+                              const double* __restrict__ norm, const double* __restrict__ centre, int measure, float* __restrict__ csc_w) {
+    const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t p = csc_pair[q];
+        csc_w[q] = isim_weight(measure, csc_r[q], norm[p], pearson ? centre[p] : 0.0);
+    }
 }
 
 __global__ void k_csr_weights(int64_t nnz, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r,
-                              const int32_t* __restrict__ rank_pair, const double* __restrict__ norm, int cosine,
+                              const int32_t* __restrict__ rank_pair, const double* __restrict__ norm, const double* __restrict__ centre, int measure,
                               float* __restrict__ csr_w) {
-    for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < nnz; f += (int64_t)gridDim.x * blockDim.x)
-        csr_w[f] = cosine ? (float)((double)csr_r[f] / norm[rank_pair[csr_idx[f]]]) : 1.0f;
+    const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < nnz; f += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t p = rank_pair[csr_idx[f]];
+        csr_w[f] = isim_weight(measure, csr_r[f], norm[p], pearson ? centre[p] : 0.0);
+    }
+}
+
+// One function per measure, fp64; the emitted similarity is the (float) of it.  d = the accumulated dot product, a_i / a_j = the
+// two items' norms of the table (the count measures: number of raters; Euclidean: sum r^2), N = number of users.
+__device__ __forceinline__ double isim_finish_product(double d, double inv_i, double inv_j) { return d * inv_i * inv_j; }   // cosine on raw ratings: inv = 1 / ||r||
+__device__ __forceinline__ double isim_finish_tanimoto(double d, double ai, double aj) { return d / (ai + aj - d); }
+__device__ __forceinline__ double isim_finish_city_block(double d, double ai, double aj) { return 1.0 / (1.0 + ai + aj - 2.0 * d); }
+__device__ __forceinline__ double isim_finish_euclidean(double d, double ai, double aj) { return 1.0 / (1.0 + sqrt(fmax(0.0, ai - 2.0 * d + aj))); }
+__device__ __forceinline__ double isim_xlogx(double x) { return x == 0.0 ? 0.0 : x * log(x); }
+// Mahout's LogLikelihood.logLikelihoodRatio on unnormalised entropies H(x...) = xlogx(sum x) - sum xlogx(x)
+__device__ __forceinline__ double isim_finish_loglikelihood(double d, double ai, double aj, double N) {
+    const double k11 = d, k12 = aj - d, k21 = ai - d, k22 = N - ai - aj + d;
+    const double row_e = isim_xlogx(k11 + k12 + k21 + k22) - isim_xlogx(k11 + k12) - isim_xlogx(k21 + k22);
+    const double col_e = isim_xlogx(k11 + k12 + k21 + k22) - isim_xlogx(k11 + k21) - isim_xlogx(k12 + k22);
+    const double mat_e = isim_xlogx(k11 + k12 + k21 + k22) - isim_xlogx(k11) - isim_xlogx(k12) - isim_xlogx(k21) - isim_xlogx(k22);
+    const double llr = row_e + col_e < mat_e ? 0.0 : 2.0 * (row_e + col_e - mat_e);
+    return 1.0 - 1.0 / (1.0 + llr);
+}
+template <int M>
+__device__ __forceinline__ double isim_finish(double d, double ai, double aj, double N) {
+    if constexpr (M == FY_SIMILARITY_TANIMOTO_COEFFICIENT) return isim_finish_tanimoto(d, ai, aj);
+    else if constexpr (M == FY_SIMILARITY_LOGLIKELIHOOD) return isim_finish_loglikelihood(d, ai, aj, N);
+    else if constexpr (M == FY_SIMILARITY_CITY_BLOCK) return isim_finish_city_block(d, ai, aj);
+    else {
+        static_assert(M == FY_SIMILARITY_EUCLIDEAN_DISTANCE, "cosine, co-occurrence and Pearson: the dot product is the similarity");
+        return isim_finish_euclidean(d, ai, aj);
+    }
 }
 
 __device__ __forceinline__ uint32_t isim_order_key(float f) {
@@ -106,6 +182,9 @@ struct ISimEpilogue {
     // packed row kernel: the accumulators hold sum_v r_vi r_vj (exact in fp64 for fp16-exact ratings); cosine = that times
     // inv_norm[i] inv_norm[j] (rank order).  nullptr: the weights were divided by the norms beforehand.
     const double* __restrict__ inv_norm;
+    // the measures with a finishing function (Tanimoto, log-likelihood, city block, Euclidean distance): a_i in rank order, and N
+    const double* __restrict__ aux;
+    double n_cols;
     // per (row, chunk) item: its top K as (order key << 32 | ~raw item id), descending
     int32_t* __restrict__ part_cnt;    // [rows_mine * nch]
     uint64_t* __restrict__ part;       // [rows_mine * nch * K]
@@ -204,7 +283,16 @@ __device__ __forceinline__ void isim_cut(uint64_t* cand, int K, int cap, uint32_
 // Only the heaviest rows are split by chunk (one workgroup per whole row left the heaviest row -- 10^5 raters, 5e7 slice
 // entries -- on a single CU for half of the kernel's run time); a light row is one item and carries its threshold from chunk
 // to chunk (splitting every row cost more in top-K work than it gained: 52 ms against 30).  The pass that streams a finished chunk through the top-K re-zeroes the accumulators it reads.
-template <bool PK>
+// similarity of (row, col) from the accumulator a.  M = FY_SIMILARITY_COSINE stands for the three measures whose dot product IS the
+// similarity (cosine, co-occurrence, Pearson: the norms are in the weights, or -- packed cosine -- in inv_norm); the others finish
+// through isim_finish<M>.  For those an untouched accumulator is not similarity 0, so a pair nobody co-rated (a == 0; exact: the
+// weights are positive) reads as NaN, which passes no comparison.
+template <int M>
+__device__ __forceinline__ float isim_row_value(const ISimEpilogue& E, double a, double row_term, int col) {
+    if constexpr (M == FY_SIMILARITY_COSINE) return E.inv_norm ? (float)isim_finish_product(a, row_term, E.inv_norm[col]) : (float)a;
+    else return a != 0.0 ? (float)isim_finish<M>(a, row_term, E.aux[col], E.n_cols) : __builtin_nanf("");
+}
+template <bool PK, int M>
 __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ next_row) {
     double* acc = fy_cooc_acc;
     uint64_t* cand = reinterpret_cast<uint64_t*>(fy_cooc_acc + A.CH);
@@ -227,7 +315,7 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
         const int ch_begin = split ? item - mine * A.nch : 0, ch_end = split ? ch_begin + 1 : A.nch;
         const int slot = mine * A.nch + ch_begin;     // where this item's list goes
         const int row = A.row0 + mine * stride;
-        const double scale_row = E.inv_norm ? E.inv_norm[row] : 1.0;
+        const double scale_row = M != FY_SIMILARITY_COSINE ? E.aux[row] : E.inv_norm ? E.inv_norm[row] : 1.0;
         for (int ch = ch_begin; ch < ch_end; ch++) {
             cooc_accumulate_row<PK>(A, row, ch, mine);
             __syncthreads();
@@ -252,7 +340,7 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
                         const int t = (int)(((int64_t)(tid * (ISIM_SAMPLE / 64) + x) * ncol) / ISIM_SAMPLE);
                         const int col = c0 + t;
                         const double a = acc[t];
-                        const float sv = E.inv_norm ? (float)(a * scale_row * E.inv_norm[col]) : (float)a;
+                        const float sv = isim_row_value<M>(E, a, scale_row, col);
                         bool ok = E.has_threshold ? (sv >= E.threshold) : (sv > 0.0f);
                         if (E.exclude_self && col == row) ok = false;
                         k4[x] = ok ? isim_order_key(sv) : 0u;
@@ -283,7 +371,7 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
                     for (int t = tid; t < ncol; t += blockDim.x) {
                         const int col = c0 + t;
                         const double a = acc[t];
-                        const float sv = E.inv_norm ? (float)(a * scale_row * E.inv_norm[col]) : (float)a;
+                        const float sv = isim_row_value<M>(E, a, scale_row, col);
                         bool ok = E.has_threshold ? (sv >= E.threshold) : (sv > 0.0f);
                         if (E.exclude_self && col == row) ok = false;
                         mine_cnt += ok && isim_order_key(sv) >= guess;
@@ -304,7 +392,7 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
                     if (t < ncol) {
                         const double a = acc[t];
                         const int col = c0 + t;
-                        const float s = E.inv_norm ? (float)(a * scale_row * E.inv_norm[col]) : (float)a;
+                        const float s = isim_row_value<M>(E, a, scale_row, col);
                         bool ok = E.has_threshold ? (s >= E.threshold) : (s > 0.0f);
                         if (E.exclude_self && col == row) ok = false;
                         const uint32_t key = isim_order_key(s);
@@ -375,8 +463,10 @@ struct SweepArgs {
     const float* __restrict__ G;
     int64_t ldm;
     int32_t Ic, K;
-    const float* __restrict__ invn32;          // [ldm + slack] 1 / norm in rank order, fp32 (0 behind Ic): the prefilter
+    // cosine: 1 / norm in rank order; the finishing measures (Tanimoto, log-likelihood, city block, Euclidean distance): a_i
+    const float* __restrict__ invn32;          // [ldm + slack] fp32 (0 behind Ic): the prefilter
     const double* __restrict__ invn;           // [Ic]
+    double n_cols;                             // N (log-likelihood)
     const int32_t* __restrict__ rank_item_raw;
     uint32_t* __restrict__ tau_g;              // [Ic]: key a candidate of the row must reach
     int32_t* __restrict__ gcnt;                // [Ic]: candidates appended
@@ -392,13 +482,33 @@ struct SweepArgs {
     float* __restrict__ out_sim;
 };
 
+// The symmetric build per measure M (FY_SIMILARITY_COSINE: similarity = G x a per-row factor x a per-column factor, the code this
+// build was written for).  sweep_pre: the fp32 value the fast path compares with the row's threshold (with its margin).  Tanimoto
+// and city block are one or two roundings of exact integers (counts below 2^24), so the margin holds for them as it does for
+// cosine; log-likelihood (cancelling x ln x terms) and Euclidean distance (a_i - 2 d + a_j cancels) have no fp32 value with a
+// relative bound: every co-rated element passes the prefilter (+inf) and is decided in fp64 by sweep_value.  An element nobody
+// co-rated (G == 0) is never a candidate.
+template <int M>
+__device__ __forceinline__ float sweep_pre(float v, float a, float b) {
+    if constexpr (M == FY_SIMILARITY_COSINE) return v * a * b;
+    else if constexpr (M == FY_SIMILARITY_TANIMOTO_COEFFICIENT) return v != 0.0f ? v / (a + b - v) : 0.0f;
+    else if constexpr (M == FY_SIMILARITY_CITY_BLOCK) return v != 0.0f ? 1.0f / (1.0f + a + b - 2.0f * v) : 0.0f;
+    else return v != 0.0f ? __builtin_inff() : 0.0f;
+}
+template <int M>
+__device__ __forceinline__ float sweep_value(const SweepArgs& A, float v, int i, int col) {
+    if constexpr (M == FY_SIMILARITY_COSINE) return (float)isim_finish_product((double)v, A.invn[i], A.invn[col]);
+    else return v != 0.0f ? (float)isim_finish<M>((double)v, A.invn[i], A.invn[col], A.n_cols) : 0.0f;
+}
+
 // wave-level: lanes with `pass` hold a candidate (row i = band row rl, column col, raw Gram value v) that survived the fp32
 // prefilter; exact value, append, histogram, and -- every 8th candidate of a row once it has K -- a new threshold for the row
+template <int M>
 __device__ __forceinline__ void sweep_take(const SweepArgs& A, uint32_t* tau_l, bool pass, int rl, int i, int col, float v, int i0) {
     const int lane = threadIdx.x & 63;
     bool trig = false;
     if (pass) {
-        const float sf = (float)((double)v * A.invn[i] * A.invn[col]);
+        const float sf = sweep_value<M>(A, v, i, col);
         const uint32_t key = __float_as_uint(sf);
         if (sf > 0.0f && key >= tau_l[rl]) {
             int bk = (int)(key >> SWEEP_KEY_SHIFT) - SWEEP_KEY_BASE;
@@ -436,6 +546,7 @@ __device__ __forceinline__ void sweep_take(const SweepArgs& A, uint32_t* tau_l, 
     }
 }
 
+template <int M>
 __global__ __launch_bounds__(256) void k_isim_sweep(SweepArgs A) {
     extern __shared__ __attribute__((aligned(16))) float fy_sweep_lds[];      // [piece + 256]: 1 / norm of the piece's columns, then 64: of the band's rows
     __shared__ uint32_t tau_l[64];
@@ -478,7 +589,7 @@ __global__ __launch_bounds__(256) void k_isim_sweep(SweepArgs A) {
                 for (int u = 0; u < U; u++) {
                     const int jj = jb + 4 * (k0 + u);
                     const float nj = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(nj_vec), k0 + u));
-                    const float s = v[u] * nj * my_inv;
+                    const float s = sweep_pre<M>(v[u], nj, my_inv);
                     // (bitwise, not &&: short-circuit evaluation turned these into exec-masked branches around the loads)
                     pm |= ((uint32_t)valid & (uint32_t)(jj < jend) & (uint32_t)(jj < i) & (uint32_t)(s > 0.0f) & (uint32_t)(s >= tauf)) << u;
                 }
@@ -487,7 +598,7 @@ __global__ __launch_bounds__(256) void k_isim_sweep(SweepArgs A) {
                     float vu = v[0];
 #pragma unroll
                     for (int q = 1; q < U; q++) vu = u == q ? v[q] : vu;
-                    sweep_take(A, tau_l, pm != 0, lane, i, jb + 4 * (k0 + u), vu, i0);
+                    sweep_take<M>(A, tau_l, pm != 0, lane, i, jb + 4 * (k0 + u), vu, i0);
                     pm &= pm - 1;
                 }
             }
@@ -529,7 +640,7 @@ __global__ __launch_bounds__(256) void k_isim_sweep(SweepArgs A) {
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
                     const int col = col_of[u] + e;
-                    const float s = vv[4 * u + e] * ri * nn[e];
+                    const float s = sweep_pre<M>(vv[4 * u + e], ri, nn[e]);
                     pm |= ((uint32_t)(T0 + u < total) & (uint32_t)(col < c1) & (uint32_t)(col > i) & (uint32_t)(col < A.Ic) & (uint32_t)(s > 0.0f) & (uint32_t)(s >= tauf)) << (4 * u + e);
                 }
             }
@@ -541,7 +652,7 @@ __global__ __launch_bounds__(256) void k_isim_sweep(SweepArgs A) {
                 int rx = r_of[0], cx = col_of[0];
 #pragma unroll
                 for (int q = 1; q < U; q++) { rx = (x >> 2) == q ? r_of[q] : rx; cx = (x >> 2) == q ? col_of[q] : cx; }
-                sweep_take(A, tau_l, pm != 0, rx, i0 + rx, cx + (x & 3), vx, i0);
+                sweep_take<M>(A, tau_l, pm != 0, rx, i0 + rx, cx + (x & 3), vx, i0);
                 pm &= pm - 1;
             }
         }
@@ -555,10 +666,17 @@ __device__ __forceinline__ void isim_wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 // the diagonal candidate of row i (not part of the triangle): sum r^2 / norm^2; 0 = none
+template <int M>
 __device__ __forceinline__ uint64_t isim_self_candidate(const SweepArgs& A, int i) {
     if (A.exclude_self) return 0ull;
-    const double inv_i = A.invn[i], nrm = 1.0 / inv_i;
-    const float sf = (float)(nrm * nrm * inv_i * inv_i);
+    float sf;
+    if constexpr (M == FY_SIMILARITY_COSINE) {
+        const double inv_i = A.invn[i], nrm = 1.0 / inv_i;
+        sf = (float)(nrm * nrm * inv_i * inv_i);
+    } else {
+        const double a = A.invn[i];      // the item's dot product with itself is its own norm (number of raters; sum r^2)
+        sf = (float)isim_finish<M>(a, a, a, A.n_cols);
+    }
     const uint32_t key = __float_as_uint(sf);
     return (sf > 0.0f && key >= A.tau0) ? (((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - A.rank_item_raw[i])) : 0ull;
 }
@@ -570,6 +688,7 @@ __device__ __forceinline__ uint64_t isim_self_candidate(const SweepArgs& A, int 
 // input).  No workgroup barrier anywhere: 59 047 workgroups with ~40 barriers each were 2.0 ms, this is one pass of waves.
 // Rows whose list overflowed in the sweep are handed to k_isim_redo.
 constexpr int FIN_SURV = 512, FIN_SMALL = 128;
+template <int M>
 __global__ __launch_bounds__(256) void k_isim_finish(SweepArgs A, int32_t* __restrict__ redo_list, int32_t* __restrict__ n_redo) {
     __shared__ uint64_t surv_all[4][FIN_SURV];
     __shared__ uint32_t hist_all[4][256];
@@ -586,7 +705,7 @@ __global__ __launch_bounds__(256) void k_isim_finish(SweepArgs A, int32_t* __res
     uint32_t* scal = scal_all[w];
     const int n = min(A.gcnt[i], A.capg);
     const uint64_t* __restrict__ L = A.glist + (int64_t)i * A.capg;
-    const uint64_t c_self = isim_self_candidate(A, i);
+    const uint64_t c_self = isim_self_candidate<M>(A, i);
     const int m = n + (c_self ? 1 : 0);
     auto get = [&](int t) -> uint64_t { return t < n ? L[t] : c_self; };
     int cnt = 0;
@@ -672,6 +791,7 @@ __global__ __launch_bounds__(256) void k_isim_finish(SweepArgs A, int32_t* __res
 
 // rows whose candidate list overflowed (massive ties inside one bucket of the sweep's histogram): every column of the row, from
 // the matrix, through the running top-K of the row-at-a-time kernel (isim_cut: exact for any input)
+template <int M>
 __global__ __launch_bounds__(256) void k_isim_redo(SweepArgs A, const int32_t* __restrict__ redo_list, const int32_t* __restrict__ n_redo) {
     __shared__ uint64_t cand[ISIM_CAP];
     __shared__ uint32_t sh_cnt, sh_tau, sh_aux[2], hist[256];
@@ -679,7 +799,6 @@ __global__ __launch_bounds__(256) void k_isim_redo(SweepArgs A, const int32_t* _
     const int n_rows = *n_redo;
     for (int x = blockIdx.x; x < n_rows; x += gridDim.x) {      // block-uniform
         const int i = redo_list[x];
-        const double inv_i = A.invn[i];
         if (tid == 0) { sh_cnt = 0; sh_tau = A.tau0; }
         __syncthreads();
         for (int base = 0; base < A.Ic; base += 256) {
@@ -688,7 +807,7 @@ __global__ __launch_bounds__(256) void k_isim_redo(SweepArgs A, const int32_t* _
             uint64_t c = 0;
             if (col < A.Ic && col != i) {
                 const float v = col > i ? A.G[(int64_t)i * A.ldm + col] : A.G[(int64_t)col * A.ldm + i];
-                const float sf = (float)((double)v * inv_i * A.invn[col]);
+                const float sf = sweep_value<M>(A, v, i, col);
                 const uint32_t key = __float_as_uint(sf);
                 want = sf > 0.0f && key >= sh_tau;
                 c = ((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - A.rank_item_raw[col]);
@@ -704,7 +823,7 @@ __global__ __launch_bounds__(256) void k_isim_redo(SweepArgs A, const int32_t* _
             __syncthreads();
             if (sh_cnt + 256 + 1 > (uint32_t)ISIM_CAP) isim_cut(cand, A.K, ISIM_CAP, hist, &sh_cnt, &sh_tau, sh_aux);   // block-uniform (+ 1: the diagonal)
         }
-        const uint64_t c_self = isim_self_candidate(A, i);
+        const uint64_t c_self = isim_self_candidate<M>(A, i);
         if (c_self && tid == 0) cand[sh_cnt++] = c_self;
         __syncthreads();
         isim_select(cand, (int)sh_cnt, A.K, hist, &sh_cnt, &sh_tau, sh_aux);
@@ -753,19 +872,57 @@ __global__ void k_isim_gram_prep(int32_t Ic, int64_t ld_pad, const int32_t* __re
         if (__float_as_uint(bm) > bounds[1]) atomicMax(&bounds[1], __float_as_uint(bm));
     }
 }
+// the same for the finishing measures: a_i (rank order, fp64: k_isim_rank_norms) as fp32 for the prefilter, and the bounds of the
+// fixed-point scale -- the count measures multiply ones (largest column sum = largest n_i, largest value 1), Euclidean distance
+// the ratings (cosine's bounds)
+__global__ void k_isim_gram_prep_aux(int32_t Ic, int64_t ld_pad, const int32_t* __restrict__ rank_pair, const float* __restrict__ colsum,
+                                     const float* __restrict__ colmax, const double* __restrict__ aux, int counts, float* __restrict__ a32,
+                                     uint32_t* __restrict__ bounds) {
+    float bs = 0.0f, bm = 0.0f;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < ld_pad; r += (int64_t)gridDim.x * blockDim.x) {
+        if (r >= Ic) { a32[r] = 0.0f; continue; }
+        a32[r] = (float)aux[r];
+        const int32_t pr = rank_pair[r];
+        bs = fmaxf(bs, (counts ? (float)aux[r] : colsum[pr]) * 1.0001f);
+        bm = fmaxf(bm, counts ? 1.0f : colmax[pr]);
+    }
+    for (int o = 32; o > 0; o >>= 1) { bs = fmaxf(bs, __shfl_down(bs, o, 64)); bm = fmaxf(bm, __shfl_down(bm, o, 64)); }
+    if ((threadIdx.x & 63) == 0) {
+        if (__float_as_uint(bs) > bounds[0]) atomicMax(&bounds[0], __float_as_uint(bs));
+        if (__float_as_uint(bm) > bounds[1]) atomicMax(&bounds[1], __float_as_uint(bm));
+    }
+}
 __global__ void k_fill_u32(int64_t n, uint32_t v, uint32_t* __restrict__ out) {
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) out[t] = v;
 }
 
 // the symmetric build; false = not applicable here (the caller runs the row-at-a-time build).  cnt / other / sim as the other build leaves them.
+template <int M>
+static void launch_isim_sweep(Context* ctx, const SweepArgs& SA, int npieces, int32_t* redo_list, int32_t* n_redo) {
+    hipStream_t st = ctx->stream;
+    k_isim_sweep<M><<<SA.nbands * npieces, 256, (size_t)(SA.piece + 256 + 64) * sizeof(float), st>>>(SA);
+    FY_KERNEL_CHECK();
+    k_isim_finish<M><<<(int)ceil_div(SA.Ic, 4), 256, 0, st>>>(SA, redo_list, n_redo);
+    FY_KERNEL_CHECK();
+    k_isim_redo<M><<<ctx->num_cus * 2, 256, 0, st>>>(SA, redo_list, n_redo);
+    FY_KERNEL_CHECK();
+}
+// aux: a_i of the finishing measures in rank order (nullptr for cosine)
 static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const Prepared& P, const double* norm, const float* colsum, const float* colmax,
-                              int32_t* cnt, int32_t* other, float* sim, double* ms_cooc, fy_stats* st_out) {
+                              const double* aux, int32_t* cnt, int32_t* other, float* sim, double* ms_cooc, fy_stats* st_out) {
     const Tuning& tune = ctx->tune;
     const int32_t Ic = P.nP, K = prm->max_similarities_per_item;
-    if (tune.isim_gram == 0 || prm->world != 1 || prm->similarity != FY_SIMILARITY_COSINE || !tune.cooc_pk || !P.ratings_fp16_exact ||
-        !P.ratings_positive || K > FIN_SURV / 2 || (prm->has_threshold && !(prm->threshold > 0.0)))
+    const int measure = prm->similarity;
+    const bool cosine = measure == FY_SIMILARITY_COSINE;
+    // the count measures multiply ones: the fixed-point sums are exact integers whatever the ratings are
+    const bool counts = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD || measure == FY_SIMILARITY_CITY_BLOCK;
+    if (!cosine && !counts && measure != FY_SIMILARITY_EUCLIDEAN_DISTANCE) return false;      // co-occurrence, Pearson: row at a time
+    if (tune.isim_gram == 0 || prm->world != 1 || !tune.cooc_pk || (!counts && (!P.ratings_fp16_exact || !P.ratings_positive)) ||
+        K > FIN_SURV / 2 || (prm->has_threshold && !(prm->threshold > 0.0)))
         return false;
-    if (tune.isim_gram < 0 && Ic < tune.isim_gram_min_items) return false;
+    // cosine takes this build from isim_gram_min_items items on.  The other measures take it only when it is forced
+    // (FY_ISIM_GRAM=1): their sweep has not been shown faster than their row-at-a-time build.
+    if (tune.isim_gram < 0 && (!cosine || Ic < tune.isim_gram_min_items)) return false;
     const int64_t ldm = round_up(Ic, 256), slack = 1024;
     if ((uint64_t)Ic * (uint64_t)ldm * 4 > ctx->total_mem / 3) return false;     // the fp32 matrix must fit comfortably
     hipStream_t st = ctx->stream;
@@ -773,7 +930,10 @@ static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const 
     DevBuf<float> invn32(ctx, (size_t)(ldm + slack));
     DevBuf<uint32_t> d_bounds(ctx, 2);
     d_bounds.zero();
-    k_isim_gram_prep<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), colsum, colmax, norm, invn.get(), invn32.get(), d_bounds.get());
+    if (cosine)
+        k_isim_gram_prep<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), colsum, colmax, norm, invn.get(), invn32.get(), d_bounds.get());
+    else
+        k_isim_gram_prep_aux<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), colsum, colmax, aux, counts ? 1 : 0, invn32.get(), d_bounds.get());
     FY_KERNEL_CHECK();
     uint32_t hb[2];
     d2h(ctx, hb, d_bounds.get(), 2);
@@ -786,7 +946,12 @@ static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const 
     EventTimer t_all(ctx);
     const size_t sp = t_all.begin();
     double ms_tables = 0.0;
-    if (!gram_half_build(ctx, P, P.csc_r.get(), bounds3, G.get(), ldm, &ms_tables, nullptr)) return false;
+    DevBuf<float> ones(ctx, counts ? (size_t)P.nnz : 1);
+    if (counts) {
+        k_fill_u32<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, 0x3F800000u /* 1.0f */, reinterpret_cast<uint32_t*>(ones.get()));
+        FY_KERNEL_CHECK();
+    }
+    if (!gram_half_build(ctx, P, counts ? ones.get() : P.csc_r.get(), bounds3, G.get(), ldm, &ms_tables, nullptr, counts ? ones.get() : nullptr)) return false;
     const int capg = tune.isim_capg;
     DevBuf<uint32_t> tau_g(ctx, (size_t)Ic);
     DevBuf<int32_t> gcnt(ctx, (size_t)Ic), overflow(ctx, (size_t)Ic);
@@ -803,17 +968,18 @@ static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const 
     FY_KERNEL_CHECK();
     DevBuf<uint32_t> hist_g(ctx, (size_t)round_up(Ic, 64) * 64);
     hist_g.zero();
-    SweepArgs SA{G.get(), ldm, Ic, K, invn32.get(), invn.get(), P.rank_item_raw.get(), tau_g.get(), gcnt.get(), glist.get(), capg, overflow.get(),
+    SweepArgs SA{G.get(), ldm, Ic, K, invn32.get(), cosine ? invn.get() : aux, (double)P.nU, P.rank_item_raw.get(), tau_g.get(), gcnt.get(), glist.get(), capg, overflow.get(),
                  hist_g.get(), (int32_t)ceil_div(Ic, 64), tune.isim_piece, tau0, prm->exclude_self, cnt, other, sim};
     const int npieces = (int)ceil_div(Ic, SA.piece);
-    k_isim_sweep<<<SA.nbands * npieces, 256, (size_t)(SA.piece + 256 + 64) * sizeof(float), st>>>(SA);
-    FY_KERNEL_CHECK();
     DevBuf<int32_t> redo_list(ctx, (size_t)Ic), n_redo(ctx, 1);
     n_redo.zero();
-    k_isim_finish<<<(int)ceil_div(Ic, 4), 256, 0, st>>>(SA, redo_list.get(), n_redo.get());
-    FY_KERNEL_CHECK();
-    k_isim_redo<<<ctx->num_cus * 2, 256, 0, st>>>(SA, redo_list.get(), n_redo.get());
-    FY_KERNEL_CHECK();
+    switch (measure) {
+        case FY_SIMILARITY_TANIMOTO_COEFFICIENT: launch_isim_sweep<FY_SIMILARITY_TANIMOTO_COEFFICIENT>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
+        case FY_SIMILARITY_LOGLIKELIHOOD: launch_isim_sweep<FY_SIMILARITY_LOGLIKELIHOOD>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
+        case FY_SIMILARITY_CITY_BLOCK: launch_isim_sweep<FY_SIMILARITY_CITY_BLOCK>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
+        case FY_SIMILARITY_EUCLIDEAN_DISTANCE: launch_isim_sweep<FY_SIMILARITY_EUCLIDEAN_DISTANCE>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
+        default: launch_isim_sweep<FY_SIMILARITY_COSINE>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
+    }
     t_all.end(sp);
     DevBuf<unsigned long long> d_cands(ctx, 1);
     d_cands.zero();
@@ -832,17 +998,39 @@ static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const 
 }
 
 // packed CSR (fy_cooc.hpp): column index relative to its chunk | the raw rating (or 1 for the co-occurrence count) as fp16
-__global__ void k_isim_pack_csr(int64_t nnz, int32_t CH, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r, int cosine,
+__global__ void k_isim_pack_csr(int64_t nnz, int32_t CH, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r, int measure,
                                 uint32_t* __restrict__ pk) {
+    const bool rating = isim_weight_is_rating(measure);
     for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < nnz; f += (int64_t)gridDim.x * blockDim.x)
-        pk[f] = (uint32_t)(csr_idx[f] % CH) | ((uint32_t)__half_as_ushort(__float2half(cosine ? csr_r[f] : 1.0f)) << 16);
+        pk[f] = (uint32_t)(csr_idx[f] % CH) | ((uint32_t)__half_as_ushort(__float2half(rating ? csr_r[f] : 1.0f)) << 16);
 }
-__global__ void k_isim_raw_weights(int64_t nnz, const float* __restrict__ csc_r, int cosine, float* __restrict__ csc_w) {
+__global__ void k_isim_raw_weights(int64_t nnz, const float* __restrict__ csc_r, int measure, float* __restrict__ csc_w) {
+    const bool rating = isim_weight_is_rating(measure);
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x)
-        csc_w[q] = cosine ? csc_r[q] : 1.0f;
+        csc_w[q] = rating ? csc_r[q] : 1.0f;
 }
 __global__ void k_isim_inv_norms(int32_t Ic, const int32_t* __restrict__ rank_pair, const double* __restrict__ norm, double* __restrict__ inv) {
     for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < Ic; r += gridDim.x * blockDim.x) inv[r] = 1.0 / norm[rank_pair[r]];
+}
+
+// a_i of the finishing measures in rank order: sum r^2 (Euclidean distance) or the number of raters (the count measures)
+__global__ void k_isim_rank_norms(int32_t Ic, const int32_t* __restrict__ rank_pair, const int32_t* __restrict__ pair_start,
+                                  const double* __restrict__ sumsq, double* __restrict__ aux) {
+    for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < Ic; r += gridDim.x * blockDim.x) {
+        const int32_t pr = rank_pair[r];
+        aux[r] = sumsq ? sumsq[pr] : (double)(pair_start[pr + 1] - pair_start[pr]);
+    }
+}
+template <int M>
+static void launch_cooc_itemsim(bool pk, int grid, int block, size_t lds, hipStream_t st, const CoocArgs& CA, const ISimEpilogue& IE, int* next_row) {
+    if (pk) {
+        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_itemsim<true, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_cooc_itemsim<true, M><<<grid, block, lds, st>>>(CA, IE, next_row);
+    } else {
+        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_itemsim<false, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_cooc_itemsim<false, M><<<grid, block, lds, st>>>(CA, IE, next_row);
+    }
+    FY_KERNEL_CHECK();
 }
 
 __global__ void k_isim_count_heavy(int32_t rows_mine, int32_t rank, int32_t world, const int32_t* __restrict__ rank_pair,
@@ -980,8 +1168,12 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
     if (prm->min_prefs_per_user < 0 || prm->max_prefs_per_user < 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "minPrefsPerUser / maxPrefsPerUser must be >= 0");
     const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
     const fy_ratings* R = filtered ? filtered.get() : R_in;
-    if (prm->similarity != FY_SIMILARITY_COSINE && prm->similarity != FY_SIMILARITY_COOCCURRENCE)
-        FY_FAIL(FY_ERR_INVALID_ARGUMENT, "similarity must be FY_SIMILARITY_COSINE or FY_SIMILARITY_COOCCURRENCE");
+    if (prm->similarity < FY_SIMILARITY_COSINE || prm->similarity > FY_SIMILARITY_PEARSON_CORRELATION)
+        FY_FAIL(FY_ERR_INVALID_ARGUMENT, "similarity must be one of the FY_SIMILARITY_* constants (0 .. %d)", (int)FY_SIMILARITY_PEARSON_CORRELATION);
+    const int measure = prm->similarity;
+    if (measure == FY_SIMILARITY_PEARSON_CORRELATION && prm->has_threshold && !(prm->threshold > 0.0))
+        FY_FAIL(FY_ERR_UNSUPPORTED, "SIMILARITY_PEARSON_CORRELATION with a threshold <= 0: a co-rated pair whose centred products cancel to 0 "
+                                    "cannot be told from a pair nobody co-rated");
     if (prm->max_similarities_per_item <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "maxSimilaritiesPerRow must be > 0");
     if (prm->max_similarities_per_item > ISIM_MAX_K)
         FY_FAIL(FY_ERR_UNSUPPORTED, "maxSimilaritiesPerRow %d exceeds the kernel limit %d", prm->max_similarities_per_item, ISIM_MAX_K);
@@ -1004,35 +1196,57 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
         sync(ctx);
         return Rs.release();
     }
+    if (measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE && !P.ratings_positive)
+        FY_FAIL(FY_ERR_UNSUPPORTED, "SIMILARITY_EUCLIDEAN_DISTANCE on data with a non-positive preference: a co-rated pair whose products sum to 0 "
+                                    "cannot be told from a pair nobody co-rated");
     const int32_t Ic = P.nP;   // single "cluster": every item is a pair
-    const int cosine = prm->similarity == FY_SIMILARITY_COSINE;
-    // packed row kernel (4-byte CSR entries, norms applied in the epilogue) when every rating is fp16-exact
+    const int cosine = measure == FY_SIMILARITY_COSINE;
+    const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    // the measures that finish (dot, a_i, a_j, N) in the epilogue; for the others the dot product is the similarity
+    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
+                          measure == FY_SIMILARITY_CITY_BLOCK || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
+    // packed row kernel (4-byte CSR entries, norms applied in the epilogue) when every rating is fp16-exact; Pearson's centred
+    // weights are not: it always takes the 8-byte-entry walk
     const Tuning& tune = ctx->tune;
-    const bool use_pk = P.ratings_fp16_exact && tune.cooc_pk;
+    const bool use_pk = P.ratings_fp16_exact && tune.cooc_pk && !pearson;
     DevBuf<double> norm(ctx, Ic), inv_norm(ctx, Ic);
     DevBuf<float> colsum(ctx, Ic), colmax(ctx, Ic);
-    k_item_norms<<<std::min<int>(Ic, ctx->num_cus * 32), 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), colsum.get(), colmax.get());
+    DevBuf<double> sumsq(ctx, measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE ? Ic : 1), centre(ctx, pearson ? Ic : 1), cnorm(ctx, pearson ? Ic : 1);
+    DevBuf<double> aux(ctx, finishes ? Ic : 1);
+    const int norm_grid = std::min<int>(Ic, ctx->num_cus * 32);
+    if (pearson)
+        k_item_norms<true><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), colsum.get(), colmax.get(), nullptr, centre.get(), cnorm.get());
+    else
+        k_item_norms<false><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), colsum.get(), colmax.get(),
+                                                       measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE ? sumsq.get() : nullptr, nullptr, nullptr);
     FY_KERNEL_CHECK();
+    if (finishes) {
+        k_isim_rank_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE ? sumsq.get() : nullptr, aux.get());
+        FY_KERNEL_CHECK();
+    }
+    const double* wnorm = pearson ? cnorm.get() : norm.get();      // the norm the pre-divided weights use
     const int K = prm->max_similarities_per_item;
     const int32_t rows_mine = (Ic - prm->rank + prm->world - 1) / prm->world;
     DevBuf<int32_t> cnt(ctx, (size_t)rows_mine + 1), off(ctx, (size_t)rows_mine + 1), other(ctx, (size_t)rows_mine * K);
     DevBuf<float> sim(ctx, (size_t)rows_mine * K);
     cnt.zero();
     double ms_sym = 0.0;
-    const bool symmetric = itemsim_symmetric(ctx, prm, P, norm.get(), colsum.get(), colmax.get(), cnt.get(), other.get(), sim.get(), &ms_sym, &Rs->st);
+    const bool symmetric = itemsim_symmetric(ctx, prm, P, norm.get(), colsum.get(), colmax.get(), finishes ? aux.get() : nullptr, cnt.get(), other.get(), sim.get(), &ms_sym, &Rs->st);
     if (symmetric) Rs->st.cooc_launches = 1;
     DevBuf<float> csc_w(ctx, symmetric ? 1 : (size_t)P.nnz), csr_w(ctx, (use_pk || symmetric) ? 1 : (size_t)P.nnz);
     DevBuf<uint32_t> csr_pk(ctx, (use_pk && !symmetric) ? (size_t)P.nnz : 1);
     if (symmetric) {
     } else if (use_pk) {
-        k_isim_raw_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_r.get(), cosine, csc_w.get());
+        k_isim_raw_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_r.get(), measure, csc_w.get());
         FY_KERNEL_CHECK();
-        k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), norm.get(), inv_norm.get());
-        FY_KERNEL_CHECK();
+        if (cosine) {
+            k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), norm.get(), inv_norm.get());
+            FY_KERNEL_CHECK();
+        }
     } else {
-        k_csc_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.csc_r.get(), norm.get(), cosine, csc_w.get());
+        k_csc_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.csc_r.get(), wnorm, centre.get(), measure, csc_w.get());
         FY_KERNEL_CHECK();
-        k_csr_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csr_idx.get(), P.csr_r.get(), P.rank_pair.get(), norm.get(), cosine, csr_w.get());
+        k_csr_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csr_idx.get(), P.csr_r.get(), P.rank_pair.get(), wnorm, centre.get(), measure, csr_w.get());
         FY_KERNEL_CHECK();
     }
 
@@ -1049,7 +1263,7 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
         SegTable segs;
         build_segments(ctx, P.csc_slot.get(), csc_w.get(), chunk_off.get(), 0, 0, (int32_t)P.nnz, nch, segs);
         if (use_pk) {
-            k_isim_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), cosine, csr_pk.get());
+            k_isim_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), measure, csr_pk.get());
             FY_KERNEL_CHECK();
         }
         CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), segs.ptr.get(), segs.seg.get(), segs.w.get(), P.csr_idx.get(),
@@ -1072,19 +1286,21 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
         CA.item_seg = item_seg.get();
         ISimEpilogue IE{P.rank_item_raw.get(), K, prm->exclude_self, prm->has_threshold, (float)prm->threshold, prm->rank,
                         prm->world, cnt.get(), other.get(), sim.get(), (use_pk && cosine) ? inv_norm.get() : nullptr,
-                        part_cnt.get(), part.get(), heavy_rows, (int32_t)n_items, cap};
+                        finishes ? aux.get() : nullptr, (double)P.nU, part_cnt.get(), part.get(), heavy_rows, (int32_t)n_items, cap};
         const size_t lds = (size_t)CH * 8 + (size_t)cap * 8;
-        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_itemsim<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_itemsim<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const int block = lds > 48 * 1024 ? 1024 : 256;
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / block, (160 * 1024) / (lds + 1024)));
         const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->num_cus * per_cu);
         DevBuf<int32_t> next_row(ctx, 1);
         next_row.zero();
         const size_t sp = t_cooc.begin();
-        if (use_pk) k_cooc_itemsim<true><<<grid, block, lds, st>>>(CA, IE, next_row.get());
-        else k_cooc_itemsim<false><<<grid, block, lds, st>>>(CA, IE, next_row.get());
-        FY_KERNEL_CHECK();
+        switch (measure) {
+            case FY_SIMILARITY_TANIMOTO_COEFFICIENT: launch_cooc_itemsim<FY_SIMILARITY_TANIMOTO_COEFFICIENT>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
+            case FY_SIMILARITY_LOGLIKELIHOOD: launch_cooc_itemsim<FY_SIMILARITY_LOGLIKELIHOOD>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
+            case FY_SIMILARITY_CITY_BLOCK: launch_cooc_itemsim<FY_SIMILARITY_CITY_BLOCK>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
+            case FY_SIMILARITY_EUCLIDEAN_DISTANCE: launch_cooc_itemsim<FY_SIMILARITY_EUCLIDEAN_DISTANCE>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
+            default: launch_cooc_itemsim<FY_SIMILARITY_COSINE>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;   // cosine, co-occurrence, Pearson
+        }
         k_isim_merge<<<std::min(rows_mine, ctx->num_cus * 8), 256, 0, st>>>(rows_mine, nch, K, part_cnt.get(), part.get(), cnt.get(), other.get(),
                                                                             sim.get());
         FY_KERNEL_CHECK();

@@ -1495,20 +1495,22 @@ static void launch_cooc_rm2(Context* ctx, const ScoreTune& tune, bool use_pk, co
 // apart; nothing in front of a row's diagonal 256-column block is written.  The same symmetric walk, segment table, item
 // list and fixed-point accumulators as the RM2 matrix build -- only the epilogue's scale differs (no (1 - lambda)^2).
 // `csc_w` = the weight of every CSC entry (the row side of a product), the column side is the raw rating of the packed
-// CSR; bounds3 = {largest column sum of the weights, largest weight, largest rating} (fx_exponent).  Returns false when the
+// CSR, or 1 for every entry when `csr_ones` (an array of nnz ones) is given; bounds3 = {largest column sum of the weights, largest
+// weight, largest rating} (fx_exponent).  Returns false when the
 // fixed-point scale cannot be used (the caller keeps its own path); everything is queued on the context's stream.
 bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, const float* bounds3, float* G, int64_t ldm, double* ms_tables,
-                         double* ms_walk) {
+                         double* ms_walk, const float* csr_ones) {
     const ScoreTune tune = score_tune(ctx);
     const int32_t Ic = P.nP;
-    if (P.K != 1 || !P.ratings_fp16_exact || !P.ratings_positive || Ic <= 0) return false;
+    // (csr_ones: both sides of every product are 1 -- exact integers whatever the ratings are)
+    if (P.K != 1 || (!csr_ones && (!P.ratings_fp16_exact || !P.ratings_positive)) || Ic <= 0) return false;
     int fxk = fx_exponent(bounds3);
     if (fxk < 0) return false;
     // Ratings that are multiples of 2^-m (half stars: m = 1): every product r r' 2^2m is an integer.  When the largest product
     // stays below 2^24 and the largest possible sum below 2^32 the walk accumulates in 32 bits (ds_add_u32: 6.5 cycles per wave
     // instruction at random addresses against 10.8 for ds_add_u64, profiles/r2/micro_lds_atomic_rate.txt) and a chunk holds
     // twice the columns: two column chunks instead of three at ML-25M shape.  Exact, like the 64-bit sums.
-    const int m = P.ratings_frac_bits;
+    const int m = csr_ones ? 0 : P.ratings_frac_bits;
     const bool acc32 = tune.isim_acc32 && m <= 4 && (double)bounds3[2] * bounds3[2] * std::ldexp(1.0, 2 * m) < 16777216.0 &&
                        (double)bounds3[0] * bounds3[2] * std::ldexp(1.0, 2 * m) < 4294967296.0;
     if (acc32) fxk = 2 * m;
@@ -1520,7 +1522,7 @@ bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, co
     EventTimer t_tab(ctx), t_walk(ctx);
     const size_t s0 = t_tab.begin();
     DevBuf<uint32_t> csr_pk(ctx, (size_t)P.nnz);
-    k_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(0, (int32_t)P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), csr_pk.get());
+    k_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(0, (int32_t)P.nnz, CH, P.csr_idx.get(), csr_ones ? csr_ones : P.csr_r.get(), csr_pk.get());
     FY_KERNEL_CHECK();
     DevBuf<int32_t> co(ctx, (size_t)P.nU * (nch + 1)), csc_rank(ctx, (size_t)P.nnz);
     build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), 0, P.nU, CH, nch, co.get(), st);

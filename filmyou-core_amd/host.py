@@ -17,7 +17,34 @@ from . import _native
 
 SIMILARITY_COSINE = "SIMILARITY_COSINE"
 SIMILARITY_COOCCURRENCE = "SIMILARITY_COOCCURRENCE"
-_SIMILARITY = {SIMILARITY_COSINE: 0, SIMILARITY_COOCCURRENCE: 1}
+SIMILARITY_TANIMOTO_COEFFICIENT = "SIMILARITY_TANIMOTO_COEFFICIENT"
+SIMILARITY_LOGLIKELIHOOD = "SIMILARITY_LOGLIKELIHOOD"
+SIMILARITY_CITY_BLOCK = "SIMILARITY_CITY_BLOCK"
+SIMILARITY_EUCLIDEAN_DISTANCE = "SIMILARITY_EUCLIDEAN_DISTANCE"
+SIMILARITY_PEARSON_CORRELATION = "SIMILARITY_PEARSON_CORRELATION"
+# name -> FY_SIMILARITY_* of include/filmyou.h (Mahout 0.8's VectorSimilarityMeasures, in its order)
+_SIMILARITY = {SIMILARITY_COSINE: 0, SIMILARITY_COOCCURRENCE: 1, SIMILARITY_TANIMOTO_COEFFICIENT: 2, SIMILARITY_LOGLIKELIHOOD: 3,
+               SIMILARITY_CITY_BLOCK: 4, SIMILARITY_EUCLIDEAN_DISTANCE: 5, SIMILARITY_PEARSON_CORRELATION: 6}
+# Mahout's measure classes, as --similarityClassname also takes them; the reference's own default is String.valueOf(X.class),
+# i.e. the name with "class " in front (BaselineRecommenderJob.java:163)
+_MEASURES_PACKAGE = "org.apache.mahout.math.hadoop.similarity.cooccurrence.measures."
+_SIMILARITY_CLASS = {"CosineSimilarity": 0, "CooccurrenceCountSimilarity": 1, "TanimotoCoefficientSimilarity": 2,
+                     "LoglikelihoodSimilarity": 3, "CityBlockSimilarity": 4, "EuclideanDistanceSimilarity": 5,
+                     "PearsonCorrelationSimilarity": 6}
+
+
+def similarity_id(similarityClassname):
+    """FY_SIMILARITY_* for a --similarityClassname value: a SIMILARITY_* name or a fully qualified Mahout measure class,
+    with or without a leading "class ".  Anything else is a ValueError."""
+    name = similarityClassname
+    if name in _SIMILARITY:
+        return _SIMILARITY[name]
+    if isinstance(name, str):
+        if name.startswith("class "):
+            name = name[len("class "):]
+        if name.startswith(_MEASURES_PACKAGE) and name[len(_MEASURES_PACKAGE):] in _SIMILARITY_CLASS:
+            return _SIMILARITY_CLASS[name[len(_MEASURES_PACKAGE):]]
+    raise ValueError("similarityClassname must be one of %s or a measure class of %s*" % (", ".join(_SIMILARITY), _MEASURES_PACKAGE))
 
 
 class FilmYouError(RuntimeError):
@@ -560,9 +587,7 @@ class RowSimilarityJob:
         a RANDOM sample in Mahout's ToItemVectorsMapper); here None = no cap, a number = a DETERMINISTIC systematic sample
         (include/filmyou.h) -- no parity with any particular Mahout run."""
         lib = _native.load()
-        if similarityClassname not in _SIMILARITY:
-            raise ValueError("similarityClassname must be SIMILARITY_COSINE or SIMILARITY_COOCCURRENCE")
-        p = _native.ItemSimParams(_SIMILARITY[similarityClassname], int(maxSimilaritiesPerRow),
+        p = _native.ItemSimParams(similarity_id(similarityClassname), int(maxSimilaritiesPerRow),
                                   1 if excludeSelfSimilarity else 0, 0 if threshold is None else 1,
                                   0.0 if threshold is None else float(threshold), int(rank), int(world), 0,
                                   int(minPrefsPerUser), 0 if maxPrefsPerUser is None else int(maxPrefsPerUser))

@@ -225,14 +225,33 @@ class RM2Job {
 class RowSimilarityJob {
    public:
     using SimilaritySink = std::function<void(int32_t item, int32_t other, float similarity)>;
+    // --similarityClassname -> FY_SIMILARITY_*: a SIMILARITY_* name of Mahout's VectorSimilarityMeasures or the fully qualified
+    // measure class, with or without the "class " that String.valueOf(X.class) puts in front (the reference's default value,
+    // BaselineRecommenderJob.java:163)
+    static int similarityId(std::string name) {
+        static const struct { const char* name; const char* cls; int id; } table[] = {
+            {"SIMILARITY_COSINE", "CosineSimilarity", FY_SIMILARITY_COSINE},
+            {"SIMILARITY_COOCCURRENCE", "CooccurrenceCountSimilarity", FY_SIMILARITY_COOCCURRENCE},
+            {"SIMILARITY_TANIMOTO_COEFFICIENT", "TanimotoCoefficientSimilarity", FY_SIMILARITY_TANIMOTO_COEFFICIENT},
+            {"SIMILARITY_LOGLIKELIHOOD", "LoglikelihoodSimilarity", FY_SIMILARITY_LOGLIKELIHOOD},
+            {"SIMILARITY_CITY_BLOCK", "CityBlockSimilarity", FY_SIMILARITY_CITY_BLOCK},
+            {"SIMILARITY_EUCLIDEAN_DISTANCE", "EuclideanDistanceSimilarity", FY_SIMILARITY_EUCLIDEAN_DISTANCE},
+            {"SIMILARITY_PEARSON_CORRELATION", "PearsonCorrelationSimilarity", FY_SIMILARITY_PEARSON_CORRELATION}};
+        for (const auto& t : table)
+            if (name == t.name) return t.id;
+        const std::string cls = "class ", pkg = "org.apache.mahout.math.hadoop.similarity.cooccurrence.measures.";
+        if (name.compare(0, cls.size(), cls) == 0) name.erase(0, cls.size());
+        if (name.compare(0, pkg.size(), pkg) == 0)
+            for (const auto& t : table)
+                if (name.compare(pkg.size(), std::string::npos, t.cls) == 0) return t.id;
+        throw std::invalid_argument("similarityClassname must be a SIMILARITY_* name or a measure class of " + pkg + "*");
+    }
     // args as passed by BaselineRecommenderJob: --similarityClassname, --maxSimilaritiesPerRow,
     // --excludeSelfSimilarity, --threshold
     int run(const Ratings& r, const std::string& similarityClassname, int maxSimilaritiesPerRow, bool excludeSelfSimilarity,
             const double* threshold, const SimilaritySink& sink) {
         fy_itemsim_params p{};
-        if (similarityClassname == "SIMILARITY_COSINE") p.similarity = FY_SIMILARITY_COSINE;
-        else if (similarityClassname == "SIMILARITY_COOCCURRENCE") p.similarity = FY_SIMILARITY_COOCCURRENCE;
-        else throw std::invalid_argument("similarityClassname must be SIMILARITY_COSINE or SIMILARITY_COOCCURRENCE");
+        p.similarity = similarityId(similarityClassname);
         p.max_similarities_per_item = maxSimilaritiesPerRow;
         p.exclude_self = excludeSelfSimilarity ? 1 : 0;
         p.has_threshold = threshold ? 1 : 0;

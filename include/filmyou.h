@@ -169,9 +169,49 @@ int fy_rm2_run(const fy_rm2_params*, int64_t nnz, const int32_t* user, const int
                fy_result** out);
 
 /* ------------------------------------------------------------------ item-item similarity build */
-enum { FY_SIMILARITY_COSINE = 0, FY_SIMILARITY_COOCCURRENCE = 1 };
+/* The seven measures Mahout 0.8's RowSimilarityJob accepts as --similarityClassname.  After the input preparation below, let
+ * r_ui be the kept preferences, n_i the number of users with a preference for item i, N the number of distinct users that still
+ * have a preference (what the reference passes as --numberOfColumns), and d = sum_u w_ui w_uj over a pair (i, j) that AT LEAST ONE
+ * USER CO-RATED (other pairs have no similarity):
+ *
+ *   constant                          column transform w_ui                    norm a_i      similarity
+ *   FY_SIMILARITY_COSINE              r_ui / ||r_.i||_2                        -             d
+ *   FY_SIMILARITY_COOCCURRENCE        1                                        -             d
+ *   FY_SIMILARITY_TANIMOTO_COEFFICIENT 1                                       n_i           d / (a_i + a_j - d)
+ *   FY_SIMILARITY_LOGLIKELIHOOD       1                                        n_i           1 - 1 / (1 + LLR(k11 = d, k12 = a_j - d, k21 = a_i - d,
+ *                                                                                                           k22 = N - a_i - a_j + d))
+ *   FY_SIMILARITY_CITY_BLOCK          1                                        n_i           1 / (1 + a_i + a_j - 2 d)
+ *   FY_SIMILARITY_EUCLIDEAN_DISTANCE  r_ui                                     sum_u r_ui^2  1 / (1 + sqrt(max(0, a_i - 2 d + a_j)))
+ *   FY_SIMILARITY_PEARSON_CORRELATION c_ui / ||c_.i||_2,                       -             d
+ *                                     c_ui = r_ui - (sum_u |r_ui|) / n_i over the item's raters
+ *
+ * LLR(k11, k12, k21, k22) = 0 if rowE + colE < matE, else 2 (rowE + colE - matE), with H(x...) = xlogx(sum x) - sum xlogx(x),
+ * xlogx(0) = 0, xlogx(x) = x ln x, rowE = H(k11 + k12, k21 + k22), colE = H(k11 + k21, k12 + k22), matE = H(k11, k12, k21, k22).
+ * The finishing arithmetic is fp64; the emitted value is its (float).  Kept: j != i when exclude_self, sim >= threshold (no
+ * threshold: sim > 0), the max_similarities_per_item best per item, ties by ascending item id.  A NaN similarity (Pearson of an
+ * item whose raters all gave the same rating) is dropped.  Mahout's consider() pre-pruning and its random down-sampling are not
+ * modelled.  "Co-rated" is decided by d != 0, which is exact for the count measures and wherever every preference is positive:
+ *   - FY_SIMILARITY_EUCLIDEAN_DISTANCE on data with a non-positive preference fails with FY_ERR_UNSUPPORTED;
+ *   - FY_SIMILARITY_PEARSON_CORRELATION with has_threshold and threshold <= 0 fails with FY_ERR_UNSUPPORTED (a co-rated pair whose
+ *     centred products cancel to 0 cannot be told from a pair nobody co-rated).
+ * A Pearson item counts as constant only where ||c_.i|| is exactly 0, i.e. where (sum |r|) / n_i reproduces the common rating bit
+ * for bit in fp64 -- true for integers and half steps; for ratings such as 0.1f with n_i not a power of two the centred values
+ * are rounding residue, the item keeps weights made of it and its similarities mean nothing (as in any fp64 evaluation of the
+ * definition).
+ * Pearson's weights are fp32 (absolute error of a similarity <= 2^-23); where the preferences are not exactly representable in
+ * fp16 the Euclidean dot product is an fp64 sum in the order the atomics land, and a_i - 2 d + a_j of two nearly identical columns
+ * cancels. */
+enum {
+    FY_SIMILARITY_COSINE = 0,
+    FY_SIMILARITY_COOCCURRENCE = 1,
+    FY_SIMILARITY_TANIMOTO_COEFFICIENT = 2,
+    FY_SIMILARITY_LOGLIKELIHOOD = 3,
+    FY_SIMILARITY_CITY_BLOCK = 4,
+    FY_SIMILARITY_EUCLIDEAN_DISTANCE = 5,
+    FY_SIMILARITY_PEARSON_CORRELATION = 6
+};
 typedef struct {
-    int32_t similarity;                 /* --similarityClassname SIMILARITY_COSINE | SIMILARITY_COOCCURRENCE */
+    int32_t similarity;                 /* --similarityClassname: one of FY_SIMILARITY_* */
     int32_t max_similarities_per_item;  /* --maxSimilaritiesPerRow (default 100, BaselineRecommenderJob.java:67) */
     int32_t exclude_self;               /* --excludeSelfSimilarity (call site passes true) */
     int32_t has_threshold;              /* 0 = RowSimilarityJob.NO_THRESHOLD */
