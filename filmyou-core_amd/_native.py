@@ -22,7 +22,8 @@ SYMBOLS = [
     "fy_abi_version", "fy_last_error", "fy_context_create", "fy_context_destroy", "fy_context_synchronize", "fy_context_reload_tuning", "fy_context_inject_alloc_failure",
     "fy_context_stream", "fy_ratings_create", "fy_ratings_destroy", "fy_ratings_nnz", "fy_ratings_drop_cache", "fy_rm2_prepare",
     "fy_rm2_partial_stats", "fy_rm2_stats_layout", "fy_rm2_set_global_stats", "fy_rm2_set_collectives", "fy_rccl_unique_id", "fy_rccl_create", "fy_rccl_collectives", "fy_rccl_counters", "fy_rccl_destroy", "fy_rccl_detach_context", "fy_rm2_score", "fy_rm2_job_destroy", "fy_rm2_run",
-    "fy_itemsim_build", "fy_itemsim_run", "fy_itemcf_recommend", "fy_cluster_assign", "fy_nmf_factorize", "fy_result_size", "fy_result_key0", "fy_result_key1", "fy_result_value",
+    "fy_itemsim_build", "fy_itemsim_run", "fy_itemcf_recommend", "fy_itemcf_recommend_filtered", "fy_ratings_shifted", "fy_itemsim_pairs",
+    "fy_simpairs_write_text", "fy_idfile_read", "fy_cluster_assign", "fy_nmf_factorize", "fy_result_size", "fy_result_key0", "fy_result_key1", "fy_result_value",
     "fy_result_aux", "fy_result_n_users", "fy_result_user_id", "fy_result_user_sum", "fy_result_n_items",
     "fy_result_item_id", "fy_result_item_coll", "fy_result_total_sum", "fy_result_free", "fy_result_stats",
     "fy_seqfile_read_int_int", "fy_seqfile_read_int_double", "fy_seqfile_read_intpair_float", "fy_seqfile_write_int_int",
@@ -152,6 +153,11 @@ class ItemCFParams(C.Structure):
                 ("rank", C.c_int32), ("world", C.c_int32), ("flags", C.c_uint32)]
 
 
+class ItemCFFilter(C.Structure):
+    _fields_ = [("has_users", C.c_int32), ("has_items", C.c_int32), ("n_users", C.c_int64), ("users", C.c_void_p),
+                ("n_items", C.c_int64), ("items", C.c_void_p)]
+
+
 class Stats(C.Structure):
     _fields_ = [("nnz", C.c_int64), ("n_users", C.c_int64), ("n_items", C.c_int64),
                 ("n_clusters_nonempty", C.c_int64), ("users_scored", C.c_int64), ("recs", C.c_int64),
@@ -230,6 +236,9 @@ def load():
     L.fy_itemsim_build.argtypes = [vp, C.POINTER(ItemSimParams), vp, pvp]
     L.fy_itemsim_run.argtypes = [C.POINTER(ItemSimParams), i64, vp, vp, vp, pvp]
     L.fy_itemcf_recommend.argtypes = [vp, C.POINTER(ItemCFParams), vp, vp, pvp]
+    L.fy_itemcf_recommend_filtered.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFFilter), vp, vp, pvp]
+    L.fy_ratings_shifted.argtypes = [vp, vp, C.c_float, pvp]
+    L.fy_itemsim_pairs.argtypes = [vp, vp, pvp]
     for name, rt in (("size", i64), ("key0", vp), ("key1", vp), ("value", vp), ("aux", vp), ("n_users", i64),
                      ("user_id", vp), ("user_sum", vp), ("n_items", i64), ("item_id", vp), ("item_coll", vp),
                      ("total_sum", C.c_double)):
@@ -247,6 +256,8 @@ def load():
     L.fy_seqfile_write_int_double.argtypes = [cp, i64, vp, vp]
     L.fy_seqfile_write_intpair_float.argtypes = [cp, i64, vp, vp, vp]
     L.fy_mapfile_write_int_double.argtypes = [cp, i64, vp, vp]
+    L.fy_simpairs_write_text.argtypes = [cp, i64, vp, vp, vp]
+    L.fy_idfile_read.argtypes = [cp, pi64, pvp]
     L.fy_buffer_free.argtypes = [vp]
     L.fy_buffer_free.restype = None
     L.fy_submap_create.argtypes = [vp, vp, i32, i64, vp, vp, pvp]

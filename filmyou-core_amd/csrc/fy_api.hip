@@ -381,6 +381,42 @@ int fy_itemcf_recommend(fy_context* c, const fy_itemcf_params* p, const fy_ratin
     FY_CATCH
 }
 
+int fy_itemcf_recommend_filtered(fy_context* c, const fy_itemcf_params* p, const fy_itemcf_filter* f, const fy_ratings* r,
+                                 fy_result* sims, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!c || !r || !p || !f || !sims) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->ctx != &c->c || sims->ctx != &c->c) { set_error("ratings / similarities belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    if (sims->kind != 1) { set_error("`similarities` is not the result of fy_itemsim_build"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::itemcf_recommend_filtered(&c->c, p, f, r, sims);
+    FY_CATCH
+}
+
+int fy_ratings_shifted(fy_context* c, const fy_ratings* r, float shift, fy_ratings** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!c || !r) { set_error("context or ratings is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->ctx != &c->c) { set_error("ratings belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::ratings_shifted(&c->c, r, shift);
+    FY_CATCH
+}
+
+int fy_itemsim_pairs(fy_context* c, fy_result* sims, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!c || !sims) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (sims->ctx != &c->c) { set_error("similarities belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    if (sims->kind != 1) { set_error("`similarities` is not the result of fy_itemsim_build"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::itemsim_pairs(&c->c, sims);
+    FY_CATCH
+}
+
 // ---------------------------------------------------------------- results
 static void rows_to_host(fy_result* r) {
     if (r->rows_on_host) return;

@@ -7,7 +7,7 @@
 // result rows live in HBM until an accessor asks for them
 struct fy_result {
     fy::Context* ctx = nullptr;
-    int kind = 0;   // 0 = RM2, 1 = item-sim
+    int kind = 0;   // 0 = RM2, 1 = item-sim, 2 = item-CF lists, 3 = item pairs
     int64_t n = 0;
     fy::DevBuf<int32_t> d_key0, d_key1, d_aux;
     fy::DevBuf<float> d_value;
@@ -40,6 +40,9 @@ void cluster_assign(Context*, int32_t n_rows, int32_t k, const double* H, int lo
                     int32_t n_clusters, int32_t* user_out, int32_t* cluster_out, int32_t* count_inout);
 void nmf_factorize(Context*, const fy_nmf_params*, const fy_ratings*, double* H, double* W, fy_stats* st);
 fy_result* itemcf_recommend(Context*, const fy_itemcf_params*, const fy_ratings*, fy_result* similarities);
+fy_result* itemcf_recommend_filtered(Context*, const fy_itemcf_params*, const fy_itemcf_filter*, const fy_ratings*, fy_result* similarities);
+fy_ratings* ratings_shifted(Context*, const fy_ratings*, float shift);
+fy_result* itemsim_pairs(Context*, fy_result* similarities);
 
 // top-N over rows of a dense score matrix (NaN = not a candidate): k_topn_fast + k_topn_select of fy_rm2.hip.
 // n_out[u] rows are written at out_off[u] for u in [0, n_rows); item ids come from rank_item_raw[column].

@@ -413,4 +413,68 @@ int fy_mapfile_write_int_double(const char* dir, int64_t n, const int32_t* key, 
     FY_SEQ_CATCH
 }
 
+/* usersFile / itemsFile: one id per line (see include/filmyou.h).  Java's Long.parseLong takes an optional sign and digits only; a line
+ * that is anything else is skipped, as is a number outside int32. */
+int fy_idfile_read(const char* path, int64_t* n, int32_t** ids) {
+    if (!path || !n || !ids) { fy::set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_SEQ_TRY
+    FILE* f = std::fopen(path, "rb");
+    if (!f) throw Fail{std::string("cannot open ") + path};
+    std::string text;
+    char buf[1 << 16];
+    size_t got;
+    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const bool bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (bad) throw Fail{std::string("read error in ") + path};
+    std::vector<int32_t> v;
+    for (size_t a = 0; a < text.size();) {
+        size_t e = text.find('\n', a);
+        if (e == std::string::npos) e = text.size();
+        size_t lo = a, hi = e;
+        while (lo < hi && (text[lo] == ' ' || text[lo] == '\t')) lo++;
+        while (hi > lo && (text[hi - 1] == ' ' || text[hi - 1] == '\t' || text[hi - 1] == '\r')) hi--;
+        a = e + 1;
+        size_t d = lo;
+        const bool neg = d < hi && text[d] == '-';
+        if (d < hi && (text[d] == '-' || text[d] == '+')) d++;
+        if (d == hi) continue;                       // blank, or a sign alone
+        int64_t x = 0;
+        bool ok = true;
+        for (; d < hi && ok; d++) {
+            if (text[d] < '0' || text[d] > '9') ok = false;
+            else if ((x = x * 10 + (text[d] - '0')) > ((int64_t)1 << 31)) ok = false;   // beyond int32 either way
+        }
+        if (!ok) continue;
+        if (neg) x = -x;
+        if (x > INT32_MAX) continue;
+        v.push_back((int32_t)x);
+    }
+    *n = (int64_t)v.size();
+    *ids = dup(v);
+    FY_SEQ_CATCH
+}
+
+int fy_simpairs_write_text(const char* file, int64_t n, const int32_t* a, const int32_t* b, const float* sim) {
+    if (!file || n < 0 || (n && (!a || !b || !sim))) { fy::set_error("bad argument"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_SEQ_TRY
+    const std::string p = file;
+    if (p.find('/') != std::string::npos) mkdirs(p.substr(0, p.rfind('/')));
+    FILE* f = std::fopen(file, "wb");
+    if (!f) throw Fail{"cannot create " + p};
+    bool ok = true;
+    for (int64_t i = 0; i < n && ok; i++) {
+        const double v = (double)sim[i];
+        char num[40];
+        for (int prec = 1; prec <= 17; prec++) {     // the shortest decimal that reads back as v
+            std::snprintf(num, sizeof num, "%.*g", prec, v);
+            if (v != v || std::strtod(num, nullptr) == v) break;
+        }
+        ok = std::fprintf(f, "%d\t%d\t%s\n", a[i], b[i], num) > 0;
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) throw Fail{"write error in " + p};
+    FY_SEQ_CATCH
+}
+
 }  // extern "C"

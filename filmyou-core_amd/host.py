@@ -183,6 +183,19 @@ class Ratings:
         self._keep = None
         self.nnz = n
 
+    @classmethod
+    def _adopt(cls, ctx, handle, nnz):
+        r = cls.__new__(cls)
+        r._lib, r.ctx, r._keep, r._h, r.nnz = _native.load(), ctx, None, handle, nnz
+        return r
+
+    def shifted(self, shift):
+        """fy_ratings_shifted: a new Ratings whose scores are float32(score + shift) -- the reference's ratingShift
+        (BaselineToItemPrefsMapper.java:60).  Nothing the jobs kept on this object is carried over."""
+        h = C.c_void_p()
+        _check(self._lib.fy_ratings_shifted(self.ctx._h, self._h, float(shift), C.byref(h)))
+        return Ratings._adopt(self.ctx, h, self.nnz)
+
     def drop_cache(self):
         """fy_ratings_drop_cache: releases what earlier jobs kept on this object (CSR / CSC, statistics, row-kernel tables)."""
         if getattr(self, "_h", None) and self.ctx._h:
@@ -279,6 +292,47 @@ class ItemSimilarities(_Result):
             self._rows = {"item": _np(L.fy_result_key0(h), n, np.int32), "other": _np(L.fy_result_key1(h), n, np.int32),
                           "sim": _np(L.fy_result_value(h), n, np.float32)}
         return self._rows
+
+    def pairs(self):
+        """fy_itemsim_pairs: the matrix as de-duplicated item pairs {"a": min id, "b": max id, "sim"}, sorted by (a, b) -- what the
+        reference's outputPathForSimilarityMatrix job writes (BaselineRecommenderJob.java:259-278).  Rows of a world == 1 build."""
+        res = C.c_void_p()
+        _check(self._lib.fy_itemsim_pairs(self._ctx._h, self._h, C.byref(res)))
+        L = self._lib
+        try:
+            n = L.fy_result_size(res)
+            return {"a": _np(L.fy_result_key0(res), n, np.int32), "b": _np(L.fy_result_key1(res), n, np.int32),
+                    "sim": _np(L.fy_result_value(res), n, np.float32)}
+        finally:
+            L.fy_result_free(res)
+
+
+def read_id_file(path):
+    """fy_idfile_read: the ids of a usersFile / itemsFile (one per line; lines that are not an int32 are skipped)."""
+    lib = _native.load()
+    n, ids = C.c_int64(), C.c_void_p()
+    _check(lib.fy_idfile_read(os.fsencode(path), C.byref(n), C.byref(ids)))
+    try:
+        return _np(ids.value, n.value, np.int32)
+    finally:
+        lib.fy_buffer_free(ids)
+
+
+def write_similarity_pairs(path, pairs):
+    """fy_simpairs_write_text: `a<TAB>b<TAB>sim` lines from ItemSimilarities.pairs()."""
+    a, b = _i32(pairs["a"]), _i32(pairs["b"])
+    sim = np.ascontiguousarray(pairs["sim"], dtype=np.float32)
+    assert len(a) == len(b) == len(sim)
+    _check(_native.load().fy_simpairs_write_text(os.fsencode(path), len(a), a.ctypes.data, b.ctypes.data, sim.ctypes.data))
+
+
+def _id_list(ids):
+    """usersFile= / itemsFile=: a path or an integer array; None = option off."""
+    if ids is None:
+        return None
+    if isinstance(ids, (str, bytes, os.PathLike)):
+        return read_id_file(ids)
+    return _i32(ids)
 
 
 def _i32(a):
@@ -543,14 +597,29 @@ class BaselineRecommenderJob:
 
     def run(self, ratings, numRecommendations=100, maxPrefsPerUser=50, maxSimilaritiesPerItem=100,
             similarityClassname=SIMILARITY_COSINE, threshold=None, booleanData=False, rank=0, world=1,
-            similarities=None):
+            similarities=None, usersFile=None, itemsFile=None, ratingShift=0.0, outputPathForSimilarityMatrix=None):
         """Returns (ItemRecommendations, ItemSimilarities).  `similarities` may be passed to skip phase 2
-        (Mahout's --startPhase)."""
+        (Mahout's --startPhase).
+
+        usersFile / itemsFile (a path of one id per line, or an integer array; None = not given): lists only for these users
+        (BaselineRecommenderJob.java:305-307), only these items may be recommended (BaselineAggregateAndRecommendReducer.java:170-181,
+        209) -- fy_itemcf_recommend_filtered, whose cost follows the users asked for.  ratingShift: every preference is
+        float32(score + ratingShift) for the similarity build and the recommendation pass alike (BaselineToItemPrefsMapper.java:60).
+        outputPathForSimilarityMatrix: the similarity matrix is also written there as de-duplicated item pairs, text
+        (BaselineRecommenderJob.java:259-278)."""
         lib = _native.load()
         ctx = self.ctx or Context(0)
         self.ctx = ctx
+        users, items = _id_list(usersFile), _id_list(itemsFile)
         own_ratings = not isinstance(ratings, Ratings)
         r = Ratings(ctx, *ratings) if own_ratings else ratings
+        if float(ratingShift) != 0.0:
+            try:
+                shifted = r.shifted(ratingShift)
+            finally:
+                if own_ratings:
+                    r.close()
+            r, own_ratings = shifted, True
         try:
             sims = similarities
             if sims is None:
@@ -558,10 +627,18 @@ class BaselineRecommenderJob:
                 sims = RowSimilarityJob(ctx).run(r, similarityClassname, maxSimilaritiesPerItem, True, threshold)
             p = _native.ItemCFParams(int(numRecommendations), int(maxPrefsPerUser), 1 if booleanData else 0, int(rank),
                                      int(world), 0)
+            if outputPathForSimilarityMatrix is not None:
+                write_similarity_pairs(outputPathForSimilarityMatrix, sims.pairs())
             res = C.c_void_p()
             try:
                 ctx.sync_tuning()
-                _check(lib.fy_itemcf_recommend(ctx._h, C.byref(p), r._h, sims._h, C.byref(res)))
+                if users is None and items is None:
+                    _check(lib.fy_itemcf_recommend(ctx._h, C.byref(p), r._h, sims._h, C.byref(res)))
+                else:
+                    f = _native.ItemCFFilter(int(users is not None), int(items is not None),
+                                             0 if users is None else len(users), None if users is None else users.ctypes.data,
+                                             0 if items is None else len(items), None if items is None else items.ctypes.data)
+                    _check(lib.fy_itemcf_recommend_filtered(ctx._h, C.byref(p), C.byref(f), r._h, sims._h, C.byref(res)))
             except FilmYouError as e:
                 raise RuntimeError("%s failed!: %s" % (self.JOB_NAME, e.message)) from e
             return ItemRecommendations(res, ctx), sims

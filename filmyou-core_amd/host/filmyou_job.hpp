@@ -8,6 +8,8 @@
 //                                throws std::runtime_error("RM2 failed!: ...") like RM2Job.java:144-147
 //   fy::host::RowSimilarityJob::run <- Mahout RowSimilarityJob as invoked at
 //                                M/baselinerecommender/BaselineRecommenderJob.java:241-253 (same option names)
+//   fy::host::BaselineRecommenderJob::run <- the job around it (BaselineRecommenderJob.java:179-328), with usersFile, itemsFile,
+//                                ratingShift and outputPathForSimilarityMatrix
 // Input/output stay in the caller's hands (the reference's Cassandra / HDFS readers and writers are unchanged): the
 // job takes rating triples and hands back rows through a sink callback shaped like writePreference
 // (M/rm/AbstractRM2Reducer.java:404-406).
@@ -266,6 +268,88 @@ class RowSimilarityJob {
         const float* s = fy_result_value(res);
         for (int64_t k = 0; k < n; k++) sink(a[k], b[k], s[k]);
         fy_result_free(res);
+        return 0;
+    }
+};
+
+// Item-based CF from the similarity phase on (M/baselinerecommender/BaselineRecommenderJob.java:179-328), with the job's option
+// names: the similarity build, then the recommendation pass on one context.  usersFile / itemsFile (paths of one id per line; empty
+// = not given, the reference's NULL), ratingShift and outputPathForSimilarityMatrix as in the reference (:74, 189, 259-278, 305-307;
+// BaselineAggregateAndRecommendReducer.java:170-181, 209; BaselineToItemPrefsMapper.java:60).
+class BaselineRecommenderJob {
+   public:
+    int numRecommendations = 100, maxPrefsPerUser = 50, maxSimilaritiesPerItem = 100;
+    std::string similarityClassname = "SIMILARITY_COSINE";
+    bool booleanData = false, hasThreshold = false;
+    double threshold = 0.0;
+    std::string usersFile, itemsFile, outputPathForSimilarityMatrix;
+    float ratingShift = 0.0f;
+    fy_stats stats{};   // of the recommendation pass
+
+    using RecommendationSink = std::function<void(int32_t user, int32_t item, float score)>;
+
+    int run(const Ratings& r, const RecommendationSink& sink, int device = 0) {
+        fy_context* ctx = nullptr;
+        fy_ratings *rt = nullptr, *shifted = nullptr;
+        fy_result *sims = nullptr, *pairs = nullptr, *res = nullptr;
+        int32_t *users = nullptr, *items = nullptr;
+        auto release = [&]() {
+            if (res) fy_result_free(res);
+            if (pairs) fy_result_free(pairs);
+            if (sims) fy_result_free(sims);
+            if (shifted) fy_ratings_destroy(shifted);
+            if (rt) fy_ratings_destroy(rt);
+            if (ctx) fy_context_destroy(ctx);
+            fy_buffer_free(users);
+            fy_buffer_free(items);
+        };
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("BaselineRecommenderJob failed!: ") + what + ": " + fy_last_error();
+            release();
+            throw std::runtime_error(msg);
+        };
+        fy_itemcf_filter f{};
+        if (!usersFile.empty()) {
+            f.has_users = 1;
+            if (fy_idfile_read(usersFile.c_str(), &f.n_users, &users) != FY_OK) fail("usersFile");
+            f.users = users;
+        }
+        if (!itemsFile.empty()) {
+            f.has_items = 1;
+            if (fy_idfile_read(itemsFile.c_str(), &f.n_items, &items) != FY_OK) fail("itemsFile");
+            f.items = items;
+        }
+        fy_itemsim_params sp{};
+        sp.similarity = RowSimilarityJob::similarityId(similarityClassname);
+        sp.max_similarities_per_item = maxSimilaritiesPerItem;
+        sp.exclude_self = 1;
+        sp.has_threshold = hasThreshold ? 1 : 0;
+        sp.threshold = threshold;
+        sp.world = 1;
+        sp.min_prefs_per_user = 1;
+        fy_itemcf_params cp{};
+        cp.num_recommendations = numRecommendations;
+        cp.max_prefs_per_user = maxPrefsPerUser;
+        cp.boolean_data = booleanData ? 1 : 0;
+        cp.world = 1;
+        if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+        if (fy_ratings_create(ctx, (int64_t)r.user.size(), r.user.data(), r.item.data(), r.score.data(), FY_HOST, &rt) != FY_OK) fail("ratings");
+        if (ratingShift != 0.0f && fy_ratings_shifted(ctx, rt, ratingShift, &shifted) != FY_OK) fail("ratingShift");
+        const fy_ratings* prefs = shifted ? shifted : rt;
+        if (fy_itemsim_build(ctx, &sp, prefs, &sims) != FY_OK) fail("similarity");
+        if (!outputPathForSimilarityMatrix.empty()) {
+            if (fy_itemsim_pairs(ctx, sims, &pairs) != FY_OK) fail("item pairs");
+            if (fy_simpairs_write_text(outputPathForSimilarityMatrix.c_str(), fy_result_size(pairs), fy_result_key0(pairs),
+                                       fy_result_key1(pairs), fy_result_value(pairs)) != FY_OK)
+                fail("outputPathForSimilarityMatrix");
+        }
+        if (fy_itemcf_recommend_filtered(ctx, &cp, &f, prefs, sims, &res) != FY_OK) fail("recommend");
+        const int64_t n = fy_result_size(res);
+        const int32_t *u = fy_result_key0(res), *i = fy_result_key1(res);
+        const float* s = fy_result_value(res);
+        for (int64_t k = 0; k < n; k++) sink(u[k], i[k], s[k]);
+        fy_result_stats(res, &stats);
+        release();
         return 0;
     }
 };

@@ -249,6 +249,44 @@ typedef struct {
 } fy_itemcf_params;
 int fy_itemcf_recommend(fy_context*, const fy_itemcf_params*, const fy_ratings*, fy_result* similarities, fy_result** out);
 
+/* ------------------------------------------------------------------ item-based CF: usersFile, itemsFile, ratingShift, item pairs
+ * The remaining options of the job around the two calls above (M/baselinerecommender/BaselineRecommenderJob.java).
+ *
+ * usersFile (BaselineRecommenderJob.java:74, 189, 305-307; Mahout's UserVectorSplitterMapper passes over every user that is not
+ * listed) and itemsFile (BaselineAggregateAndRecommendReducer.java:61, 170-181: itemsToRecommendFor; :209: only a listed item
+ * enters the top-N queue).  has_* = 0 is the reference's NULL file name: the option is off.  The id arrays are HOST arrays of raw
+ * ids in any order; a duplicate counts once; a user without a kept preference, an id outside the data and an item nobody rated
+ * are passed over without an error; an option that is on with an empty list gives an empty result (Mahout's empty id set).
+ * A user's list is the numRecommendations best predictions AMONG THE ALLOWED ITEMS (the allow-list is applied where a cell
+ * becomes a prediction, not to the finished list); everything else -- the user's own items excluded, at least two contributing
+ * preferences, NaN, the arithmetic, the 2048 limit, the row order (users in the order of the unrestricted job, best first) -- is
+ * fy_itemcf_recommend's, and with both options off the call IS fy_itemcf_recommend.  (rank, world) shard the requested users.
+ * The dense accumulators are sized by the users asked for.  fy_result_stats: users_scored = users that received a list, recs,
+ * ms_prepare (structure of the ratings), ms_tables (similarity rows by column + the request's list and bitmap), ms_score
+ * (accumulate + predictions), ms_topn, ms_total. */
+typedef struct {
+    int32_t has_users;  int32_t has_items;       /* 0 = option not given (NULL file in the reference) */
+    int64_t n_users;    const int32_t* users;    /* HOST, raw user ids, any order, duplicates allowed */
+    int64_t n_items;    const int32_t* items;    /* HOST, raw item ids */
+} fy_itemcf_filter;
+int fy_itemcf_recommend_filtered(fy_context*, const fy_itemcf_params*, const fy_itemcf_filter*,
+                                 const fy_ratings*, fy_result* similarities, fy_result** out);
+/* ratingShift (BaselinePreparePreferenceMatrixJob.java:105-106, 201, 223; BaselineToItemPrefsMapper.java:51, 60): a NEW ratings
+ * object whose scores are (float)(score + shift), added in fp32 like the mapper's `float prefValue`; ids as they are.  Nothing
+ * the jobs kept on the source object is carried over.  The baseline job feeds it to the similarity build and to the
+ * recommendation pass alike; shifted preferences may be non-positive, and what the similarity build does with such data holds
+ * (FY_ERR_UNSUPPORTED for FY_SIMILARITY_EUCLIDEAN_DISTANCE). */
+int fy_ratings_shifted(fy_context*, const fy_ratings*, float shift, fy_ratings** out);
+/* outputPathForSimilarityMatrix (BaselineRecommenderJob.java:259-278: Mahout 0.8's ItemSimilarityJob.MostSimilarItemPairsMapper /
+ * Reducer into a TextOutputFormat).  Those classes are third-party and restated from memory, as every Mahout class in this
+ * package: PARITY UNPINNED.  `similarities` = the rows of a world == 1 fy_itemsim_build.  Result rows (key0 = min id, key1 = max id,
+ * value = similarity, aux = 0): every unordered pair that occurs in at least one of the two items' rows, once, sorted by
+ * (min, max); where both rows hold the pair the value is the one in the row of the smaller id.
+ * fy_simpairs_write_text writes `a<TAB>b<TAB>sim` lines, sim = the shortest decimal (%.{1..17}g) that reads back as the float
+ * widened to double; byte-for-byte agreement with Java's Double.toString is NOT claimed.  Host-only. */
+int fy_itemsim_pairs(fy_context*, fy_result* similarities, fy_result** out);
+int fy_simpairs_write_text(const char* file, int64_t n, const int32_t* a, const int32_t* b, const float* sim);
+
 /* ------------------------------------------------------------------ cluster assignment (the stage in front of the RM2 job)
  * Replaces ClusterAssignmentJob's map-only jobs and CountClustersJob (M/nmf/clustering/ClusterAssignmentJob.java:60-135,
  * FindClusterMapper.java:37-45, FindSubClusterMapper.java:46-76, CountReducer.java:31-45): for every row j of H (n_rows x k
@@ -444,6 +482,10 @@ int fy_seqfile_write_int_int(const char* file, int64_t n, const int32_t* key, co
 int fy_seqfile_write_int_double(const char* file, int64_t n, const int32_t* key, const double* value);
 int fy_seqfile_write_intpair_float(const char* file, int64_t n, const int32_t* first, const int32_t* second, const float* value);
 int fy_mapfile_write_int_double(const char* dir, int64_t n, const int32_t* key, const double* value);   /* rm2/itemColl: data + index */
+/* usersFile / itemsFile: a text file with one id per line.  A line that is not an integer (blank, `abc`, `12x`) is skipped like the
+ * reference's "itemsFile line ignored" (BaselineAggregateAndRecommendReducer.java:173-179), and so is an id that does not fit
+ * int32 (no such id can be in the ratings); blanks around the number and a missing last newline are accepted.  Host-only. */
+int fy_idfile_read(const char* path, int64_t* n, int32_t** ids);
 void fy_buffer_free(void*);
 
 #ifdef __cplusplus
