@@ -8,6 +8,7 @@
 
 #include "fy_prep.hpp"
 #include "fy_rm2.hpp"
+#include "fy_rm2_request.hpp"
 
 namespace fy {
 static thread_local char g_err[512] = "";
@@ -69,6 +70,8 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_COOC_MAX_CH")) { int v = atoi(e); if (v >= 64 && v <= 20224) { t.cooc_max_ch = v; t.cooc_max_ch_forced = true; } }
     if (const char* e = getenv("FY_TOPN_FORCE_SELECT")) t.force_select = atoi(e) != 0;
     if (const char* e = getenv("FY_MAX_SURV_FRAC")) { double v = atof(e); if (v >= 0.0) t.max_surv_frac = v; }
+    if (const char* e = getenv("FY_REQ_FULL_SHARE")) { double v = atof(e); if (v >= 0.0) t.req_full_share = v; }
+    if (const char* e = getenv("FY_REQ_CHUNK")) { int v = atoi(e); if (v >= 64 && v <= 16384 && v % 64 == 0) t.req_chunk = v; }
     if (const char* e = getenv("FY_ISIM_HEAVY")) t.isim_heavy = std::max(0, atoi(e));
     if (const char* e = getenv("FY_ISIM_GRAM")) t.isim_gram = atoi(e) != 0;
     if (const char* e = getenv("FY_ISIM_GRAM_MIN_ITEMS")) t.isim_gram_min_items = std::max(0, atoi(e));
@@ -283,6 +286,17 @@ int fy_rm2_score(fy_rm2_job* j, fy_result** out) {
     FY_CATCH
 }
 
+int fy_rm2_score_users(fy_rm2_job* j, const fy_rm2_request* rq, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !rq) { set_error("job or request is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (rq->n_users < 0 || (rq->n_users > 0 && !rq->users)) { set_error("users is NULL or n_users < 0"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(job_context(j));
+    *out = fy::rm2_score_users(j, rq);
+    FY_CATCH
+}
+
 void fy_rm2_job_destroy(fy_rm2_job* j) {
     if (!j) return;
     fy::Context* ctx = nullptr;
@@ -466,6 +480,12 @@ double fy_result_total_sum(fy_result* r) { return r ? r->total_sum : 0.0; }
 int fy_result_stats(fy_result* r, fy_stats* out) {
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     *out = r->st;
+    return FY_OK;
+}
+int fy_result_request_stats(fy_result* r, fy_rm2_request_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_request_stats) { set_error("not a result of fy_rm2_score_users"); return FY_ERR_STATE; }
+    *out = r->rq;
     return FY_OK;
 }
 void fy_result_free(fy_result* r) {

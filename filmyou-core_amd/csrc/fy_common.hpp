@@ -100,6 +100,11 @@ struct Tuning {
     bool panel_two_phase = true;       // FY_PANEL_TWO_PHASE=0: every cluster start to end on its lane (round 2)
     int panel_max_ch = 4096;           // chunk width of the row kernel in panel mode: five workgroups per CU (measured, 50 clusters, row kernel ms: 8192 -> 67, 6144 -> 54, 4096 -> 46)
     double max_surv_frac = 0.25;       // a pruned batch whose surviving blocks exceed this fraction falls back to the full pass
+    // restricted RM2 pass (fy_rm2_request.hip)
+    double req_full_share = 1.0;       // FY_REQ_FULL_SHARE: a cluster of which more than this share of the users is asked for is scored by the full pass and the
+                                       // unrequested rows are dropped (0 = every touched cluster, >= 1 = never).  Not measured yet ("RM2 on
+                                       // request"), so the default never falls back; ONE cluster that does costs the rank's whole full job
+    int req_chunk = 8192;              // FY_REQ_CHUNK: columns (64-bit LDS accumulators) a workgroup of the slab build owns
     // item-item similarity build (fy_itemsim.hip)
     int isim_heavy = 4096;             // row-at-a-time kernel: raters above which a row is split by column chunk
     int isim_gram = -1;                // symmetric Gram + band sweep: -1 = by size (cosine, >= isim_gram_min_items items), 0 = never, 1 = whenever possible

@@ -21,6 +21,7 @@
 #include "fy_prep.hpp"
 #include <chrono>
 #include "fy_rm2.hpp"
+#include "fy_rm2_request.hpp"
 
 namespace fy {
 
@@ -1322,6 +1323,7 @@ static void stray_allow_lds();
 
 #include "fy_rm2_kernels.hpp"   // scoring, top-N, branch-and-bound and cooperative-rank kernels (part of this translation unit)
 
+static_assert(TOPN_MAX == fy::TOPN_LIST_MAX, "fy_rm2.hpp states the top-N kernels' limit for the other translation units");
 static void stray_allow_lds() {   // k_score_stray: (Uc + 1) rater offsets of dynamic LDS, up to 128 KB
     FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_stray), hipFuncAttributeMaxDynamicSharedMemorySize, (STRAY_UCAP + 1) * (int)sizeof(int32_t)));
 }
@@ -1394,6 +1396,7 @@ struct RM2Static {
     std::vector<float> fx_bounds;       // 3 per cluster (host): max sum of weights, max weight, max rating
     double ms_build = 0;
     TableCache tables;
+    std::shared_ptr<void> request_state;   // what fy_rm2_score_users builds from the ratings and the clustering alone and keeps (fy_rm2_request.hip)
     bool matches(const fy_rm2_params* prm, int64_t n_map, const int32_t* mu, const int32_t* mc, const int32_t* cc) const {
         if (K != prm->number_of_clusters || rank != prm->rank || world != prm->world || (int64_t)map_user.size() != n_map || has_count != (cc != nullptr)) return false;
         if (n_map && (memcmp(map_user.data(), mu, (size_t)n_map * 4) || memcmp(map_cluster.data(), mc, (size_t)n_map * 4))) return false;
@@ -3349,6 +3352,26 @@ void fy::rm2_set_collectives(fy_rm2_job* J, const fy_collectives* c) {
     if (!c || !c->all_gather || !c->reduce_scatter_f32) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "fy_collectives needs all_gather and reduce_scatter_f32");
     J->coll = *c;
     J->have_coll = true;
+}
+
+// what a restricted request (fy_rm2_request.hip) reads of the job
+void fy::rm2_request_view(fy_rm2_job* J, RequestView& V) {
+    if (J->have_coll) FY_FAIL(FY_ERR_UNSUPPORTED, "fy_rm2_score_users: the job has collectives installed (the cooperative path serves no requests)");
+    if (!J->have_global) {
+        if (J->prm.world == 1) rm2_set_global_stats(J, J->partial.get(), 1);
+        else FY_FAIL(FY_ERR_STATE, "world > 1: call fy_rm2_set_global_stats before fy_rm2_score_users");
+    }
+    V.ctx = J->ctx;
+    V.prm = J->prm;
+    V.P = &J->P;
+    V.slot_lo = J->slot_lo;
+    V.slot_hi = J->slot_hi;
+    V.have_coll = J->have_coll;
+    V.stats = J->stats.get();
+    V.b_rank = J->b_rank.get();
+    V.walk_rank = J->walk_rank.get();
+    V.usum_slot = J->usum_slot.get();
+    V.state = &J->S->request_state;
 }
 
 void fy::rm2_partial_stats(fy_rm2_job* J, double** buf, int64_t* len) {

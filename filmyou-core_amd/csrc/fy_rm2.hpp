@@ -15,6 +15,8 @@ struct fy_result {
     fy::DevBuf<double> d_user_sum, d_icoll;
     double total_sum = 0.0;
     fy_stats st{};
+    bool has_request_stats = false;   // a result of fy_rm2_score_users
+    fy_rm2_request_stats rq{};
     // host mirrors, filled on first access
     bool rows_on_host = false, sums_on_host = false;
     std::vector<int32_t> h_key0, h_key1, h_aux, h_user_id, h_item_id;
@@ -44,6 +46,7 @@ fy_result* itemcf_recommend_filtered(Context*, const fy_itemcf_params*, const fy
 fy_ratings* ratings_shifted(Context*, const fy_ratings*, float shift);
 fy_result* itemsim_pairs(Context*, fy_result* similarities);
 
+constexpr int TOPN_LIST_MAX = 2048;   // longest list of the top-N kernels (TOPN_MAX of fy_rm2_kernels.hpp)
 // top-N over rows of a dense score matrix (NaN = not a candidate): k_topn_fast + k_topn_select of fy_rm2.hip.
 // n_out[u] rows are written at out_off[u] for u in [0, n_rows); item ids come from rank_item_raw[column].
 void launch_topn_rows(Context* ctx, hipStream_t st, const float* S, int64_t ldS, int32_t n_cols, int32_t n_rows,

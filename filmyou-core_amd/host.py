@@ -256,6 +256,9 @@ class Recommendations(_Result):
         self.size = L.fy_result_size(handle)
         self._rows = None
         self._sums = None
+        # fy_rm2_score_users only: what the request touched (None on the result of a full job)
+        rq = _native.RM2RequestStats()
+        self.request_stats = rq.as_dict() if L.fy_result_request_stats(handle, C.byref(rq)) == 0 else None
 
     def rows(self):
         if self._rows is None:
@@ -397,8 +400,10 @@ class RM2Job:
                 r.close()
 
     def run(self, ratings, clustering=None, clustering_count=None, rank=0, world=1, exchange=None,
-            workspace_bytes=0, collectives=None, cache=True):
+            workspace_bytes=0, collectives=None, cache=True, usersFile=None):
         """ratings: a ``Ratings`` or a (user, item, score) triple of arrays.
+        usersFile: a path of one user id per line (read_id_file) or an integer array: lists for these users alone, with the work
+          sized by the request (PreparedRM2.score_users); None = the whole job.  Not with collectives= (ValueError).
         clustering: (users, clusters) arrays = the reference's `clustering` file; None routes everyone to cluster 0.
         clustering_count: array of numberOfClusters sizes = the `clusteringCount` file (validated when given).
         world > 1 needs one of
@@ -412,8 +417,11 @@ class RM2Job:
           statistics, the row kernel's tables); a later job over the same object and the same clustering starts from it
           (stats["prepared_from_cache"]).  cache=False = FY_RM2_NO_CACHE: build everything, keep nothing (the cold job).
         Raises RuntimeError("RM2 failed!: ...") on any failure, like RM2Job.java:144-147."""
+        if usersFile is not None and collectives is not None:
+            raise ValueError("usersFile cannot be combined with collectives: the cooperative path serves no requests")
         if world > 1 and exchange is None and collectives is None:
             raise ValueError("world > 1 needs collectives (or at least an exchange for the item statistics)")
+        users = _id_list(usersFile)
         prepared = self.prepare(ratings, clustering, clustering_count, rank, world, workspace_bytes, cache=cache)
         try:
             if collectives is not None:
@@ -421,6 +429,8 @@ class RM2Job:
             elif world > 1:
                 ptr, n = prepared.partial_stats()
                 prepared.set_global_stats(exchange(ptr, n))
+            if users is not None:
+                return prepared.score_users(users)
             return prepared.score()
         finally:
             prepared.close()
@@ -476,6 +486,8 @@ class RM2Job:
                 stale = [outp]
         if stale:
             raise RuntimeError("%s failed!: output directory %s already exists%s" % (self.JOB_NAME, outp, "" if world == 1 else " and holds " + ", ".join(stale[:4])))
+        if conf.get("usersFile") is not None and "usersFile" not in kw:
+            kw["usersFile"] = conf.get("usersFile")
         rec = self.run((user, item, score), clustering=(cu, cc), clustering_count=count, rank=rank, world=world, **kw)
         try:
             rows = rec.rows()
@@ -551,6 +563,20 @@ class PreparedRM2:
                 if getattr(self, "_comm_error", None) is not None:
                     raise RuntimeError("%s failed!: collective: %r" % (RM2Job.JOB_NAME, self._comm_error)) from self._comm_error
                 raise
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (RM2Job.JOB_NAME, e.message)) from e
+        return Recommendations(res, self._ctx)
+
+    def score_users(self, ids):
+        """fy_rm2_score_users: the rows score() would emit for the listed raw user ids (any order, duplicates and unknown ids
+        passed over), with the work sized by the request.  Any number of calls, before or after score(); the job stays valid.
+        Returns a ``Recommendations`` with ``request_stats`` beside ``stats``."""
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int32)
+        rq = _native.RM2Request(len(ids), ids.ctypes.data if len(ids) else None)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            _check(self._lib.fy_rm2_score_users(self._h, C.byref(rq), C.byref(res)))
         except FilmYouError as e:
             raise RuntimeError("%s failed!: %s" % (RM2Job.JOB_NAME, e.message)) from e
         return Recommendations(res, self._ctx)

@@ -152,6 +152,49 @@ class RM2Job {
     }
     int64_t allGathers = 0, reduceScatters = 0, collectiveBytes = 0;   // of the last runRank
 
+    // RM2 on request (fy_rm2_score_users): the lists of the listed raw user ids alone, with the work sized by the request --
+    // "usersFile" of the Python host.  `users` empty = read the configuration key usersFile (one id per line, fy_idfile_read).
+    // One GPU: context, ratings, prepare, the request.  requestStats holds what the request touched.
+    fy_rm2_request_stats requestStats{};
+    int runUsers(const Ratings& r, const Clustering& c, std::vector<int32_t> users, const PreferenceSink& sink, int device = 0) {
+        fy_rm2_params p = params();
+        if (users.empty() && conf_.has("usersFile")) {
+            int64_t n = 0;
+            int32_t* ids = nullptr;
+            if (fy_idfile_read(conf_.get("usersFile").c_str(), &n, &ids) != FY_OK) throw std::runtime_error(std::string("RM2 failed!: ") + fy_last_error());
+            users.assign(ids, ids + n);
+            fy_buffer_free(ids);
+        }
+        fy_context* ctx = nullptr;
+        fy_ratings* rt = nullptr;
+        fy_rm2_job* job = nullptr;
+        fy_result* res = nullptr;
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("RM2 failed!: ") + what + ": " + fy_last_error();
+            if (job) fy_rm2_job_destroy(job);
+            if (rt) fy_ratings_destroy(rt);
+            if (ctx) fy_context_destroy(ctx);
+            throw std::runtime_error(msg);
+        };
+        std::vector<int32_t> cc = counts(c, p.number_of_clusters);
+        if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+        if (fy_ratings_create(ctx, (int64_t)r.user.size(), r.user.data(), r.item.data(), r.score.data(), FY_HOST, &rt) != FY_OK) fail("ratings");
+        if (fy_rm2_prepare(ctx, &p, rt, (int64_t)c.user.size(), c.user.data(), c.cluster.data(), cc.empty() ? nullptr : cc.data(), &job) != FY_OK) fail("prepare");
+        const fy_rm2_request rq{(int64_t)users.size(), users.data()};
+        if (fy_rm2_score_users(job, &rq, &res) != FY_OK) fail("score_users");
+        const int64_t n = fy_result_size(res);
+        const int32_t *u = fy_result_key0(res), *i = fy_result_key1(res), *cl = fy_result_aux(res);
+        const float* s = fy_result_value(res);
+        for (int64_t k = 0; k < n; k++) sink(u[k], i[k], s[k], cl[k]);
+        fy_result_stats(res, &stats);
+        fy_result_request_stats(res, &requestStats);
+        fy_result_free(res);
+        fy_rm2_job_destroy(job);
+        fy_ratings_destroy(rt);
+        fy_context_destroy(ctx);
+        return 0;
+    }
+
     // RM2Job.run on the reference's own files (M/rm/RM2Job.java:76-100 with useCassandraInput / Output = false): ratings from
     // <mapred.input.dir>, <directory>/<clustering>, <directory>/<clusteringCount>; writes <directory>/rm2/userSum,
     // <directory>/rm2/itemColl (MapFile) and the recommendations under <mapred.output.dir>.  Files: fy_seqfile_* (layout

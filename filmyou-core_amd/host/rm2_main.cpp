@@ -29,6 +29,9 @@ static int main_files(char** a) {
 int main(int argc, char** argv) {
     if (argc == 9 && strcmp(argv[1], "--files") == 0) return main_files(argv + 2);
     bool rccl = false;
+    // rm2_main --users <users.txt> <ratings.txt> ... : RM2Job::runUsers, lists for the ids of the usersFile alone
+    const char* users_file = nullptr;
+    if (argc == 9 && strcmp(argv[1], "--users") == 0) { users_file = argv[2]; argv += 2; argc -= 2; }
     if (argc == 8 && strcmp(argv[1], "--rccl") == 0) { rccl = true; argv++; argc--; }
     if (argc != 7) { fprintf(stderr, "usage: %s ratings clustering lambda numberOfItems numberOfClusters numberOfRecommendations\n", argv[0]); return 2; }
     fy::host::Ratings r;
@@ -51,9 +54,14 @@ int main(int argc, char** argv) {
     conf.set("numberOfClusters", argv[5]);
     conf.set("numberOfRecommendations", argv[6]);
     try {
+        if (users_file) conf.set("usersFile", users_file);      // (the job copies its configuration)
         fy::host::RM2Job job(conf);
         auto sink = [](int32_t user, int32_t item, float score, int32_t cluster) { printf("%d %d %.9g %d\n", user, item, score, cluster); };
-        if (rccl) {
+        if (users_file) {
+            job.runUsers(r, c, {}, sink);
+            fprintf(stderr, "request users_known %lld clusters_touched %lld slab_rows %lld full_pass_clusters %lld\n", (long long)job.requestStats.users_known,
+                    (long long)job.requestStats.clusters_touched, (long long)job.requestStats.slab_rows, (long long)job.requestStats.full_pass_clusters);
+        } else if (rccl) {
             char id[128];
             if (fy_rccl_unique_id(id) != FY_OK) { fprintf(stderr, "RM2 failed!: %s\n", fy_last_error()); return 1; }
             job.runRank(r, c, sink, 0, 0, 1, id);

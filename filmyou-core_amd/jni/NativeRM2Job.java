@@ -39,6 +39,33 @@ public class NativeRM2Job extends AbstractJob {
             int numberOfClusters, long nnz, ByteBuffer user, ByteBuffer item, ByteBuffer score, long nMap,
             ByteBuffer mapUser, ByteBuffer mapCluster, ByteBuffer clusterCount, int rank, int world, int localDevice, byte[] rcclId);
 
+    /** One GPU, lists for the listed users alone (fy_rm2_prepare + fy_rm2_score_users): the configuration key usersFile. */
+    private static native long runUsers(double lambda, int numberOfItems, int numberOfRecommendations, int filterUsers,
+            int numberOfClusters, long nnz, ByteBuffer user, ByteBuffer item, ByteBuffer score, long nMap,
+            ByteBuffer mapUser, ByteBuffer mapCluster, ByteBuffer clusterCount, int localDevice, long nUsers, ByteBuffer users);
+
+    /** usersFile: one id per line; a line that is not an int is skipped (like the reference's "itemsFile line ignored") */
+    public static final String USERS_FILE_NAME = "usersFile";
+
+    private static ByteBuffer readIds(final String path) throws java.io.IOException {
+        final java.util.ArrayList<Integer> ids = new java.util.ArrayList<Integer>();
+        try (java.io.BufferedReader in = new java.io.BufferedReader(new java.io.FileReader(path))) {
+            for (String line = in.readLine(); line != null; line = in.readLine()) {
+                try {
+                    ids.add(Integer.parseInt(line.trim()));
+                } catch (NumberFormatException e) {
+                    // skipped
+                }
+            }
+        }
+        final ByteBuffer b = ByteBuffer.allocateDirect(4 * Math.max(1, ids.size())).order(ByteOrder.nativeOrder());
+        for (int k = 0; k < ids.size(); k++) {
+            b.putInt(4 * k, ids.get(k));
+        }
+        b.limit(4 * ids.size());
+        return b;
+    }
+
     /** fy_rccl_unique_id: called by rank 0 only */
     public static native byte[] rcclUniqueId();
 
@@ -105,7 +132,17 @@ public class NativeRM2Job extends AbstractJob {
         }
         final int rank = conf.getInt(RANK_NAME, 0), world = conf.getInt(WORLD_NAME, 1);
         // run() throws RuntimeException("RM2 failed!: ...") exactly where RM2Job threw "<jobName> failed!"
-        final long h = run(Double.valueOf(conf.get(RM2Job.LAMBDA_NAME)), conf.getInt(RMRecommenderDriver.numberOfItems, -1),
+        final String usersFile = conf.get(USERS_FILE_NAME);
+        if (usersFile != null && world > 1) {
+            throw new IllegalArgumentException("usersFile cannot be combined with filmyou.world > 1 (the collective path serves no requests)");
+        }
+        final ByteBuffer ids = usersFile != null ? readIds(usersFile) : null;
+        final long h = usersFile != null
+                ? runUsers(Double.valueOf(conf.get(RM2Job.LAMBDA_NAME)), conf.getInt(RMRecommenderDriver.numberOfItems, -1),
+                        conf.getInt(RMRecommenderDriver.numberOfRecommendations, -1), conf.getInt(RMRecommenderDriver.filterUsers, 0),
+                        numberOfClusters, nnz, coo[0], coo[1], coo[2], nMap, map[0], map[1], clusterCount,
+                        conf.getInt("filmyou.localDevice", 0), ids.limit() / 4, ids)
+                : run(Double.valueOf(conf.get(RM2Job.LAMBDA_NAME)), conf.getInt(RMRecommenderDriver.numberOfItems, -1),
                 conf.getInt(RMRecommenderDriver.numberOfRecommendations, -1), conf.getInt(RMRecommenderDriver.filterUsers, 0),
                 numberOfClusters, nnz, coo[0], coo[1], coo[2], nMap, map[0], map[1], clusterCount, rank, world,
                 conf.getInt("filmyou.localDevice", rank), world > 1 ? unhex(conf.get(RCCL_ID_NAME)) : null);

@@ -91,6 +91,35 @@ JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_run(JNIEnv* env,
     return reinterpret_cast<jlong>(out);
 }
 
+// private static native long runUsers(... , int localDevice, long nUsers, ByteBuffer users): one GPU, fy_rm2_score_users
+JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_runUsers(JNIEnv* env, jclass, jdouble lambda, jint numberOfItems,
+                                                                           jint numberOfRecommendations, jint filterUsers,
+                                                                           jint numberOfClusters, jlong nnz, jobject user, jobject item,
+                                                                           jobject score, jlong nMap, jobject mapUser,
+                                                                           jobject mapCluster, jobject clusterCount, jint localDevice,
+                                                                           jlong nUsers, jobject users) {
+    fy_rm2_params p;
+    std::memset(&p, 0, sizeof p);
+    p.lambda = lambda;
+    p.number_of_items = numberOfItems;
+    p.number_of_recommendations = numberOfRecommendations;
+    p.filter_users = filterUsers;
+    p.number_of_clusters = numberOfClusters;
+    p.rank = 0;
+    p.world = 1;
+    JniResult* out = new JniResult;
+    fy_rm2_job* job = nullptr;
+    int rc = fy_context_create(localDevice, &out->ctx);
+    if (rc == FY_OK) rc = fy_ratings_create(out->ctx, nnz, direct<int32_t>(env, user), direct<int32_t>(env, item), direct<float>(env, score), FY_HOST, &out->ratings);
+    if (rc == FY_OK) rc = fy_rm2_prepare(out->ctx, &p, out->ratings, nMap, direct<int32_t>(env, mapUser), direct<int32_t>(env, mapCluster),
+                                         direct<int32_t>(env, clusterCount), &job);
+    const fy_rm2_request rq{nUsers, nUsers > 0 ? direct<int32_t>(env, users) : nullptr};
+    if (rc == FY_OK) rc = fy_rm2_score_users(job, &rq, &out->res);
+    if (job) fy_rm2_job_destroy(job);
+    if (rc != FY_OK) { release(out); throw_runtime(env, "RM2"); return 0; }
+    return reinterpret_cast<jlong>(out);
+}
+
 // public static native byte[] rcclUniqueId();
 JNIEXPORT jbyteArray JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_rcclUniqueId(JNIEnv* env, jclass) {
     char id[128];

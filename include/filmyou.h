@@ -163,6 +163,36 @@ void fy_rccl_detach_context(fy_rccl*);    /* ... unless this was called: the con
 int fy_rm2_score(fy_rm2_job*, fy_result** out);
 void fy_rm2_job_destroy(fy_rm2_job*);
 
+/* RM2 on request: the lists of the named users alone ("these users just rated something"), with the work sized by the request.
+ * Works on a prepared job whose global statistics are in place (after fy_rm2_set_global_stats, or world == 1); may be called any
+ * number of times on one job, before or after fy_rm2_score, and leaves the job as it was.  The result holds exactly the rows
+ * fy_rm2_score of the same job would emit for the listed users: filterUsers, "no candidate left -> no list",
+ * numberOfRecommendations, the (float) cast, -inf at lambda = 0 or U_c = 1, the cluster column, ties by ascending item id, users in
+ * the order of the unrestricted job, best first.  `users`: HOST array of raw ids in any order; a duplicate counts once; an id
+ * without a kept rating, an id outside the data and a negative id are passed over without an error; n_users == 0 gives an empty
+ * result; users == NULL with n_users > 0 is FY_ERR_INVALID_ARGUMENT.  (rank, world) of the job shard the requested users as they
+ * shard the full job's users (replicated and sharded prep).  A job with collectives installed answers FY_ERR_UNSUPPORTED.
+ * Per cluster that holds a requested user only the rows G[j][.] of the co-rating matrix with j rated by a requested user are
+ * formed -- an fp64 slab in HBM, bit-reproducible, at most fy_rm2_params::workspace_bytes at a time (the users of a cluster are
+ * taken in batches; one user whose own rows do not fit fails with FY_ERR_OUT_OF_MEMORY) -- and the whole pass is fp64 (DESIGN.md
+ * section 2b).  A cluster of which more than FY_REQ_FULL_SHARE of the users is asked for (default: never) is scored by the full pass instead,
+ * which runs the rank's whole full job once (full_pass_clusters).
+ * fy_result_stats of the result: users_scored, recs, log_terms (of the requested users), pair_contribs (products the slab kernel
+ * accumulated), cooc_matrix_bytes (slab bytes written), ms_tables, ms_cooc, ms_score, ms_topn, ms_total. */
+typedef struct { int64_t n_users; const int32_t* users; } fy_rm2_request;   /* HOST, raw ids, any order */
+int fy_rm2_score_users(fy_rm2_job*, const fy_rm2_request*, fy_result** out);
+typedef struct {
+    int64_t users_asked;         /* n_users of the request */
+    int64_t users_known;         /* distinct requested users with a kept rating that this rank emits lists for */
+    int64_t clusters_touched;    /* clusters that hold one of them */
+    int64_t batches;             /* slabs built */
+    int64_t slab_rows;           /* rows of all slabs (sum over the batches of |J|) */
+    int64_t slab_bytes_peak;     /* largest slab */
+    int64_t slab_pair_contribs;  /* sum over the slab rows j of sum over the raters v of j of n_v */
+    int64_t full_pass_clusters;  /* touched clusters scored by the full pass with the unrequested rows dropped */
+} fy_rm2_request_stats;
+int fy_result_request_stats(fy_result*, fy_rm2_request_stats* out);          /* FY_ERR_STATE on any other result */
+
 /* One call = one complete single-GPU job on host buffers (what the JNI shim calls): context on device 0. */
 int fy_rm2_run(const fy_rm2_params*, int64_t nnz, const int32_t* user, const int32_t* item, const float* score,
                int64_t n_map, const int32_t* map_user, const int32_t* map_cluster, const int32_t* cluster_count,
