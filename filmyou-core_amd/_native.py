@@ -12,15 +12,15 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_itemsim.hip", "fy_itemcf.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_refine.hpp"]  # fy_itemcf.hip uses fy_prep.hpp / fy_rm2.hpp
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemcf.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_ratings_update.hpp", "fy_refine.hpp"]  # fy_itemcf.hip uses fy_prep.hpp / fy_rm2.hpp
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
 # every symbol include/filmyou.h declares (tests check the library exports exactly these)
 SYMBOLS = [
     "fy_abi_version", "fy_last_error", "fy_context_create", "fy_context_destroy", "fy_context_synchronize", "fy_context_reload_tuning", "fy_context_inject_alloc_failure",
-    "fy_context_stream", "fy_ratings_create", "fy_ratings_destroy", "fy_ratings_nnz", "fy_ratings_drop_cache", "fy_rm2_prepare",
+    "fy_context_stream", "fy_ratings_create", "fy_ratings_destroy", "fy_ratings_nnz", "fy_ratings_drop_cache", "fy_ratings_apply", "fy_ratings_copy_out", "fy_rm2_prepare",
     "fy_rm2_partial_stats", "fy_rm2_stats_layout", "fy_rm2_set_global_stats", "fy_rm2_set_collectives", "fy_rccl_unique_id", "fy_rccl_create", "fy_rccl_collectives", "fy_rccl_counters", "fy_rccl_destroy", "fy_rccl_detach_context", "fy_rm2_score", "fy_rm2_score_users", "fy_result_request_stats", "fy_rm2_job_destroy", "fy_rm2_run",
     "fy_itemsim_build", "fy_itemsim_run", "fy_itemcf_recommend", "fy_itemcf_recommend_filtered", "fy_ratings_shifted", "fy_itemsim_pairs",
     "fy_simpairs_write_text", "fy_idfile_read", "fy_cluster_assign", "fy_nmf_factorize", "fy_result_size", "fy_result_key0", "fy_result_key1", "fy_result_value",
@@ -171,6 +171,14 @@ class RM2RequestStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RatingsUpdateStats(C.Structure):
+    _fields_ = [("n_writes", C.c_int64), ("n_superseded", C.c_int64), ("n_replaced", C.c_int64), ("n_inserted", C.c_int64),
+                ("n_deleted", C.c_int64), ("n_delete_missed", C.c_int64), ("n_source_dropped", C.c_int64), ("nnz_out", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("nnz", C.c_int64), ("n_users", C.c_int64), ("n_items", C.c_int64),
                 ("n_clusters_nonempty", C.c_int64), ("users_scored", C.c_int64), ("recs", C.c_int64),
@@ -227,6 +235,8 @@ def load():
     L.fy_ratings_nnz.restype = i64
     L.fy_ratings_drop_cache.argtypes = [vp]
     L.fy_ratings_drop_cache.restype = None
+    L.fy_ratings_apply.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_int, pvp, C.POINTER(RatingsUpdateStats)]
+    L.fy_ratings_copy_out.argtypes = [vp, vp, vp, vp]
     L.fy_rm2_prepare.argtypes = [vp, C.POINTER(RM2Params), vp, i64, vp, vp, vp, pvp]
     L.fy_rm2_partial_stats.argtypes = [vp, pvp, C.POINTER(i64)]
     L.fy_rm2_set_global_stats.argtypes = [vp, vp, i32]

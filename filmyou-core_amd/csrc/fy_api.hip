@@ -8,6 +8,7 @@
 
 #include "fy_prep.hpp"
 #include "fy_rm2.hpp"
+#include "fy_ratings_update.hpp"
 #include "fy_rm2_request.hpp"
 
 namespace fy {
@@ -72,6 +73,7 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_MAX_SURV_FRAC")) { double v = atof(e); if (v >= 0.0) t.max_surv_frac = v; }
     if (const char* e = getenv("FY_REQ_FULL_SHARE")) { double v = atof(e); if (v >= 0.0) t.req_full_share = v; }
     if (const char* e = getenv("FY_REQ_CHUNK")) { int v = atoi(e); if (v >= 64 && v <= 16384 && v % 64 == 0) t.req_chunk = v; }
+    if (const char* e = getenv("FY_UPD_LDS_KEYS")) { int v = atoi(e); if (v >= 0 && v <= fy::UPD_LDS_KEYS_MAX) t.upd_lds_keys = v; }
     if (const char* e = getenv("FY_ISIM_HEAVY")) t.isim_heavy = std::max(0, atoi(e));
     if (const char* e = getenv("FY_ISIM_GRAM")) t.isim_gram = atoi(e) != 0;
     if (const char* e = getenv("FY_ISIM_GRAM_MIN_ITEMS")) t.isim_gram_min_items = std::max(0, atoi(e));
@@ -227,6 +229,33 @@ void fy_ratings_drop_cache(fy_ratings* r) {
     }
     if (old && r->ctx) (void)hipStreamSynchronize(r->ctx->stream);     // nothing queued may still read what is released next
     old.reset();
+}
+
+int fy_ratings_apply(fy_context* c, const fy_ratings* r, int64_t n, const int32_t* user, const int32_t* item, const float* score,
+                     const uint8_t* remove_or_null, int location, fy_ratings** out, fy_ratings_update_stats* stats_or_null) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (n < 0 || (n > 0 && (!user || !item || !score))) { set_error("write arrays are NULL or n < 0"); return FY_ERR_INVALID_ARGUMENT; }
+    if (location != FY_HOST && location != FY_DEVICE) { set_error("location must be FY_HOST or FY_DEVICE"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!c || !r) { set_error("context or ratings is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->ctx != &c->c) { set_error("ratings belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::ratings_apply(&c->c, r, n, user, item, score, remove_or_null, location, stats_or_null);
+    FY_CATCH
+}
+
+int fy_ratings_copy_out(const fy_ratings* r, int32_t* user, int32_t* item, float* score) {
+    if (!r) { set_error("ratings is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->nnz > 0 && (!user || !item || !score)) { set_error("output arrays are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->nnz == 0) return FY_OK;
+    FY_TRY
+    select_device(r->ctx);
+    fy::d2h(r->ctx, user, r->user.get(), (size_t)r->nnz);
+    fy::d2h(r->ctx, item, r->item.get(), (size_t)r->nnz);
+    fy::d2h(r->ctx, score, r->score.get(), (size_t)r->nnz);
+    fy::sync(r->ctx);
+    FY_CATCH
 }
 
 // ---------------------------------------------------------------- RM2

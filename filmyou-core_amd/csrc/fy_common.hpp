@@ -105,6 +105,9 @@ struct Tuning {
                                        // unrequested rows are dropped (0 = every touched cluster, >= 1 = never).  Not measured yet ("RM2 on
                                        // request"), so the default never falls back; ONE cluster that does costs the rank's whole full job
     int req_chunk = 8192;              // FY_REQ_CHUNK: columns (64-bit LDS accumulators) a workgroup of the slab build owns
+    // ratings update (fy_ratings_update.hip)
+    int upd_lds_keys = 4096;           // FY_UPD_LDS_KEYS: a batch of at most this many distinct keys is searched in LDS (32 KiB of keys beside the 32 KiB
+                                       // user bitmap: two workgroups per CU), a larger one in global memory (0 = always); at most 8192
     // item-item similarity build (fy_itemsim.hip)
     int isim_heavy = 4096;             // row-at-a-time kernel: raters above which a row is split by column chunk
     int isim_gram = -1;                // symmetric Gram + band sweep: -1 = by size (cosine, >= isim_gram_min_items items), 0 = never, 1 = whenever possible

@@ -196,6 +196,47 @@ class Ratings:
         _check(self._lib.fy_ratings_shifted(self.ctx._h, self._h, float(shift), C.byref(h)))
         return Ratings._adopt(self.ctx, h, self.nnz)
 
+    def updated(self, user, item, score, remove=None):
+        """fy_ratings_apply: a new Ratings from this one and a batch of writes (user, item, score[, remove]) taken in order, with
+        the ratings table's semantics -- the last write per (user, item) counts, a write replaces the stored row, a non-zero
+        `remove` entry deletes it (include/filmyou.h states the rules).  Numpy arrays or torch tensors on the context's GPU
+        (remove: uint8 / bool).  This object is only read: what the jobs kept on it stays valid; the new object starts with
+        none.  The counters are in ``.update_stats`` of the result."""
+        self.ctx.sync_tuning()
+        if _is_torch_tensor(user):
+            import torch
+            assert user.is_cuda and item.is_cuda and score.is_cuda and (remove is None or remove.is_cuda), "device tensors expected"
+            assert user.dtype == torch.int32 and item.dtype == torch.int32 and score.dtype == torch.float32
+            user, item, score = user.contiguous(), item.contiguous(), score.contiguous()
+            if remove is not None:
+                remove = (remove != 0).to(torch.uint8).contiguous()
+            torch.cuda.current_stream(user.device).synchronize()   # producer stream != the context's stream
+            n, loc = user.numel(), 1
+            ptrs = (user.data_ptr(), item.data_ptr(), score.data_ptr(), remove.data_ptr() if remove is not None else None)
+            n_remove = n if remove is None else remove.numel()
+        else:
+            user = np.ascontiguousarray(user, dtype=np.int32)
+            item = np.ascontiguousarray(item, dtype=np.int32)
+            score = np.ascontiguousarray(score, dtype=np.float32)
+            if remove is not None:
+                remove = np.ascontiguousarray(np.asarray(remove) != 0, dtype=np.uint8)
+            n, loc = len(user), 0
+            ptrs = (user.ctypes.data, item.ctypes.data, score.ctypes.data, remove.ctypes.data if remove is not None else None)
+            n_remove = n if remove is None else len(remove)
+        assert n == len(item) == len(score) == n_remove
+        h, st = C.c_void_p(), _native.RatingsUpdateStats()
+        _check(self._lib.fy_ratings_apply(self.ctx._h, self._h, n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], loc, C.byref(h), C.byref(st)))
+        r = Ratings._adopt(self.ctx, h, st.nnz_out)
+        r.update_stats = st.as_dict()
+        return r
+
+    def to_host(self):
+        """fy_ratings_copy_out: (user, item, score) numpy arrays of the COO as it lives in HBM, in its order."""
+        n = int(self._lib.fy_ratings_nnz(self._h))
+        user, item, score = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        _check(self._lib.fy_ratings_copy_out(self._h, user.ctypes.data, item.ctypes.data, score.ctypes.data))
+        return user, item, score
+
     def drop_cache(self):
         """fy_ratings_drop_cache: releases what earlier jobs kept on this object (CSR / CSC, statistics, row-kernel tables)."""
         if getattr(self, "_h", None) and self.ctx._h:

@@ -65,6 +65,45 @@ struct Clustering {   // the `clustering` and `clusteringCount` side files
     std::vector<int32_t> count;   // optional, numberOfClusters entries
 };
 
+// A batch of writes against the ratings table, in order (fy_ratings_apply): put = INSERT / UPDATE of (user, item), del = DELETE.
+struct Writes {
+    std::vector<int32_t> user, item;
+    std::vector<float> score;
+    std::vector<uint8_t> remove;
+    void put(int32_t u, int32_t i, float s) { user.push_back(u); item.push_back(i); score.push_back(s); remove.push_back(0); }
+    void del(int32_t u, int32_t i) { user.push_back(u); item.push_back(i); score.push_back(0.0f); remove.push_back(1); }
+};
+
+// The ratings after the batch, with the table's semantics (include/filmyou.h: the last write per key counts, survivors in source
+// order, then the live writes in batch order): context, ratings, fy_ratings_apply, the COO copied back.  A host that keeps its
+// fy_ratings resident calls fy_ratings_apply itself and never moves the old ratings; this mirror works on host records like the
+// job classes below.  Throws std::runtime_error("applyWrites failed!: ...").
+inline Ratings applyWrites(const Ratings& source, const Writes& w, fy_ratings_update_stats* stats = nullptr, int device = 0) {
+    fy_context* ctx = nullptr;
+    fy_ratings *src = nullptr, *upd = nullptr;
+    auto fail = [&](const char* what) {
+        const std::string msg = std::string("applyWrites failed!: ") + what + ": " + fy_last_error();
+        if (upd) fy_ratings_destroy(upd);
+        if (src) fy_ratings_destroy(src);
+        if (ctx) fy_context_destroy(ctx);
+        throw std::runtime_error(msg);
+    };
+    if (w.item.size() != w.user.size() || w.score.size() != w.user.size() || w.remove.size() != w.user.size())
+        throw std::invalid_argument("applyWrites: the arrays of the batch differ in length");
+    if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+    if (fy_ratings_create(ctx, (int64_t)source.user.size(), source.user.data(), source.item.data(), source.score.data(), FY_HOST, &src) != FY_OK) fail("ratings");
+    if (fy_ratings_apply(ctx, src, (int64_t)w.user.size(), w.user.data(), w.item.data(), w.score.data(), w.remove.data(), FY_HOST, &upd, stats) != FY_OK)
+        fail("apply");
+    Ratings out;
+    const size_t n = (size_t)fy_ratings_nnz(upd);
+    out.user.resize(n); out.item.resize(n); out.score.resize(n);
+    if (fy_ratings_copy_out(upd, out.user.data(), out.item.data(), out.score.data()) != FY_OK) fail("copy_out");
+    fy_ratings_destroy(upd);
+    fy_ratings_destroy(src);
+    fy_context_destroy(ctx);
+    return out;
+}
+
 // writePreference(context, userId, itemId, score, cluster)
 using PreferenceSink = std::function<void(int32_t user, int32_t item, float score, int32_t cluster)>;
 

@@ -33,6 +33,9 @@ int main(int argc, char** argv) {
     const char* users_file = nullptr;
     if (argc == 9 && strcmp(argv[1], "--users") == 0) { users_file = argv[2]; argv += 2; argc -= 2; }
     if (argc == 8 && strcmp(argv[1], "--rccl") == 0) { rccl = true; argv++; argc--; }
+    // rm2_main --writes <writes.txt> <ratings.txt> ... : fy::host::applyWrites first ("user item score remove" per line, in order), the job on the result
+    const char* writes_file = nullptr;
+    if (argc == 9 && !users_file && strcmp(argv[1], "--writes") == 0) { writes_file = argv[2]; argv += 2; argc -= 2; }
     if (argc != 7) { fprintf(stderr, "usage: %s ratings clustering lambda numberOfItems numberOfClusters numberOfRecommendations\n", argv[0]); return 2; }
     fy::host::Ratings r;
     fy::host::Clustering c;
@@ -54,6 +57,19 @@ int main(int argc, char** argv) {
     conf.set("numberOfClusters", argv[5]);
     conf.set("numberOfRecommendations", argv[6]);
     try {
+        if (writes_file) {
+            fy::host::Writes w;
+            f = fopen(writes_file, "r");
+            if (!f) { perror(writes_file); return 2; }
+            int gone;
+            while (fscanf(f, "%d %d %f %d", &u, &i, &s, &gone) == 4) { if (gone) w.del(u, i); else w.put(u, i, s); }
+            fclose(f);
+            fy_ratings_update_stats us{};
+            r = fy::host::applyWrites(r, w, &us);
+            fprintf(stderr, "writes %lld superseded %lld replaced %lld inserted %lld deleted %lld delete_missed %lld source_dropped %lld nnz_out %lld\n",
+                    (long long)us.n_writes, (long long)us.n_superseded, (long long)us.n_replaced, (long long)us.n_inserted, (long long)us.n_deleted,
+                    (long long)us.n_delete_missed, (long long)us.n_source_dropped, (long long)us.nnz_out);
+        }
         if (users_file) conf.set("usersFile", users_file);      // (the job copies its configuration)
         fy::host::RM2Job job(conf);
         auto sink = [](int32_t user, int32_t item, float score, int32_t cluster) { printf("%d %d %.9g %d\n", user, item, score, cluster); };

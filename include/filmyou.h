@@ -88,6 +88,43 @@ int64_t fy_ratings_nnz(const fy_ratings*);
  * job is ~2.5 GB).  Jobs over ONE ratings object must not run concurrently; distinct ratings objects (and contexts) may. */
 void fy_ratings_drop_cache(fy_ratings*);
 
+/* Ratings that take writes.  The reference's table is ratings(user int, item int, score float, PRIMARY KEY (user, item)): in CQL a
+ * write to an existing key replaces the row and a DELETE removes it.  fy_ratings_apply makes a NEW, independent ratings object from
+ * `source` and a batch of n writes (user, item, score, remove) taken in order; the batch is resolved on the GPU (csrc/
+ * fy_ratings_update.hip) and the source is neither uploaded again nor modified: what the jobs kept on it stays
+ * valid, the new object starts with none.  `remove_or_null`: n bytes, NULL = no deletes; a non-zero byte makes that write a delete
+ * of its key, whose score is ignored.
+ *   1. Later writes to one (user, item) supersede earlier ones of the batch: only the LAST write per key counts -- the batch equals
+ *      replaying it row by row against the table.
+ *   2. Every entry of the source whose key appears anywhere in the batch is dropped, also when the key's last write is a delete;
+ *      several source entries with that key are all dropped (a write cures an old duplicate).
+ *   3. The result is the surviving source entries IN THEIR SOURCE ORDER, followed by the last writes that are not deletes, in the
+ *      order of their positions in the batch.
+ *   4. Scores are stored as given, exactly as fy_ratings_create stores them: a score <= 0 is a stored rating, not a delete (the RM2
+ *      mappers' score > 0 filter and the item-CF ratingShift treat it as they do today); NaN and negative ids get nothing at this
+ *      point, as in fy_ratings_create, and the jobs report what they report today.  Keys compare as 64 bits made of the two 32-bit
+ *      patterns, so any id is a key.
+ *   5. The id bounds kept with the new object are those of its own contents.
+ *   6. An empty batch gives a copy; an empty source gives the batch resolved by rule 1.
+ * `location` (FY_HOST / FY_DEVICE) says where user / item / score / remove_or_null live, as in fy_ratings_create; the arrays may be
+ * freed when the call returns.  n > 2^31 - 1 is FY_ERR_UNSUPPORTED.  On any failure *out is NULL and the source is intact.
+ * Counters (stats_or_null):
+ *   n_writes          n
+ *   n_superseded      writes that are not the last of their key
+ *   n_replaced        last non-delete writes whose key was in the source
+ *   n_inserted        last non-delete writes whose key was not in the source
+ *   n_deleted         last deletes whose key was in the source
+ *   n_delete_missed   last deletes whose key was not in the source
+ *   n_source_dropped  source entries dropped (more than n_replaced + n_deleted only when the source held duplicates)
+ *   nnz_out           entries of the result = nnz of the source - n_source_dropped + n_replaced + n_inserted */
+typedef struct { int64_t n_writes, n_superseded, n_replaced, n_inserted, n_deleted, n_delete_missed,
+                 n_source_dropped, nnz_out; } fy_ratings_update_stats;
+int fy_ratings_apply(fy_context*, const fy_ratings* source, int64_t n, const int32_t* user, const int32_t* item,
+                     const float* score, const uint8_t* remove_or_null, int location,
+                     fy_ratings** out, fy_ratings_update_stats* stats_or_null);
+/* The COO as it lives in HBM, copied to HOST arrays of fy_ratings_nnz entries each (synchronises the ratings' context). */
+int fy_ratings_copy_out(const fy_ratings*, int32_t* user, int32_t* item, float* score);
+
 /* ------------------------------------------------------------------ RM2 job
  * Field names follow the Hadoop Configuration keys of M/rmrecommender/RMRecommenderDriver.java:49-120. */
 typedef struct {
