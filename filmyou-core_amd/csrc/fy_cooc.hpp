@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "fy_common.hpp"
+#include "fy_rm2_plan.hpp"   // pick_chunks
 
 namespace fy {
 
@@ -423,19 +424,6 @@ void build_chunk_offsets(Context* ctx, const int32_t* rowptr, const int32_t* csr
 // 256-column blocks up to the padded row length, which overshoots a chunk whose width is not a multiple of 256 by < 256
 __host__ __device__ inline int cooc_lds_columns(int CH) { return (CH % 256 == 0) ? CH : ((CH + 255) / 256) * 256 + 256; }
 
-// picks the chunk width for a cluster with Ic items: whole row when it fits the LDS budget.  Chunks are multiples of 256
-// columns whenever there are several (a wave of the epilogue then owns exactly one 256-column block, fy_rm2.hip).
-inline void pick_chunks(int32_t Ic, int32_t max_ch, int32_t& CH, int32_t& nch) {
-    if (Ic <= max_ch) {
-        CH = (int32_t)round_up(Ic > 0 ? Ic : 1, 64);
-        nch = 1;
-    } else {
-        const int32_t cap = max_ch >= 256 ? (max_ch / 256) * 256 : max_ch;
-        const int32_t gran = max_ch >= 256 ? 256 : 64;
-        nch = (int32_t)ceil_div(Ic, cap);
-        CH = (int32_t)std::min<int64_t>(cap, round_up(ceil_div(Ic, nch), gran));
-        nch = (int32_t)ceil_div(Ic, CH);
-    }
-}
+// (pick_chunks, the chunk width of a cluster: fy_rm2_plan.hpp)
 
 }  // namespace fy

@@ -21,6 +21,7 @@
 #include "fy_prep.hpp"
 #include <chrono>
 #include "fy_rm2.hpp"
+#include "fy_rm2_plan.hpp"
 #include "fy_rm2_request.hpp"
 
 namespace fy {
@@ -1444,21 +1445,10 @@ static void owner_range(const fy_rm2_job* J, int k, int32_t& lo, int32_t& hi) {
     hi = (int32_t)(n * (k + 1) / W);
 }
 
-// launch-shape knobs: fy::Tuning (fy_common.hpp), read from the environment ONCE when the context is created
+// launch-shape knobs: fy::Tuning (fy_tuning.hpp), read from the environment ONCE when the context is created
 // (fy_context_create / fy_context_reload_tuning in fy_api.hip) -- no job reads the environment.
 using ScoreTune = fy::Tuning;
-static inline const ScoreTune& score_tune(const Context* ctx) { return ctx->tune; }
 
-// Exponent k of the fixed-point scale 2^k of a cluster (CoocArgs::fx_scale): the largest k with (largest contribution) * 2^k < 2^51
-// and (largest possible Gram entry) * 2^k < 2^62, from the cluster's bounds (sum and maximum of the segment weights r / s^2 per
-// item, largest rating).  Returns a negative number when the bounds are unusable (the fp64 path is taken then).
-static int fx_exponent(const float* bounds3) {
-    const double wsum = bounds3[0], wmax = bounds3[1], rmax = bounds3[2];
-    if (!(wsum > 0.0) || !(wmax > 0.0) || !(rmax > 0.0) || !std::isfinite(wsum * rmax)) return -1;
-    const int k1 = 51 - (std::ilogb(wmax * rmax) + 1), k2 = 62 - (std::ilogb(wsum * rmax) + 1);
-    const int k = std::min(std::min(k1, k2), 1000);
-    return k >= 24 ? k : -1;
-}
 
 // launch shape of the RM2 row kernel: as many workgroups per CU as the LDS accumulators allow (fp32: two for ML-25M's
 // 19 712-column chunks), 2048 threads per CU at most
@@ -1503,7 +1493,7 @@ static void launch_cooc_rm2(Context* ctx, const ScoreTune& tune, bool use_pk, co
 // fixed-point scale cannot be used (the caller keeps its own path); everything is queued on the context's stream.
 bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, const float* bounds3, float* G, int64_t ldm, double* ms_tables,
                          double* ms_walk, const float* csr_ones) {
-    const ScoreTune tune = score_tune(ctx);
+    const ScoreTune tune = ctx->tune;
     const int32_t Ic = P.nP;
     // (csr_ones: both sides of every product are 1 -- exact integers whatever the ratings are)
     if (P.K != 1 || (!csr_ones && (!P.ratings_fp16_exact || !P.ratings_positive)) || Ic <= 0) return false;
@@ -1600,52 +1590,127 @@ static void launch_cooc_rm2_multi(Context* ctx, const ScoreTune& tune, std::vect
     FY_KERNEL_CHECK();
 }
 
-// user slices (workgroups per column chunk) of a scoring launch over `nb` users and `chunks` column chunks: a wave walks up to
-// users_per_wave users, but a small batch (one cluster of many: 3 250 users at 50 clusters) is cut finer so that the launch
-// still has ~8 workgroups per CU -- with 16 users per wave such a launch had 102 workgroups for 256 CUs (1.4 ms per cluster
-// for work that takes 0.14 ms of the one-cluster job)
-static int score_slices(const Context* ctx, const ScoreTune& tune, int64_t nb, int chunks) {
-    const int64_t coarse = ceil_div(nb, 4 * (int64_t)tune.users_per_wave), finest = ceil_div(nb, 4);
-    const int64_t fill = ceil_div(8 * (int64_t)ctx->num_cus, std::max(1, chunks));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(tune.max_slices, std::min(finest, std::max(coarse, fill))));
-}
+// the host-side plan (fy_rm2_plan.hpp) states the kernels' limits for itself: the two sides must agree
+static_assert(PLAN_TOPN_MAX == TOPN_MAX && PLAN_TOPN_SAMPLE == TOPN_SAMPLE && PLAN_TOPN_LONG == TOPN_LONG && PLAN_SEED_CHUNKS_MAX == SEED_CHUNKS_MAX &&
+                  PLAN_PRUNE_BLOCK == PRUNE_BLOCK && PLAN_STRAY_UCAP == STRAY_UCAP,
+              "fy_rm2_plan.hpp and fy_rm2_kernels.hpp disagree about a limit");
 
-// Super-blocks of the bound pass (k_score_sup): the fine 256-column blocks [seed_blocks, nblk) in at most 64 groups -- the first 48
-// one block each (that is where survivors are: the columns are in popularity order and RM2 scores fall steeply with it), the rest
-// in 16 groups of growing width.  first[s] .. first[s + 1] are the fine blocks of group s.
-static void sup_block_map(int seed_blocks, int nblk, std::vector<int32_t>& first) {
-    first.clear();
-    const int R = std::max(0, nblk - seed_blocks);
-    if (R <= 64) {
-        for (int s = 0; s <= R; s++) first.push_back(seed_blocks + s);
-        return;
-    }
-    for (int s = 0; s < 48; s++) first.push_back(seed_blocks + s);
-    const int rem = R - 48;
-    int64_t cum = 0;
-    for (int k = 0; k < 16; k++) {            // widths ~ (k + 1): 1 + 2 + .. + 16 = 136 parts
-        first.push_back(seed_blocks + 48 + (int32_t)((int64_t)rem * cum / 136));
-        cum += k + 1;
-    }
-    first.push_back(nblk);
-    for (size_t k = 1; k < first.size(); k++) first[k] = std::max(first[k], first[k - 1]);      // (monotone; a group may be empty)
-}
+// ================================================================ what the flows of one fy_rm2_score share
+// scratch of one lane (a HIP stream the clusters of a job are spread over), or -- two-phase panel mode -- of one cluster
+struct Lane {
+    hipStream_t st;
+    DevBuf<float> M, S;
+    DevBuf<int32_t> overflow, any_overflow;
+    // branch and bound
+    DevBuf<float> Bmax, amax, bmax, UB, tau;
+    DevBuf<float> Gp, Bmax64, amax64, bmax64;    // column-panel mode
+    DevBuf<uint32_t> Brep;
+    DevBuf<uint16_t> surv;
+    DevBuf<uint8_t> surv_mask;     // panel mode: which 64-column sub-blocks of a surviving block passed the bound
+    DevBuf<int2> strayT;           // co-rater tables of k_score_stray
+    DevBuf<int2> stray_items;
+    DevBuf<int32_t> n_heavy;       // k_count_heavy
+    DevBuf<int32_t> need;          // lazy mirror: column blocks with survivors
+    DevBuf<float> Bsup, asup, bsupb, UBs;      // super-block bounds (k_score_sup)
+    DevBuf<double> head32, tail32;             // unrounded fp64 rows / columns the refinement pass reads (k_refine_rows)
+    DevBuf<int32_t> colmap;
+    DevBuf<int32_t> sup_first;
+    DevBuf<int32_t> n_quads, quad_prefix;
+    DevBuf<char> scan_tmp;         // temporary storage of the lane's scans
+    DevBuf<int2> item_seg, item_seg_t;      // (_t: the tail-row bound launch of a cluster whose row kernels are batched)
+    DevBuf<int32_t> item_id, item_id_t;
+    DevBuf<float> Ssurv;   // packed scores of the surviving blocks (pruned clusters)
+};
 
-// one cluster's launch plan
-struct Plan {
-    int c;
-    int32_t Uc, sbase, pbase, Ic, a, b, CH, nch, q0, nq;
-    int64_t ldm, B;
-    bool pack24, prune, coop, half, panel;
-    bool psym;       // symmetric panel mode: head rows x head columns by a half walk + mirror, head rows x tail columns not at all (k_panel_colmax)
-    bool flat;       // one of many small unpruned clusters whose kernels run in ONE launch each (fy_rm2_kernels.hpp: FlatDesc)
-    int32_t panel_cols, nsub;
-    int64_t ldb64;
-    // panel mode: the rows from p_eff on ("tail rows") are walked only over their first tail_chunks chunks (= the columns in
-    // front of p_eff, a chunk boundary behind the panel); their block bounds behind p_eff come from k_tail_blocks' CSR
-    int32_t tail_chunks, p_eff, tail_width;
-    int32_t nblk;
-    int64_t ldb;
+// the per-job device arrays every flow reads (score_preamble builds them, in this order)
+struct JobArrays {
+    DevBuf<double> icoll_mine;           // sharded prep: p(i|C) of this rank's own dense items (the result's itemColl is the global one)
+    DevBuf<double> d_total;
+    DevBuf<double> p_rank;
+    DevBuf<float> a_rank, b_rank32;
+    DevBuf<double2> pb_rank;
+    DevBuf<float> csr_x, csr_e, csr_q;   // per-rating values of the scoring kernels (SideValues)
+    DevBuf<float> d_gscale;
+    DevBuf<int32_t> d_cshift;
+};
+
+// The per-rating values (x, e, q: what the SCORING kernels read): with the packed walk nothing in front of the scoring reads them, and
+// what runs until then -- the table kernels, then the one-cluster job's row kernel with ONE workgroup per CU beside its 157 KB of LDS
+// accumulators -- leaves wave slots and most of the memory system idle.  They are computed on a side stream; the plain one-cluster
+// flow joins behind its row kernel, every other flow (several lanes, cooperative ranks, flat batches) before its lanes start.
+class SideValues {
+  public:
+    explicit SideValues(Context* c) : ctx(c) {}
+    SideValues(const SideValues&) = delete;
+    SideValues& operator=(const SideValues&) = delete;
+    ~SideValues() {     // (a failed job: the side kernel must not outlive the arrays it writes)
+        if (!joined && sv) (void)hipStreamSynchronize(sv);
+        if (in) (void)hipEventDestroy(in);
+        if (out) (void)hipEventDestroy(out);
+    }
+    // queues k_csr_values behind what `main_stream` holds: on the side stream when `beside` (and FY_OVERLAP_VALUES), else on main_stream
+    void launch(hipStream_t main_stream, bool beside, const Prepared& P, double lambda, JobArrays& A) {
+        if (launched) return;
+        launched = true;
+        hipStream_t vs = main_stream;
+        if (beside && ctx->tune.overlap_values) {
+            if (ctx->aux.empty()) {
+                hipStream_t x;
+                FY_HIP(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
+                ctx->aux.push_back(x);
+            }
+            sv = ctx->aux[0];
+            FY_HIP(hipEventCreateWithFlags(&in, hipEventDisableTiming));
+            FY_HIP(hipEventCreateWithFlags(&out, hipEventDisableTiming));
+            FY_HIP(hipEventRecord(in, main_stream));
+            FY_HIP(hipStreamWaitEvent(sv, in, 0));
+            vs = sv;
+        }
+        k_csr_values<<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
+                                                                         P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
+                                                                         A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get());
+        FY_KERNEL_CHECK();
+        if (vs != main_stream) {
+            FY_HIP(hipEventRecord(out, sv));
+            joined = false;
+        }
+    }
+    // `s` waits for the values (nothing to do when they were queued on the main stream, or somebody has joined already)
+    void join(hipStream_t s) {
+        if (joined) return;
+        joined = true;
+        FY_HIP(hipStreamWaitEvent(s, out, 0));
+    }
+
+  private:
+    Context* ctx;
+    hipStream_t sv = nullptr;
+    hipEvent_t in = nullptr, out = nullptr;
+    bool launched = false, joined = true;
+};
+
+// Read-only view of one job's scoring state: every flow below (and score_cluster_coop, fy_rm2_coop.hpp) receives it by const
+// reference.  The device arrays are not written through it; the timers and counters it points to are the job's own.
+struct ScoreShared {
+    fy_rm2_job* J;
+    fy_result* R;
+    const ScoreTune* tune;            // the context's knobs, seed_chunks resolved (JobPlan::seed_chunks)
+    const JobPlan* jp;
+    const float *b_rank;              // b_i (fp32), rank order
+    const double *b_rank64, *p_rank;  // b_i and p(i|C) in fp64 (the refinement pass)
+    const float *a_rank, *csc_x, *csr_x, *csr_e, *csr_q;
+    const uint32_t* csr_pk;        // packed CSR for the row kernel (nullptr: csr_idx / csr_x); csc_x then holds x / s_v
+    const int32_t *n_out, *out_off;   // this rank's users, by slot - lo
+    const double* pvpi;               // this rank's users, by slot - lo (the complete value; pv_all below is zero on ranks != 0)
+    int32_t lo;
+    const std::vector<int32_t>* csr_range;     // first / last CSR entry of every planned cluster: [2 * plan], [2 * plan + 1]
+    SideValues* side;
+    EventTimer *t_cooc, *t_score, *t_topn, *t_mirror;
+    unsigned long long* prune_counters;      // [0] surviving blocks, [1] log terms evaluated by the three pruned passes, [2] users sent to k_topn_select, [3] stray blocks (panel mode), [4] bound repairs, [5] list rows scored again by the refinement pass
+    int64_t *blocks_total, *seed_terms_cols, *coop_survived, *fallback_survived;
+    int64_t* coop_pair_contribs;      // cooperative clusters: ordered off-diagonal co-rating pairs of this rank's matrix rows
+    const int32_t* cshift;            // [cluster]: c of the packed matrix format (k_user_meta)
+    const float* gscale;              // [cluster], host: 2^-c
 };
 
 #include "fy_rm2_coop.hpp"   // score_cluster_coop: a cluster scored by all ranks together (part of this translation unit)
@@ -1694,8 +1759,6 @@ static void build_tables_all(Context* ctx, const Prepared& P, const std::vector<
         hsd.push_back(t);
         cnt_total += (int64_t)p.nq + 1;
     }
-    for (size_t pi = 0; pi < np; pi++)
-        if (plans[pi].p_eff < plans[pi].Ic) { /* co_tail offsets were assigned above in plan order */ }
     // (co_tail_off: two entries per slot of every plan with tail rows, in plan order)
     {
         int64_t off = 0;
@@ -1986,6 +2049,1134 @@ static void sharded_side_outputs(fy_rm2_job* J, fy_result* R, const double* d_to
     sync(ctx);      // (the flags and positions are released here)
 }
 
+// ================================================================ fy_rm2_score: one function per flow, in the order they run
+// (fy::rm2_score at the end of this section is the sequence; what to run is decided by plan_job, fy_rm2_plan.hpp)
+
+// ---- 1. p(i|C), per-(cluster,item) statistics, per-rating values
+// (sharded prep: the job's own dense items are this rank's clusters' items; the result's itemColl is the global one, built at the end)
+static void score_preamble(fy_rm2_job* J, fy_result* R, const PackPlan& pack, bool use_pk, JobArrays& A, SideValues& side) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    hipStream_t st = ctx->stream;
+    const int32_t nP = P.nP, nI = P.nI, K = P.K;
+    const double lambda = J->prm.lambda;
+    if (J->S->sharded) A.icoll_mine.alloc(ctx, nI); else R->d_icoll.alloc(ctx, nI);
+    double* const d_icoll = J->S->sharded ? A.icoll_mine.get() : R->d_icoll.get();
+    A.d_total.alloc(ctx, 1);
+    k_item_coll<<<grid_for(nI), 256, 0, st>>>(nI, J->stats.get(), d_icoll, A.d_total.get());
+    FY_KERNEL_CHECK();
+    A.p_rank.alloc(ctx, nP);
+    A.a_rank.alloc(ctx, nP);
+    A.b_rank32.alloc(ctx, nP);
+    A.pb_rank.alloc(ctx, nP);
+    k_pair_p<<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
+                                           A.b_rank32.get(), A.pb_rank.get());
+    FY_KERNEL_CHECK();
+    A.csr_x.alloc(ctx, P.nnz);
+    A.csr_e.alloc(ctx, P.nnz);
+    A.csr_q.alloc(ctx, P.nnz);
+    // the row kernel's tables live with the static part of the job (TableCache): a warm job finds them built
+    TableCache& tc = J->S->tables;
+    // (normally written by fy_rm2_prepare's statistics pass; here only when the walk's kind changed between the two calls)
+    if (!tc.have_x || tc.csc_x.size() != (size_t)P.nnz || tc.csc_x_over_s.size() != (use_pk ? (size_t)P.nnz : 1)) {
+        tc.valid = tc.have_x = false;
+        tc.csc_x.alloc(ctx, P.nnz);
+        tc.csc_x_over_s.alloc(ctx, use_pk ? (size_t)P.nnz : 1);
+        k_csc_x<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_slot.get(), P.csc_r.get(), J->usum_slot.get(), tc.csc_x.get(),
+                                                 use_pk ? tc.csc_x_over_s.get() : nullptr);
+        FY_KERNEL_CHECK();
+        tc.have_x = true;
+    }
+    // (which clusters keep packed 24-bit rows, and their scales 2^-c: plan_pack24)
+    A.d_gscale.alloc(ctx, (size_t)K);
+    A.d_cshift.alloc(ctx, (size_t)K);
+    h2d(ctx, A.d_gscale.get(), pack.h_gscale.data(), (size_t)K);
+    h2d(ctx, A.d_cshift.get(), pack.h_cshift.data(), (size_t)K);
+    // (the packed walk reads the packed CSR; the PLAIN walk's row kernel reads x itself: no overlap there.  Measured on one box, ML-25M
+    // shape, ms per cold job: side stream from here 20.08, launched right in front of the row kernel 20.15, main stream 20.30 / 20.48 --
+    // the table kernels in between wait on the L2's request rate and on dependent loads, and leave more room than the row kernel.)
+    side.launch(st, use_pk, P, lambda, A);
+}
+
+// ---- 2. per-user meta for this rank's slots [lo, hi), output offsets; returns the number of list entries the rank emits
+struct UserMeta {
+    DevBuf<double> pvpi;
+    DevBuf<int32_t> n_out, out_off;
+    DevBuf<unsigned long long> counters;
+};
+static int64_t user_meta_and_offsets(fy_rm2_job* J, fy_result* R, int32_t lo, int32_t hi, const int32_t* d_cshift, UserMeta& U) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    const fy_rm2_params& prm = J->prm;
+    hipStream_t st = ctx->stream;
+    const int32_t nmine = hi - lo;
+    U.pvpi.alloc(ctx, (size_t)nmine + 1);
+    U.n_out.alloc(ctx, (size_t)nmine + 1);
+    U.out_off.alloc(ctx, (size_t)nmine + 1);
+    U.counters.alloc(ctx, 2);
+    U.counters.zero();
+    U.n_out.zero();
+    if (nmine > 0) {
+        k_user_meta<<<grid_for(nmine), 256, 0, st>>>(lo, hi, P.slot2du.get(), P.uid.get(), P.ucluster.get(), P.udeg.get(),
+                                                      P.d_csize.get(), P.d_pcstart.get(), prm.number_of_items,
+                                                      prm.number_of_recommendations, prm.filter_users, d_cshift, U.pvpi.get(), U.n_out.get(), U.counters.get());
+        FY_KERNEL_CHECK();
+    }
+    exclusive_scan_i32(ctx, U.n_out.get(), U.out_off.get(), (size_t)nmine + 1);
+    const int64_t n_recs = fetch(ctx, U.out_off.get() + nmine);
+    {
+        unsigned long long hc[2];
+        d2h(ctx, hc, U.counters.get(), 2);
+        sync(ctx);
+        R->st.log_terms = (int64_t)hc[0];
+        R->st.users_scored = (int64_t)hc[1];
+    }
+    R->n = n_recs;
+    R->st.recs = n_recs;
+    R->d_key0.alloc(ctx, (size_t)n_recs);
+    R->d_key1.alloc(ctx, (size_t)n_recs);
+    R->d_value.alloc(ctx, (size_t)n_recs);
+    R->d_aux.alloc(ctx, (size_t)n_recs);
+    return n_recs;
+}
+
+// ---- 3. the lanes' streams and scratch, sized by the plan (JobPlan::*_el)
+static void alloc_lanes(Context* ctx, const JobPlan& jp, std::vector<Lane>& lanes) {
+    hipStream_t st = ctx->stream;
+    const int NS = jp.NS;
+    const bool two_phase = jp.two_phase;
+    const size_t m_el = jp.m_el, s_el = jp.s_el, ov_el = jp.ov_el, bm_el = jp.bm_el, ub_el = jp.ub_el, am_el = jp.am_el, gp_el = jp.gp_el, b64_el = jp.b64_el,
+                 a64_el = jp.a64_el, is_el = jp.is_el;
+    if (NS > 1 && ctx->aux.size() < (size_t)NS) {
+        while (ctx->aux.size() < (size_t)NS) {
+            hipStream_t x;
+            FY_HIP(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
+            ctx->aux.push_back(x);
+        }
+    }
+    for (int l = 0; l < NS; l++) {
+        Lane& L = lanes[l];
+        L.st = NS > 1 ? ctx->aux[l] : st;
+        L.M.alloc(ctx, m_el);
+        L.S.alloc(ctx, s_el);
+        L.overflow.alloc(ctx, ov_el);
+        L.any_overflow.alloc(ctx, 1);
+        L.n_heavy.alloc(ctx, 1);
+        L.Bmax.alloc(ctx, bm_el);
+        L.amax.alloc(ctx, am_el);
+        L.bmax.alloc(ctx, am_el);
+        L.Gp.alloc(ctx, two_phase ? 1 : gp_el);
+        L.Bmax64.alloc(ctx, two_phase ? 1 : b64_el);
+        L.Brep.alloc(ctx, gp_el > 1 && !two_phase ? b64_el * 4 / 3 + 4 : 1);     // (b64_el counts floats for 3-byte entries)
+        L.amax64.alloc(ctx, two_phase ? 1 : a64_el);
+        L.bmax64.alloc(ctx, two_phase ? 1 : a64_el);
+        L.UB.alloc(ctx, ub_el);
+        L.tau.alloc(ctx, ov_el);
+        L.surv.alloc(ctx, ub_el);
+        L.surv_mask.alloc(ctx, gp_el > 1 ? ub_el : 1);
+        L.n_quads.alloc(ctx, ov_el + 1);
+        L.quad_prefix.alloc(ctx, ov_el + 1);
+        L.item_seg.alloc(ctx, is_el);
+        L.item_id.alloc(ctx, is_el);
+    }
+}
+
+// ---- 4. the row kernel's tables: kept with the job's static part -- a job over the same ratings, clustering and launch plan
+// (the signature) re-uses them
+static std::vector<int32_t> table_signature(const JobPlan& jp) {
+    const std::vector<Plan>& plans = jp.plans;
+    std::vector<int32_t> sig;
+    sig.push_back(jp.use_pk ? 1 : 0);
+    sig.push_back(plans.size() > 1 && !jp.any_coop ? 1 : 0);
+    for (auto& p : plans) {
+        const int32_t v[8] = {p.c, p.CH, p.nch, p.half ? 1 : 0, p.panel ? 1 : 0, p.p_eff, p.tail_chunks, (p.coop ? 1 : 0) | (p.flat ? 2 : 0) | (p.psym ? 4 : 0)};
+        sig.insert(sig.end(), v, v + 8);
+    }
+    return sig;
+}
+
+// One cluster's tables: packed CSR with chunk-relative indices for its CH, chunk offsets, segment table (+ the tail rows'
+// one-chunk table over the block-compressed CSR in panel mode).  `co` = scratch for p.Uc * (p.nch + 1) offsets.
+static void build_tables(fy_rm2_job* J, const JobPlan& jp, size_t pi, const std::vector<int32_t>& csr_range, hipStream_t ts, int32_t* co) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    TableCache& tc = J->S->tables;
+    const bool use_pk = jp.use_pk;
+    const Plan& p = jp.plans[pi];
+    const int32_t f0 = csr_range[2 * pi], f1 = csr_range[2 * pi + 1];
+    if (use_pk && f1 > f0) {
+        k_pack_csr<<<grid_for(f1 - f0), 256, 0, ts>>>(f0, f1, p.CH, P.csr_idx.get(), P.csr_r.get(), tc.csr_pk.get());
+        FY_KERNEL_CHECK();
+    }
+    if (p.coop) return;
+    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), p.sbase, p.Uc, p.CH, p.nch, co, ts);
+    // (exact table sizes: round 2 sized the tables by upper bounds inside the lanes; the lanes build no tables any more)
+    build_segments(ctx, P.csc_slot.get(), use_pk ? tc.csc_x_over_s.get() : tc.csc_x.get(), co, p.sbase, p.q0, p.nq, p.nch, tc.segs[pi], ts,
+                   p.half ? tc.csc_rank.get() : nullptr, P.csr_idx.get(), p.CH, nullptr, 0, 0, p.half ? tc.samples.get() : nullptr);
+    if (p.p_eff < p.Ic) {
+        k_tail_blocks<<<std::min<int>(p.Uc, ctx->num_cus * 16), 256, 0, ts>>>(p.sbase, p.Uc, p.p_eff, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(),
+                                                                  tc.y_pk.get(), co);
+        FY_KERNEL_CHECK();
+        build_segments(ctx, P.csc_slot.get(), tc.csc_x_over_s.get(), co, p.sbase, p.q0, p.nq, 1, tc.segs_tail[pi], ts, nullptr, nullptr, 0,
+                       tc.csc_rank.get(), p.p_eff, 0);
+    }
+}
+
+// Everything the row kernels of the plan need, on the main stream before the lanes fork; nothing when a job with the same signature
+// has left them (`tables_cached`).  Fills csr_range; `co_lane` keeps the chunk-offset scratch of build_tables alive.
+static void build_job_tables(fy_rm2_job* J, const JobPlan& jp, bool tables_cached, std::vector<int32_t>& csr_range, std::vector<DevBuf<int32_t>>& co_lane) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    hipStream_t st = ctx->stream;
+    TableCache& tc = J->S->tables;
+    const std::vector<Plan>& plans = jp.plans;
+    if (!tables_cached) {
+        tc.valid = false;
+        tc.segs.clear();
+        tc.segs_tail.clear();
+        tc.segs.resize(plans.size());
+        tc.segs_tail.resize(plans.size());
+        tc.csr_pk.alloc(ctx, jp.use_pk ? (size_t)P.nnz : 1);
+        tc.y_pk.alloc(ctx, jp.any_tail ? (size_t)P.nnz : 1);     // k_tail_blocks
+        tc.csc_rank.alloc(ctx, jp.any_half ? (size_t)P.nnz : 1);     // row (rank inside its cluster) of every CSC entry
+        if (jp.any_half) {
+            k_csc_rank<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.pair_rank.get(), tc.csc_rank.get());
+            FY_KERNEL_CHECK();
+            build_csr_samples(ctx, P.nnz, P.csr_idx.get(), tc.samples, st);
+        }
+    }
+    // first / last CSR entry of every planned cluster (slots are cluster-major): one round trip for all of them
+    csr_range.assign(2 * plans.size() + 2, 0);
+    {
+        std::vector<int32_t> where(2 * plans.size());
+        for (size_t pi = 0; pi < plans.size(); pi++) {
+            where[2 * pi] = plans[pi].sbase;
+            where[2 * pi + 1] = plans[pi].sbase + plans[pi].Uc;
+        }
+        gather_to_host_i32(ctx, P.rowptr.get(), where, csr_range.data());
+    }
+    // With several lanes and no cooperative cluster the tables are built by the lane that uses them, right before the row
+    // kernel: table building is mostly host round trips (sizes of the segment tables), 23 ms for 50 clusters during which the
+    // chip idled; in a lane they hide behind the other lanes' kernels.  (A cooperative job packs every cluster's CSR up front.)
+    // Several clusters and none of them cooperative: ONE table over all of them, built here on the main stream (build_tables_all).
+    // (Round 2 let every lane build its cluster's tables right before the row kernel, to hide their host round trips behind the
+    // other lanes: 20 ms of tables at 50 clusters.)
+    const bool all_at_once = plans.size() > 1 && !jp.any_coop;
+    co_lane.resize((size_t)jp.NS);
+    if (!all_at_once)
+        for (auto& b : co_lane) b.alloc(ctx, jp.co_all);
+    if (tables_cached) return;
+    if (all_at_once) build_tables_all(ctx, P, plans, csr_range, jp.use_pk, tc, st);
+    else
+        for (size_t pi = 0; pi < plans.size(); pi++) build_tables(J, jp, pi, csr_range, st, co_lane[0].get());
+}
+
+// ---- 5. flat batch (Plan::flat): matrix build, scores and lists of all those clusters, one launch per kernel, on the main stream
+struct FlatBuffers {      // (kept by fy_rm2_score until the job has drained)
+    DevBuf<char> flatM;
+    DevBuf<float> flatS;
+    DevBuf<int2> flat_seg;
+    DevBuf<int32_t> flat_id, flat_ov, flat_flags, flat_cnt;
+    DevBuf<CoocLaunch> d_flat_launch;
+    DevBuf<FlatDesc> d_flat[2];
+};
+static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
+    fy_rm2_job* J = X.J;
+    Context* ctx = X.J->ctx;
+    const Prepared& P = X.J->P;
+    fy_result* R = X.R;
+    const ScoreTune& tune = *X.tune;
+    const fy_rm2_params& prm = X.J->prm;
+    const JobPlan& jp = *X.jp;
+    hipStream_t st = ctx->stream;
+    TableCache& tc = J->S->tables;
+    const int32_t lo = X.lo;
+    const double lambda = prm.lambda;
+    constexpr int VEC = 4;   // floats per lane of the scoring kernel: column chunk = 256 items
+    for (size_t first = 0; first < jp.plans.size();) {
+        std::vector<CoocLaunch> fb;
+        std::vector<FlatDesc> fd[2];       // [0] fp32 rows, [1] 24-bit rows
+        SyncOnUnwind fb_fd_guard(st);      // (their uploads are queued below; the batch's own synchronisation is at its end)
+        size_t m_bytes = 0, s_el = 0, i_el = 0, u_el = 0, n_flat = 0, last = first;
+        int64_t batch_bytes = 0;
+        for (; last < jp.plans.size(); last++) {
+            const Plan& p = jp.plans[last];
+            if (!p.flat) continue;
+            if (n_flat && batch_bytes + flat_need(p) > jp.flat_budget) break;
+            batch_bytes += flat_need(p);
+            m_bytes += round_up((int64_t)p.Ic * p.ldm * (p.pack24 ? 3 : 4), 256);
+            s_el += (size_t)(p.b - p.a) * p.ldm;
+            i_el += (size_t)p.Ic * p.nch;
+            u_el += (size_t)(p.b - p.a);
+            n_flat++;
+        }
+        if (n_flat) {
+            F.flatM.alloc(ctx, m_bytes);
+            F.flatS.alloc(ctx, s_el);
+            F.flat_seg.alloc(ctx, i_el);
+            F.flat_id.alloc(ctx, i_el);
+            F.flat_ov.alloc(ctx, u_el);
+            F.flat_flags.alloc(ctx, 2 * n_flat);       // per cluster: n_heavy, any_overflow
+            size_t m_at = 0, s_at = 0, i_at = 0, u_at = 0, k = 0;
+            int max_grid[2] = {0, 0}, max_users[2] = {0, 0};
+            for (size_t pi = first; pi < last; pi++) {
+                const Plan& p = jp.plans[pi];
+                if (!p.flat) continue;
+                const int c = p.c;
+                const int32_t nb = p.b - p.a;
+                float* const Mc = reinterpret_cast<float*>(F.flatM.get() + m_at);
+                float* const Sc = F.flatS.get() + s_at;
+                CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), tc.segs[pi].ptr_(), tc.segs[pi].seg_(), tc.segs[pi].w_(), P.csr_idx.get(),
+                            X.csr_x, p.pbase, p.sbase, p.Ic, p.CH, p.nch, 0, p.Ic, p.q0, p.nq, nullptr, 0, X.csr_pk, nullptr,
+                            (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
+                const int fxk = fx_exponent(&J->fx_bounds[3 * (size_t)c]);
+                CA.fx_scale = std::ldexp(1.0, fxk);
+                const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale[(size_t)c];
+                MEpilogue ME{Mc, p.ldm, (float)w2s, std::ldexp(w2s, -fxk), p.pack24 ? 1 : 0, nullptr, p.ldb, 0, 0, nullptr, p.ldb64, nullptr};
+                const int n_items = (int)cooc_item_count(p.Ic, p.CH, p.nch, false);
+                CA.item_seg = F.flat_seg.get() + i_at;
+                CA.item_id = F.flat_id.get() + i_at;
+                CA.item_grab = cooc_item_grab((size_t)c < P.cluster_deg2.size() ? P.cluster_deg2[c] : P.sum_deg2, n_items);
+                fb.push_back(CoocLaunch{CA, ME, n_items, 0});
+
+                const int n_chunks = (int)ceil_div(p.Ic, 64 * VEC);
+                // (the chip is filled by all clusters of the batch together: ~8 work-groups per CU over the whole launch)
+                const int64_t fill = ceil_div(8 * (int64_t)ctx->num_cus, (int64_t)std::max(1, n_chunks) * (int64_t)n_flat);
+                const int n_slices = (int)std::max<int64_t>(1, std::min<int64_t>(tune.max_slices, std::min<int64_t>(ceil_div(nb, 4), std::max<int64_t>(ceil_div(nb, 4 * (int64_t)tune.users_per_wave), fill))));
+                FlatDesc d{};
+                ScoreArgs& SA = d.SA;
+                SA.M = Mc; SA.ldm = p.ldm; SA.Ic = p.Ic; SA.a_rank = X.a_rank + p.pbase; SA.b_rank = X.b_rank + p.pbase;
+                SA.rb_off = P.rowptr.get() + p.sbase;
+                SA.csr_idx = P.csr_idx.get(); SA.csr_e = X.csr_e; SA.csr_q = X.csr_q;
+                SA.pvpi = X.pvpi; SA.n_out = X.n_out; SA.slot_lo = lo; SA.slot_base = p.sbase; SA.slot0 = p.a; SA.n_users = nb;
+                SA.S = Sc; SA.ldS = p.ldm; SA.n_slices = n_slices; SA.n_chunks = n_chunks;
+                d.n_heavy = F.flat_flags.get() + 2 * k;
+                d.any_overflow = F.flat_flags.get() + 2 * k + 1;
+                SA.n_heavy = tune.score_heavy > 0 ? d.n_heavy : nullptr;
+                d.heavy_thresh = tune.score_heavy > 0 ? std::min(tune.score_heavy, 32) : 0x7FFFFFFF;
+                d.TA = TopNArgs{Sc, p.ldm, p.Ic, X.n_out, X.out_off, P.rank_item_raw.get() + p.pbase, P.slot2du.get(), P.uid.get(), lo, p.a, c,
+                                R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(), 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+                d.overflow = F.flat_ov.get() + u_at;
+                d.score_grid = n_chunks * n_slices;
+                d.n_users = nb;
+                const int f = p.pack24 ? 1 : 0;
+                max_grid[f] = std::max(max_grid[f], d.score_grid);
+                max_users[f] = std::max(max_users[f], nb);
+                fd[f].push_back(d);
+                m_at += (size_t)round_up((int64_t)p.Ic * p.ldm * (p.pack24 ? 3 : 4), 256);
+                s_at += (size_t)nb * p.ldm;
+                i_at += (size_t)p.Ic * p.nch;
+                u_at += (size_t)nb;
+                k++;
+            }
+            const size_t sp = X.t_cooc->begin(st);
+            launch_cooc_rm2_multi(ctx, tune, fb, false, F.d_flat_launch, F.flat_cnt, st, true);
+            X.t_cooc->end(sp, st);
+            R->st.cooc_launches++;
+            for (int f = 0; f < 2; f++) {
+                if (fd[f].empty()) continue;
+                const unsigned ny = (unsigned)fd[f].size();
+                F.d_flat[f].alloc(ctx, fd[f].size());
+                FY_HIP(hipMemcpyAsync(F.d_flat[f].get(), fd[f].data(), fd[f].size() * sizeof(FlatDesc), hipMemcpyHostToDevice, st));
+                const size_t ss = X.t_score->begin(st);
+                k_count_heavy_multi<<<(ny + 63) / 64, 64, 0, st>>>(F.d_flat[f].get(), (int32_t)ny);
+                FY_KERNEL_CHECK();
+                if (f) k_score_multi<4, true, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
+                else k_score_multi<4, false, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
+                FY_KERNEL_CHECK();
+                X.t_score->end(ss, st);
+                R->st.score_launches++;
+                const size_t tt = X.t_topn->begin(st);
+                k_topn_fast_multi<<<dim3((unsigned)max_users[f], ny), 256, 0, st>>>(F.d_flat[f].get(), tune.force_select);
+                FY_KERNEL_CHECK();
+                k_topn_select_multi<<<dim3((unsigned)max_users[f], ny), 256, 0, st>>>(F.d_flat[f].get(), X.prune_counters + 2);
+                FY_KERNEL_CHECK();
+                X.t_topn->end(tt, st);
+            }
+            FY_HIP(hipStreamSynchronize(st));     // the host vectors behind the descriptor uploads leave scope here
+        }
+        first = last;
+    }
+}
+
+// ---- 6. two-phase panel mode: every cluster of a group keeps its own panel ...
+struct PanelBuf {
+    DevBuf<float> Gp, Bmax64, amax64, bmax64;
+    DevBuf<uint32_t> Brep;
+    DevBuf<double> head32, tail32;     // (refinement pass: per cluster, like the panels -- built in phase 1, read in phase 3)
+};
+struct PanelPtrs {
+    float *Gp, *Bmax64;
+    uint32_t* Brep;
+    float *amax64, *bmax64;
+};
+// (host-side sources of uploads and the device buffers of the batched launches: declared in FRONT of the LaneGuard, so that the
+// guard -- which drains every lane and the main stream -- is destroyed before them on every path)
+struct PanelSet {
+    std::vector<PanelBuf> pbuf;        // [plan]
+    std::vector<Lane> plane;           // [plan]: the cluster's own scoring scratch
+    std::vector<CoocLaunch> batch_main, batch_tail;      // phase 1: the row kernels of all panel clusters, launched together
+    DevBuf<CoocLaunch> d_batch_main, d_batch_tail;
+    DevBuf<int32_t> d_cnt_main, d_cnt_tail;
+    DevBuf<PanelDesc> d_panel_desc;
+    std::vector<PanelDesc> hpd;                          // (lives as long as its upload may be in flight)
+};
+static void group_buffers(Context* ctx, const JobPlan& jp, int seed_chunks, const std::vector<Lane>& lanes, int grp, PanelSet& PS) {
+    const std::vector<Plan>& plans = jp.plans;
+    std::vector<PanelBuf>& pbuf = PS.pbuf;
+    std::vector<Lane>& plane = PS.plane;
+    for (size_t pi = 0; pi < plans.size(); pi++) {
+        const Plan& p = plans[pi];
+        if (!p.panel || jp.group_of[pi] != grp) continue;
+        pbuf[pi].Gp.alloc(ctx, (size_t)p.Ic * p.panel_cols * 3 / 4 + 4);
+        pbuf[pi].Bmax64.alloc(ctx, (size_t)p.Ic * p.ldb64 * 3 / 4 + 4);
+        pbuf[pi].Brep.alloc(ctx, (size_t)p.Ic * p.ldb64 + 4);
+        pbuf[pi].amax64.alloc(ctx, (size_t)p.ldb64);
+        pbuf[pi].bmax64.alloc(ctx, (size_t)p.ldb64);
+    }
+    // ... and its own scoring scratch, so that NO host round trip separates the clusters: phase 2 queues seed + bound pass, select, second
+    // bound and the survivor count of every cluster, ONE wait reads all counts (pinned host memory), phase 3 queues the survivor
+    // passes and top-N.  (With one scratch set per lane the host waited for every cluster's count before it could queue the next
+    // cluster of that lane: 50 round trips during which the other lanes ran dry.)
+    for (size_t pi = 0; pi < plans.size(); pi++) {
+        const Plan& p = plans[pi];
+        if (!p.panel || jp.group_of[pi] != grp) continue;
+        Lane& W = plane[pi];
+        const size_t nbp = (size_t)(p.b - p.a);
+        const size_t seed_cols = (size_t)std::min<int64_t>(ceil_div(p.Ic, 256), seed_chunks) * 256;
+        W.st = lanes[pi % jp.NS].st;
+        W.M.alloc(ctx, 1); W.Bmax.alloc(ctx, 1); W.amax.alloc(ctx, 1); W.bmax.alloc(ctx, 1);
+        W.Gp.alloc(ctx, 1); W.Bmax64.alloc(ctx, 1); W.Brep.alloc(ctx, 1); W.amax64.alloc(ctx, 1); W.bmax64.alloc(ctx, 1);
+        W.item_seg.alloc(ctx, (size_t)p.Ic * p.nch); W.item_id.alloc(ctx, (size_t)p.Ic * p.nch);
+        W.item_seg_t.alloc(ctx, (size_t)std::max(1, p.Ic - p.p_eff)); W.item_id_t.alloc(ctx, (size_t)std::max(1, p.Ic - p.p_eff));
+        W.S.alloc(ctx, nbp * seed_cols);
+        W.overflow.alloc(ctx, nbp);
+        W.any_overflow.alloc(ctx, 1);
+        W.n_heavy.alloc(ctx, 1);
+        W.UB.alloc(ctx, nbp * (size_t)p.ldb64);
+        W.tau.alloc(ctx, nbp);
+        W.surv.alloc(ctx, nbp * (size_t)p.ldb64);
+        W.surv_mask.alloc(ctx, nbp * (size_t)p.ldb64);
+        W.n_quads.alloc(ctx, nbp + 1);
+        W.quad_prefix.alloc(ctx, nbp + 1);
+    }
+}
+
+// Error path: anything thrown while the lanes run (an allocation, a launch, a collective) unwinds the lanes' buffers, the segment
+// tables and the per-job arrays back into the caching allocator while kernels of OTHER lanes may still be reading
+// them.  The guard drains every lane and the main stream first (objects are destroyed in reverse order of
+// declaration: fy_rm2_score declares the lanes, the PanelSet and the per-job arrays before it, so it runs before they are released).
+// (The flat batches run on the main stream alone, in front of the guard: their uploads' sources have their own SyncOnUnwind.)
+struct LaneGuard {
+    Context* ctx;
+    hipEvent_t fork = nullptr;
+    int32_t* pinned = nullptr;
+    ~LaneGuard() {
+        for (hipStream_t x : ctx->aux) (void)hipStreamSynchronize(x);
+        (void)hipStreamSynchronize(ctx->stream);
+        if (fork) (void)hipEventDestroy(fork);
+        if (pinned) (void)hipHostFree(pinned);
+    }
+};
+
+// ---- 7. one cluster on a lane
+// one visit of a cluster by the group / phase loop (score_clusters)
+struct ClusterVisit {
+    size_t pi;                   // its plan
+    int grp, phase;
+    Lane* L;                     // scratch: the lane's, or (two-phase panel mode, phases 2 and 3) the cluster's own
+    hipStream_t ls;
+    PanelPtrs PP;
+    DevBuf<double>*H32, *T32;    // fp64 head rows / tail columns of the refinement pass: the lane's, or the cluster's own
+    Lane* own;                   // two-phase panel mode: the cluster's own scratch (PanelSet::plane), else null
+    PanelSet* PS;
+    int32_t* pinned;             // two-phase panel mode: [plan] survivor counts, read by the host between phases 2 and 3
+};
+// numbers the matrix build and the scoring of one cluster agree on
+struct ClusterNumbers {
+    int fxk;                     // exponent of the fixed-point walk, < 0: fp64 accumulators
+    double w2s;                  // (1-l)^2 and the packed format's 2^-c
+    bool refine;
+    int32_t head_rows;
+    int64_t ld_head;
+};
+static ClusterNumbers cluster_numbers(const ScoreShared& X, const Plan& p) {
+    const fy_rm2_job* J = X.J;
+    const ScoreTune& tune = *X.tune;
+    const double lambda = J->prm.lambda;
+    const int c = p.c;
+    ClusterNumbers N{};
+    N.fxk = (X.jp->use_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)c]) : -1;
+    N.w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale[(size_t)c];     // (1-l)^2 and the packed format's 2^-c
+    // refinement (k_refine_rows): packed clusters keep the unrounded fp32 values of their first 256 rows (and, in symmetric panel
+    // mode, of the first 256 columns of the tail rows)
+    N.refine = tune.refine && p.pack24 && !p.coop && N.fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
+    // (as many head rows / columns as the seed is wide, 256 .. 1024: N = 50 -> 256, N = 100 -> 512; a multiple of 4)
+    N.head_rows = (int32_t)std::min<int64_t>(p.Ic & ~3, std::max<int64_t>(256, std::min<int64_t>(1024, (int64_t)tune.seed_chunks * 256)));
+    N.ld_head = p.psym ? (int64_t)p.p_eff : p.ldm;
+    return N;
+}
+// FY_DEBUG_SYNC=1: drain the device and say where the job is
+static void checkpoint(const ScoreShared& X, const ClusterVisit& V, const char* what) {
+    if (X.tune->debug_sync != 1) return;
+    const hipError_t e = hipDeviceSynchronize();
+    fprintf(stderr, "[fy] group %d/%d phase %d plan %zu (cluster %d): %s -> %s\n", V.grp, X.jp->n_groups, V.phase, V.pi, X.jp->plans[V.pi].c, what, hipGetErrorString(e));
+    fflush(stderr);
+}
+
+// -- M build: the cluster's matrix (or panel), its block maxima, mirror pass and super-block bounds.  In phase 1 with batched row
+// kernels the launches are only collected (PanelSet::batch_main / batch_tail; launch_panel_batch queues them for the whole group).
+static void build_cluster_matrix(const ScoreShared& X, const ClusterVisit& V, const ClusterNumbers& N) {
+    fy_rm2_job* J = X.J;
+    Context* ctx = X.J->ctx;
+    const Prepared& P = X.J->P;
+    fy_result* R = X.R;
+    const ScoreTune& tune = *X.tune;
+    const JobPlan& jp = *X.jp;
+    TableCache& tc = J->S->tables;
+    const size_t pi = V.pi;
+    const int phase = V.phase;
+    const Plan& p = jp.plans[pi];
+    Lane& L = *V.L;
+    hipStream_t ls = V.ls;
+    const PanelPtrs& PP = V.PP;
+    const int c = p.c;
+    const int32_t sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, CH = p.CH, nch = p.nch;
+    const int64_t ldm = p.ldm;
+    const bool pack24 = p.pack24;
+    const int fxk = N.fxk;
+    const double w2s = N.w2s;
+    CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), tc.segs[pi].ptr_(), tc.segs[pi].seg_(), tc.segs[pi].w_(), P.csr_idx.get(),
+                X.csr_x, pbase, sbase, Ic, CH, nch, 0, Ic, p.q0, p.nq, nullptr, 0, X.csr_pk, nullptr,
+                (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
+    CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;
+    MEpilogue ME{L.M.get(), ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0,
+                 pack24 ? 1 : 0, (p.prune && !p.panel) ? L.Bmax.get() : nullptr, p.ldb, 0,
+                 p.panel ? p.panel_cols : 0, p.panel ? PP.Bmax64 : nullptr, p.ldb64, p.panel ? PP.Brep : nullptr};
+    if (p.panel) ME.M = PP.Gp;
+    if (N.refine) {
+        V.H32->alloc(ctx, (size_t)N.head_rows * N.ld_head + 4);
+        if (p.psym) V.T32->alloc(ctx, (size_t)std::max(1, Ic - p.p_eff) * N.head_rows + 4);
+        ME.head32 = V.H32->get();
+        ME.ld_head = N.ld_head;
+        ME.head_rows = N.head_rows;
+        ME.tail32 = p.psym ? V.T32->get() : nullptr;
+        ME.tail_from = p.p_eff;
+    }
+    if (p.panel) {
+        R->st.panel_clusters++;
+        FY_HIP(hipMemsetAsync(PP.Bmax64, 0, (size_t)Ic * p.ldb64 * 3, ls));
+        k_block_amax<<<grid_for(p.ldb64), 256, 0, ls>>>(Ic, (int32_t)p.ldb64, X.a_rank + pbase, X.b_rank + pbase, PP.amax64,
+                                                       PP.bmax64, 64);
+        FY_KERNEL_CHECK();
+    } else if (p.prune) {
+        FY_HIP(hipMemsetAsync(L.Bmax.get(), 0, (size_t)Ic * p.ldb * 3, ls));
+        k_block_amax<<<grid_for(p.ldb), 256, 0, ls>>>(Ic, (int32_t)p.ldb, X.a_rank + pbase, X.b_rank + pbase, L.amax.get(), L.bmax.get());
+        FY_KERNEL_CHECK();
+    }
+    const size_t sp = X.t_cooc->begin(ls);
+    const bool batched = phase == 1 && tune.panel_multi_launch && jp.use_pk && fxk >= 0 && !tune.cooc_f32;     // (k_cooc_rm2_multi)
+    if (p.p_eff < Ic) {   // panel mode: bounds of the tail rows behind p_eff (one item per row, see k_tail_blocks)
+        CoocArgs CB{P.rank_pair.get(), P.pair_start.get(), tc.segs_tail[pi].ptr_(), tc.segs_tail[pi].seg_(), tc.segs_tail[pi].w_(), P.csr_idx.get(),
+                    X.csr_x, pbase, sbase, Ic, p.tail_width, 1, p.p_eff, Ic - p.p_eff, p.q0, p.nq, nullptr, 0, tc.y_pk.get(), nullptr, CA.pk_bytes};
+        CB.fx_scale = CA.fx_scale;
+        MEpilogue MB{reinterpret_cast<float*>(reinterpret_cast<char*>(PP.Bmax64) + (size_t)(p.p_eff / 64) * 3), p.tail_width, ME.w2, ME.fx_inv, 1,
+                     nullptr, 0, 0, 0, nullptr, 0, nullptr, p.ldb64, 1};
+        int2* const tseg = batched ? V.own->item_seg_t.get() : L.item_seg.get();
+        int32_t* const tid = batched ? V.own->item_id_t.get() : L.item_id.get();
+        if (!batched) {      // (batched: k_item_list_multi, in front of the launch)
+            k_item_list<<<grid_for((int64_t)(Ic - p.p_eff)), 256, 0, ls>>>(CB, tseg, tid);
+            FY_KERNEL_CHECK();
+        }
+        CB.item_seg = tseg;
+        CB.item_id = tid;
+        CB.item_grab = 8;      // a tail row's bound item is a handful of segments
+        if (batched) V.PS->batch_tail.push_back(CoocLaunch{CB, MB, Ic - p.p_eff, 0});
+        else {
+            FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
+            launch_cooc_rm2(ctx, tune, jp.use_pk, CB, MB, Ic - p.p_eff, L.any_overflow.get(), ls);
+            R->st.cooc_launches++;
+        }
+        CA.tail_row0 = p.p_eff;
+        CA.tail_chunks = p.tail_chunks;
+    }
+    {
+        CA.half = (p.half || p.psym) ? 1 : 0;
+        if (p.psym) { CA.half_rows = p.p_eff; CA.head_chunks = p.tail_chunks; }
+        const int n_items = p.psym ? (int)(cooc_half_item_index(p.p_eff - 1, p.tail_chunks - 1, CH, p.tail_chunks) + 1 + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
+                            : CA.tail_chunks > 0 ? (int)((int64_t)p.p_eff * nch + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
+                                                 : (int)cooc_item_count(Ic, CH, nch, p.half);
+        int2* const mseg = batched ? V.own->item_seg.get() : L.item_seg.get();
+        int32_t* const mid = batched ? V.own->item_id.get() : L.item_id.get();
+        if (!batched) {
+            k_item_list<<<grid_for((int64_t)Ic * nch), 256, 0, ls>>>(CA, mseg, mid);
+            FY_KERNEL_CHECK();
+        }
+        CA.item_seg = mseg;
+        CA.item_id = mid;
+        CA.item_grab = cooc_item_grab(((size_t)c < P.cluster_deg2.size() ? P.cluster_deg2[c] : P.sum_deg2) / (p.half ? 2 : 1), n_items);
+        if (batched) V.PS->batch_main.push_back(CoocLaunch{CA, ME, n_items, 0});
+        else {
+            FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
+            launch_cooc_rm2(ctx, tune, jp.use_pk, CA, ME, n_items, L.any_overflow.get(), ls);
+        }
+    }
+    X.t_cooc->end(sp, ls);
+    X.side->join(ls);      // (the scoring kernels behind this point read the per-rating values)
+    checkpoint(X, V, "row kernel queued / run");
+    if (!batched) R->st.cooc_launches++;
+    if (p.half) {    // lower triangle + the block maxima in front of / on the diagonal
+        const size_t sm = X.t_mirror->begin(ls);
+        // pruned flow: LAZY mirror -- the seed pass reads the seed columns of every row, the bound pass the block maxima, the
+        // survivor pass the surviving column blocks (mirrored below, once they are known); nothing else of the lower triangle
+        // is ever read, so it is not written (round 3 moved 10.7 GB here to fill a triangle of which a few per cent were read)
+        const bool lazy = p.prune && tune.lazy_mirror;
+        launch_mirror(ctx, L.M.get(), ldm, Ic, p.prune ? L.Bmax.get() : nullptr, p.ldb, ls, nullptr, lazy ? std::min(tune.seed_chunks, p.nblk) : 0x7FFFFFFF);
+        X.t_mirror->end(sm, ls);
+    }
+    // (not for long lists: their survivors -- 14 % of the blocks at N = 1000 -- spread over the whole popularity order, the 16 wide
+    // groups behind the first 48 blocks all survive and hand every block to the survivor pass: measured, the batch falls back to
+    // the full pass, 261 -> 471 ms)
+    if (p.prune && !p.panel && tune.sup_bounds && !jp.long_seed) {      // super-block bounds for the seed pass (k_score_sup)
+        const int seed_b = std::min(tune.seed_chunks, p.nblk);
+        std::vector<int32_t> first;
+        sup_block_map(seed_b, p.nblk, first);
+        const int n_sup = (int)first.size() - 1;
+        first.resize(65, first.back());
+        L.sup_first.alloc(ctx, 65);
+        L.Bsup.alloc(ctx, (size_t)Ic * 64);
+        L.asup.alloc(ctx, 64);
+        L.bsupb.alloc(ctx, 64);
+        FY_HIP(hipMemcpyAsync(L.sup_first.get(), first.data(), 65 * sizeof(int32_t), hipMemcpyHostToDevice, ls));
+        FY_HIP(hipStreamSynchronize(ls));      // (`first` is a host temporary; one cluster: no other lane is waiting)
+        const size_t sb = X.t_score->begin(ls);
+        k_build_bsup<<<std::min<int>((Ic + 3) / 4, ctx->num_cus * 32), 256, 0, ls>>>(Ic, n_sup, L.sup_first.get(), L.Bmax.get(), p.ldb, L.Bsup.get());
+        FY_KERNEL_CHECK();
+        k_sup_amax<<<1, 64, 0, ls>>>(n_sup, L.sup_first.get(), L.amax.get(), L.bmax.get(), L.asup.get(), L.bsupb.get());
+        FY_KERNEL_CHECK();
+        X.t_score->end(sb, ls);
+    }
+}
+
+// -- scoring + top-N of the cluster's users of this rank, in user batches that fit the score scratch: the plain full pass, or the
+// three pruned passes (seed + bounds, survivor selection, survivors) with the full pass as their fallback.  A two-phase panel
+// cluster is visited twice: phase 2 queues the front up to the survivor count, phase 3 the rest.
+static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const ClusterNumbers& N) {
+    fy_rm2_job* J = X.J;
+    Context* ctx = X.J->ctx;
+    const Prepared& P = X.J->P;
+    fy_result* R = X.R;
+    const ScoreTune& tune = *X.tune;
+    const fy_rm2_params& prm = X.J->prm;
+    const JobPlan& jp = *X.jp;
+    TableCache& tc = J->S->tables;
+    const size_t pi = V.pi;
+    const int phase = V.phase;
+    const Plan& p = jp.plans[pi];
+    Lane& L = *V.L;
+    hipStream_t ls = V.ls;
+    const PanelPtrs& PP = V.PP;
+    const int c = p.c;
+    const int32_t sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, a = p.a, b = p.b;
+    const int64_t ldm = p.ldm;
+    const bool pack24 = p.pack24;
+    const int32_t lo = X.lo;
+    const double lambda = prm.lambda;
+    const double w2s = N.w2s;
+    const bool refine = N.refine;
+    const int32_t head_rows = N.head_rows;
+    const int64_t ld_head = N.ld_head;
+    const DevBuf<double>&H32 = *V.H32, &T32 = *V.T32;
+    constexpr int VEC = 4;   // floats per lane of the scoring kernel: column chunk = 256 items
+    const int64_t ldS = ldm, B = p.B;
+    const int n_chunks = (int)ceil_div(Ic, 64 * VEC);
+    const int32_t* row_off = P.rowptr.get() + sbase;   // the users' CSR rows: [slot - sbase], [slot - sbase + 1]
+    auto score_args = [&](const float* Mx, int64_t ldmx, int32_t Icx, const float* ax, int32_t s0, int32_t nb, float* Sx, int64_t ldSx,
+                          int n_slices, int nchunks) {
+        ScoreArgs SA{};
+        SA.M = Mx; SA.ldm = ldmx; SA.Ic = Icx; SA.a_rank = ax; SA.b_rank = X.b_rank + pbase; SA.rb_off = row_off;
+        SA.csr_idx = P.csr_idx.get(); SA.csr_e = X.csr_e; SA.csr_q = X.csr_q;
+        SA.pvpi = X.pvpi; SA.n_out = X.n_out; SA.slot_lo = lo; SA.slot_base = sbase; SA.slot0 = s0; SA.n_users = nb;
+        SA.S = Sx; SA.ldS = ldSx; SA.n_slices = n_slices; SA.n_chunks = nchunks;
+        if (tune.score_heavy > 0) {     // (stream order: every scoring launch of the batch follows)
+            // a small batch (one cluster of many) cannot fill the chip with a wave per user and its launch lasts as long as its
+            // longest list on ONE wave (ML-1M shape in 50 clusters: 0.14 ms per cluster for 120 users): there every user with
+            // more than a few batches is walked by a whole workgroup
+            const int heavy = (int64_t)nb * nchunks < 8 * (int64_t)ctx->num_cus ? std::min(tune.score_heavy, 32) : tune.score_heavy;
+            k_count_heavy<<<1, 64, 0, ls>>>(P.rowptr.get() + s0, nb, heavy, L.n_heavy.get());
+            SA.n_heavy = L.n_heavy.get();
+        }
+        return SA;
+    };
+    // ill-conditioned list rows of a range of users, scored again in fp64 from the fp32 head rows (k_refine_rows); after the lists stand
+    auto refine_rows = [&](int32_t s0, int32_t nb) {
+        if (!refine || nb <= 0) return;
+        const size_t tt = X.t_topn->begin(ls);
+        const int32_t n_ids = J->S->max_item + 1;
+        L.colmap.alloc(ctx, (size_t)n_ids);
+        FY_HIP(hipMemsetAsync(L.colmap.get(), 0xFF, (size_t)n_ids * sizeof(int32_t), ls));
+        k_refine_colmap<<<(head_rows + 255) / 256, 256, 0, ls>>>(head_rows, P.rank_item_raw.get() + pbase, L.colmap.get());
+        FY_KERNEL_CHECK();
+        RefineArgs RA{};
+        RA.slot0 = s0; RA.n_users = nb; RA.slot_lo = lo; RA.slot_base = sbase;
+        RA.n_out = X.n_out; RA.out_off = X.out_off; RA.out_item = R->d_key1.get(); RA.out_score = R->d_value.get(); RA.out_item_w = R->d_key1.get();
+        RA.rowptr = P.rowptr.get(); RA.csr_idx = P.csr_idx.get(); RA.csr_r = P.csr_r.get(); RA.usum_slot = J->usum_slot.get();
+        RA.p_rank = X.p_rank + pbase; RA.b_rank = X.b_rank64 + pbase;
+        RA.colmap = L.colmap.get(); RA.max_item = J->S->max_item;
+        RA.head_rows = head_rows;
+        RA.head32 = H32.get(); RA.ld_head = ld_head; RA.tail32 = p.psym ? T32.get() : nullptr; RA.tail_from = p.p_eff;
+        if (!RA.head32 || (p.psym && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", c);
+        RA.unscale = 1.0 / (double)X.gscale[(size_t)c];
+        RA.lambda = lambda; RA.ln_items = std::log((double)prm.number_of_items); RA.ln_users = std::log((double)p.Uc);
+        RA.users_minus_1 = (double)(p.Uc - 1);
+        RA.refine_c = tune.refine_c;
+        RA.n_refined = X.prune_counters + 5;
+        int lp2 = 64;
+        while (lp2 < std::min<int>(prm.number_of_recommendations, Ic)) lp2 <<= 1;
+        k_refine_rows<<<(nb + 3) / 4, 256, (size_t)4 * lp2 * sizeof(uint64_t), ls>>>(RA);
+        FY_KERNEL_CHECK();
+        X.t_topn->end(tt, ls);
+    };
+    // the plain full pass over a range of users: every log term, like the reference's loop (AbstractRM2Reducer.java:332-356)
+    auto full_pass = [&](int32_t s0, int32_t nb, float* Sx) {
+        const int n_slices = score_slices(ctx->num_cus, tune, nb, n_chunks);
+        ScoreArgs SA = score_args(L.M.get(), ldm, Ic, X.a_rank + pbase, s0, nb, Sx, ldS, n_slices, n_chunks);
+        const size_t ss = X.t_score->begin(ls);
+        if (pack24) k_score<4, true, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+        else k_score<4, false, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+        FY_KERNEL_CHECK();
+        X.t_score->end(ss, ls);
+        R->st.score_launches++;
+        TopNArgs TA{Sx, ldS, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(), lo, s0, c,
+                    R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(), 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+        const size_t tt = X.t_topn->begin(ls);
+        FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
+        if (prm.number_of_recommendations > TOPN_LONG)
+            k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select,
+                                                                                                 fy_topn_long_cap(prm.number_of_recommendations));
+        else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
+        FY_KERNEL_CHECK();
+        k_topn_select<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), X.prune_counters + 2);
+        FY_KERNEL_CHECK();
+        X.t_topn->end(tt, ls);
+        refine_rows(s0, nb);
+    };
+    for (int32_t s0 = a; s0 < b; s0 += (int32_t)B) {
+        const int32_t nb = (int32_t)std::min<int64_t>(B, b - s0);
+        if (!p.prune) { full_pass(s0, nb, L.S.get()); continue; }
+        const int seed_chunks = std::min(n_chunks, tune.seed_chunks);
+        const bool use_sup = tune.sup_bounds && !p.panel && !jp.long_seed;      // bounds over super-blocks, evaluated by the seed chunk's own waves
+        const int n_slices = score_slices(ctx->num_cus, tune, nb, seed_chunks + (use_sup ? 0 : (int)(p.ldb / 256)));
+        // front in phase 2, back in phase 3 (the whole cluster in one batch: its CSR range is on the host already)
+        const bool split = jp.two_phase && p.panel && s0 == sbase && nb == p.Uc;
+        if (phase == 3 && !split) continue;
+        size_t ss = X.t_score->begin(ls);
+        const int seed_blocks = seed_chunks;
+        const int64_t SC = (int64_t)seed_chunks * 256;   // pitch of the compact score rows: seed columns only
+        // only the seed columns and the surviving blocks of a score row are ever written or read
+        // (1) + (3) ONE launch: exact scores of the seed columns (the most popular candidates) and the upper bounds
+        // of all 256-column blocks (the same kernel on the block-maximum matrix); the grid's tail -- the waves
+        // that walk the heaviest users -- is paid once instead of twice
+        // panel mode: the stored rows are panel_cols wide and the bound matrix has one column per 64-column sub-block
+        const float* Gmat = p.panel ? PP.Gp : L.M.get();
+        const int64_t gld = p.panel ? (int64_t)p.panel_cols : ldm;
+        // (A two-level bound -- 256-column block maxima first, the 64-column sub-block bounds only for the surviving blocks -- was
+        // built and measured in round 3: the first level reads a quarter of the bytes, but five times as many blocks reach the
+        // second level, whose per-(user, block) gathers of Bmax64 rows cost more than the streamed pass saved: 113 -> 129 ms at 50
+        // clusters.  Removed.)
+        const int64_t bld = p.panel ? p.ldb64 : p.ldb;           // pitch of the bound matrix, of UB and of the survivor lists
+        const int bchunks = (int)(bld / 256);
+        int32_t hv[3] = {0, 0, 0};   // survivors, first / last CSR entry of the batch
+        if (phase != 3) {
+        if (use_sup) {
+            ScoreArgs SU = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks);
+            L.UBs.alloc(ctx, (size_t)nb * 64);
+            SU.Bsup = L.Bsup.get(); SU.asup = L.asup.get(); SU.bsup_b = L.bsupb.get(); SU.UBsup = L.UBs.get();
+            SU.n_sup = std::min(64, std::max(0, p.nblk - seed_chunks));
+            k_score_sup<<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
+            FY_KERNEL_CHECK();
+        }
+        ScoreArgs SA = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks + bchunks);
+        SA.chunks1 = seed_chunks;
+        SA.M2 = p.panel ? PP.Bmax64 : L.Bmax.get();
+        SA.ldm2 = bld;
+        SA.Ic2 = p.panel ? p.nsub : p.nblk;
+        SA.a2 = p.panel ? PP.amax64 : L.amax.get();
+        SA.b2 = p.panel ? PP.bmax64 : L.bmax.get();
+        SA.S2 = L.UB.get();
+        SA.ldS2 = bld;
+        SA.no_mask2 = 1;
+        if (!use_sup) {
+            k_score<4, true, 8><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+            FY_KERNEL_CHECK();
+        }
+        // (2) tau_u = N-th best seed score; the sorted seed head is also the user's list unless a block survives
+        TopNArgs T1{L.S.get(), SC, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(),
+                    lo, s0, c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
+                    1, seed_chunks * 256, L.surv.get(), L.n_quads.get(), bld, L.tau.get()};
+        if (jp.long_seed) {
+            k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(T1, L.overflow.get(), L.any_overflow.get(), 0,
+                                                                                                 fy_topn_long_cap(prm.number_of_recommendations));
+        } else {
+            int lp2 = 64;                   // the sort's size: the seed columns, at most TOPN_SAMPLE
+            while (lp2 < std::min<int>(std::min<int>(Ic, seed_chunks * 256), TOPN_SAMPLE)) lp2 <<= 1;
+            const unsigned sg = (unsigned)((nb + 3) / 4);
+            if (lp2 <= 64) k_topn_seed<1><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+            else if (lp2 == 128) k_topn_seed<2><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+            else if (lp2 == 256) k_topn_seed<4><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+            else if (lp2 == 512) k_topn_seed<8><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+            else k_topn_seed<16><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+        }
+        FY_KERNEL_CHECK();
+        // (4) the blocks whose bound reaches tau_u, in ascending order
+        FY_HIP(hipMemsetAsync(L.n_quads.get(), 0, ((size_t)nb + 1) * sizeof(int32_t), ls));
+        if (p.panel)
+            k_bound_select_sub<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), bld, p.nsub, p.nblk, seed_blocks, L.tau.get(),
+                                                                               X.pvpi + (s0 - lo), nb, bld, L.surv.get(), L.surv_mask.get(), L.n_quads.get());
+        else if (use_sup)
+            k_bound_select_sup<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UBs.get(), std::min(64, std::max(0, p.nblk - seed_chunks)), L.sup_first.get(), L.tau.get(),
+                                                                               X.pvpi + (s0 - lo), nb, p.ldb, L.surv.get(), L.n_quads.get());
+        else
+            k_bound_select<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), p.ldb, p.nblk, seed_blocks, L.tau.get(), X.pvpi + (s0 - lo), nb,
+                                                                           L.surv.get(), L.n_quads.get());
+        FY_KERNEL_CHECK();
+        if (tune.debug_sync == 3 && !p.panel) {      // which blocks survive, and for how many users
+            DevBuf<int32_t> cnt(ctx, (size_t)p.nblk + 1);
+            FY_HIP(hipMemsetAsync(cnt.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
+            k_surv_block_counts<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, cnt.get());
+            std::vector<int32_t> hc((size_t)p.nblk + 1);
+            FY_HIP(hipMemcpyAsync(hc.data(), cnt.get(), hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+            FY_HIP(hipStreamSynchronize(ls));
+            int distinct = 0;
+            long long total = 0;
+            for (int b2 = 0; b2 < p.nblk; b2++) { distinct += hc[b2] > 0; total += hc[b2]; }
+            fprintf(stderr, "[fy] cluster %d: %lld surviving (user, block) pairs in %d distinct blocks of %d:", c, total, distinct, p.nblk);
+            for (int b2 = 0; b2 < p.nblk; b2++)
+                if (hc[b2]) fprintf(stderr, " %d:%d", b2, hc[b2]);
+            fprintf(stderr, "\n");
+        }
+        if (p.panel && tune.panel_repair) {
+            // (4b) sub-blocks that hold an item the user rated: bound again without the user's own co-ratings
+            RepairArgs RA{L.surv.get(), L.surv_mask.get(), L.n_quads.get(), bld, nb, s0, lo, p.p_eff, Ic, P.rowptr.get(), P.csr_idx.get(),
+                          X.csr_x, X.csr_e, X.csr_q, PP.Bmax64, PP.Brep, p.ldb64, PP.amax64, PP.bmax64,
+                          L.tau.get(), X.pvpi, (float)w2s, X.prune_counters};
+            k_bound_repair<<<std::min<int>(nb, ctx->num_cus * 16), 256, 0, ls>>>(RA);
+            FY_KERNEL_CHECK();
+        }
+        if (p.half && !p.panel && tune.lazy_mirror) {      // lazy mirror, second pass: the column blocks with survivors
+            const size_t sm = X.t_mirror->begin(ls);
+            L.need.alloc(ctx, (size_t)p.nblk + 1);
+            FY_HIP(hipMemsetAsync(L.need.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
+            k_flag_surviving_blocks<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, L.need.get());
+            FY_KERNEL_CHECK();
+            launch_mirror(ctx, L.M.get(), ldm, Ic, nullptr, p.ldb, ls, L.need.get(), 0, false);
+            X.t_mirror->end(sm, ls);
+        }
+        exclusive_scan_i32(ctx, L.n_quads.get(), L.quad_prefix.get(), (size_t)nb + 1, ls, &L.scan_tmp);
+        if (split) {      // the count goes to pinned memory; the host does not wait here
+            FY_HIP(hipMemcpyAsync(&V.pinned[pi], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+            X.t_score->end(ss, ls);
+            checkpoint(X, V, "front (seed + bound, select, second bound)");
+            continue;
+        }
+        }      // phase != 3
+        // (5) exact scores of the survivors, packed: 256 floats per surviving block at entry quad_prefix[u] + k
+        if (!split) FY_HIP(hipMemcpyAsync(&hv[0], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+        else hv[0] = V.pinned[pi];
+        if (s0 == sbase && nb == p.Uc) {      // the whole cluster: its CSR range is on the host already
+            hv[1] = (*X.csr_range)[2 * pi];
+            hv[2] = (*X.csr_range)[2 * pi + 1];
+        } else {
+            FY_HIP(hipMemcpyAsync(&hv[1], P.rowptr.get() + s0, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+            FY_HIP(hipMemcpyAsync(&hv[2], P.rowptr.get() + s0 + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+        }
+        if (!split) FY_HIP(hipStreamSynchronize(ls));   // (everything queued on this lane before has finished: Ssurv may be re-sized)
+        const int32_t n_surv_total = hv[0];
+        const int64_t blocks_checked = (int64_t)nb * std::max(0, p.nblk - seed_blocks);
+        if (!p.panel && (double)n_surv_total > tune.max_surv_frac * (double)blocks_checked) {     // (panel mode has no full matrix to fall back on)
+            // The threshold did not bite (e.g. lambda = 0: a user who rated an item nobody else of the cluster rated has
+            // only -inf scores, tau = -inf keeps every block): the survivor pass would cost more than the plain full pass
+            // and 1 KB of scratch per survivor.  Redo the batch with the full pass, in sub-batches that fit the workspace.
+            X.t_score->end(ss, ls);
+            if (p.half && tune.lazy_mirror) {      // the plain full pass reads every row whole: the rest of the lower triangle now
+                const size_t sm = X.t_mirror->begin(ls);
+                launch_mirror(ctx, L.M.get(), ldm, Ic, nullptr, p.ldb, ls, nullptr, 0x7FFFFFFF, false);
+                X.t_mirror->end(sm, ls);
+            }
+            const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((jp.ws / jp.NS) / (ldm * 4), nb));
+            DevBuf<float> Sfull(ctx, (size_t)(sub * ldm));
+            for (int32_t t0 = s0; t0 < s0 + nb; t0 += (int32_t)sub) full_pass(t0, (int32_t)std::min<int64_t>(sub, s0 + nb - t0), Sfull.get());
+            FY_HIP(hipStreamSynchronize(ls));   // Sfull goes back to the allocator
+            R->st.prune_fallbacks++;
+            R->st.score_launches++;          // the fused seed + bound launch that was thrown away
+            *X.blocks_total += blocks_checked;
+            *X.fallback_survived += n_surv_total;
+            *X.seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (seed_chunks * 256 + p.ldb + ldm);
+            continue;
+        }
+        L.Ssurv.alloc(ctx, (size_t)std::max(1, n_surv_total) * PRUNE_BLOCK);
+        if (n_surv_total > 0) {
+            ScoreArgs SQ = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.Ssurv.get(), 0, n_slices, n_chunks);
+            const int panel_blocks = p.panel ? p.panel_cols / 256 : 0x7FFFFFFF;
+            k_score_blocks<8><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
+                                                                L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, bld, X.prune_counters, panel_blocks,
+                                                                p.panel ? L.surv_mask.get() : nullptr);
+            FY_KERNEL_CHECK();
+            if (p.panel && panel_blocks < p.nblk) {     // survivors behind the panel: exact, from the sparse data
+                const size_t slds = ((size_t)p.Uc + 1) * sizeof(int32_t);
+                const int sgrid = std::min<int>(n_surv_total, ctx->num_cus * (int)std::max<size_t>(1, std::min<size_t>(6, (150 * 1024) / (slds + 34 * 1024))));
+                L.strayT.alloc(ctx, (size_t)sgrid * STRAY_TCAP);
+                L.stray_items.alloc(ctx, (size_t)n_surv_total + 1);      // (a group holds at least one surviving block)
+                FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
+                k_stray_items<<<grid_for(nb), 256, 0, ls>>>(L.quad_prefix.get(), L.surv.get(), bld, nb, panel_blocks, L.stray_items.get(),
+                                                           L.any_overflow.get());
+                FY_KERNEL_CHECK();
+                StrayArgs ST{L.quad_prefix.get(), L.surv.get(), L.surv_mask.get(), bld, nb, s0, lo, sbase, p.Uc, panel_blocks, Ic, pbase,
+                             P.rowptr.get(), P.csr_idx.get(), X.csr_e, X.csr_q, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(),
+                             tc.csc_x.get(), X.a_rank + pbase, X.b_rank + pbase, X.pvpi,
+                             (float)w2s, L.Ssurv.get(), L.strayT.get(), X.prune_counters, L.stray_items.get(),
+                             L.any_overflow.get()};
+                k_score_stray<<<sgrid, 256, slds, ls>>>(ST);
+                FY_KERNEL_CHECK();
+            }
+        }
+        X.t_score->end(ss, ls);
+        R->st.score_launches += 2;   // the fused seed + bound launch and the survivor pass
+        *X.blocks_total += blocks_checked;
+        // log terms of the seed and bound passes of this batch: (ratings of its users) x (columns walked)
+        *X.seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (seed_chunks * 256 + (use_sup ? 64 : bld));
+        const int32_t seed_cols_p = seed_chunks * 256;
+        TopNArgs TA{L.S.get(), (int64_t)seed_cols_p, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase,
+                    P.slot2du.get(), P.uid.get(), lo, s0, c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
+                    2, seed_cols_p, L.surv.get(), L.n_quads.get(), bld, L.tau.get(), L.Ssurv.get(), L.quad_prefix.get()};
+        const size_t tt = X.t_topn->begin(ls);
+        FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
+        if (jp.long_seed)
+            k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select,
+                                                                                                 fy_topn_long_cap(prm.number_of_recommendations));
+        else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
+        FY_KERNEL_CHECK();
+        k_topn_select<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), X.prune_counters + 2);
+        FY_KERNEL_CHECK();
+        X.t_topn->end(tt, ls);
+        refine_rows(s0, nb);
+        checkpoint(X, V, "back (survivors, strays, lists)");
+    }
+}
+
+static void visit_cluster(const ScoreShared& X, const ClusterVisit& V) {
+    const JobPlan& jp = *X.jp;
+    const Plan& p = jp.plans[V.pi];
+    const Lane& L = *V.L;
+    const PanelPtrs& PP = V.PP;
+    checkpoint(X, V, "start");
+    if (p.panel && (!PP.Gp || !PP.Bmax64 || !PP.Brep || !PP.amax64 || !PP.bmax64 || (jp.two_phase && (!L.S.get() || !L.UB.get() || !L.n_quads.get()) && V.phase != 1)))
+        FY_FAIL(FY_ERR_STATE, "internal: cluster %d (plan %zu, group %d of %d, phase %d) has no panel buffers", p.c, V.pi, V.grp, jp.n_groups, V.phase);
+    if (p.coop) {
+        score_cluster_coop(X, p, V.ls);
+        return;
+    }
+    const ClusterNumbers N = cluster_numbers(X, p);
+    const bool do_build = !(V.phase >= 2 && p.panel), do_score = V.phase != 1;
+    if (do_build) build_cluster_matrix(X, V, N);
+    if (do_score) score_cluster(X, V, N);
+}
+
+// phase 1 of a group: the row kernels of all its panel clusters in two launches, then (symmetric panel mode) the lower triangle of
+// every panel's square and the head rows' bounds
+static void launch_panel_batch(const ScoreShared& X, int grp, PanelSet& PS) {
+    Context* ctx = X.J->ctx;
+    fy_result* R = X.R;
+    const ScoreTune& tune = *X.tune;
+    const JobPlan& jp = *X.jp;
+    hipStream_t st = ctx->stream;
+    std::vector<PanelBuf>& pbuf = PS.pbuf;
+    std::vector<CoocLaunch>&batch_main = PS.batch_main, &batch_tail = PS.batch_tail;
+    std::vector<PanelDesc>& hpd = PS.hpd;
+    DevBuf<PanelDesc>& d_panel_desc = PS.d_panel_desc;
+    const size_t sp = X.t_cooc->begin(st);
+    launch_cooc_rm2_multi(ctx, tune, batch_tail, true, PS.d_batch_tail, PS.d_cnt_tail, st, true);
+    launch_cooc_rm2_multi(ctx, tune, batch_main, false, PS.d_batch_main, PS.d_cnt_main, st, true);
+    X.t_cooc->end(sp, st);
+    // symmetric panel mode: the lower triangle of every panel's square, then the head rows' bounds (three launches for all clusters)
+    int max_cols = 0, max_nsub = 0;
+    for (size_t pi = 0; pi < jp.plans.size(); pi++) {
+        const Plan& p = jp.plans[pi];
+        if (!p.psym || jp.group_of[pi] != grp) continue;
+        hpd.push_back(PanelDesc{pbuf[pi].Gp.get(), pbuf[pi].Bmax64.get(), pbuf[pi].Brep.get(), p.panel_cols, p.ldb64, p.Ic, p.p_eff, p.nsub, 0});
+        max_cols = std::max(max_cols, p.panel_cols);
+        max_nsub = std::max(max_nsub, p.nsub);
+    }
+    if (!hpd.empty()) {
+        // operand check on the host (round 3: these launches faulted at address 0x1000 when a half-built group handed them the
+        // descriptors of clusters whose panels were not allocated): every panel pointer set, every shape what the kernels' grids assume
+        for (size_t k = 0; k < hpd.size(); k++) {
+            const PanelDesc& d = hpd[k];
+            if (!d.Gp || !d.Bmax64 || !d.Brep || d.panel_cols <= 0 || d.panel_cols % 256 != 0 || d.p_eff != d.panel_cols || d.Ic < d.p_eff || d.nsub <= 0 ||
+                d.ldb64 < d.nsub)
+                FY_FAIL(FY_ERR_STATE, "internal: panel %zu of %zu of a batched mirror / column-maximum launch is unusable (Gp %p Bmax64 %p Brep %p panel_cols %d p_eff %d Ic %d nsub %d ldb64 %lld)",
+                        k, hpd.size(), (const void*)d.Gp, (const void*)d.Bmax64, (const void*)d.Brep, (int)d.panel_cols, (int)d.p_eff, (int)d.Ic, (int)d.nsub, (long long)d.ldb64);
+        }
+        const size_t sm = X.t_mirror->begin(st);
+        d_panel_desc.alloc(ctx, hpd.size());
+        FY_HIP(hipMemcpyAsync(d_panel_desc.get(), hpd.data(), hpd.size() * sizeof(PanelDesc), hipMemcpyHostToDevice, st));
+        const unsigned nz = (unsigned)hpd.size();
+        if (max_cols / 256 > 1) {
+            FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mirror_tiles_multi), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * MIRROR_PITCH));
+            k_mirror_tiles_multi<<<dim3((unsigned)(max_cols / 128), (unsigned)(max_cols / 256 - 1), nz), 1024, 128 * MIRROR_PITCH, st>>>(d_panel_desc.get());
+            FY_KERNEL_CHECK();
+        }
+        k_mirror_diag_multi<<<dim3((unsigned)(max_cols / 256), nz), 256, 0, st>>>(d_panel_desc.get());
+        FY_KERNEL_CHECK();
+        k_panel_colmax<<<dim3((unsigned)(max_cols / 256), (unsigned)ceil_div(max_nsub, 16), nz), 256, 0, st>>>(d_panel_desc.get());
+        FY_KERNEL_CHECK();
+        X.t_mirror->end(sm, st);
+    }
+    if (tune.debug_sync == 1) {
+        const hipError_t e = hipDeviceSynchronize();
+        fprintf(stderr, "[fy] group %d/%d: batched row kernels, mirror, column maxima -> %s\n", grp, jp.n_groups, hipGetErrorString(e));
+        fflush(stderr);
+    }
+    R->st.cooc_launches += (batch_tail.empty() ? 0 : 1) + 1;
+}
+
+// The clusters outside the flat batches.  One phase (0): every cluster start to end on its lane.  Two-phase panel mode, per group:
+// phase 1 = the panels of all panel-mode clusters on the main stream, phase 2 = everything else on the lanes up to the survivor
+// counts, phase 3 = the panel clusters' survivor passes and lists.
+static void score_clusters(const ScoreShared& X, std::vector<Lane>& lanes, PanelSet& PS, LaneGuard& guard) {
+    Context* ctx = X.J->ctx;
+    const ScoreTune& tune = *X.tune;
+    const JobPlan& jp = *X.jp;
+    hipStream_t st = ctx->stream;
+    std::vector<PanelBuf>& pbuf = PS.pbuf;
+    std::vector<Lane>& plane = PS.plane;
+    for (int grp = 0; grp < jp.n_groups; grp++) {
+    if (jp.two_phase) {
+        if (grp > 0) {       // the previous group's kernels have drained (below): its panels and scratch go back to the allocator
+            for (size_t pi = 0; pi < jp.plans.size(); pi++)
+                if (jp.plans[pi].panel && jp.group_of[pi] == grp - 1) { pbuf[pi] = PanelBuf(); plane[pi] = Lane(); }
+        }
+        group_buffers(ctx, jp, tune.seed_chunks, lanes, grp, PS);
+        PS.batch_main.clear();
+        PS.batch_tail.clear();
+        PS.hpd.clear();
+    }
+    for (int phase = jp.two_phase ? 1 : 0; phase <= (jp.two_phase ? 3 : 0); phase++) {
+    const auto host_t0 = std::chrono::steady_clock::now();
+    struct PhaseClock {
+        const std::chrono::steady_clock::time_point t0;
+        int grp, phase;
+        bool on;
+        ~PhaseClock() {
+            if (on) fprintf(stderr, "[fy] group %d phase %d: host queued for %.3f ms\n", grp, phase, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        }
+    } phase_clock{host_t0, grp, phase, tune.debug_sync != 0};
+    if (phase == 3) {             // every cluster's survivor count has been queued: one wait for all of them
+        for (int l = 0; l < jp.NS; l++) FY_HIP(hipStreamSynchronize(lanes[l].st));
+        FY_HIP(hipStreamSynchronize(st));
+    }
+    if ((phase == 0 || phase == 2) && jp.NS > 1) {   // the lanes start after everything queued on the main stream so far
+        if (guard.fork) { FY_HIP(hipEventDestroy(guard.fork)); guard.fork = nullptr; }
+        FY_HIP(hipEventCreateWithFlags(&guard.fork, hipEventDisableTiming));
+        FY_HIP(hipEventRecord(guard.fork, st));
+        for (int l = 0; l < jp.NS; l++) FY_HIP(hipStreamWaitEvent(lanes[l].st, guard.fork, 0));
+    }
+
+    for (size_t pi = 0; pi < jp.plans.size(); pi++) {
+        const Plan& p = jp.plans[pi];
+        if (p.flat) continue;                  // done above
+        if (jp.group_of[pi] != grp) continue;     // (clusters outside panel mode are in group 0)
+        if ((phase == 1 || phase == 3) && !p.panel) continue;
+        const bool own = jp.two_phase && p.panel;      // the cluster's own panel and scratch (PanelSet), else the lane's
+        Lane& L = phase == 1 ? lanes[0] : (own ? plane[pi] : lanes[pi % jp.NS]);
+        const PanelPtrs PP = own ? PanelPtrs{pbuf[pi].Gp.get(), pbuf[pi].Bmax64.get(), pbuf[pi].Brep.get(), pbuf[pi].amax64.get(), pbuf[pi].bmax64.get()}
+                                 : PanelPtrs{L.Gp.get(), L.Bmax64.get(), L.Brep.get(), L.amax64.get(), L.bmax64.get()};
+        visit_cluster(X, ClusterVisit{pi, grp, phase, &L, phase == 1 ? st : L.st, PP, own ? &pbuf[pi].head32 : &L.head32, own ? &pbuf[pi].tail32 : &L.tail32,
+                                      own ? &plane[pi] : nullptr, &PS, guard.pinned});
+    }
+    if (phase == 1 && (!PS.batch_main.empty() || !PS.batch_tail.empty())) launch_panel_batch(X, grp, PS);
+    if (tune.debug_sync == 2) {
+        (void)hipDeviceSynchronize();
+        fprintf(stderr, "[fy] group %d phase %d: %.3f ms from its first queued operation to the drained device\n", grp, phase,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count());
+    }
+    }      // phase
+    if (grp + 1 < jp.n_groups) {     // the next group re-uses this group's memory: everything queued so far must have finished
+        for (int l = 0; l < jp.NS; l++) FY_HIP(hipStreamSynchronize(lanes[l].st));
+        FY_HIP(hipStreamSynchronize(st));
+    }
+    }      // group
+    if (jp.NS > 1) {   // join: the main stream continues after every lane has drained
+        for (int l = 0; l < jp.NS; l++) {
+            hipEvent_t done;
+            FY_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+            FY_HIP(hipEventRecord(done, lanes[l].st));
+            FY_HIP(hipStreamWaitEvent(st, done, 0));
+            FY_HIP(hipEventDestroy(done));
+        }
+    }
+}
+
+// ---- 8. what the job says about itself: counters of the pruned passes, the tables, the bytes the row kernels stored
+static void fill_score_stats(const ScoreShared& X, bool tables_cached, const std::vector<int32_t>& sig) {
+    fy_rm2_job* J = X.J;
+    Context* ctx = X.J->ctx;
+    fy_result* R = X.R;
+    const JobPlan& jp = *X.jp;
+    TableCache& tc = J->S->tables;
+    const bool all_at_once = jp.plans.size() > 1 && !jp.any_coop;
+    unsigned long long hc[6];
+    d2h(ctx, hc, X.prune_counters, 6);
+    sync(ctx);
+    if (!tables_cached && !all_at_once) {        // (build_tables_all counts its one table itself)
+        tc.total_segments = 0;
+        for (auto& t : tc.segs) tc.total_segments += t.n_seg;
+        for (auto& t : tc.segs_tail) tc.total_segments += t.n_seg;
+    }
+    tc.sig = sig;          // every table of the plan has been built and used: a later job with the same plan re-uses them
+    tc.valid = true;
+    R->st.cooc_segments = tc.total_segments;
+    for (auto& p : jp.plans) {       // what the row kernels store (the mirror pass and the column maxima are priced separately)
+        const int64_t eb = p.pack24 ? 3 : 4;
+        if (p.coop) continue;
+        if (p.panel) R->st.cooc_matrix_bytes += (int64_t)p.Ic * p.panel_cols * 3 + (int64_t)p.Ic * p.ldb64 * 7;
+        else R->st.cooc_matrix_bytes += eb * (p.half ? (int64_t)p.Ic * (p.Ic + 256) / 2 : (int64_t)p.Ic * p.Ic) + (p.prune ? (int64_t)p.Ic * p.nblk * 3 : 0);
+    }
+    R->st.topn_select_users = (int64_t)hc[2];
+    R->st.stray_blocks = (int64_t)hc[3];
+    R->st.bound_repairs = (int64_t)hc[4];
+    R->st.rows_refined = (int64_t)hc[5];
+    R->st.blocks_survived = (int64_t)hc[0] + *X.coop_survived + *X.fallback_survived;
+    R->st.blocks_total = *X.blocks_total;
+    R->st.log_terms_evaluated = *X.blocks_total ? (int64_t)hc[1] + *X.seed_terms_cols : 0;
+}
+
+// what plan_job reads of the job (the owner ranges and n_recs are filled in by fy_rm2_score once they are known)
+static PlanInput plan_input(const fy_rm2_job* J) {
+    const Prepared& P = J->P;
+    const fy_rm2_params& prm = J->prm;
+    PlanInput in;
+    in.K = P.K;
+    in.nU = P.nU;
+    in.csize = P.csize;
+    in.ucstart = P.ucstart;
+    in.pcstart = P.pcstart;
+    in.cluster_q = P.cluster_q;
+    in.cluster_deg2 = P.cluster_deg2;
+    in.sum_deg2 = P.sum_deg2;
+    in.ratings_fp16_exact = P.ratings_fp16_exact;
+    in.fx_bounds = J->fx_bounds;
+    in.number_of_recommendations = prm.number_of_recommendations;
+    in.rank = prm.rank;
+    in.world = prm.world;
+    in.lambda = prm.lambda;
+    in.workspace_bytes = prm.workspace_bytes;
+    in.tune = J->ctx->tune;
+    in.total_mem = J->ctx->total_mem;
+    in.sharded = J->S->sharded;
+    in.have_coll = J->have_coll;
+    return in;
+}
 fy_result* fy::rm2_score(fy_rm2_job* J) {
     Context* ctx = J->ctx;
     Prepared& P = J->P;
@@ -2025,1307 +3216,88 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
         sync(ctx);
         return R.release();
     }
-    const int32_t nU = P.nU, nP = P.nP, nI = P.nI, K = P.K;
-    const double lambda = prm.lambda;
-    ScoreTune tune = score_tune(ctx);
-    // tau_u is the N-th best of the seed scores: a seed of only a few N columns gives a weak threshold and many survivors
-    // (Netflix shape, N = 100: 2.7 % of the blocks survive a 256-column seed, 0.1 % a 512-column one)
-    // (round 4: also for long lists -- the reference's default is N = 1000, RMRecommenderDriver.java:95 -- whose seed is 5 N columns too:
-    // 5120 of ML-25M's 59 047; up to round 3 the seed stopped at 1024 columns, whose 1000th best is no threshold at all, and such
-    // jobs took the plain full pass)
-    if (tune.seed_chunks == 0) tune.seed_chunks = (int)std::min<int64_t>(SEED_CHUNKS_MAX, std::max<int64_t>(1, ceil_div(5 * (int64_t)prm.number_of_recommendations, 256)));
-    // lists the one-wave seed sort cannot hold (k_topn_seed: at most TOPN_SAMPLE seed columns, lists of at most TOPN_LONG items) take
-    // k_topn_long in its seed / merge modes
-    const bool long_seed = tune.seed_chunks * 256 > TOPN_SAMPLE || prm.number_of_recommendations > TOPN_LONG;
-    const bool short_seed_ok = tune.seed_forced || 5 * (int64_t)prm.number_of_recommendations <= 4 * 256;     // (the cooperative path's limit)
-    const bool pack24_allowed = tune.pack24 != 0;
-    int64_t coop_pair_contribs = 0;   // cooperative clusters: ordered off-diagonal co-rating pairs of this rank's matrix rows
-    bool any_coop = false;
-
-    // ---- p(i|C), per-(cluster,item) statistics, per-rating values
-    // (sharded prep: the job's own dense items are this rank's clusters' items; the result's itemColl is the global one, built at the end)
-    DevBuf<double> icoll_mine;
-    if (J->S->sharded) icoll_mine.alloc(ctx, nI); else R->d_icoll.alloc(ctx, nI);
-    double* const d_icoll = J->S->sharded ? icoll_mine.get() : R->d_icoll.get();
-    DevBuf<double> d_total(ctx, 1);
-    k_item_coll<<<grid_for(nI), 256, 0, st>>>(nI, J->stats.get(), d_icoll, d_total.get());
-    FY_KERNEL_CHECK();
-    DevBuf<double> p_rank(ctx, nP);
-    DevBuf<double>& b_rank = J->b_rank;
-    DevBuf<float> a_rank(ctx, nP), b_rank32(ctx, nP);
-    DevBuf<double2> pb_rank(ctx, nP);
-    k_pair_p<<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, b_rank.get(), p_rank.get(), a_rank.get(),
-                                           b_rank32.get(), pb_rank.get());
-    FY_KERNEL_CHECK();
-    DevBuf<float> csr_x(ctx, P.nnz), csr_e(ctx, P.nnz), csr_q(ctx, P.nnz);
+    const int32_t nU = P.nU, nI = P.nI;
+    PlanInput in = plan_input(J);
+    ScoreTune tune = ctx->tune;
+    tune.seed_chunks = plan_seed(tune, prm.number_of_recommendations).seed_chunks;     // (0 = from the list length)
     const bool use_pk = tune.cooc_pk && P.ratings_fp16_exact;   // packed CSR for the row kernel
-    // the row kernel's tables live with the static part of the job (TableCache): a warm job finds them built
-    TableCache& tc = J->S->tables;
-    DevBuf<float>&csc_x = tc.csc_x, &csc_x_over_s = tc.csc_x_over_s;
-    DevBuf<uint32_t>&csr_pk = tc.csr_pk, &y_pk = tc.y_pk;
-    DevBuf<int32_t>& csc_rank = tc.csc_rank;
-    std::vector<SegTable>&segs = tc.segs, &segs_tail = tc.segs_tail;
-    // (normally written by fy_rm2_prepare's statistics pass; here only when the walk's kind changed between the two calls)
-    if (!tc.have_x || csc_x.size() != (size_t)P.nnz || csc_x_over_s.size() != (use_pk ? (size_t)P.nnz : 1)) {
-        tc.valid = tc.have_x = false;
-        csc_x.alloc(ctx, P.nnz);
-        csc_x_over_s.alloc(ctx, use_pk ? (size_t)P.nnz : 1);
-        k_csc_x<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_slot.get(), P.csc_r.get(), J->usum_slot.get(), csc_x.get(),
-                                                 use_pk ? csc_x_over_s.get() : nullptr);
-        FY_KERNEL_CHECK();
-        tc.have_x = true;
-    }
-    // packed (24-bit) matrix rows only where bandwidth matters: small clusters keep exact fp32 rows (their scores are small, and the
-    // reference's own fixture is asserted with an ABSOLUTE 1e-4, T/util/HadoopIntegrationTest.java:53).  A packed cluster's matrix is
-    // scaled by 2^-c so that every entry is < 1 (FY_P24_SHIFT): G[j][i] = w2 sum_v (r_vj / s_v^2) r_vi <= w2 * (largest column sum
-    // of r / s^2) * (largest rating), the bounds of the fixed-point scale.
-    std::vector<float> h_gscale((size_t)K, 1.0f);
-    std::vector<int32_t> h_cshift((size_t)K, 0);
-    std::vector<char> cluster_pack24((size_t)K, 0);
-    for (int c = 0; c < K; c++) {
-        const int32_t Ic_c = P.pcstart[c + 1] - P.pcstart[c];
-        if (!pack24_allowed || Ic_c < tune.pack24_min_items || J->fx_bounds.size() < 3 * (size_t)(c + 1)) continue;
-        const double gmax = (1.0 - lambda) * (1.0 - lambda) * (double)J->fx_bounds[3 * (size_t)c] * (double)J->fx_bounds[3 * (size_t)c + 2];
-        if (!(gmax >= 0.0) || !std::isfinite(gmax)) continue;                     // unusable bound: fp32 rows
-        const int cs = gmax > 0.0 ? std::max(0, std::ilogb(gmax) + 1) : 0;
-        if (cs > 64) continue;
-        cluster_pack24[c] = 1;
-        h_cshift[c] = cs;
-        h_gscale[c] = std::ldexp(1.0f, -cs);
-    }
-    DevBuf<float> d_gscale(ctx, (size_t)K);
-    DevBuf<int32_t> d_cshift(ctx, (size_t)K);
-    h2d(ctx, d_gscale.get(), h_gscale.data(), (size_t)K);
-    h2d(ctx, d_cshift.get(), h_cshift.data(), (size_t)K);
-    // The per-rating values (x, e, q: what the SCORING kernels read): with the packed walk nothing in front of the scoring reads them, and
-    // what runs until then -- the table kernels, then the one-cluster job's row kernel with ONE workgroup per CU beside its 157 KB of LDS
-    // accumulators -- leaves wave slots and most of the memory system idle.  They are computed on a side stream; the plain one-cluster
-    // flow joins behind its row kernel, every other flow (several lanes, cooperative ranks, flat batches) before its lanes start.
-    struct SideValues {
-        Context* ctx;
-        hipStream_t sv = nullptr;
-        hipEvent_t in = nullptr, out = nullptr;
-        bool launched = false, joined = true;
-        ~SideValues() {     // (a failed job: the side kernel must not outlive the arrays it writes)
-            if (!joined && sv) (void)hipStreamSynchronize(sv);
-            if (in) (void)hipEventDestroy(in);
-            if (out) (void)hipEventDestroy(out);
-        }
-    } side{ctx};
-    auto launch_values = [&](hipStream_t main_stream, bool beside) {
-        if (side.launched) return;
-        side.launched = true;
-        hipStream_t vs = main_stream;
-        if (beside && tune.overlap_values) {
-            if (ctx->aux.empty()) {
-                hipStream_t x;
-                FY_HIP(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-                ctx->aux.push_back(x);
-            }
-            side.sv = ctx->aux[0];
-            FY_HIP(hipEventCreateWithFlags(&side.in, hipEventDisableTiming));
-            FY_HIP(hipEventCreateWithFlags(&side.out, hipEventDisableTiming));
-            FY_HIP(hipEventRecord(side.in, main_stream));
-            FY_HIP(hipStreamWaitEvent(side.sv, side.in, 0));
-            vs = side.sv;
-        }
-        k_csr_values<<<grid_for((int64_t)nU * 64, 256), 256, 0, vs>>>(nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
-                                                                       P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
-                                                                       pb_rank.get(), lambda, d_gscale.get(), csr_x.get(), csr_e.get(), csr_q.get());
-        FY_KERNEL_CHECK();
-        if (vs != main_stream) {
-            FY_HIP(hipEventRecord(side.out, side.sv));
-            side.joined = false;
-        }
-    };
-    auto join_values = [&](hipStream_t s) {
-        if (side.joined) return;
-        side.joined = true;
-        FY_HIP(hipStreamWaitEvent(s, side.out, 0));
-    };
-    // (the packed walk reads the packed CSR; the PLAIN walk's row kernel reads x itself: no overlap there.  Measured on one box, ML-25M
-    // shape, ms per cold job: side stream from here 20.08, launched right in front of the row kernel 20.15, main stream 20.30 / 20.48 --
-    // the table kernels in between wait on the L2's request rate and on dependent loads, and leave more room than the row kernel.)
-    launch_values(st, use_pk);
+    const PackPlan pack = plan_pack24(in);
 
+    // ---- 1. the preamble
+    JobArrays A;
+    SideValues side(ctx);
+    score_preamble(J, R.get(), pack, use_pk, A, side);
     t_tables.end(span_tables);
-    // ---- which users this rank emits lists for
-    J->count_balanced = false;
-    if (prm.world > 1 && !J->S->sharded && J->have_coll && tune.coop && tune.prune && pack24_allowed) {     // (a cooperative cluster must be a packed one: checked per plan below)
-        int nonempty = 0, c1 = -1;
-        for (int c = 0; c < K; c++)
-            if (P.csize[c] > 0) { nonempty++; c1 = c; }
-        if (nonempty == 1) {   // one neighbourhood: it is scored cooperatively when it is big enough for the branch and bound
-            const int32_t Ic1 = P.pcstart[c1 + 1] - P.pcstart[c1];
-            J->count_balanced = Ic1 >= tune.pack24_min_items && Ic1 >= tune.prune_min_items && ceil_div(Ic1, PRUNE_BLOCK) < 0xFFFF &&
-                                P.nU >= prm.world && short_seed_ok && !long_seed;
-        }
-    }
-    int32_t own_lo, own_hi;
-    owner_range(J, prm.rank, own_lo, own_hi);
-    // ---- per-user meta for this rank's slots, output offsets
-    const int32_t lo = own_lo, hi = own_hi, nmine = hi - lo;
-    DevBuf<double> pvpi(ctx, (size_t)nmine + 1);
-    DevBuf<int32_t> n_out(ctx, (size_t)nmine + 1), out_off(ctx, (size_t)nmine + 1);
-    DevBuf<unsigned long long> counters(ctx, 2);
-    counters.zero();
-    n_out.zero();
-    if (nmine > 0) {
-        k_user_meta<<<grid_for(nmine), 256, 0, st>>>(lo, hi, P.slot2du.get(), P.uid.get(), P.ucluster.get(), P.udeg.get(),
-                                                      P.d_csize.get(), P.d_pcstart.get(), prm.number_of_items,
-                                                      prm.number_of_recommendations, prm.filter_users, d_cshift.get(), pvpi.get(), n_out.get(), counters.get());
-        FY_KERNEL_CHECK();
-    }
-    exclusive_scan_i32(ctx, n_out.get(), out_off.get(), (size_t)nmine + 1);
-    const int64_t n_recs = fetch(ctx, out_off.get() + nmine);
-    {
-        unsigned long long hc[2];
-        d2h(ctx, hc, counters.get(), 2);
-        sync(ctx);
-        R->st.log_terms = (int64_t)hc[0];
-        R->st.users_scored = (int64_t)hc[1];
-    }
-    R->n = n_recs;
-    R->st.recs = n_recs;
-    R->d_key0.alloc(ctx, (size_t)n_recs);
-    R->d_key1.alloc(ctx, (size_t)n_recs);
-    R->d_value.alloc(ctx, (size_t)n_recs);
-    R->d_aux.alloc(ctx, (size_t)n_recs);
 
-    // ---- clusters that hold users of this rank
-    int64_t max_Ic = 0;
-    for (int c = 0; c < K; c++) {
-        if (P.csize[c] == 0) continue;
-        R->st.n_clusters_nonempty++;
-        const int32_t a = std::max(lo, P.ucstart[c]), b = std::min(hi, P.ucstart[c + 1]);
-        if (a < b) max_Ic = std::max<int64_t>(max_Ic, P.pcstart[c + 1] - P.pcstart[c]);
+    // ---- 2. which users this rank emits lists for; their meta and output offsets
+    J->count_balanced = plan_count_balanced(in);
+    in.own_lo.resize((size_t)prm.world);
+    in.own_hi.resize((size_t)prm.world);
+    for (int k = 0; k < prm.world; k++) owner_range(J, k, in.own_lo[(size_t)k], in.own_hi[(size_t)k]);
+    const int32_t lo = in.own_lo[(size_t)prm.rank], hi = in.own_hi[(size_t)prm.rank];
+    UserMeta U;
+    in.n_recs = user_meta_and_offsets(J, R.get(), lo, hi, A.d_cshift.get(), U);
+    for (int c = 0; c < P.K; c++)
+        if (P.csize[c] > 0) R->st.n_clusters_nonempty++;
+
+    // ---- the plan (pure host arithmetic: fy_rm2_plan.hpp)
+    JobPlan jp;
+    try {
+        jp = plan_job(in);
+    } catch (const PlanError& e) {
+        FY_FAIL(e.code, "%s", e.msg.c_str());
     }
-    const int32_t eff_top = (int32_t)std::min<int64_t>(prm.number_of_recommendations, max_Ic);
-    if (eff_top > TOPN_MAX)
-        FY_FAIL(FY_ERR_UNSUPPORTED, "min(numberOfRecommendations, items per cluster) = %d exceeds the top-N kernel limit %d", eff_top, TOPN_MAX);
-    if (n_recs > 0 && max_Ic > 0) {
-        const int64_t ws = prm.workspace_bytes > 0 ? prm.workspace_bytes : tune.workspace_default;
-        const int max_ch_lds = tune.cooc_max_ch;   // fp64 accumulators in LDS
+    int64_t coop_pair_contribs = 0;
+    if (in.n_recs > 0 && jp.max_Ic > 0) {
+        const std::vector<Plan>& plans = jp.plans;
         cooc_rm2_allow_lds();
         stray_allow_lds();
+        // (the side stream's per-rating values, see SideValues: only the plain one-cluster flow lets them run beside its row kernel)
+        if (!(jp.NS == 1 && plans.size() == 1 && !plans[0].coop && !plans[0].flat && !plans[0].panel)) side.join(st);
 
-        // ---- per-cluster plan; the clusters are spread over up to four "lanes" (HIP streams with their own M / score
-        // scratch): the tail of one cluster's launches -- its heaviest user sits on a single wave for milliseconds, and
-        // most of its M rows have a handful of raters -- overlaps the next clusters' work instead of idling the chip.
-        std::vector<Plan> plans;
-        constexpr int VEC = 4;   // floats per lane of the scoring kernel: column chunk = 256 items
-        for (int c = 0; c < K; c++) {
-            Plan p{};
-            p.c = c;
-            p.Uc = P.csize[c];
-            if (p.Uc == 0) continue;
-            p.sbase = P.ucstart[c];
-            p.pbase = P.pcstart[c];
-            p.Ic = P.pcstart[c + 1] - p.pbase;
-            p.a = std::max(lo, p.sbase);
-            p.b = std::min(hi, p.sbase + p.Uc);
-            if (p.a >= p.b || p.Ic == 0) continue;
-            p.ldm = round_up(p.Ic, 256);
-            p.pack24 = cluster_pack24[c] != 0;
-            // (the item ids of the row kernel hold the chunk in 8 bits, k_item_list: at most 255 chunks per row -- a forced
-            // FY_COOC_MAX_CH too small for that is widened)
-            pick_chunks(p.Ic, std::max<int>(max_ch_lds, (int)round_up(ceil_div(p.Ic, 255), 256)), p.CH, p.nch);
-            if (p.nch >= 256) FY_FAIL(FY_ERR_UNSUPPORTED, "cluster %d: %d items need %d column chunks (limit 255)", c, p.Ic, p.nch);
-            p.q0 = P.cluster_q[c];
-            p.nq = P.cluster_q[c + 1] - p.q0;
-            // branch-and-bound over 256-column blocks: only where the matrix is big enough for the bound pass to pay
-            p.nblk = (int32_t)ceil_div(p.Ic, PRUNE_BLOCK);
-            p.ldb = round_up(p.nblk, 256);
-            // (the threshold is the N-th best of at most 1024 seed scores: for lists longer than ~200 items it is too weak --
-            // N = 1000 at ML-25M shape: 77 % of the blocks survive and the three passes cost twice the plain one)
-            // (and clusters of a few hundred users are not pruned at all: their seed thresholds are weak -- at 400 clusters of ML-25M
-            // shape, 406 users each, 16-44 % of the blocks survive and the plain full pass is 1.6x faster than any pruned variant)
-            // (long lists: the seed is 5 N columns; where that is more than a third of the cluster's items the bound has nothing left to
-            // exclude and the plain full pass is taken)
-            p.prune = tune.prune && p.pack24 && p.Ic >= tune.prune_min_items && p.nblk < 0xFFFF && p.Uc >= tune.prune_min_users &&
-                      (tune.seed_forced || 3 * (int64_t)tune.seed_chunks * 256 <= (int64_t)p.Ic);
-            if (J->count_balanced && !p.prune) FY_FAIL(FY_ERR_STATE, "internal: count-balanced ownership without a cooperative cluster");
-            // all ranks hold users of this cluster and can talk to each other: score it together, every rank with its
-            // share of the matrix rows (score_cluster_coop)
-            p.coop = false;
-            if (p.prune && tune.coop && short_seed_ok && !long_seed && ((prm.world > 1 && J->have_coll) || tune.coop_force)) {
-                p.coop = true;
-                for (int k = 0; k < prm.world; k++) {
-                    int32_t lo_k, hi_k;
-                    owner_range(J, k, lo_k, hi_k);
-                    if (std::max(lo_k, p.sbase) >= std::min(hi_k, p.sbase + p.Uc)) p.coop = false;
-                }
-            }
-            // symmetric walk: packed rows only (small clusters keep exact fp32 rows and the plain walk); a cooperative rank
-            // owns whole rows of the matrix, so it walks them whole
-            p.half = tune.cooc_half && p.pack24 && !p.coop && p.nch < 256;
-            p.panel = false;
-            p.panel_cols = 0;
-            p.tail_chunks = 0;
-            p.p_eff = p.Ic;
-            p.tail_width = 0;
-            p.nsub = (int32_t)ceil_div(p.Ic, 64);
-            p.ldb64 = round_up(p.nsub, 256);
-            plans.push_back(p);
-        }
-        {   // column-panel mode: many pruned clusters on this rank (the reference's regime: numberOfClusters ~ 50)
-            int n_pruned = 0;
-            for (auto& p : plans) n_pruned += (p.prune && !p.coop) ? 1 : 0;
-            // Long lists are pruned only where a few big clusters keep their dense matrices.  Measured at 50 clusters of ML-25M shape with
-            // N = 1000 (round 4): 41 % of the (user, block) pairs survive the bound of a 3 250-user cluster and 10 M of them lie behind
-            // the panel -- 14.9 s per job against 0.67 s for the plain full pass; one cluster: 14 % survive, 271 against 471 ms.
-            // (and on dense per-cluster matrices instead of panels: 29 568 184 of 29 568 241 blocks survive -- a 3 250-user neighbourhood's
-            // 1000th best score is no threshold -- every cluster falls back to the full pass, 957 ms)
-            if (long_seed && n_pruned >= tune.panel_min_clusters && !tune.seed_forced) {
-                for (auto& p : plans)
-                    if (!p.coop) p.prune = false;
-                n_pruned = 0;
-            }
-            // A cluster that takes the plain full pass reads its WHOLE matrix.  The symmetric walk + mirror pass pays where the walk is
-            // bound by its pair visits (one cluster of ML-25M shape: 6.5e9 visits, 8 ms; the mirror 2.6 ms); a cluster of many (50
-            // clusters: 1.3e8 visits each for 2.6e9 matrix elements) is bound by the rows it WRITES -- 1.65 ms for the half matrix plus 4.3 ms
-            // to mirror 7.8 GB, against ~3.3 ms for the full walk: such clusters walk full rows and skip the mirror.
-            for (auto& p : plans) {
-                const double deg2 = (size_t)p.c < P.cluster_deg2.size() ? (double)P.cluster_deg2[p.c] : (double)P.sum_deg2;
-                if (!p.prune && !p.coop && p.half && tune.full_walk_sparse && deg2 < (double)p.Ic * (double)p.Ic) p.half = false;
-            }
-            if (n_pruned >= tune.panel_min_clusters)
-                for (auto& p : plans)
-                    if (p.prune && !p.coop && use_pk && p.nch < 256 && p.nsub < 0xFFFF && p.Uc <= STRAY_UCAP) {
-                        p.panel = true;
-                        p.half = false;      // a row's block maxima need the whole row
-                        // (the item ids of the row kernel hold the chunk in 8 bits)
-                        pick_chunks(p.Ic, std::min<int>(max_ch_lds, std::max<int>(tune.panel_max_ch, (int)round_up(ceil_div(p.Ic, 255), 256))), p.CH, p.nch);
-                        // smaller clusters keep a wider panel: their survivors reach further down the popularity order (measured,
-                        // ML-25M shape, ms per job with 4096 / 8192 columns: 50 clusters of 3250 users 124 / 141, 100 clusters of
-                        // 1625 users 295 / 227, 200 clusters of 812 users 919 / 509 -- the difference is blocks behind the panel)
-                        const int64_t want_cols = (int64_t)tune.panel_cols * (p.Uc < tune.panel_wide_below_users ? 2 : 1);
-                        p.panel_cols = (int32_t)std::min<int64_t>(p.ldm, std::max<int64_t>(round_up(want_cols, 256), (int64_t)tune.seed_chunks * 256));
-                        // (symmetric panel mode needs the head rows = the panel's columns: whole chunks of a width that divides the panel)
-                        // Either the chunk width is re-picked so that it divides the panel, or -- where that would take too many rows out of
-                        // the head (the rows with EXACT sub-block maxima; a tail row's bounds behind the panel are sums, and looser: Netflix
-                        // shape in 50 clusters, chunks of 3584 columns: 7168 head rows; with 4096 head rows 3867 instead of 58 blocks survive
-                        // behind the panel and the job takes 713 instead of 175 ms) -- the panel is widened to the chunks that cover it.
-                        // (Widening from 1.25 x instead of 1.5 x the panel: 200 clusters of ML-25M shape 285 -> 299 ms, 25 clusters 59.8 -> 62.6 ms.)
-                        const int64_t p_eff_chunks = std::min<int64_t>(ceil_div(p.panel_cols, p.CH) * (int64_t)p.CH, p.Ic);
-                        if (tune.panel_sym && p.panel_cols % p.CH != 0 && 2 * p_eff_chunks > 3 * (int64_t)p.panel_cols && p_eff_chunks % 256 == 0 && p_eff_chunks < p.Ic)
-                            p.panel_cols = (int32_t)p_eff_chunks;
-                        if (tune.panel_sym && p.panel_cols % p.CH != 0) {
-                            const int32_t lim = std::min<int>(max_ch_lds, std::max<int>(tune.panel_max_ch, (int)round_up(ceil_div(p.Ic, 255), 256)));
-                            for (int32_t parts = 1; parts <= 8; parts++) {
-                                const int32_t w = p.panel_cols / parts;
-                                if (p.panel_cols % parts == 0 && w % 256 == 0 && w <= lim && ceil_div(p.Ic, w) < 256) { p.CH = w; p.nch = (int32_t)ceil_div(p.Ic, w); break; }
-                            }
-                        }
-                        p.tail_chunks = (int32_t)ceil_div(p.panel_cols, p.CH);
-                        p.p_eff = (int32_t)std::min<int64_t>((int64_t)p.tail_chunks * p.CH, p.Ic);
-                        if (p.p_eff % 256 != 0 || p.tail_chunks >= p.nch) { p.p_eff = p.Ic; p.tail_chunks = 0; }   // one chunk, or a ragged one: no tail rows
-                        p.tail_width = (int32_t)(p.ldb64 - p.p_eff / 64);
-                    }
-        }
-        const int64_t flat_budget = tune.flat_budget > 0 ? tune.flat_budget : (int64_t)std::min<uint64_t>(ctx->total_mem / 4, (uint64_t)std::max<int64_t>(ws, (int64_t)8 << 30));
-        auto flat_need = [](const Plan& p) {
-            return (int64_t)p.Ic * p.ldm * (p.pack24 ? 3 : 4) + (int64_t)(p.b - p.a) * p.ldm * 4 + (int64_t)p.Ic * p.nch * 12 + 4096;
-        };
-        {   // flat batch: the small unpruned clusters of a multi-cluster job, every kernel of their chain ONE launch for all of them
-            // (FlatDesc, fy_rm2_kernels.hpp).  The matrices and score rows of the clusters of one batch are resident together; a job
-            // whose clusters do not fit the budget takes several batches.
-            int n_flat = 0;
-            const bool can = tune.flat_batch && plans.size() > 1 && use_pk && tune.cooc_fx && !tune.cooc_f32 && !J->fx_bounds.empty() &&
-                             prm.number_of_recommendations <= TOPN_LONG;
-            for (auto& p : plans) {
-                p.flat = false;
-                if (!can || p.prune || p.coop || p.panel) continue;
-                if (fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) < 0) continue;
-                if (flat_need(p) > flat_budget) continue;
-                p.flat = true;
-                n_flat++;
-            }
-            if (n_flat < 2)
-                for (auto& p : plans) p.flat = false;
-            for (auto& p : plans) p.psym = false;
-            for (auto& p : plans)
-                if (p.flat) p.half = false;      // (a mirror pass per cluster would be two more launches each)
-        }
-        bool any_panel = false;
-        for (auto& p : plans) any_panel = any_panel || p.panel;
-        // Two phases for panel-mode jobs (round 3): the matrix panels of ALL clusters are built first, back to back on the main stream
-        // (persistent row kernels that fill every CU's LDS gain nothing from running beside another cluster's), each into its own
-        // buffers; then the clusters' light scoring kernels overlap on the lanes.  With one set of buffers per LANE (round 2) two lanes
-        // were the optimum and mostly waited for each other's row kernels.  Needs every cluster's panel resident: 45 GB at 50 clusters
-        // of ML-25M shape.
-        int64_t panel_bytes = 0;
-        int n_panel = 0;
-        for (auto& p : plans)
-            if (p.panel) { n_panel++; panel_bytes += (int64_t)p.Ic * p.panel_cols * 3 + (int64_t)p.Ic * p.ldb64 * 7 + 64; }
-        // (more panels than fit a third of the HBM: the clusters are taken in GROUPS, each through all phases -- 100 clusters of ML-25M
-        // shape keep 127 GB of panels)
-        const bool two_phase = tune.panel_two_phase && n_panel >= 2;
-        std::vector<int> group_of(plans.size(), 0);
-        int n_groups = 1;
-        if (two_phase) {
-            const int64_t limit = tune.panel_group_bytes > 0 ? tune.panel_group_bytes : (int64_t)(ctx->total_mem / 3);
-            int64_t in_group = 0;
-            int g = 0;
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                const Plan& p = plans[pi];
-                if (!p.panel) continue;
-                const int64_t need = (int64_t)p.Ic * p.panel_cols * 3 + (int64_t)p.Ic * p.ldb64 * 7 + (int64_t)(p.b - p.a) * p.ldb64 * 7 + (int64_t)p.Ic * p.nch * 12;
-                if (in_group > 0 && in_group + need > limit) { g++; in_group = 0; }
-                in_group += need;
-                group_of[pi] = g;
-            }
-            n_groups = g + 1;
-        }
-        (void)panel_bytes;
-        // Symmetric panel mode (two-phase jobs, batched fixed-point row kernels): G is symmetric, so (1) inside the panel's square
-        // [0, p_eff)^2 the head rows are walked like the one-cluster job's -- only the columns behind the row, k_mirror_* fills the
-        // rest -- and (2) the head rows are not walked over the tail columns at all: those co-ratings are the tail rows' with the head
-        // columns, which the tail rows walk and STORE (Gp[j][i], j >= p_eff > i), and the only thing the head rows needed them for,
-        // the maxima of their 64-column sub-blocks, are column maxima of the stored panel (k_panel_colmax).  Half the pair visits.
-        if (two_phase && tune.panel_sym && tune.panel_multi_launch && use_pk && tune.cooc_fx && !tune.cooc_f32 && !J->fx_bounds.empty())
-            for (auto& p : plans)
-                p.psym = p.panel && p.tail_chunks > 0 && p.p_eff < p.Ic && p.p_eff == p.panel_cols && p.p_eff % 256 == 0 && p.a == p.sbase && p.b == p.sbase + p.Uc &&
-                         fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) >= 0;
-        // (lanes: one-phase panel mode 2 -- more lanes only queue behind each other's row kernels; two-phase 8 -- only light kernels are left
-        // on the lanes: measured at 50 clusters, ms per job: 2 lanes 98.0, 4: 95.9, 8: 93.1)
-        const int want_lanes = tune.lanes_forced ? tune.lanes : (two_phase ? std::max(tune.lanes, 8) : (any_panel ? std::min(tune.lanes, tune.panel_lanes) : tune.lanes));
-        const int NS = (int)std::min<size_t>(plans.size() > 1 ? (size_t)want_lanes : 1, plans.size());
-        // (the side stream's per-rating values, see above: only the plain one-cluster flow lets them run beside its row kernel)
-        if (!(NS == 1 && plans.size() == 1 && !plans[0].coop && !plans[0].flat && !plans[0].panel)) join_values(st);
-        struct Lane {
-            hipStream_t st;
-            DevBuf<float> M, S;
-            DevBuf<int32_t> overflow, any_overflow;
-            // branch and bound
-            DevBuf<float> Bmax, amax, bmax, UB, tau;
-            DevBuf<float> Gp, Bmax64, amax64, bmax64;    // column-panel mode
-            DevBuf<uint32_t> Brep;
-            DevBuf<uint16_t> surv;
-            DevBuf<uint8_t> surv_mask;     // panel mode: which 64-column sub-blocks of a surviving block passed the bound
-            DevBuf<int2> strayT;           // co-rater tables of k_score_stray
-            DevBuf<int2> stray_items;
-            DevBuf<int32_t> n_heavy;       // k_count_heavy
-            DevBuf<int32_t> need;          // lazy mirror: column blocks with survivors
-            DevBuf<float> Bsup, asup, bsupb, UBs;      // super-block bounds (k_score_sup)
-            DevBuf<double> head32, tail32;             // unrounded fp64 rows / columns the refinement pass reads (k_refine_rows)
-            DevBuf<int32_t> colmap;
-            DevBuf<int32_t> sup_first;
-            DevBuf<int32_t> n_quads, quad_prefix;
-            DevBuf<char> scan_tmp;         // temporary storage of the lane's scans
-            DevBuf<int2> item_seg, item_seg_t;      // (_t: the tail-row bound launch of a cluster whose row kernels are batched)
-            DevBuf<int32_t> item_id, item_id_t;
-            DevBuf<float> Ssurv;   // packed scores of the surviving blocks (pruned clusters)
-        };
-        std::vector<Lane> lanes((size_t)NS);
-        {
-            size_t is_el = 1;
-            for (auto& p : plans)
-                if (!p.flat) is_el = std::max(is_el, (size_t)p.Ic * p.nch);
-            size_t m_el = 1, s_el = 1, ov_el = 1, bm_el = 1, ub_el = 1, am_el = 1, gp_el = 1, b64_el = 1, a64_el = 1;
-            for (auto& p : plans) {
-                p.B = std::min<int64_t>(std::max<int64_t>(1, (ws / NS) / (p.ldm * 4)), p.b - p.a);
-                // pruned clusters keep only the seed columns of a score row (the survivors' scores are packed, see below):
-                // all users of the rank in one batch
-                const int64_t seed_cols = (int64_t)std::min<int64_t>(ceil_div(p.Ic, 256), tune.seed_chunks) * 256;
-                if (p.prune || p.flat) p.B = p.b - p.a;
-                if (p.coop || p.flat) continue;   // allocate for themselves
-                if (p.panel) {
-                    gp_el = std::max(gp_el, (size_t)p.Ic * p.panel_cols * 3 / 4 + 4);
-                    b64_el = std::max(b64_el, (size_t)p.Ic * p.ldb64 * 3 / 4 + 4);
-                    a64_el = std::max(a64_el, (size_t)p.ldb64);
-
-                    s_el = std::max(s_el, (size_t)(p.B * seed_cols));
-                    ov_el = std::max(ov_el, (size_t)p.B);
-                    ub_el = std::max(ub_el, (size_t)(p.B * p.ldb64));
-                    continue;
-                }
-                m_el = std::max(m_el, (size_t)(p.Ic * p.ldm));
-                s_el = std::max(s_el, (size_t)(p.B * (p.prune ? seed_cols : p.ldm)));
-                ov_el = std::max(ov_el, (size_t)p.B);
-                if (p.prune) {
-                    bm_el = std::max(bm_el, (size_t)(p.Ic * p.ldb));
-                    ub_el = std::max(ub_el, (size_t)(p.B * p.ldb));
-                    am_el = std::max(am_el, (size_t)p.ldb);
-                }
-            }
-            if (NS > 1 && ctx->aux.size() < (size_t)NS) {
-                while (ctx->aux.size() < (size_t)NS) {
-                    hipStream_t x;
-                    FY_HIP(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-                    ctx->aux.push_back(x);
-                }
-            }
-            for (int l = 0; l < NS; l++) {
-                Lane& L = lanes[l];
-                L.st = NS > 1 ? ctx->aux[l] : st;
-                L.M.alloc(ctx, m_el);
-                L.S.alloc(ctx, s_el);
-                L.overflow.alloc(ctx, ov_el);
-                L.any_overflow.alloc(ctx, 1);
-                L.n_heavy.alloc(ctx, 1);
-                L.Bmax.alloc(ctx, bm_el);
-                L.amax.alloc(ctx, am_el);
-                L.bmax.alloc(ctx, am_el);
-                L.Gp.alloc(ctx, two_phase ? 1 : gp_el);
-                L.Bmax64.alloc(ctx, two_phase ? 1 : b64_el);
-                L.Brep.alloc(ctx, gp_el > 1 && !two_phase ? b64_el * 4 / 3 + 4 : 1);     // (b64_el counts floats for 3-byte entries)
-                L.amax64.alloc(ctx, two_phase ? 1 : a64_el);
-                L.bmax64.alloc(ctx, two_phase ? 1 : a64_el);
-                L.UB.alloc(ctx, ub_el);
-                L.tau.alloc(ctx, ov_el);
-                L.surv.alloc(ctx, ub_el);
-                L.surv_mask.alloc(ctx, gp_el > 1 ? ub_el : 1);
-                L.n_quads.alloc(ctx, ov_el + 1);
-                L.quad_prefix.alloc(ctx, ov_el + 1);
-                L.item_seg.alloc(ctx, is_el);
-                L.item_id.alloc(ctx, is_el);
-            }
-        }
-        DevBuf<unsigned long long> prune_counters(ctx, 6);   // ... [5] list rows scored again by the refinement pass   // [0] surviving blocks, [1] log terms evaluated by the three pruned passes, [2] users sent to k_topn_select, [3] stray blocks (panel mode)
+        // ---- 3. lanes
+        std::vector<Lane> lanes((size_t)jp.NS);
+        alloc_lanes(ctx, jp, lanes);
+        DevBuf<unsigned long long> prune_counters(ctx, 6);   // (ScoreShared::prune_counters)
         prune_counters.zero();
         int64_t prune_blocks_total = 0, prune_seed_terms_cols = 0, coop_survived = 0, fallback_survived = 0;
-        for (auto& p : plans) any_coop = any_coop || p.coop;
-        // segment tables of the row kernel, one per cluster (built on the main stream before the lanes fork, or by the lanes): kept
-        // with the job's static part -- a job over the same ratings, clustering and launch plan re-uses them
-        bool any_tail = false, any_half = false;
-        size_t co_all = 1;
-        for (auto& p : plans) {
-            any_tail = any_tail || p.p_eff < p.Ic;
-            co_all = std::max(co_all, (size_t)p.Uc * (p.nch + 1));
-            any_half = any_half || p.half || p.p_eff < p.Ic;
-        }
-        std::vector<int32_t> sig;
-        sig.push_back(use_pk ? 1 : 0);
-        sig.push_back(plans.size() > 1 && !any_coop ? 1 : 0);
-        for (auto& p : plans) {
-            const int32_t v[8] = {p.c, p.CH, p.nch, p.half ? 1 : 0, p.panel ? 1 : 0, p.p_eff, p.tail_chunks, (p.coop ? 1 : 0) | (p.flat ? 2 : 0) | (p.psym ? 4 : 0)};
-            sig.insert(sig.end(), v, v + 8);
-        }
+
+        // ---- 4. tables
+        TableCache& tc = J->S->tables;
+        const std::vector<int32_t> sig = table_signature(jp);
         const bool tables_cached = tc.valid && tc.sig == sig;
         R->st.tables_from_cache = tables_cached ? 1 : 0;
         span_tables = t_tables.begin();
-        if (!tables_cached) {
-            tc.valid = false;
-            segs.clear();
-            segs_tail.clear();
-            segs.resize(plans.size());
-            segs_tail.resize(plans.size());
-            csr_pk.alloc(ctx, use_pk ? (size_t)P.nnz : 1);
-            y_pk.alloc(ctx, any_tail ? (size_t)P.nnz : 1);     // k_tail_blocks
-            csc_rank.alloc(ctx, any_half ? (size_t)P.nnz : 1);     // row (rank inside its cluster) of every CSC entry
-            if (any_half) {
-                k_csc_rank<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.pair_rank.get(), csc_rank.get());
-                FY_KERNEL_CHECK();
-                build_csr_samples(ctx, P.nnz, P.csr_idx.get(), tc.samples, st);
-            }
-        }
-        // first / last CSR entry of every planned cluster (slots are cluster-major): one round trip for all of them
-        std::vector<int32_t> csr_range(2 * plans.size() + 2, 0);
-        {
-            std::vector<int32_t> where(2 * plans.size());
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                where[2 * pi] = plans[pi].sbase;
-                where[2 * pi + 1] = plans[pi].sbase + plans[pi].Uc;
-            }
-            gather_to_host_i32(ctx, P.rowptr.get(), where, csr_range.data());
-        }
-        // One cluster's tables: packed CSR with chunk-relative indices for its CH, chunk offsets, segment table (+ the tail rows'
-        // one-chunk table over the block-compressed CSR in panel mode).  `co` = scratch for p.Uc * (p.nch + 1) offsets.
-        const bool bounded_tables = false;     // (round 2: tables sized by upper bounds inside the lanes; the lanes build no tables any more)
-        auto build_tables = [&](size_t pi, hipStream_t ts, int32_t* co) {
-            if (tables_cached) return;
-            const Plan& p = plans[pi];
-            const int32_t f0 = csr_range[2 * pi], f1 = csr_range[2 * pi + 1];
-            if (use_pk && f1 > f0) {
-                k_pack_csr<<<grid_for(f1 - f0), 256, 0, ts>>>(f0, f1, p.CH, P.csr_idx.get(), P.csr_r.get(), csr_pk.get());
-                FY_KERNEL_CHECK();
-            }
-            if (p.coop) return;
-            build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), p.sbase, p.Uc, p.CH, p.nch, co, ts);
-            // In a lane the tables are sized by an upper bound instead of a count read back from the device (an entry of rater v
-            // has at most n_v / 64 + nch segments): the host does not wait, the lane's queue stays full
-            const int64_t deg2_c = (size_t)p.c < P.cluster_deg2.size() ? P.cluster_deg2[p.c] : 0;
-            const int64_t seg_bound = bounded_tables && deg2_c > 0 ? deg2_c / 64 + (int64_t)p.nq * p.nch + 64 : 0;
-            build_segments(ctx, P.csc_slot.get(), use_pk ? csc_x_over_s.get() : csc_x.get(), co, p.sbase, p.q0, p.nq, p.nch, segs[pi], ts,
-                           p.half ? csc_rank.get() : nullptr, P.csr_idx.get(), p.CH, nullptr, 0, seg_bound, p.half ? tc.samples.get() : nullptr);
-            if (p.p_eff < p.Ic) {
-                k_tail_blocks<<<std::min<int>(p.Uc, ctx->num_cus * 16), 256, 0, ts>>>(p.sbase, p.Uc, p.p_eff, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(),
-                                                                          y_pk.get(), co);
-                FY_KERNEL_CHECK();
-                build_segments(ctx, P.csc_slot.get(), csc_x_over_s.get(), co, p.sbase, p.q0, p.nq, 1, segs_tail[pi], ts, nullptr, nullptr, 0,
-                               csc_rank.get(), p.p_eff, bounded_tables && deg2_c > 0 ? deg2_c / 64 + (int64_t)p.nq + 64 : 0);
-            }
-        };
-        // With several lanes and no cooperative cluster the tables are built by the lane that uses them, right before the row
-        // kernel: table building is mostly host round trips (sizes of the segment tables), 23 ms for 50 clusters during which the
-        // chip idled; in a lane they hide behind the other lanes' kernels.  (A cooperative job packs every cluster's CSR up front.)
-        // Several clusters and none of them cooperative: ONE table over all of them, built here on the main stream (build_tables_all).
-        // (Round 2 let every lane build its cluster's tables right before the row kernel, to hide their host round trips behind the
-        // other lanes: 20 ms of tables at 50 clusters.)
-        const bool all_at_once = plans.size() > 1 && !any_coop;
-        const bool lazy_tables = false;
-        std::vector<DevBuf<int32_t>> co_lane((size_t)NS);
-        if (!all_at_once)
-            for (auto& b : co_lane) b.alloc(ctx, co_all);
-        if (all_at_once) {
-            if (!tables_cached) build_tables_all(ctx, P, plans, csr_range, use_pk, tc, st);
-        } else if (!lazy_tables)
-            for (size_t pi = 0; pi < plans.size(); pi++) build_tables(pi, st, co_lane[0].get());
+        std::vector<int32_t> csr_range;
+        std::vector<DevBuf<int32_t>> co_lane;
+        build_job_tables(J, jp, tables_cached, csr_range, co_lane);
         t_tables.end(span_tables);
-        // ---- flat batch (Plan::flat): matrix build, scores and lists of all those clusters, one launch per kernel, on the main stream
-        DevBuf<char> flatM;
-        DevBuf<float> flatS;
-        DevBuf<int2> flat_seg;
-        DevBuf<int32_t> flat_id, flat_ov, flat_flags, flat_cnt;
-        DevBuf<CoocLaunch> d_flat_launch;
-        DevBuf<FlatDesc> d_flat[2];
-        for (size_t first = 0; first < plans.size();) {
-            std::vector<CoocLaunch> fb;
-            std::vector<FlatDesc> fd[2];       // [0] fp32 rows, [1] 24-bit rows
-            SyncOnUnwind fb_fd_guard(st);      // (their uploads are queued below; the batch's own synchronisation is at its end)
-            size_t m_bytes = 0, s_el = 0, i_el = 0, u_el = 0, n_flat = 0, last = first;
-            int64_t batch_bytes = 0;
-            for (; last < plans.size(); last++) {
-                const Plan& p = plans[last];
-                if (!p.flat) continue;
-                if (n_flat && batch_bytes + flat_need(p) > flat_budget) break;
-                batch_bytes += flat_need(p);
-                m_bytes += round_up((int64_t)p.Ic * p.ldm * (p.pack24 ? 3 : 4), 256);
-                s_el += (size_t)(p.b - p.a) * p.ldm;
-                i_el += (size_t)p.Ic * p.nch;
-                u_el += (size_t)(p.b - p.a);
-                n_flat++;
-            }
-            if (n_flat) {
-                flatM.alloc(ctx, m_bytes);
-                flatS.alloc(ctx, s_el);
-                flat_seg.alloc(ctx, i_el);
-                flat_id.alloc(ctx, i_el);
-                flat_ov.alloc(ctx, u_el);
-                flat_flags.alloc(ctx, 2 * n_flat);       // per cluster: n_heavy, any_overflow
-                size_t m_at = 0, s_at = 0, i_at = 0, u_at = 0, k = 0;
-                int max_grid[2] = {0, 0}, max_users[2] = {0, 0};
-                for (size_t pi = first; pi < last; pi++) {
-                    const Plan& p = plans[pi];
-                    if (!p.flat) continue;
-                    const int c = p.c;
-                    const int32_t nb = p.b - p.a;
-                    float* const Mc = reinterpret_cast<float*>(flatM.get() + m_at);
-                    float* const Sc = flatS.get() + s_at;
-                    CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), segs[pi].ptr_(), segs[pi].seg_(), segs[pi].w_(), P.csr_idx.get(),
-                                csr_x.get(), p.pbase, p.sbase, p.Ic, p.CH, p.nch, 0, p.Ic, p.q0, p.nq, nullptr, 0, csr_pk.get(), nullptr,
-                                (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
-                    const int fxk = fx_exponent(&J->fx_bounds[3 * (size_t)c]);
-                    CA.fx_scale = std::ldexp(1.0, fxk);
-                    const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)h_gscale[(size_t)c];
-                    MEpilogue ME{Mc, p.ldm, (float)w2s, std::ldexp(w2s, -fxk), p.pack24 ? 1 : 0, nullptr, p.ldb, 0, 0, nullptr, p.ldb64, nullptr};
-                    const int n_items = (int)cooc_item_count(p.Ic, p.CH, p.nch, false);
-                    CA.item_seg = flat_seg.get() + i_at;
-                    CA.item_id = flat_id.get() + i_at;
-                    CA.item_grab = cooc_item_grab((size_t)c < P.cluster_deg2.size() ? P.cluster_deg2[c] : P.sum_deg2, n_items);
-                    fb.push_back(CoocLaunch{CA, ME, n_items, 0});
 
-                    const int n_chunks = (int)ceil_div(p.Ic, 64 * VEC);
-                    // (the chip is filled by all clusters of the batch together: ~8 work-groups per CU over the whole launch)
-                    const int64_t fill = ceil_div(8 * (int64_t)ctx->num_cus, (int64_t)std::max(1, n_chunks) * (int64_t)n_flat);
-                    const int n_slices = (int)std::max<int64_t>(1, std::min<int64_t>(tune.max_slices, std::min<int64_t>(ceil_div(nb, 4), std::max<int64_t>(ceil_div(nb, 4 * (int64_t)tune.users_per_wave), fill))));
-                    FlatDesc d{};
-                    ScoreArgs& SA = d.SA;
-                    SA.M = Mc; SA.ldm = p.ldm; SA.Ic = p.Ic; SA.a_rank = a_rank.get() + p.pbase; SA.b_rank = b_rank32.get() + p.pbase;
-                    SA.rb_off = P.rowptr.get() + p.sbase;
-                    SA.csr_idx = P.csr_idx.get(); SA.csr_e = csr_e.get(); SA.csr_q = csr_q.get();
-                    SA.pvpi = pvpi.get(); SA.n_out = n_out.get(); SA.slot_lo = lo; SA.slot_base = p.sbase; SA.slot0 = p.a; SA.n_users = nb;
-                    SA.S = Sc; SA.ldS = p.ldm; SA.n_slices = n_slices; SA.n_chunks = n_chunks;
-                    d.n_heavy = flat_flags.get() + 2 * k;
-                    d.any_overflow = flat_flags.get() + 2 * k + 1;
-                    SA.n_heavy = tune.score_heavy > 0 ? d.n_heavy : nullptr;
-                    d.heavy_thresh = tune.score_heavy > 0 ? std::min(tune.score_heavy, 32) : 0x7FFFFFFF;
-                    d.TA = TopNArgs{Sc, p.ldm, p.Ic, n_out.get(), out_off.get(), P.rank_item_raw.get() + p.pbase, P.slot2du.get(), P.uid.get(), lo, p.a, c,
-                                    R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(), 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-                    d.overflow = flat_ov.get() + u_at;
-                    d.score_grid = n_chunks * n_slices;
-                    d.n_users = nb;
-                    const int f = p.pack24 ? 1 : 0;
-                    max_grid[f] = std::max(max_grid[f], d.score_grid);
-                    max_users[f] = std::max(max_users[f], nb);
-                    fd[f].push_back(d);
-                    m_at += (size_t)round_up((int64_t)p.Ic * p.ldm * (p.pack24 ? 3 : 4), 256);
-                    s_at += (size_t)nb * p.ldm;
-                    i_at += (size_t)p.Ic * p.nch;
-                    u_at += (size_t)nb;
-                    k++;
-                }
-                const size_t sp = t_cooc.begin(st);
-                launch_cooc_rm2_multi(ctx, tune, fb, false, d_flat_launch, flat_cnt, st, true);
-                t_cooc.end(sp, st);
-                R->st.cooc_launches++;
-                for (int f = 0; f < 2; f++) {
-                    if (fd[f].empty()) continue;
-                    const unsigned ny = (unsigned)fd[f].size();
-                    d_flat[f].alloc(ctx, fd[f].size());
-                    FY_HIP(hipMemcpyAsync(d_flat[f].get(), fd[f].data(), fd[f].size() * sizeof(FlatDesc), hipMemcpyHostToDevice, st));
-                    const size_t ss = t_score.begin(st);
-                    k_count_heavy_multi<<<(ny + 63) / 64, 64, 0, st>>>(d_flat[f].get(), (int32_t)ny);
-                    FY_KERNEL_CHECK();
-                    if (f) k_score_multi<4, true, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(d_flat[f].get(), P.csr_idx.get(), csr_e.get(), csr_q.get(), pvpi.get(), n_out.get());
-                    else k_score_multi<4, false, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(d_flat[f].get(), P.csr_idx.get(), csr_e.get(), csr_q.get(), pvpi.get(), n_out.get());
-                    FY_KERNEL_CHECK();
-                    t_score.end(ss, st);
-                    R->st.score_launches++;
-                    const size_t tt = t_topn.begin(st);
-                    k_topn_fast_multi<<<dim3((unsigned)max_users[f], ny), 256, 0, st>>>(d_flat[f].get(), tune.force_select);
-                    FY_KERNEL_CHECK();
-                    k_topn_select_multi<<<dim3((unsigned)max_users[f], ny), 256, 0, st>>>(d_flat[f].get(), prune_counters.get() + 2);
-                    FY_KERNEL_CHECK();
-                    t_topn.end(tt, st);
-                }
-                FY_HIP(hipStreamSynchronize(st));     // the host vectors behind the descriptor uploads leave scope here
-            }
-            first = last;
-        }
-        struct PanelBuf {
-            DevBuf<float> Gp, Bmax64, amax64, bmax64;
-            DevBuf<uint32_t> Brep;
-            DevBuf<double> head32, tail32;     // (refinement pass: per cluster, like the panels -- built in phase 1, read in phase 3)
-        };
-        struct PanelPtrs {
-            float *Gp, *Bmax64;
-            uint32_t* Brep;
-            float *amax64, *bmax64;
-        };
-        std::vector<PanelBuf> pbuf(two_phase ? plans.size() : 0);
-        std::vector<Lane> plane(two_phase ? plans.size() : 0);
-        auto group_buffers = [&](int grp) {
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                const Plan& p = plans[pi];
-                if (!p.panel || group_of[pi] != grp) continue;
-                pbuf[pi].Gp.alloc(ctx, (size_t)p.Ic * p.panel_cols * 3 / 4 + 4);
-                pbuf[pi].Bmax64.alloc(ctx, (size_t)p.Ic * p.ldb64 * 3 / 4 + 4);
-                pbuf[pi].Brep.alloc(ctx, (size_t)p.Ic * p.ldb64 + 4);
-                pbuf[pi].amax64.alloc(ctx, (size_t)p.ldb64);
-                pbuf[pi].bmax64.alloc(ctx, (size_t)p.ldb64);
-            }
-        // ... and its own scoring scratch, so that NO host round trip separates the clusters: phase 2 queues seed + bound pass, select, second
-        // bound and the survivor count of every cluster, ONE wait reads all counts (pinned host memory), phase 3 queues the survivor
-        // passes and top-N.  (With one scratch set per lane the host waited for every cluster's count before it could queue the next
-        // cluster of that lane: 50 round trips during which the other lanes ran dry.)
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                const Plan& p = plans[pi];
-                if (!p.panel || group_of[pi] != grp) continue;
-                Lane& W = plane[pi];
-                const size_t nbp = (size_t)(p.b - p.a);
-                const size_t seed_cols = (size_t)std::min<int64_t>(ceil_div(p.Ic, 256), tune.seed_chunks) * 256;
-                W.st = lanes[pi % NS].st;
-                W.M.alloc(ctx, 1); W.Bmax.alloc(ctx, 1); W.amax.alloc(ctx, 1); W.bmax.alloc(ctx, 1);
-                W.Gp.alloc(ctx, 1); W.Bmax64.alloc(ctx, 1); W.Brep.alloc(ctx, 1); W.amax64.alloc(ctx, 1); W.bmax64.alloc(ctx, 1);
-                W.item_seg.alloc(ctx, (size_t)p.Ic * p.nch); W.item_id.alloc(ctx, (size_t)p.Ic * p.nch);
-                W.item_seg_t.alloc(ctx, (size_t)std::max(1, p.Ic - p.p_eff)); W.item_id_t.alloc(ctx, (size_t)std::max(1, p.Ic - p.p_eff));
-                W.S.alloc(ctx, nbp * seed_cols);
-                W.overflow.alloc(ctx, nbp);
-                W.any_overflow.alloc(ctx, 1);
-                W.n_heavy.alloc(ctx, 1);
-                W.UB.alloc(ctx, nbp * (size_t)p.ldb64);
-                W.tau.alloc(ctx, nbp);
-                W.surv.alloc(ctx, nbp * (size_t)p.ldb64);
-                W.surv_mask.alloc(ctx, nbp * (size_t)p.ldb64);
-                W.n_quads.alloc(ctx, nbp + 1);
-                W.quad_prefix.alloc(ctx, nbp + 1);
-            }
-        };
-        // Error path: anything thrown below (an allocation, a launch, a collective) unwinds the lanes' buffers, the segment
-        // tables and the per-job arrays back into the caching allocator while kernels of OTHER lanes may still be reading
-        // them.  The guard drains every lane and the main stream first (members are destroyed in reverse order of
-        // declaration: `lanes`, `segs` and the DevBufs above were declared before it, so it runs before they are released).
-        // (The flat batch above runs on the main stream alone, in front of the guard: its uploads' sources have their own SyncOnUnwind.)
-        // (host-side sources of uploads and the device buffers of the batched launches: declared in FRONT of the guard, so that the
-        // guard -- which drains every lane and the main stream -- is destroyed before them on every path)
-        std::vector<CoocLaunch> batch_main, batch_tail;      // phase 1: the row kernels of all panel clusters, launched together
-        DevBuf<CoocLaunch> d_batch_main, d_batch_tail;
-        DevBuf<int32_t> d_cnt_main, d_cnt_tail;
-        DevBuf<PanelDesc> d_panel_desc;
-        std::vector<PanelDesc> hpd;                          // (lives as long as its upload may be in flight)
-        struct LaneGuard {
-            Context* ctx;
-            hipEvent_t fork = nullptr;
-            int32_t* pinned = nullptr;
-            ~LaneGuard() {
-                for (hipStream_t x : ctx->aux) (void)hipStreamSynchronize(x);
-                (void)hipStreamSynchronize(ctx->stream);
-                if (fork) (void)hipEventDestroy(fork);
-                if (pinned) (void)hipHostFree(pinned);
-            }
-        } guard{ctx};
-        if (two_phase) FY_HIP(hipHostMalloc(reinterpret_cast<void**>(&guard.pinned), plans.size() * sizeof(int32_t), hipHostMallocDefault));
-        // phase 0: every cluster start to end on its lane.  two_phase: phase 1 = the panels of all panel-mode clusters on the main stream,
-        // phase 2 = everything else on the lanes.
-        for (int grp = 0; grp < n_groups; grp++) {
-        if (two_phase) {
-            if (grp > 0) {       // the previous group's kernels have drained (below): its panels and scratch go back to the allocator
-                for (size_t pi = 0; pi < plans.size(); pi++)
-                    if (plans[pi].panel && group_of[pi] == grp - 1) { pbuf[pi] = PanelBuf(); plane[pi] = Lane(); }
-            }
-            group_buffers(grp);
-            batch_main.clear();
-            batch_tail.clear();
-            hpd.clear();
-        }
-        for (int phase = two_phase ? 1 : 0; phase <= (two_phase ? 3 : 0); phase++) {
-        const auto host_t0 = std::chrono::steady_clock::now();
-        struct PhaseClock {
-            const std::chrono::steady_clock::time_point t0;
-            int grp, phase;
-            bool on;
-            ~PhaseClock() {
-                if (on) fprintf(stderr, "[fy] group %d phase %d: host queued for %.3f ms\n", grp, phase, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            }
-        } phase_clock{host_t0, grp, phase, tune.debug_sync != 0};
-        if (phase == 3) {             // every cluster's survivor count has been queued: one wait for all of them
-            for (int l = 0; l < NS; l++) FY_HIP(hipStreamSynchronize(lanes[l].st));
-            FY_HIP(hipStreamSynchronize(st));
-        }
-        if ((phase == 0 || phase == 2) && NS > 1) {   // the lanes start after everything queued on the main stream so far
-            if (guard.fork) { FY_HIP(hipEventDestroy(guard.fork)); guard.fork = nullptr; }
-            FY_HIP(hipEventCreateWithFlags(&guard.fork, hipEventDisableTiming));
-            FY_HIP(hipEventRecord(guard.fork, st));
-            for (int l = 0; l < NS; l++) FY_HIP(hipStreamWaitEvent(lanes[l].st, guard.fork, 0));
-        }
+        const ScoreShared X{J, R.get(), &tune, &jp, A.b_rank32.get(), J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
+                            use_pk ? tc.csc_x_over_s.get() : tc.csc_x.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get(), use_pk ? tc.csr_pk.get() : nullptr,
+                            U.n_out.get(), U.out_off.get(), U.pvpi.get(), lo, &csr_range, &side, &t_cooc, &t_score, &t_topn, &t_mirror, prune_counters.get(),
+                            &prune_blocks_total, &prune_seed_terms_cols, &coop_survived, &fallback_survived, &coop_pair_contribs, A.d_cshift.get(),
+                            jp.h_gscale.data()};
 
-        for (size_t pi = 0; pi < plans.size(); pi++) {
-            const Plan& p = plans[pi];
-            if (p.flat) continue;                  // done above
-            if (group_of[pi] != grp) continue;     // (clusters outside panel mode are in group 0)
-            if ((phase == 1 || phase == 3) && !p.panel) continue;
-            Lane& L = phase == 1 ? lanes[0] : (two_phase && p.panel ? plane[pi] : lanes[pi % NS]);
-            hipStream_t ls = phase == 1 ? st : L.st;
-            const bool do_build = !(phase >= 2 && p.panel), do_score = phase != 1;
-            const PanelPtrs PP = two_phase && p.panel ? PanelPtrs{pbuf[pi].Gp.get(), pbuf[pi].Bmax64.get(), pbuf[pi].Brep.get(), pbuf[pi].amax64.get(), pbuf[pi].bmax64.get()}
-                                                      : PanelPtrs{L.Gp.get(), L.Bmax64.get(), L.Brep.get(), L.amax64.get(), L.bmax64.get()};
-            auto checkpoint = [&](const char* what) {
-                if (tune.debug_sync != 1) return;
-                const hipError_t e = hipDeviceSynchronize();
-                fprintf(stderr, "[fy] group %d/%d phase %d plan %zu (cluster %d): %s -> %s\n", grp, n_groups, phase, pi, p.c, what, hipGetErrorString(e));
-                fflush(stderr);
-            };
-            checkpoint("start");
-            if (p.panel && (!PP.Gp || !PP.Bmax64 || !PP.Brep || !PP.amax64 || !PP.bmax64 || (two_phase && (!L.S.get() || !L.UB.get() || !L.n_quads.get()) && phase != 1)))
-                FY_FAIL(FY_ERR_STATE, "internal: cluster %d (plan %zu, group %d of %d, phase %d) has no panel buffers", p.c, pi, grp, n_groups, phase);
-            const int c = p.c;
-            const int32_t sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, a = p.a, b = p.b, CH = p.CH, nch = p.nch;
-            const int64_t ldm = p.ldm;
-            const bool pack24 = p.pack24;
-            if (p.coop) {
-                CoopShared X{J, R.get(), &tune, b_rank32.get(), a_rank.get(), use_pk ? csc_x_over_s.get() : csc_x.get(), csr_x.get(), csr_e.get(), csr_q.get(),
-                             use_pk ? csr_pk.get() : nullptr,
-                             n_out.get(), out_off.get(), pvpi.get(), lo, &t_cooc, &t_score, &t_topn, prune_counters.get(),
-                             &prune_blocks_total, &prune_seed_terms_cols, &coop_survived, &coop_pair_contribs, d_cshift.get(), h_gscale[(size_t)c]};
-                score_cluster_coop(X, p, ls);
-                continue;
-            }
+        // ---- 5. flat batches
+        FlatBuffers flat;
+        score_flat_batches(X, flat);
 
-            if (lazy_tables) {
-                const size_t stb = t_tables.begin(ls);
-                build_tables(pi, ls, co_lane[pi % NS].get());
-                t_tables.end(stb, ls);
-            }
-            // -- M build
-            CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), segs[pi].ptr_(), segs[pi].seg_(), segs[pi].w_(), P.csr_idx.get(),
-                        csr_x.get(), pbase, sbase, Ic, CH, nch, 0, Ic, p.q0, p.nq, nullptr, 0, use_pk ? csr_pk.get() : nullptr, nullptr,
-                        (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
-            const int fxk = (use_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)c]) : -1;
-            CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;
-            const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)h_gscale[(size_t)c];     // (1-l)^2 and the packed format's 2^-c
-            MEpilogue ME{L.M.get(), ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0,
-                         pack24 ? 1 : 0, (p.prune && !p.panel) ? L.Bmax.get() : nullptr, p.ldb, 0,
-                         p.panel ? p.panel_cols : 0, p.panel ? PP.Bmax64 : nullptr, p.ldb64, p.panel ? PP.Brep : nullptr};
-            if (p.panel) ME.M = PP.Gp;
-            // refinement (k_refine_rows): packed clusters keep the unrounded fp32 values of their first 256 rows (and, in symmetric panel
-            // mode, of the first 256 columns of the tail rows)
-            const bool refine = tune.refine && pack24 && !p.coop && fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && Ic >= 8;
-            // (as many head rows / columns as the seed is wide, 256 .. 1024: N = 50 -> 256, N = 100 -> 512; a multiple of 4)
-            const int32_t head_rows = (int32_t)std::min<int64_t>(Ic & ~3, std::max<int64_t>(256, std::min<int64_t>(1024, (int64_t)tune.seed_chunks * 256)));
-            const int64_t ld_head = p.psym ? (int64_t)p.p_eff : ldm;
-            DevBuf<double>& H32 = (two_phase && p.panel) ? pbuf[pi].head32 : L.head32;
-            DevBuf<double>& T32 = (two_phase && p.panel) ? pbuf[pi].tail32 : L.tail32;
-            if (refine && do_build) {
-                H32.alloc(ctx, (size_t)head_rows * ld_head + 4);
-                if (p.psym) T32.alloc(ctx, (size_t)std::max(1, Ic - p.p_eff) * head_rows + 4);
-                ME.head32 = H32.get();
-                ME.ld_head = ld_head;
-                ME.head_rows = head_rows;
-                ME.tail32 = p.psym ? T32.get() : nullptr;
-                ME.tail_from = p.p_eff;
-            }
-            if (do_build) {
-            if (p.panel) {
-                R->st.panel_clusters++;
-                FY_HIP(hipMemsetAsync(PP.Bmax64, 0, (size_t)Ic * p.ldb64 * 3, ls));
-                k_block_amax<<<grid_for(p.ldb64), 256, 0, ls>>>(Ic, (int32_t)p.ldb64, a_rank.get() + pbase, b_rank32.get() + pbase, PP.amax64,
-                                                               PP.bmax64, 64);
-                FY_KERNEL_CHECK();
-            } else if (p.prune) {
-                FY_HIP(hipMemsetAsync(L.Bmax.get(), 0, (size_t)Ic * p.ldb * 3, ls));
-                k_block_amax<<<grid_for(p.ldb), 256, 0, ls>>>(Ic, (int32_t)p.ldb, a_rank.get() + pbase, b_rank32.get() + pbase, L.amax.get(), L.bmax.get());
-                FY_KERNEL_CHECK();
-            }
-            const size_t sp = t_cooc.begin(ls);
-            const bool batched = phase == 1 && tune.panel_multi_launch && use_pk && fxk >= 0 && !tune.cooc_f32;     // (k_cooc_rm2_multi)
-            if (p.p_eff < Ic) {   // panel mode: bounds of the tail rows behind p_eff (one item per row, see k_tail_blocks)
-                CoocArgs CB{P.rank_pair.get(), P.pair_start.get(), segs_tail[pi].ptr_(), segs_tail[pi].seg_(), segs_tail[pi].w_(), P.csr_idx.get(),
-                            csr_x.get(), pbase, sbase, Ic, p.tail_width, 1, p.p_eff, Ic - p.p_eff, p.q0, p.nq, nullptr, 0, y_pk.get(), nullptr, CA.pk_bytes};
-                CB.fx_scale = CA.fx_scale;
-                MEpilogue MB{reinterpret_cast<float*>(reinterpret_cast<char*>(PP.Bmax64) + (size_t)(p.p_eff / 64) * 3), p.tail_width, ME.w2, ME.fx_inv, 1,
-                             nullptr, 0, 0, 0, nullptr, 0, nullptr, p.ldb64, 1};
-                int2* const tseg = batched ? plane[pi].item_seg_t.get() : L.item_seg.get();
-                int32_t* const tid = batched ? plane[pi].item_id_t.get() : L.item_id.get();
-                if (!batched) {      // (batched: k_item_list_multi, in front of the launch)
-                    k_item_list<<<grid_for((int64_t)(Ic - p.p_eff)), 256, 0, ls>>>(CB, tseg, tid);
-                    FY_KERNEL_CHECK();
-                }
-                CB.item_seg = tseg;
-                CB.item_id = tid;
-                CB.item_grab = 8;      // a tail row's bound item is a handful of segments
-                if (batched) batch_tail.push_back(CoocLaunch{CB, MB, Ic - p.p_eff, 0});
-                else {
-                    FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
-                    launch_cooc_rm2(ctx, tune, use_pk, CB, MB, Ic - p.p_eff, L.any_overflow.get(), ls);
-                    R->st.cooc_launches++;
-                }
-                CA.tail_row0 = p.p_eff;
-                CA.tail_chunks = p.tail_chunks;
-            }
-            {
-                CA.half = (p.half || p.psym) ? 1 : 0;
-                if (p.psym) { CA.half_rows = p.p_eff; CA.head_chunks = p.tail_chunks; }
-                const int n_items = p.psym ? (int)(cooc_half_item_index(p.p_eff - 1, p.tail_chunks - 1, CH, p.tail_chunks) + 1 + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
-                                    : CA.tail_chunks > 0 ? (int)((int64_t)p.p_eff * nch + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
-                                                         : (int)cooc_item_count(Ic, CH, nch, p.half);
-                int2* const mseg = batched ? plane[pi].item_seg.get() : L.item_seg.get();
-                int32_t* const mid = batched ? plane[pi].item_id.get() : L.item_id.get();
-                if (!batched) {
-                    k_item_list<<<grid_for((int64_t)Ic * nch), 256, 0, ls>>>(CA, mseg, mid);
-                    FY_KERNEL_CHECK();
-                }
-                CA.item_seg = mseg;
-                CA.item_id = mid;
-                CA.item_grab = cooc_item_grab(((size_t)c < P.cluster_deg2.size() ? P.cluster_deg2[c] : P.sum_deg2) / (p.half ? 2 : 1), n_items);
-                if (batched) batch_main.push_back(CoocLaunch{CA, ME, n_items, 0});
-                else {
-                    FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
-                    launch_cooc_rm2(ctx, tune, use_pk, CA, ME, n_items, L.any_overflow.get(), ls);
-                }
-            }
-            t_cooc.end(sp, ls);
-            join_values(ls);      // (the scoring kernels behind this point read the per-rating values)
-            checkpoint("row kernel queued / run");
-            if (!batched) R->st.cooc_launches++;
-            if (p.half) {    // lower triangle + the block maxima in front of / on the diagonal
-                const size_t sm = t_mirror.begin(ls);
-                // pruned flow: LAZY mirror -- the seed pass reads the seed columns of every row, the bound pass the block maxima, the
-                // survivor pass the surviving column blocks (mirrored below, once they are known); nothing else of the lower triangle
-                // is ever read, so it is not written (round 3 moved 10.7 GB here to fill a triangle of which a few per cent were read)
-                const bool lazy = p.prune && tune.lazy_mirror;
-                launch_mirror(ctx, L.M.get(), ldm, Ic, p.prune ? L.Bmax.get() : nullptr, p.ldb, ls, nullptr, lazy ? std::min(tune.seed_chunks, p.nblk) : 0x7FFFFFFF);
-                t_mirror.end(sm, ls);
-            }
-            // (not for long lists: their survivors -- 14 % of the blocks at N = 1000 -- spread over the whole popularity order, the 16 wide
-            // groups behind the first 48 blocks all survive and hand every block to the survivor pass: measured, the batch falls back to
-            // the full pass, 261 -> 471 ms)
-            if (p.prune && !p.panel && tune.sup_bounds && !long_seed) {      // super-block bounds for the seed pass (k_score_sup)
-                const int seed_b = std::min(tune.seed_chunks, p.nblk);
-                std::vector<int32_t> first;
-                sup_block_map(seed_b, p.nblk, first);
-                const int n_sup = (int)first.size() - 1;
-                first.resize(65, first.back());
-                L.sup_first.alloc(ctx, 65);
-                L.Bsup.alloc(ctx, (size_t)Ic * 64);
-                L.asup.alloc(ctx, 64);
-                L.bsupb.alloc(ctx, 64);
-                FY_HIP(hipMemcpyAsync(L.sup_first.get(), first.data(), 65 * sizeof(int32_t), hipMemcpyHostToDevice, ls));
-                FY_HIP(hipStreamSynchronize(ls));      // (`first` is a host temporary; one cluster: no other lane is waiting)
-                const size_t sb = t_score.begin(ls);
-                k_build_bsup<<<std::min<int>((Ic + 3) / 4, ctx->num_cus * 32), 256, 0, ls>>>(Ic, n_sup, L.sup_first.get(), L.Bmax.get(), p.ldb, L.Bsup.get());
-                FY_KERNEL_CHECK();
-                k_sup_amax<<<1, 64, 0, ls>>>(n_sup, L.sup_first.get(), L.amax.get(), L.bmax.get(), L.asup.get(), L.bsupb.get());
-                FY_KERNEL_CHECK();
-                t_score.end(sb, ls);
-            }
-            }      // do_build
-            if (!do_score) continue;
-
-            // -- scoring + top-N in user batches that fit the score scratch
-            const int64_t ldS = ldm, B = p.B;
-            const int n_chunks = (int)ceil_div(Ic, 64 * VEC);
-            const int32_t* row_off = P.rowptr.get() + sbase;   // the users' CSR rows: [slot - sbase], [slot - sbase + 1]
-            auto score_args = [&](const float* Mx, int64_t ldmx, int32_t Icx, const float* ax, int32_t s0, int32_t nb, float* Sx, int64_t ldSx,
-                                  int n_slices, int nchunks) {
-                ScoreArgs SA{};
-                SA.M = Mx; SA.ldm = ldmx; SA.Ic = Icx; SA.a_rank = ax; SA.b_rank = b_rank32.get() + pbase; SA.rb_off = row_off;
-                SA.csr_idx = P.csr_idx.get(); SA.csr_e = csr_e.get(); SA.csr_q = csr_q.get();
-                SA.pvpi = pvpi.get(); SA.n_out = n_out.get(); SA.slot_lo = lo; SA.slot_base = sbase; SA.slot0 = s0; SA.n_users = nb;
-                SA.S = Sx; SA.ldS = ldSx; SA.n_slices = n_slices; SA.n_chunks = nchunks;
-                if (tune.score_heavy > 0) {     // (stream order: every scoring launch of the batch follows)
-                    // a small batch (one cluster of many) cannot fill the chip with a wave per user and its launch lasts as long as its
-                    // longest list on ONE wave (ML-1M shape in 50 clusters: 0.14 ms per cluster for 120 users): there every user with
-                    // more than a few batches is walked by a whole workgroup
-                    const int heavy = (int64_t)nb * nchunks < 8 * (int64_t)ctx->num_cus ? std::min(tune.score_heavy, 32) : tune.score_heavy;
-                    k_count_heavy<<<1, 64, 0, ls>>>(P.rowptr.get() + s0, nb, heavy, L.n_heavy.get());
-                    SA.n_heavy = L.n_heavy.get();
-                }
-                return SA;
-            };
-            // ill-conditioned list rows of a range of users, scored again in fp64 from the fp32 head rows (k_refine_rows); after the lists stand
-            auto refine_rows = [&](int32_t s0, int32_t nb) {
-                if (!refine || nb <= 0) return;
-                const size_t tt = t_topn.begin(ls);
-                const int32_t n_ids = J->S->max_item + 1;
-                L.colmap.alloc(ctx, (size_t)n_ids);
-                FY_HIP(hipMemsetAsync(L.colmap.get(), 0xFF, (size_t)n_ids * sizeof(int32_t), ls));
-                k_refine_colmap<<<(head_rows + 255) / 256, 256, 0, ls>>>(head_rows, P.rank_item_raw.get() + pbase, L.colmap.get());
-                FY_KERNEL_CHECK();
-                RefineArgs RA{};
-                RA.slot0 = s0; RA.n_users = nb; RA.slot_lo = lo; RA.slot_base = sbase;
-                RA.n_out = n_out.get(); RA.out_off = out_off.get(); RA.out_item = R->d_key1.get(); RA.out_score = R->d_value.get(); RA.out_item_w = R->d_key1.get();
-                RA.rowptr = P.rowptr.get(); RA.csr_idx = P.csr_idx.get(); RA.csr_r = P.csr_r.get(); RA.usum_slot = J->usum_slot.get();
-                RA.p_rank = p_rank.get() + pbase; RA.b_rank = b_rank.get() + pbase;
-                RA.colmap = L.colmap.get(); RA.max_item = J->S->max_item;
-                RA.head_rows = head_rows;
-                RA.head32 = H32.get(); RA.ld_head = ld_head; RA.tail32 = p.psym ? T32.get() : nullptr; RA.tail_from = p.p_eff;
-                if (!RA.head32 || (p.psym && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", c);
-                RA.unscale = 1.0 / (double)h_gscale[(size_t)c];
-                RA.lambda = lambda; RA.ln_items = std::log((double)prm.number_of_items); RA.ln_users = std::log((double)p.Uc);
-                RA.users_minus_1 = (double)(p.Uc - 1);
-                RA.refine_c = tune.refine_c;
-                RA.n_refined = prune_counters.get() + 5;
-                int lp2 = 64;
-                while (lp2 < std::min<int>(prm.number_of_recommendations, Ic)) lp2 <<= 1;
-                k_refine_rows<<<(nb + 3) / 4, 256, (size_t)4 * lp2 * sizeof(uint64_t), ls>>>(RA);
-                FY_KERNEL_CHECK();
-                t_topn.end(tt, ls);
-            };
-            // the plain full pass over a range of users: every log term, like the reference's loop (AbstractRM2Reducer.java:332-356)
-            auto full_pass = [&](int32_t s0, int32_t nb, float* Sx) {
-                const int n_slices = score_slices(ctx, tune, nb, n_chunks);
-                ScoreArgs SA = score_args(L.M.get(), ldm, Ic, a_rank.get() + pbase, s0, nb, Sx, ldS, n_slices, n_chunks);
-                const size_t ss = t_score.begin(ls);
-                if (pack24) k_score<4, true, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-                else k_score<4, false, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-                FY_KERNEL_CHECK();
-                t_score.end(ss, ls);
-                R->st.score_launches++;
-                TopNArgs TA{Sx, ldS, Ic, n_out.get(), out_off.get(), P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(), lo, s0, c,
-                            R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(), 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-                const size_t tt = t_topn.begin(ls);
-                FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
-                if (prm.number_of_recommendations > TOPN_LONG)
-                    k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select,
-                                                                                                         fy_topn_long_cap(prm.number_of_recommendations));
-                else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
-                FY_KERNEL_CHECK();
-                k_topn_select<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), prune_counters.get() + 2);
-                FY_KERNEL_CHECK();
-                t_topn.end(tt, ls);
-                refine_rows(s0, nb);
-            };
-            for (int32_t s0 = a; s0 < b; s0 += (int32_t)B) {
-                const int32_t nb = (int32_t)std::min<int64_t>(B, b - s0);
-                if (!p.prune) { full_pass(s0, nb, L.S.get()); continue; }
-                const int seed_chunks = std::min(n_chunks, tune.seed_chunks);
-                const bool use_sup = tune.sup_bounds && !p.panel && !long_seed;      // bounds over super-blocks, evaluated by the seed chunk's own waves
-                const int n_slices = score_slices(ctx, tune, nb, seed_chunks + (use_sup ? 0 : (int)(p.ldb / 256)));
-                // front in phase 2, back in phase 3 (the whole cluster in one batch: its CSR range is on the host already)
-                const bool split = two_phase && p.panel && s0 == sbase && nb == p.Uc;
-                if (phase == 3 && !split) continue;
-                size_t ss = t_score.begin(ls);
-                const int seed_blocks = seed_chunks;
-                const int64_t SC = (int64_t)seed_chunks * 256;   // pitch of the compact score rows: seed columns only
-                // only the seed columns and the surviving blocks of a score row are ever written or read
-                // (1) + (3) ONE launch: exact scores of the seed columns (the most popular candidates) and the upper bounds
-                // of all 256-column blocks (the same kernel on the block-maximum matrix); the grid's tail -- the waves
-                // that walk the heaviest users -- is paid once instead of twice
-                // panel mode: the stored rows are panel_cols wide and the bound matrix has one column per 64-column sub-block
-                const float* Gmat = p.panel ? PP.Gp : L.M.get();
-                const int64_t gld = p.panel ? (int64_t)p.panel_cols : ldm;
-                // (A two-level bound -- 256-column block maxima first, the 64-column sub-block bounds only for the surviving blocks -- was
-                // built and measured in round 3: the first level reads a quarter of the bytes, but five times as many blocks reach the
-                // second level, whose per-(user, block) gathers of Bmax64 rows cost more than the streamed pass saved: 113 -> 129 ms at 50
-                // clusters.  Removed.)
-                const int64_t bld = p.panel ? p.ldb64 : p.ldb;           // pitch of the bound matrix, of UB and of the survivor lists
-                const int bchunks = (int)(bld / 256);
-                int32_t hv[3] = {0, 0, 0};   // survivors, first / last CSR entry of the batch
-                if (phase != 3) {
-                if (use_sup) {
-                    ScoreArgs SU = score_args(Gmat, gld, Ic, a_rank.get() + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks);
-                    L.UBs.alloc(ctx, (size_t)nb * 64);
-                    SU.Bsup = L.Bsup.get(); SU.asup = L.asup.get(); SU.bsup_b = L.bsupb.get(); SU.UBsup = L.UBs.get();
-                    SU.n_sup = std::min(64, std::max(0, p.nblk - seed_chunks));
-                    k_score_sup<<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
-                    FY_KERNEL_CHECK();
-                }
-                ScoreArgs SA = score_args(Gmat, gld, Ic, a_rank.get() + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks + bchunks);
-                SA.chunks1 = seed_chunks;
-                SA.M2 = p.panel ? PP.Bmax64 : L.Bmax.get();
-                SA.ldm2 = bld;
-                SA.Ic2 = p.panel ? p.nsub : p.nblk;
-                SA.a2 = p.panel ? PP.amax64 : L.amax.get();
-                SA.b2 = p.panel ? PP.bmax64 : L.bmax.get();
-                SA.S2 = L.UB.get();
-                SA.ldS2 = bld;
-                SA.no_mask2 = 1;
-                if (!use_sup) {
-                    k_score<4, true, 8><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-                    FY_KERNEL_CHECK();
-                }
-                // (2) tau_u = N-th best seed score; the sorted seed head is also the user's list unless a block survives
-                TopNArgs T1{L.S.get(), SC, Ic, n_out.get(), out_off.get(), P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(),
-                            lo, s0, c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
-                            1, seed_chunks * 256, L.surv.get(), L.n_quads.get(), bld, L.tau.get()};
-                if (long_seed) {
-                    k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(T1, L.overflow.get(), L.any_overflow.get(), 0,
-                                                                                                         fy_topn_long_cap(prm.number_of_recommendations));
-                } else {
-                    int lp2 = 64;                   // the sort's size: the seed columns, at most TOPN_SAMPLE
-                    while (lp2 < std::min<int>(std::min<int>(Ic, seed_chunks * 256), TOPN_SAMPLE)) lp2 <<= 1;
-                    const unsigned sg = (unsigned)((nb + 3) / 4);
-                    if (lp2 <= 64) k_topn_seed<1><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                    else if (lp2 == 128) k_topn_seed<2><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                    else if (lp2 == 256) k_topn_seed<4><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                    else if (lp2 == 512) k_topn_seed<8><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                    else k_topn_seed<16><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                }
-                FY_KERNEL_CHECK();
-                // (4) the blocks whose bound reaches tau_u, in ascending order
-                FY_HIP(hipMemsetAsync(L.n_quads.get(), 0, ((size_t)nb + 1) * sizeof(int32_t), ls));
-                if (p.panel)
-                    k_bound_select_sub<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), bld, p.nsub, p.nblk, seed_blocks, L.tau.get(),
-                                                                                       pvpi.get() + (s0 - lo), nb, bld, L.surv.get(), L.surv_mask.get(), L.n_quads.get());
-                else if (use_sup)
-                    k_bound_select_sup<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UBs.get(), std::min(64, std::max(0, p.nblk - seed_chunks)), L.sup_first.get(), L.tau.get(),
-                                                                                       pvpi.get() + (s0 - lo), nb, p.ldb, L.surv.get(), L.n_quads.get());
-                else
-                    k_bound_select<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), p.ldb, p.nblk, seed_blocks, L.tau.get(), pvpi.get() + (s0 - lo), nb,
-                                                                                   L.surv.get(), L.n_quads.get());
-                FY_KERNEL_CHECK();
-                if (tune.debug_sync == 3 && !p.panel) {      // which blocks survive, and for how many users
-                    DevBuf<int32_t> cnt(ctx, (size_t)p.nblk + 1);
-                    FY_HIP(hipMemsetAsync(cnt.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
-                    k_surv_block_counts<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, cnt.get());
-                    std::vector<int32_t> hc((size_t)p.nblk + 1);
-                    FY_HIP(hipMemcpyAsync(hc.data(), cnt.get(), hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-                    FY_HIP(hipStreamSynchronize(ls));
-                    int distinct = 0;
-                    long long total = 0;
-                    for (int b2 = 0; b2 < p.nblk; b2++) { distinct += hc[b2] > 0; total += hc[b2]; }
-                    fprintf(stderr, "[fy] cluster %d: %lld surviving (user, block) pairs in %d distinct blocks of %d:", c, total, distinct, p.nblk);
-                    for (int b2 = 0; b2 < p.nblk; b2++)
-                        if (hc[b2]) fprintf(stderr, " %d:%d", b2, hc[b2]);
-                    fprintf(stderr, "\n");
-                }
-                if (p.panel && tune.panel_repair) {
-                    // (4b) sub-blocks that hold an item the user rated: bound again without the user's own co-ratings
-                    RepairArgs RA{L.surv.get(), L.surv_mask.get(), L.n_quads.get(), bld, nb, s0, lo, p.p_eff, Ic, P.rowptr.get(), P.csr_idx.get(),
-                                  csr_x.get(), csr_e.get(), csr_q.get(), PP.Bmax64, PP.Brep, p.ldb64, PP.amax64, PP.bmax64,
-                                  L.tau.get(), pvpi.get(), (float)w2s, prune_counters.get()};
-                    k_bound_repair<<<std::min<int>(nb, ctx->num_cus * 16), 256, 0, ls>>>(RA);
-                    FY_KERNEL_CHECK();
-                }
-                if (p.half && !p.panel && tune.lazy_mirror) {      // lazy mirror, second pass: the column blocks with survivors
-                    const size_t sm = t_mirror.begin(ls);
-                    L.need.alloc(ctx, (size_t)p.nblk + 1);
-                    FY_HIP(hipMemsetAsync(L.need.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
-                    k_flag_surviving_blocks<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, L.need.get());
-                    FY_KERNEL_CHECK();
-                    launch_mirror(ctx, L.M.get(), ldm, Ic, nullptr, p.ldb, ls, L.need.get(), 0, false);
-                    t_mirror.end(sm, ls);
-                }
-                exclusive_scan_i32(ctx, L.n_quads.get(), L.quad_prefix.get(), (size_t)nb + 1, ls, &L.scan_tmp);
-                if (split) {      // the count goes to pinned memory; the host does not wait here
-                    FY_HIP(hipMemcpyAsync(&guard.pinned[pi], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-                    t_score.end(ss, ls);
-                    checkpoint("front (seed + bound, select, second bound)");
-                    continue;
-                }
-                }      // phase != 3
-                // (5) exact scores of the survivors, packed: 256 floats per surviving block at entry quad_prefix[u] + k
-                if (!split) FY_HIP(hipMemcpyAsync(&hv[0], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-                else hv[0] = guard.pinned[pi];
-                if (s0 == sbase && nb == p.Uc) {      // the whole cluster: its CSR range is on the host already
-                    hv[1] = csr_range[2 * pi];
-                    hv[2] = csr_range[2 * pi + 1];
-                } else {
-                    FY_HIP(hipMemcpyAsync(&hv[1], P.rowptr.get() + s0, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-                    FY_HIP(hipMemcpyAsync(&hv[2], P.rowptr.get() + s0 + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-                }
-                if (!split) FY_HIP(hipStreamSynchronize(ls));   // (everything queued on this lane before has finished: Ssurv may be re-sized)
-                const int32_t n_surv_total = hv[0];
-                const int64_t blocks_checked = (int64_t)nb * std::max(0, p.nblk - seed_blocks);
-                if (!p.panel && (double)n_surv_total > tune.max_surv_frac * (double)blocks_checked) {     // (panel mode has no full matrix to fall back on)
-                    // The threshold did not bite (e.g. lambda = 0: a user who rated an item nobody else of the cluster rated has
-                    // only -inf scores, tau = -inf keeps every block): the survivor pass would cost more than the plain full pass
-                    // and 1 KB of scratch per survivor.  Redo the batch with the full pass, in sub-batches that fit the workspace.
-                    t_score.end(ss, ls);
-                    if (p.half && tune.lazy_mirror) {      // the plain full pass reads every row whole: the rest of the lower triangle now
-                        const size_t sm = t_mirror.begin(ls);
-                        launch_mirror(ctx, L.M.get(), ldm, Ic, nullptr, p.ldb, ls, nullptr, 0x7FFFFFFF, false);
-                        t_mirror.end(sm, ls);
-                    }
-                    const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((ws / NS) / (ldm * 4), nb));
-                    DevBuf<float> Sfull(ctx, (size_t)(sub * ldm));
-                    for (int32_t t0 = s0; t0 < s0 + nb; t0 += (int32_t)sub) full_pass(t0, (int32_t)std::min<int64_t>(sub, s0 + nb - t0), Sfull.get());
-                    FY_HIP(hipStreamSynchronize(ls));   // Sfull goes back to the allocator
-                    R->st.prune_fallbacks++;
-                    R->st.score_launches++;          // the fused seed + bound launch that was thrown away
-                    prune_blocks_total += blocks_checked;
-                    fallback_survived += n_surv_total;
-                    prune_seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (seed_chunks * 256 + p.ldb + ldm);
-                    continue;
-                }
-                L.Ssurv.alloc(ctx, (size_t)std::max(1, n_surv_total) * PRUNE_BLOCK);
-                if (n_surv_total > 0) {
-                    ScoreArgs SQ = score_args(Gmat, gld, Ic, a_rank.get() + pbase, s0, nb, L.Ssurv.get(), 0, n_slices, n_chunks);
-                    const int panel_blocks = p.panel ? p.panel_cols / 256 : 0x7FFFFFFF;
-                    k_score_blocks<8><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
-                                                                        L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, bld, prune_counters.get(), panel_blocks,
-                                                                        p.panel ? L.surv_mask.get() : nullptr);
-                    FY_KERNEL_CHECK();
-                    if (p.panel && panel_blocks < p.nblk) {     // survivors behind the panel: exact, from the sparse data
-                        const size_t slds = ((size_t)p.Uc + 1) * sizeof(int32_t);
-                        const int sgrid = std::min<int>(n_surv_total, ctx->num_cus * (int)std::max<size_t>(1, std::min<size_t>(6, (150 * 1024) / (slds + 34 * 1024))));
-                        L.strayT.alloc(ctx, (size_t)sgrid * STRAY_TCAP);
-                        L.stray_items.alloc(ctx, (size_t)n_surv_total + 1);      // (a group holds at least one surviving block)
-                        FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
-                        k_stray_items<<<grid_for(nb), 256, 0, ls>>>(L.quad_prefix.get(), L.surv.get(), bld, nb, panel_blocks, L.stray_items.get(),
-                                                                   L.any_overflow.get());
-                        FY_KERNEL_CHECK();
-                        StrayArgs ST{L.quad_prefix.get(), L.surv.get(), L.surv_mask.get(), bld, nb, s0, lo, sbase, p.Uc, panel_blocks, Ic, pbase,
-                                     P.rowptr.get(), P.csr_idx.get(), csr_e.get(), csr_q.get(), P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(),
-                                     csc_x.get(), a_rank.get() + pbase, b_rank32.get() + pbase, pvpi.get(),
-                                     (float)w2s, L.Ssurv.get(), L.strayT.get(), prune_counters.get(), L.stray_items.get(),
-                                     L.any_overflow.get()};
-                        k_score_stray<<<sgrid, 256, slds, ls>>>(ST);
-                        FY_KERNEL_CHECK();
-                    }
-                }
-                t_score.end(ss, ls);
-                R->st.score_launches += 2;   // the fused seed + bound launch and the survivor pass
-                prune_blocks_total += blocks_checked;
-                // log terms of the seed and bound passes of this batch: (ratings of its users) x (columns walked)
-                prune_seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (seed_chunks * 256 + (use_sup ? 64 : bld));
-                const int32_t seed_cols_p = seed_chunks * 256;
-                TopNArgs TA{L.S.get(), (int64_t)seed_cols_p, Ic, n_out.get(), out_off.get(), P.rank_item_raw.get() + pbase,
-                            P.slot2du.get(), P.uid.get(), lo, s0, c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
-                            2, seed_cols_p, L.surv.get(), L.n_quads.get(), bld, L.tau.get(), L.Ssurv.get(), L.quad_prefix.get()};
-                const size_t tt = t_topn.begin(ls);
-                FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
-                if (long_seed)
-                    k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select,
-                                                                                                         fy_topn_long_cap(prm.number_of_recommendations));
-                else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
-                FY_KERNEL_CHECK();
-                k_topn_select<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), prune_counters.get() + 2);
-                FY_KERNEL_CHECK();
-                t_topn.end(tt, ls);
-                refine_rows(s0, nb);
-                checkpoint("back (survivors, strays, lists)");
-            }
-        }
-        if (phase == 1 && (!batch_main.empty() || !batch_tail.empty())) {     // the row kernels of all panel clusters: two launches
-            const size_t sp = t_cooc.begin(st);
-            launch_cooc_rm2_multi(ctx, tune, batch_tail, true, d_batch_tail, d_cnt_tail, st, true);
-            launch_cooc_rm2_multi(ctx, tune, batch_main, false, d_batch_main, d_cnt_main, st, true);
-            t_cooc.end(sp, st);
-            // symmetric panel mode: the lower triangle of every panel's square, then the head rows' bounds (three launches for all clusters)
-            int max_cols = 0, max_nsub = 0;
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                const Plan& p = plans[pi];
-                if (!p.psym || group_of[pi] != grp) continue;
-                hpd.push_back(PanelDesc{pbuf[pi].Gp.get(), pbuf[pi].Bmax64.get(), pbuf[pi].Brep.get(), p.panel_cols, p.ldb64, p.Ic, p.p_eff, p.nsub, 0});
-                max_cols = std::max(max_cols, p.panel_cols);
-                max_nsub = std::max(max_nsub, p.nsub);
-            }
-            if (!hpd.empty()) {
-                // operand check on the host (round 3: these launches faulted at address 0x1000 when a half-built group handed them the
-                // descriptors of clusters whose panels were not allocated): every panel pointer set, every shape what the kernels' grids assume
-                for (size_t k = 0; k < hpd.size(); k++) {
-                    const PanelDesc& d = hpd[k];
-                    if (!d.Gp || !d.Bmax64 || !d.Brep || d.panel_cols <= 0 || d.panel_cols % 256 != 0 || d.p_eff != d.panel_cols || d.Ic < d.p_eff || d.nsub <= 0 ||
-                        d.ldb64 < d.nsub)
-                        FY_FAIL(FY_ERR_STATE, "internal: panel %zu of %zu of a batched mirror / column-maximum launch is unusable (Gp %p Bmax64 %p Brep %p panel_cols %d p_eff %d Ic %d nsub %d ldb64 %lld)",
-                                k, hpd.size(), (const void*)d.Gp, (const void*)d.Bmax64, (const void*)d.Brep, (int)d.panel_cols, (int)d.p_eff, (int)d.Ic, (int)d.nsub, (long long)d.ldb64);
-                }
-                const size_t sm = t_mirror.begin(st);
-                d_panel_desc.alloc(ctx, hpd.size());
-                FY_HIP(hipMemcpyAsync(d_panel_desc.get(), hpd.data(), hpd.size() * sizeof(PanelDesc), hipMemcpyHostToDevice, st));
-                const unsigned nz = (unsigned)hpd.size();
-                if (max_cols / 256 > 1) {
-                    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mirror_tiles_multi), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * MIRROR_PITCH));
-                    k_mirror_tiles_multi<<<dim3((unsigned)(max_cols / 128), (unsigned)(max_cols / 256 - 1), nz), 1024, 128 * MIRROR_PITCH, st>>>(d_panel_desc.get());
-                    FY_KERNEL_CHECK();
-                }
-                k_mirror_diag_multi<<<dim3((unsigned)(max_cols / 256), nz), 256, 0, st>>>(d_panel_desc.get());
-                FY_KERNEL_CHECK();
-                k_panel_colmax<<<dim3((unsigned)(max_cols / 256), (unsigned)ceil_div(max_nsub, 16), nz), 256, 0, st>>>(d_panel_desc.get());
-                FY_KERNEL_CHECK();
-                t_mirror.end(sm, st);
-            }
-            if (tune.debug_sync == 1) {
-                const hipError_t e = hipDeviceSynchronize();
-                fprintf(stderr, "[fy] group %d/%d: batched row kernels, mirror, column maxima -> %s\n", grp, n_groups, hipGetErrorString(e));
-                fflush(stderr);
-            }
-            R->st.cooc_launches += (batch_tail.empty() ? 0 : 1) + 1;
-        }
-        if (tune.debug_sync == 2) {
-            (void)hipDeviceSynchronize();
-            fprintf(stderr, "[fy] group %d phase %d: %.3f ms from its first queued operation to the drained device\n", grp, phase,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count());
-        }
-        }      // phase
-        if (grp + 1 < n_groups) {     // the next group re-uses this group's memory: everything queued so far must have finished
-            for (int l = 0; l < NS; l++) FY_HIP(hipStreamSynchronize(lanes[l].st));
-            FY_HIP(hipStreamSynchronize(st));
-        }
-        }      // group
-        if (NS > 1) {   // join: the main stream continues after every lane has drained
-            for (int l = 0; l < NS; l++) {
-                hipEvent_t done;
-                FY_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-                FY_HIP(hipEventRecord(done, lanes[l].st));
-                FY_HIP(hipStreamWaitEvent(st, done, 0));
-                FY_HIP(hipEventDestroy(done));
-            }
-        }
+        // ---- 6. + 7. every other cluster on its lane (two-phase panel mode: group by group)
+        PanelSet PS;
+        PS.pbuf.resize(jp.two_phase ? plans.size() : 0);
+        PS.plane.resize(jp.two_phase ? plans.size() : 0);
+        LaneGuard guard{ctx};
+        if (jp.two_phase) FY_HIP(hipHostMalloc(reinterpret_cast<void**>(&guard.pinned), plans.size() * sizeof(int32_t), hipHostMallocDefault));
+        score_clusters(X, lanes, PS, guard);
         // (the guard's destructor drains the lanes and the main stream before any buffer of this scope is released)
-        {
-            unsigned long long hc[6];
-            d2h(ctx, hc, prune_counters.get(), 6);
-            sync(ctx);
-            if (!tables_cached && !all_at_once) {        // (build_tables_all counts its one table itself)
-                tc.total_segments = 0;
-                for (auto& t : segs) tc.total_segments += t.n_seg;
-                for (auto& t : segs_tail) tc.total_segments += t.n_seg;
-            }
-            tc.sig = sig;          // every table of the plan has been built and used: a later job with the same plan re-uses them
-            tc.valid = true;
-            R->st.cooc_segments = tc.total_segments;
-            for (auto& p : plans) {       // what the row kernels store (the mirror pass and the column maxima are priced separately)
-                const int64_t eb = p.pack24 ? 3 : 4;
-                if (p.coop) continue;
-                if (p.panel) R->st.cooc_matrix_bytes += (int64_t)p.Ic * p.panel_cols * 3 + (int64_t)p.Ic * p.ldb64 * 7;
-                else R->st.cooc_matrix_bytes += eb * (p.half ? (int64_t)p.Ic * (p.Ic + 256) / 2 : (int64_t)p.Ic * p.Ic) + (p.prune ? (int64_t)p.Ic * p.nblk * 3 : 0);
-            }
-            R->st.topn_select_users = (int64_t)hc[2];
-            R->st.stray_blocks = (int64_t)hc[3];
-            R->st.bound_repairs = (int64_t)hc[4];
-            R->st.rows_refined = (int64_t)hc[5];
-            R->st.blocks_survived = (int64_t)hc[0] + coop_survived + fallback_survived;
-            R->st.blocks_total = prune_blocks_total;
-            R->st.log_terms_evaluated = prune_blocks_total ? (int64_t)hc[1] + prune_seed_terms_cols : 0;
-        }
+
+        // ---- 8. stats
+        fill_score_stats(X, tables_cached, sig);
     }
     // rm2/userSum and rm2/itemColl stay in HBM until somebody asks for them
     if (J->S->sharded) {
-        sharded_side_outputs(J, R.get(), d_total.get());
+        sharded_side_outputs(J, R.get(), A.d_total.get());
     } else {
         R->d_user_id.alloc(ctx, nU);
         R->d_user_sum.alloc(ctx, nU);
@@ -3335,10 +3307,10 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
         d2d(ctx, R->d_item_id.get(), P.iid.get(), nI);
     }
     t_total.end(span_total);
-    d2h(ctx, &R->total_sum, d_total.get(), 1);
+    d2h(ctx, &R->total_sum, A.d_total.get(), 1);
     sync(ctx);
     // (bench.py prices the row kernel with (pair_contribs - nnz) / 2 unordered pairs: a cooperative rank walked only its rows)
-    R->st.pair_contribs = any_coop ? coop_pair_contribs + P.nnz : P.sum_deg2;
+    R->st.pair_contribs = jp.any_coop ? coop_pair_contribs + P.nnz : P.sum_deg2;
     R->st.ms_cooc = t_cooc.total_ms();
     R->st.ms_score = t_score.total_ms();
     R->st.ms_topn = t_topn.total_ms();

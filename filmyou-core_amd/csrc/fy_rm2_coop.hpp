@@ -1,6 +1,7 @@
 // fy_rm2_coop.hpp -- host orchestration of the cooperative multi-rank path (fy_collectives, include/filmyou.h).
-// NOT a standalone header: one section of fy_rm2.hip's translation unit (needs fy_rm2_job, ScoreTune, Plan and the kernels),
-// split out for size.
+// NOT a standalone header: one section of fy_rm2.hip's translation unit (needs fy_rm2_job, ScoreShared, Plan and the kernels),
+// split out for size.  score_cluster_coop is the cooperative counterpart of build_cluster_matrix + score_cluster (fy_rm2.hip): visit_cluster
+// hands it the same ScoreShared and the cluster's Plan (Plan::coop, decided by plan_job, fy_rm2_plan.hpp).
 #pragma once
 
 // ================================================================ cooperative ranks: one cluster scored by all ranks together
@@ -10,23 +11,6 @@
 // rows, and a reduce-scatter hands the owner of each user the complete sums.  Three exchanges follow the three pruned
 // passes: seed columns, block bounds, surviving blocks.  Rank 0 contributes pvpi; a rated candidate is masked (NaN) by
 // the rank that holds its row, and NaN survives the sum.
-struct CoopShared {
-    fy_rm2_job* J;
-    fy_result* R;
-    const ScoreTune* tune;
-    const float *b_rank;              // b_i (fp32), rank order
-    const float *a_rank, *csc_x, *csr_x, *csr_e, *csr_q;
-    const uint32_t* csr_pk;        // packed CSR for the row kernel (nullptr: csr_idx / csr_x); csc_x then holds x / s_v
-    const int32_t *n_out, *out_off;   // this rank's users, by slot - lo
-    const double* pvpi;               // this rank's users, by slot - lo (the complete value; pv_all below is zero on ranks != 0)
-    int32_t lo;
-    EventTimer *t_cooc, *t_score, *t_topn;
-    unsigned long long* prune_counters;
-    int64_t *blocks_total, *seed_terms_cols, *coop_survived, *coop_pair_contribs;
-    const int32_t* cshift;            // [cluster]: c of the packed matrix format (k_user_meta)
-    float gscale;                     // 2^-c of THIS cluster
-};
-
 static void coll_all_gather(fy_rm2_job* J, const void* send, void* recv, int64_t bytes, hipStream_t st) {
     if (!J->have_coll) {   // world == 1 (forced cooperative mode, tests): the identity
         if (bytes) FY_HIP(hipMemcpyAsync(recv, send, (size_t)bytes, hipMemcpyDeviceToDevice, st));
@@ -44,7 +28,7 @@ static void coll_reduce_scatter(fy_rm2_job* J, const float* send, float* recv, i
     if (rc) FY_FAIL(FY_ERR_COLLECTIVE, "reduce_scatter callback returned %d", rc);
 }
 
-static void score_cluster_coop(const CoopShared& X, const Plan& p, hipStream_t ls) {
+static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t ls) {
     fy_rm2_job* J = X.J;
     Context* ctx = J->ctx;
     Prepared& P = J->P;
@@ -132,7 +116,7 @@ static void score_cluster_coop(const CoopShared& X, const Plan& p, hipStream_t l
                         (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
             const int fxk = (X.csr_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) : -1;
             CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;
-            const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale;      // (1-l)^2 and the packed format's 2^-c
+            const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale[(size_t)p.c];      // (1-l)^2 and the packed format's 2^-c
             MEpilogue ME{const_cast<float*>(Mshift), ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0,
                          1, const_cast<float*>(Bshift), ldb, 1};
             const size_t sp = X.t_cooc->begin(ls);
@@ -164,7 +148,7 @@ static void score_cluster_coop(const CoopShared& X, const Plan& p, hipStream_t l
     if (me != 0) FY_HIP(hipMemsetAsync(pv_all.get(), 0, (size_t)Uc * sizeof(double), ls));   // pvpi enters the sum once
 
     size_t ss = X.t_score->begin(ls);   // the spans of ms_score cover this rank's kernels, not the waits inside the collectives
-    auto slices_for = [&](int32_t nb) { return score_slices(ctx, tune, nb, seed_chunks + bchunks); };
+    auto slices_for = [&](int32_t nb) { return score_slices(ctx->num_cus, tune, nb, seed_chunks + bchunks); };
     // ---- (1) partial seed scores AND partial block bounds of every user in one launch per owner (one grid tail, see
     // rm2_score); (2) two reduce-scatters; (3) tau + the speculative lists; (5) the owner keeps the blocks that reach tau
     for (int k = 0; k < W; k++) {
