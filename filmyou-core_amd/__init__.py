@@ -12,12 +12,12 @@ All compute happens in libfilmyou_hip.so (hand-written HIP for gfx950); there is
 """
 from . import _native
 from ._native import build, LIB_PATH
-from .host import (BaselineRecommenderJob, ClusterAssignmentJob, Configuration, Context, FilmYouError, ItemRecommendations, ItemSimilarities, NMFDriver, PreparedRM2, Ratings, Recommendations, RM2Job,
+from .host import (BaselineRecommenderJob, ClusterAssignmentJob, Configuration, Context, FilmYouError, ItemRecommendations, ItemSimilarities, NMFDriver, PreparedItemSimilarity, PreparedRM2, Ratings, Recommendations, RM2Job,
                    RowSimilarityJob, SIMILARITY_COSINE, SIMILARITY_COOCCURRENCE, SIMILARITY_TANIMOTO_COEFFICIENT, SIMILARITY_LOGLIKELIHOOD,
                    SIMILARITY_CITY_BLOCK, SIMILARITY_EUCLIDEAN_DISTANCE, SIMILARITY_PEARSON_CORRELATION, ClusterRefinementJob, RMRecommenderDriver,
                    SubClusterMappingJob, SubClusterMappings, read_id_file, write_similarity_pairs)
 
-__all__ = ["build", "BaselineRecommenderJob", "ClusterAssignmentJob", "ItemRecommendations", "NMFDriver", "LIB_PATH", "Configuration", "Context", "FilmYouError", "ItemSimilarities", "PreparedRM2", "Ratings",
+__all__ = ["build", "BaselineRecommenderJob", "ClusterAssignmentJob", "ItemRecommendations", "NMFDriver", "LIB_PATH", "Configuration", "Context", "FilmYouError", "ItemSimilarities", "PreparedItemSimilarity", "PreparedRM2", "Ratings",
            "Recommendations", "RM2Job", "RowSimilarityJob", "SIMILARITY_COSINE", "SIMILARITY_COOCCURRENCE", "SIMILARITY_TANIMOTO_COEFFICIENT",
            "SIMILARITY_LOGLIKELIHOOD", "SIMILARITY_CITY_BLOCK", "SIMILARITY_EUCLIDEAN_DISTANCE", "SIMILARITY_PEARSON_CORRELATION", "_native",
            "ClusterRefinementJob", "RMRecommenderDriver", "SubClusterMappingJob", "SubClusterMappings", "read_id_file",

@@ -10,6 +10,7 @@
 #include "fy_rm2.hpp"
 #include "fy_ratings_update.hpp"
 #include "fy_rm2_request.hpp"
+#include "fy_itemsim_request.hpp"
 
 namespace fy {
 static thread_local char g_err[512] = "";
@@ -80,6 +81,8 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_ISIM_CAPG")) { int v = atoi(e); if (v >= 1 && v <= 2040) t.isim_capg = v; }
     if (const char* e = getenv("FY_ISIM_ACC32")) t.isim_acc32 = atoi(e) != 0;
     if (const char* e = getenv("FY_ISIM_PIECE")) { int v = atoi(e); if (v >= 64 && v <= 8192 && v % 64 == 0) t.isim_piece = v; }
+    if (const char* e = getenv("FY_ISIM_REQ_CHUNK")) { int v = atoi(e); if (v >= 64 && v <= 16384 && v % 64 == 0) t.isim_req_chunk = v; }
+    if (const char* e = getenv("FY_ISIM_REQ_ROWS")) t.isim_req_rows = std::max(0, atoi(e));
 }
 
 // Every entry point that reaches the GPU selects its context's device first: allocations, new streams and kernel attributes
@@ -394,6 +397,36 @@ int fy_itemsim_run(const fy_itemsim_params* p, int64_t nnz, const int32_t* user,
     return rc;
 }
 
+int fy_itemsim_prepare(fy_context* c, const fy_itemsim_params* p, const fy_ratings* r, fy_itemsim_job** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!c || !r || !p) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->ctx != &c->c) { set_error("ratings belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::itemsim_prepare(&c->c, p, r);
+    FY_CATCH
+}
+
+int fy_itemsim_rows(fy_itemsim_job* j, const fy_itemsim_request* rq, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !rq) { set_error("job or request is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (rq->n_items < 0 || (rq->n_items > 0 && !rq->items)) { set_error("items is NULL or n_items < 0"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(j->ctx);
+    *out = fy::itemsim_rows(j, rq);
+    FY_CATCH
+}
+
+void fy_itemsim_job_destroy(fy_itemsim_job* j) {
+    if (!j) return;
+    fy::Context* ctx = j->ctx;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    delete j;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
+}
+
 int fy_cluster_assign(fy_context* c, int32_t n_rows, int32_t k, const double* H, int location, int32_t first_user,
                       int32_t cluster_offset, int32_t n_clusters, int32_t* user_out, int32_t* cluster_out, int32_t* count_inout) {
     if (!c) { set_error("context is NULL"); return FY_ERR_INVALID_ARGUMENT; }
@@ -515,6 +548,12 @@ int fy_result_request_stats(fy_result* r, fy_rm2_request_stats* out) {
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     if (!r->has_request_stats) { set_error("not a result of fy_rm2_score_users"); return FY_ERR_STATE; }
     *out = r->rq;
+    return FY_OK;
+}
+int fy_result_itemsim_request_stats(fy_result* r, fy_itemsim_request_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_itemsim_request_stats) { set_error("not a result of fy_itemsim_rows"); return FY_ERR_STATE; }
+    *out = r->irq;
     return FY_OK;
 }
 void fy_result_free(fy_result* r) {

@@ -25,6 +25,8 @@
 #include <memory>
 
 #include "fy_cooc.hpp"
+#include "fy_itemsim_kernels.hpp"
+#include "fy_itemsim_request.hpp"
 #include "fy_prep.hpp"
 #include "fy_rm2.hpp"
 
@@ -128,170 +130,11 @@ __global__ void k_csr_weights(int64_t nnz, const int32_t* __restrict__ csr_idx, 
     }
 }
 
-// One function per measure, fp64; the emitted similarity is the (float) of it.  d = the accumulated dot product, a_i / a_j = the
-// two items' norms of the table (the count measures: number of raters; Euclidean: sum r^2), N = number of users.
-__device__ __forceinline__ double isim_finish_product(double d, double inv_i, double inv_j) { return d * inv_i * inv_j; }   // cosine on raw ratings: inv = 1 / ||r||
-__device__ __forceinline__ double isim_finish_tanimoto(double d, double ai, double aj) { return d / (ai + aj - d); }
-__device__ __forceinline__ double isim_finish_city_block(double d, double ai, double aj) { return 1.0 / (1.0 + ai + aj - 2.0 * d); }
-__device__ __forceinline__ double isim_finish_euclidean(double d, double ai, double aj) { return 1.0 / (1.0 + sqrt(fmax(0.0, ai - 2.0 * d + aj))); }
-__device__ __forceinline__ double isim_xlogx(double x) { return x == 0.0 ? 0.0 : x * log(x); }
-// Mahout's LogLikelihood.logLikelihoodRatio on unnormalised entropies H(x...) = xlogx(sum x) - sum xlogx(x)
-__device__ __forceinline__ double isim_finish_loglikelihood(double d, double ai, double aj, double N) {
-    const double k11 = d, k12 = aj - d, k21 = ai - d, k22 = N - ai - aj + d;
-    const double row_e = isim_xlogx(k11 + k12 + k21 + k22) - isim_xlogx(k11 + k12) - isim_xlogx(k21 + k22);
-    const double col_e = isim_xlogx(k11 + k12 + k21 + k22) - isim_xlogx(k11 + k21) - isim_xlogx(k12 + k22);
-    const double mat_e = isim_xlogx(k11 + k12 + k21 + k22) - isim_xlogx(k11) - isim_xlogx(k12) - isim_xlogx(k21) - isim_xlogx(k22);
-    const double llr = row_e + col_e < mat_e ? 0.0 : 2.0 * (row_e + col_e - mat_e);
-    return 1.0 - 1.0 / (1.0 + llr);
-}
-template <int M>
-__device__ __forceinline__ double isim_finish(double d, double ai, double aj, double N) {
-    if constexpr (M == FY_SIMILARITY_TANIMOTO_COEFFICIENT) return isim_finish_tanimoto(d, ai, aj);
-    else if constexpr (M == FY_SIMILARITY_LOGLIKELIHOOD) return isim_finish_loglikelihood(d, ai, aj, N);
-    else if constexpr (M == FY_SIMILARITY_CITY_BLOCK) return isim_finish_city_block(d, ai, aj);
-    else {
-        static_assert(M == FY_SIMILARITY_EUCLIDEAN_DISTANCE, "cosine, co-occurrence and Pearson: the dot product is the similarity");
-        return isim_finish_euclidean(d, ai, aj);
-    }
-}
-
-__device__ __forceinline__ uint32_t isim_order_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float isim_order_unkey(uint32_t k) {
-    const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    return __uint_as_float(b);
-}
-
-constexpr int ISIM_CAP = 2048;      // candidate buffer (LDS)
-constexpr int ISIM_MAX_K = 1024;
-constexpr int ISIM_SAMPLE = 256;       // columns sampled for the first threshold guess of a row
-constexpr int ISIM_SAMPLE_RANK = 5;    // ... whose 5th largest is the guess (expected: ~5 * columns / 256 values above it)
-
-struct ISimEpilogue {
-    const int32_t* __restrict__ rank_item_raw;
-    int32_t K;
-    int32_t exclude_self;
-    int32_t has_threshold;
-    float threshold;
-    int32_t rank, world;     // this launch builds rows rank, rank + world, ...
-    int32_t* __restrict__ out_cnt;     // [rows_mine]
-    int32_t* __restrict__ out_other;   // [rows_mine * K]
-    float* __restrict__ out_sim;       // [rows_mine * K]
-    // packed row kernel: the accumulators hold sum_v r_vi r_vj (exact in fp64 for fp16-exact ratings); cosine = that times
-    // inv_norm[i] inv_norm[j] (rank order).  nullptr: the weights were divided by the norms beforehand.
-    const double* __restrict__ inv_norm;
-    // the measures with a finishing function (Tanimoto, log-likelihood, city block, Euclidean distance): a_i in rank order, and N
-    const double* __restrict__ aux;
-    double n_cols;
-    // per (row, chunk) item: its top K as (order key << 32 | ~raw item id), descending
-    int32_t* __restrict__ part_cnt;    // [rows_mine * nch]
-    uint64_t* __restrict__ part;       // [rows_mine * nch * K]
-    int32_t heavy_rows;                // leading rows of the launch that are split by chunk
-    int32_t n_items;                   // heavy_rows * nch + (rows - heavy_rows)
-    int32_t cap;                       // candidate buffer entries in LDS (power of two, >= 2 K, <= ISIM_CAP)
-};
-
-__device__ __forceinline__ void isim_sort_desc(uint64_t* v, int P2) {
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P2; i += blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const uint64_t x = v[i], y = v[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (x < y) : (x > y)) { v[i] = y; v[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// Cuts the n candidates in LDS down to (at least) the K best without sorting them: two 256-bin histogram levels over the
-// order keys (bits 31..24, then 23..16) locate a 16-bit key prefix T with  #(key >= T) >= K  and  #(key >= T + 1 prefix) < K;
-// everything below T goes.  ~8 barriers instead of the 66 of a 2048-element bitonic sort (rocprof: the sorts were half
-// of the kernel).  Returns the new count through sh_cnt and the new threshold through sh_tau; all threads call it.
-// Ties inside the last prefix all stay, so the result may hold more than K entries -- if it would not fit behind the next
-// streaming step the caller falls back to the exact sort.
-__device__ __forceinline__ void isim_select(uint64_t* cand, int n, int K, uint32_t* hist, uint32_t* sh_cnt, uint32_t* sh_tau,
-                                            uint32_t* sh_aux) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    if (n <= K) {   // block-uniform: nothing to cut
-        return;
-    }
-    uint32_t prefix = 0, above = 0;
-    for (int level = 0; level < 2; level++) {
-        const int shift = level == 0 ? 24 : 16;
-        for (int b = tid; b < 256; b += nt) hist[b] = 0;
-        __syncthreads();
-        for (int i = tid; i < n; i += nt) {
-            const uint32_t key = (uint32_t)(cand[i] >> 32);
-            if (level == 0 || (key >> 24) == (prefix >> 24)) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t cum = above;
-            int b = 255;
-            for (; b > 0; b--) {
-                if (cum + hist[b] >= (uint32_t)K) break;
-                cum += hist[b];
-            }
-            sh_aux[0] = prefix | ((uint32_t)b << shift);
-            sh_aux[1] = cum;
-        }
-        __syncthreads();
-        prefix = sh_aux[0];
-        above = sh_aux[1];
-        __syncthreads();
-    }
-    // keep key >= prefix (in place: all reads happen before the first write)
-    uint64_t mine[ISIM_CAP / 256];
-    int have = 0;
-    for (int i = tid; i < n; i += nt) {
-        const uint64_t c = cand[i];
-        if ((uint32_t)(c >> 32) >= prefix && have < ISIM_CAP / 256) mine[have++] = c;
-    }
-    __syncthreads();
-    if (tid == 0) *sh_cnt = 0;
-    __syncthreads();
-    for (int k = 0; k < have; k++) cand[atomicAdd(sh_cnt, 1u)] = mine[k];
-    if (tid == 0) *sh_tau = prefix;
-    __syncthreads();
-}
-
-// buffer (nearly) full: keep the K best (plus ties inside the last key prefix); exact sort when even that does not make room
-__device__ __forceinline__ void isim_cut(uint64_t* cand, int K, int cap, uint32_t* hist, uint32_t* sh_cnt, uint32_t* sh_tau, uint32_t* sh_aux) {
-    const int tid = threadIdx.x;
-    isim_select(cand, (int)*sh_cnt, K, hist, sh_cnt, sh_tau, sh_aux);
-    if (*sh_cnt + min((uint32_t)blockDim.x, (uint32_t)cap / 2) > (uint32_t)cap) {   // massive ties inside one key prefix (block-uniform)
-        const int n = (int)*sh_cnt;
-        __syncthreads();
-        for (int i = n + tid; i < cap; i += blockDim.x) cand[i] = 0ull;
-        __syncthreads();
-        isim_sort_desc(cand, cap);
-        if (tid == 0) {
-            *sh_cnt = (uint32_t)min(n, K);
-            if (n >= K) *sh_tau = (uint32_t)(cand[K - 1] >> 32);   // inclusive: a later tie with a smaller item id still wins
-        }
-        __syncthreads();
-    }
-}
-
 // dynamic LDS: [CH doubles accumulators][ISIM_CAP uint64 candidates].  Persistent workgroups pull (row, column chunk) ITEMS
 // from a global counter (heavy rows first) and leave the top K of that chunk; k_isim_merge folds a row's chunks together.
 // Only the heaviest rows are split by chunk (one workgroup per whole row left the heaviest row -- 10^5 raters, 5e7 slice
 // entries -- on a single CU for half of the kernel's run time); a light row is one item and carries its threshold from chunk
 // to chunk (splitting every row cost more in top-K work than it gained: 52 ms against 30).  The pass that streams a finished chunk through the top-K re-zeroes the accumulators it reads.
-// similarity of (row, col) from the accumulator a.  M = FY_SIMILARITY_COSINE stands for the three measures whose dot product IS the
-// similarity (cosine, co-occurrence, Pearson: the norms are in the weights, or -- packed cosine -- in inv_norm); the others finish
-// through isim_finish<M>.  For those an untouched accumulator is not similarity 0, so a pair nobody co-rated (a == 0; exact: the
-// weights are positive) reads as NaN, which passes no comparison.
-template <int M>
-__device__ __forceinline__ float isim_row_value(const ISimEpilogue& E, double a, double row_term, int col) {
-    if constexpr (M == FY_SIMILARITY_COSINE) return E.inv_norm ? (float)isim_finish_product(a, row_term, E.inv_norm[col]) : (float)a;
-    else return a != 0.0 ? (float)isim_finish<M>(a, row_term, E.aux[col], E.n_cols) : __builtin_nanf("");
-}
 template <bool PK, int M>
 __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ next_row) {
     double* acc = fy_cooc_acc;
@@ -1041,38 +884,6 @@ __global__ void k_isim_count_heavy(int32_t rows_mine, int32_t rank, int32_t worl
     }
 }
 
-// one workgroup per row: fold the chunks' top-K lists (each sorted, disjoint columns) into the row's top K
-__global__ __launch_bounds__(256) void k_isim_merge(int32_t rows_mine, int32_t nch, int32_t K, const int32_t* __restrict__ part_cnt,
-                                                    const uint64_t* __restrict__ part, int32_t* __restrict__ out_cnt,
-                                                    int32_t* __restrict__ out_other, float* __restrict__ out_sim) {
-    __shared__ uint64_t buf[2 * ISIM_MAX_K];
-    const int tid = threadIdx.x;
-    for (int m = blockIdx.x; m < rows_mine; m += gridDim.x) {
-        int have = 0;
-        for (int ch = 0; ch < nch; ch++) {
-            const int n = part_cnt[(int64_t)m * nch + ch];
-            if (n == 0) continue;    // block-uniform
-            for (int i = tid; i < n; i += blockDim.x) buf[have + i] = part[((int64_t)m * nch + ch) * K + i];
-            const int tot = have + n;
-            if (have == 0) { have = n; __syncthreads(); continue; }   // a single list is already sorted
-            int P2 = 1;
-            while (P2 < tot) P2 <<= 1;
-            for (int i = tot + tid; i < P2; i += blockDim.x) buf[i] = 0ull;
-            __syncthreads();
-            isim_sort_desc(buf, P2);
-            have = min(tot, K);
-        }
-        __syncthreads();
-        if (tid == 0) out_cnt[m] = have;
-        for (int i = tid; i < have; i += blockDim.x) {
-            const uint64_t c = buf[i];
-            out_other[(int64_t)m * K + i] = 0x7FFFFFFF - (int32_t)(uint32_t)c;
-            out_sim[(int64_t)m * K + i] = isim_order_unkey((uint32_t)(c >> 32));
-        }
-        __syncthreads();
-    }
-}
-
 __global__ void k_isim_compact(int32_t rows_mine, int32_t K, int32_t rank, int32_t world, const int32_t* __restrict__ cnt,
                                const int32_t* __restrict__ off, const int32_t* __restrict__ other, const float* __restrict__ sim,
                                const int32_t* __restrict__ rank_item_raw, int32_t* __restrict__ o_item,
@@ -1164,10 +975,12 @@ static std::unique_ptr<fy_ratings> filter_user_prefs(Context* ctx, const fy_rati
     return F;
 }
 
-fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in) {
+// what both entry points (the full build, the prepared job) refuse, in the order the full build has always checked it: the input
+// preparation's options before the preparation runs, the rest behind it
+static void isim_check_prefs(const fy_itemsim_params* prm) {
     if (prm->min_prefs_per_user < 0 || prm->max_prefs_per_user < 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "minPrefsPerUser / maxPrefsPerUser must be >= 0");
-    const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
-    const fy_ratings* R = filtered ? filtered.get() : R_in;
+}
+static void isim_check_params(const fy_itemsim_params* prm) {
     if (prm->similarity < FY_SIMILARITY_COSINE || prm->similarity > FY_SIMILARITY_PEARSON_CORRELATION)
         FY_FAIL(FY_ERR_INVALID_ARGUMENT, "similarity must be one of the FY_SIMILARITY_* constants (0 .. %d)", (int)FY_SIMILARITY_PEARSON_CORRELATION);
     const int measure = prm->similarity;
@@ -1178,6 +991,19 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
     if (prm->max_similarities_per_item > ISIM_MAX_K)
         FY_FAIL(FY_ERR_UNSUPPORTED, "maxSimilaritiesPerRow %d exceeds the kernel limit %d", prm->max_similarities_per_item, ISIM_MAX_K);
     if (prm->world <= 0 || prm->rank < 0 || prm->rank >= prm->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", prm->rank, prm->world);
+}
+static void isim_check_euclidean(int measure, const Prepared& P) {
+    if (measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE && !P.ratings_positive)
+        FY_FAIL(FY_ERR_UNSUPPORTED, "SIMILARITY_EUCLIDEAN_DISTANCE on data with a non-positive preference: a co-rated pair whose products sum to 0 "
+                                    "cannot be told from a pair nobody co-rated");
+}
+
+fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in) {
+    isim_check_prefs(prm);
+    const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
+    const fy_ratings* R = filtered ? filtered.get() : R_in;
+    isim_check_params(prm);
+    const int measure = prm->similarity;
     hipStream_t st = ctx->stream;
     std::unique_ptr<fy_result> Rs(new fy_result);
     Rs->ctx = ctx;
@@ -1196,9 +1022,7 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
         sync(ctx);
         return Rs.release();
     }
-    if (measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE && !P.ratings_positive)
-        FY_FAIL(FY_ERR_UNSUPPORTED, "SIMILARITY_EUCLIDEAN_DISTANCE on data with a non-positive preference: a co-rated pair whose products sum to 0 "
-                                    "cannot be told from a pair nobody co-rated");
+    isim_check_euclidean(measure, P);
     const int32_t Ic = P.nP;   // single "cluster": every item is a pair
     const int cosine = measure == FY_SIMILARITY_COSINE;
     const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
@@ -1334,6 +1158,130 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
     Rs->st.ms_cooc = symmetric ? ms_sym : t_cooc.total_ms();
     Rs->st.ms_total = t_total.total_ms();
     return Rs.release();
+}
+
+// ================================================================ the prepared job (fy_itemsim_prepare; requests: fy_itemsim_request.hip)
+// per item in rank order: the sum of the raters' degrees (what a request for the item walks), one wave per item
+__global__ void k_isim_req_walk(int32_t Ic, const int32_t* __restrict__ rank_pair, const int32_t* __restrict__ pair_start,
+                                const int32_t* __restrict__ csc_slot, const int32_t* __restrict__ rowptr, long long* __restrict__ walk) {
+    const int wpb = blockDim.x >> 6, lane = threadIdx.x & 63;
+    for (int32_t r = blockIdx.x * wpb + (threadIdx.x >> 6); r < Ic; r += gridDim.x * wpb) {
+        const int32_t pr = rank_pair[r];
+        long long s = 0;
+        for (int32_t q = pair_start[pr] + lane; q < pair_start[pr + 1]; q += 64) {
+            const int32_t v = csc_slot[q];
+            s += rowptr[v + 1] - rowptr[v];
+        }
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        if (lane == 0) walk[r] = s;
+    }
+}
+// Pearson in fp64: the centred, normalised preference of every CSR entry (0 on a constant item, whose pairs drop out through unit[])
+__global__ void k_isim_req_pearson_weights(int64_t nnz, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r,
+                                           const int32_t* __restrict__ rank_pair, const double* __restrict__ centre, const double* __restrict__ cnorm,
+                                           double* __restrict__ csr_w) {
+    for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < nnz; f += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t p = rank_pair[csr_idx[f]];
+        const double cn = cnorm[p];
+        csr_w[f] = cn != 0.0 ? ((double)csr_r[f] - centre[p]) * (1.0 / cn) : 0.0;
+    }
+}
+// ... and per item in rank order the factor of its similarities: 1, NaN for a constant item (0 / 0 in the statement)
+__global__ void k_isim_req_pearson_unit(int32_t Ic, const int32_t* __restrict__ rank_pair, const double* __restrict__ cnorm, double* __restrict__ unit) {
+    for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < Ic; r += gridDim.x * blockDim.x)
+        unit[r] = cnorm[rank_pair[r]] != 0.0 ? 1.0 : __longlong_as_double(0x7FF8000000000000ll);
+}
+
+fy_itemsim_job* itemsim_prepare(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in) {
+    isim_check_prefs(prm);
+    const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
+    const fy_ratings* R = filtered ? filtered.get() : R_in;
+    isim_check_params(prm);
+    const int measure = prm->similarity;
+    hipStream_t st = ctx->stream;
+    std::unique_ptr<fy_itemsim_job> J(new fy_itemsim_job);
+    J->ctx = ctx;
+    J->prm = *prm;
+    Prepared& P = J->P;
+    build_structure(ctx, R, 1, 0, nullptr, nullptr, nullptr, true, P);
+    if (P.nnz == 0) {
+        sync(ctx);
+        return J.release();
+    }
+    isim_check_euclidean(measure, P);
+    const int32_t Ic = P.nP;
+    const bool cosine = measure == FY_SIMILARITY_COSINE, pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    const bool euclidean = measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
+    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
+                          measure == FY_SIMILARITY_CITY_BLOCK || euclidean;
+    // the norms of the full build, by its kernels (fixed summation order)
+    DevBuf<double> norm(ctx, Ic), sumsq(ctx, euclidean ? Ic : 1);
+    J->centre.alloc(ctx, pearson ? Ic : 1);
+    J->cnorm.alloc(ctx, pearson ? Ic : 1);
+    J->inv_norm.alloc(ctx, (cosine || pearson) ? Ic : 1);
+    J->aux.alloc(ctx, finishes ? Ic : 1);
+    J->csr_w.alloc(ctx, pearson ? (size_t)P.nnz : 1);
+    const int norm_grid = std::min<int>(Ic, ctx->num_cus * 32);
+    if (pearson)
+        k_item_norms<true><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), nullptr, nullptr, nullptr, J->centre.get(), J->cnorm.get());
+    else
+        k_item_norms<false><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), nullptr, nullptr, euclidean ? sumsq.get() : nullptr, nullptr,
+                                                       nullptr);
+    FY_KERNEL_CHECK();
+    if (finishes) {
+        k_isim_rank_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), euclidean ? sumsq.get() : nullptr, J->aux.get());
+        FY_KERNEL_CHECK();
+    }
+    if (cosine) {
+        k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), norm.get(), J->inv_norm.get());
+        FY_KERNEL_CHECK();
+    }
+    if (pearson) {
+        k_isim_req_pearson_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csr_idx.get(), P.csr_r.get(), P.rank_pair.get(), J->centre.get(), J->cnorm.get(),
+                                                                   J->csr_w.get());
+        FY_KERNEL_CHECK();
+        k_isim_req_pearson_unit<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), J->cnorm.get(), J->inv_norm.get());
+        FY_KERNEL_CHECK();
+    }
+    // the request kernel's column chunks and every user's row offsets at their boundaries
+    // (FY_ISIM_REQ_CHUNK is the widest chunk; the chunks of a row are balanced: ML-25M shape, 59 047 columns = 8 chunks of 7424, whose
+    // 58 KiB of accumulators + 16 KiB of candidates + 1 KiB of static LDS let two workgroups share a CU -- at the full 8192 only one fits)
+    J->nch = (int32_t)ceil_div(Ic, std::min<int64_t>(ctx->tune.isim_req_chunk, round_up(Ic, 64)));
+    J->CH = (int32_t)round_up(ceil_div(Ic, J->nch), 64);
+    J->choff.alloc(ctx, (size_t)P.nU * (size_t)(J->nch + 1));
+    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), 0, P.nU, J->CH, J->nch, J->choff.get());
+    DevBuf<long long> d_walk(ctx, Ic);
+    k_isim_req_walk<<<grid_for((int64_t)Ic * 64, 256), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.rowptr.get(), d_walk.get());
+    FY_KERNEL_CHECK();
+    // host mirrors a request is planned from: raw ids ascending -> popularity rank, the walk per rank; and the bound of every row's
+    // entries for the fixed-point scale: |d_ji| <= ||w_.j|| ||w_.i|| (Cauchy-Schwarz) <= ||w_.j|| max_i ||w_.i||, which is
+    // n_j for the count measures (w = 1, d_ji <= n_j) and 1 for Pearson's normalised columns
+    std::vector<int32_t> raw((size_t)Ic), rank_pair((size_t)Ic), pair_start((size_t)Ic + 1);
+    std::vector<double> h_norm((size_t)Ic), h_bound((size_t)Ic);
+    J->walk.resize((size_t)Ic);
+    d2h(ctx, raw.data(), P.rank_item_raw.get(), (size_t)Ic);
+    d2h(ctx, rank_pair.data(), P.rank_pair.get(), (size_t)Ic);
+    d2h(ctx, pair_start.data(), P.pair_start.get(), (size_t)Ic + 1);
+    d2h(ctx, h_norm.data(), norm.get(), (size_t)Ic);
+    d2h(ctx, J->walk.data(), d_walk.get(), (size_t)Ic);
+    sync(ctx);
+    std::vector<std::pair<int32_t, int32_t>> by_raw((size_t)Ic);
+    for (int32_t r = 0; r < Ic; r++) by_raw[(size_t)r] = {raw[(size_t)r], r};
+    std::sort(by_raw.begin(), by_raw.end());
+    J->raw_sorted.resize((size_t)Ic);
+    J->rank_of_sorted.resize((size_t)Ic);
+    for (int32_t k = 0; k < Ic; k++) { J->raw_sorted[(size_t)k] = by_raw[(size_t)k].first; J->rank_of_sorted[(size_t)k] = by_raw[(size_t)k].second; }
+    const bool weight_is_rating = isim_weight_is_rating(measure);
+    double max_norm = 0.0;
+    for (double x : h_norm) max_norm = std::max(max_norm, x);
+    for (int32_t r = 0; r < Ic; r++) {
+        const int32_t pr = rank_pair[(size_t)r];
+        h_bound[(size_t)r] = pearson ? 1.0 : weight_is_rating ? h_norm[(size_t)pr] * max_norm : (double)(pair_start[(size_t)pr + 1] - pair_start[(size_t)pr]);
+    }
+    J->bound.alloc(ctx, Ic);
+    h2d(ctx, J->bound.get(), h_bound.data(), (size_t)Ic);
+    sync(ctx);      // the host sources of the upload and the scratch of this function go away
+    return J.release();
 }
 
 }  // namespace fy

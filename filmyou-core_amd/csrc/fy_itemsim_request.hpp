@@ -1,0 +1,31 @@
+// fy_itemsim_request.hpp -- the prepared item-similarity job (fy_itemsim_prepare: fy_itemsim.hip) and its request pass
+// (fy_itemsim_rows: fy_itemsim_request.hip).
+#pragma once
+#include <vector>
+
+#include "fy_prep.hpp"
+#include "fy_rm2.hpp"
+
+// Everything the similarity job derives from the ratings and the parameters alone.  The job owns its buffers: nothing hangs on
+// the fy_ratings object, which may be destroyed after prepare.  A request only reads it.
+struct fy_itemsim_job {
+    fy::Context* ctx = nullptr;
+    fy_itemsim_params prm{};
+    fy::Prepared P;                    // one-cluster structure after the input preparation (nnz == 0: nothing else is filled)
+    int32_t CH = 0, nch = 0;           // column chunk of the request kernel (FY_ISIM_REQ_CHUNK at prepare) and chunks per row
+    fy::DevBuf<int32_t> choff;         // [nU * (nch + 1)]: first entry of a user's CSR row inside every chunk (build_chunk_offsets)
+    // per item in rank order
+    fy::DevBuf<double> inv_norm;       // cosine: 1 / ||r_.i||; Pearson: 1 (NaN for a constant item); else unused
+    fy::DevBuf<double> aux;            // the finishing measures' a_i (k_isim_rank_norms)
+    fy::DevBuf<double> bound;          // >= |d| of every entry of the item's row: the fixed-point scale of the row
+    // Pearson: per item in pair order, and the centred, normalised preference per CSR entry (0 on a constant item)
+    fy::DevBuf<double> centre, cnorm, csr_w;
+    // host: raw item ids ascending with their popularity rank, and per rank the sum of the raters' degrees
+    std::vector<int32_t> raw_sorted, rank_of_sorted;
+    std::vector<long long> walk;
+};
+
+namespace fy {
+fy_itemsim_job* itemsim_prepare(Context*, const fy_itemsim_params*, const fy_ratings*);
+fy_result* itemsim_rows(fy_itemsim_job*, const fy_itemsim_request*);
+}  // namespace fy

@@ -75,6 +75,10 @@ struct Tuning {
     int isim_capg = 2040;              // candidates a row of the band sweep may collect before it is redone exactly (<= 2040: k_isim_finish sorts them in LDS)
     int isim_piece = 4096;             // columns per piece of the band sweep (measured, ML-25M shape, build ms: 2048 11.90, 4096 11.90, 8192 12.2, 16384 12.0, 32768 12.5, 65536 14.1)
     int isim_acc32 = 1;                // 32-bit fixed-point accumulators in the symmetric build's walk when the products are exact integers
+    // item similarity on request (fy_itemsim_request.hip); neither changes a result
+    int isim_req_chunk = 8192;         // FY_ISIM_REQ_CHUNK: most columns (64-bit LDS accumulators) a workgroup of the row kernel owns (a row's chunks are balanced); read at fy_itemsim_prepare,
+                                       // which keeps the row offsets for this width
+    int isim_req_rows = 0;             // FY_ISIM_REQ_ROWS: rows per batch of a request (0 = as many as the partial lists of workspace_default hold)
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -324,11 +324,17 @@ class Recommendations(_Result):
 class ItemSimilarities(_Result):
     """Rows of the similarity matrix: (item, other item, similarity), grouped by item, best first."""
 
-    def __init__(self, handle, ctx=None):
+    def __init__(self, handle, ctx=None, request=False):
         super().__init__(handle, ctx)
         self.stats = self._stats()
         self.size = self._lib.fy_result_size(handle)
         self._rows = None
+        # request=True (a result of fy_itemsim_rows): what the request touched; None on the result of a full build
+        self.request_stats = None
+        if request:
+            rq = _native.ItemSimRequestStats()
+            _check(self._lib.fy_result_itemsim_request_stats(handle, C.byref(rq)))
+            self.request_stats = rq.as_dict()
 
     def rows(self):
         if self._rows is None:
@@ -723,18 +729,58 @@ class RowSimilarityJob:
     def __init__(self, ctx=None):
         self.ctx = ctx
 
+    @staticmethod
+    def _params(similarityClassname, maxSimilaritiesPerRow, excludeSelfSimilarity, threshold, rank, world, minPrefsPerUser, maxPrefsPerUser):
+        return _native.ItemSimParams(similarity_id(similarityClassname), int(maxSimilaritiesPerRow),
+                                     1 if excludeSelfSimilarity else 0, 0 if threshold is None else 1,
+                                     0.0 if threshold is None else float(threshold), int(rank), int(world), 0,
+                                     int(minPrefsPerUser), 0 if maxPrefsPerUser is None else int(maxPrefsPerUser))
+
+    def prepare(self, ratings, similarityClassname=SIMILARITY_COSINE, maxSimilaritiesPerRow=100,
+                excludeSelfSimilarity=True, threshold=None, rank=0, world=1, minPrefsPerUser=1, maxPrefsPerUser=None):
+        """fy_itemsim_prepare: everything the job derives from the ratings and these options alone, once (O(nnz)); the options
+        mean what they mean for ``run``.  Returns a ``PreparedItemSimilarity`` whose ``rows(ids)`` answers requests for the
+        rows of named items.  ``ratings`` (a ``Ratings`` or a triple of arrays) may be closed afterwards."""
+        lib = _native.load()
+        p = self._params(similarityClassname, maxSimilaritiesPerRow, excludeSelfSimilarity, threshold, rank, world, minPrefsPerUser,
+                         maxPrefsPerUser)
+        ctx = self.ctx or Context(0)
+        self.ctx = ctx
+        own_ratings = not isinstance(ratings, Ratings)
+        r = Ratings(ctx, *ratings) if own_ratings else ratings
+        job = C.c_void_p()
+        try:
+            try:
+                ctx.sync_tuning()
+                _check(lib.fy_itemsim_prepare(ctx._h, C.byref(p), r._h, C.byref(job)))
+            except FilmYouError as e:
+                raise RuntimeError("%s failed!: %s" % (self.JOB_NAME, e.message)) from e
+            return PreparedItemSimilarity(job, ctx)
+        finally:
+            if own_ratings:
+                r.close()
+
     def run(self, ratings, similarityClassname=SIMILARITY_COSINE, maxSimilaritiesPerRow=100,
-            excludeSelfSimilarity=True, threshold=None, rank=0, world=1, minPrefsPerUser=1, maxPrefsPerUser=None):
+            excludeSelfSimilarity=True, threshold=None, rank=0, world=1, minPrefsPerUser=1, maxPrefsPerUser=None, itemsFile=None):
         """minPrefsPerUser / maxPrefsPerUser: the input preparation in front of the similarity job
         (BaselinePreparePreferenceMatrixJob.java:104, 126-129).  Users with fewer preferences than minPrefsPerUser are
         dropped (reference default 1).  maxPrefsPerUser = the reference's maxPrefsPerUserInItemSimilarity (its default 1000 draws
         a RANDOM sample in Mahout's ToItemVectorsMapper); here None = no cap, a number = a DETERMINISTIC systematic sample
-        (include/filmyou.h) -- no parity with any particular Mahout run."""
+        (include/filmyou.h) -- no parity with any particular Mahout run.
+        itemsFile: a path of one item id per line (read_id_file) or an integer array: the rows of these items alone, with the
+        work sized by the request (prepare + PreparedItemSimilarity.rows); None = the whole matrix."""
+        if itemsFile is not None:
+            # read before any device work (an array goes to rows() as it is: ids outside int32 are dropped there, not wrapped)
+            items = read_id_file(itemsFile) if isinstance(itemsFile, (str, bytes, os.PathLike)) else np.asarray(itemsFile)
+            prepared = self.prepare(ratings, similarityClassname, maxSimilaritiesPerRow, excludeSelfSimilarity, threshold, rank, world,
+                                    minPrefsPerUser, maxPrefsPerUser)
+            try:
+                return prepared.rows(items)
+            finally:
+                prepared.close()
         lib = _native.load()
-        p = _native.ItemSimParams(similarity_id(similarityClassname), int(maxSimilaritiesPerRow),
-                                  1 if excludeSelfSimilarity else 0, 0 if threshold is None else 1,
-                                  0.0 if threshold is None else float(threshold), int(rank), int(world), 0,
-                                  int(minPrefsPerUser), 0 if maxPrefsPerUser is None else int(maxPrefsPerUser))
+        p = self._params(similarityClassname, maxSimilaritiesPerRow, excludeSelfSimilarity, threshold, rank, world, minPrefsPerUser,
+                         maxPrefsPerUser)
         ctx = self.ctx or Context(0)
         self.ctx = ctx
         own_ratings = not isinstance(ratings, Ratings)
@@ -750,6 +796,46 @@ class RowSimilarityJob:
         finally:
             if own_ratings:
                 r.close()
+
+
+class PreparedItemSimilarity:
+    """A prepared item-similarity job (fy_itemsim_job): the structure of the ratings, the per-item norms and the request
+    kernel's row offsets are in HBM; the ratings object it was made from is no longer needed."""
+
+    def __init__(self, handle, ctx):
+        self._lib = _native.load()
+        self._h = handle
+        self._ctx = ctx
+
+    def rows(self, ids):
+        """fy_itemsim_rows: the rows the full build would emit for the listed raw item ids (any order, duplicates and unknown
+        ids passed over), with the work sized by the request.  Any number of calls; the job stays as it was.  Returns an
+        ``ItemSimilarities`` with ``request_stats`` beside ``stats``."""
+        ids = np.asarray(ids).reshape(-1)
+        if ids.dtype != np.int32:      # an id outside int32 is outside the data: passed over, never wrapped into range (as read_id_file does)
+            ids = np.asarray(ids, dtype=np.int64) if len(ids) else np.zeros(0, dtype=np.int64)
+            ids = ids[(ids >= -2 ** 31) & (ids < 2 ** 31)]
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        rq = _native.ItemSimRequest(len(ids), ids.ctypes.data if len(ids) else None)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            _check(self._lib.fy_itemsim_rows(self._h, C.byref(rq), C.byref(res)))
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (RowSimilarityJob.JOB_NAME, e.message)) from e
+        return ItemSimilarities(res, self._ctx, request=True)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._ctx._h:
+                self._lib.fy_itemsim_job_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ClusterAssignmentJob:

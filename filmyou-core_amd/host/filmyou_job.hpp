@@ -352,6 +352,47 @@ class RowSimilarityJob {
         fy_result_free(res);
         return 0;
     }
+    // The rows of the listed items alone (Mahout's ItemBasedRecommender.mostSimilarItems, one row each): fy_itemsim_prepare, one
+    // fy_itemsim_rows request, everything released.  Unknown and repeated ids are passed over.  requestStats: what the request touched.
+    fy_itemsim_request_stats requestStats{};
+    int runItems(const Ratings& r, std::vector<int32_t> items, const std::string& similarityClassname, int maxSimilaritiesPerRow,
+                 bool excludeSelfSimilarity, const double* threshold, const SimilaritySink& sink, int device = 0) {
+        fy_itemsim_params p{};
+        p.similarity = similarityId(similarityClassname);
+        p.max_similarities_per_item = maxSimilaritiesPerRow;
+        p.exclude_self = excludeSelfSimilarity ? 1 : 0;
+        p.has_threshold = threshold ? 1 : 0;
+        p.threshold = threshold ? *threshold : 0.0;
+        p.rank = 0;
+        p.world = 1;
+        fy_context* ctx = nullptr;
+        fy_ratings* rt = nullptr;
+        fy_itemsim_job* job = nullptr;
+        fy_result* res = nullptr;
+        auto release = [&]() {
+            fy_result_free(res);
+            fy_itemsim_job_destroy(job);
+            fy_ratings_destroy(rt);
+            fy_context_destroy(ctx);
+        };
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("RowSimilarityJob failed!: ") + what + ": " + fy_last_error();
+            release();
+            throw std::runtime_error(msg);
+        };
+        if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+        if (fy_ratings_create(ctx, (int64_t)r.user.size(), r.user.data(), r.item.data(), r.score.data(), FY_HOST, &rt) != FY_OK) fail("ratings");
+        if (fy_itemsim_prepare(ctx, &p, rt, &job) != FY_OK) fail("prepare");
+        const fy_itemsim_request rq{(int64_t)items.size(), items.empty() ? nullptr : items.data()};
+        if (fy_itemsim_rows(job, &rq, &res) != FY_OK) fail("rows");
+        const int64_t n = fy_result_size(res);
+        const int32_t *a = fy_result_key0(res), *b = fy_result_key1(res);
+        const float* s = fy_result_value(res);
+        for (int64_t k = 0; k < n; k++) sink(a[k], b[k], s[k]);
+        fy_result_itemsim_request_stats(res, &requestStats);
+        release();
+        return 0;
+    }
 };
 
 // Item-based CF from the similarity phase on (M/baselinerecommender/BaselineRecommenderJob.java:179-328), with the job's option

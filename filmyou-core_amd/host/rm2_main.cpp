@@ -26,8 +26,35 @@ static int main_files(char** a) {
     return 0;
 }
 
+// rm2_main --similar-items <items.txt> <ratings.txt> <similarityClassname> <K>
+//   : RowSimilarityJob::runItems, the similarity rows of the ids of the items file alone.  Prints "item other sim".
+static int main_similar_items(char** a) {
+    fy::host::Ratings r;
+    FILE* f = fopen(a[1], "r");
+    if (!f) { perror(a[1]); return 2; }
+    int u, i; float s;
+    while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) r.add(u, i, s);
+    fclose(f);
+    int64_t n = 0;
+    int32_t* ids = nullptr;
+    if (fy_idfile_read(a[0], &n, &ids) != FY_OK) { fprintf(stderr, "RowSimilarityJob failed!: %s\n", fy_last_error()); return 1; }
+    std::vector<int32_t> items(ids, ids + n);
+    fy_buffer_free(ids);
+    try {
+        fy::host::RowSimilarityJob job;
+        job.runItems(r, items, a[2], atoi(a[3]), true, nullptr, [](int32_t item, int32_t other, float sim) { printf("%d %d %.9g\n", item, other, sim); });
+        fprintf(stderr, "request items_known %lld rows_emitted %lld batches %lld pair_contribs %lld\n", (long long)job.requestStats.items_known,
+                (long long)job.requestStats.rows_emitted, (long long)job.requestStats.batches, (long long)job.requestStats.pair_contribs);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 9 && strcmp(argv[1], "--files") == 0) return main_files(argv + 2);
+    if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
     bool rccl = false;
     // rm2_main --users <users.txt> <ratings.txt> ... : RM2Job::runUsers, lists for the ids of the usersFile alone
     const char* users_file = nullptr;

@@ -299,6 +299,47 @@ int fy_itemsim_build(fy_context*, const fy_itemsim_params*, const fy_ratings*, f
 int fy_itemsim_run(const fy_itemsim_params*, int64_t nnz, const int32_t* user, const int32_t* item,
                    const float* score, fy_result** out);
 
+/* ------------------------------------------------------------------ item similarity on request: the rows of named items
+ * "Items similar to this one" (Mahout's ItemBasedRecommender.mostSimilarItems) is one row of the similarity matrix.
+ * fy_itemsim_prepare builds, once per ratings object, everything the similarity job derives from the ratings and the parameters
+ * alone (O(nnz)): it validates exactly what fy_itemsim_build validates (same codes, same messages), applies the input
+ * preparation, builds the CSR / CSC, the per-item norms / counts / sum r^2 / Pearson centres (fixed summation order) and the row
+ * offsets of the request kernel's column chunks.  The job owns its buffers; the ratings may be destroyed after prepare.  A job
+ * over an empty preference matrix is valid and answers every request with an empty result.  To follow a write, prepare again on
+ * the new ratings object (fy_ratings_apply).
+ * fy_itemsim_rows answers any number of requests and leaves the job as it was.  The result (a similarity result like
+ * fy_itemsim_build's) holds exactly the rows fy_itemsim_build with the same parameters would emit for the listed items: the
+ * full build's item order (popularity rank), within a row best first, ties by ascending raw item id, exclude_self,
+ * sim >= threshold / sim > 0, NaN dropped, the max_similarities_per_item best.  `items`: HOST array of raw ids in any order; a
+ * duplicate counts once; an id nobody rated, an id outside the data, a negative id and an item lost to the input preparation are
+ * passed over without an error; n_items == 0 gives an empty result; items == NULL with n_items > 0 is
+ * FY_ERR_INVALID_ARGUMENT.  (rank, world) of the parameters: a rank answers only for the requested items whose row its full
+ * build would own (popularity rank % world == rank).
+ * Work: sum over the requested items j of sum over the raters v of j of n_v products; nothing in a request runs over all
+ * ratings or all users.  Values: the dot product d of a pair is accumulated in 64-bit fixed point (scale per row from a bound
+ * of the row's entries; signed contributions add modulo 2^64), so it does not depend on the order of the atomics and two runs
+ * give the same bits; it is exact whenever every product is a multiple of the grid and the sum fits -- half stars, integers,
+ * the count measures.  The weights are the raw preference (cosine, Euclidean distance), 1 (the count measures) or the centred,
+ * normalised preference in fp64 (Pearson); the finish is the full build's fp64 arithmetic.  On half-star or integer preferences
+ * the rows are bitwise the full build's for every measure but Pearson; Pearson, and cosine on preferences that are not
+ * fp16-exact, differ from the full build (whose weights are fp32 there) within the bounds stated above.
+ * fy_result_stats of a request result: n_users (N after the input preparation), n_items, nnz, recs, pair_contribs (below),
+ * cooc_launches (= batches), ms_prepare = 0, ms_cooc (row kernel), ms_topn (merge + compaction), ms_total. */
+typedef struct fy_itemsim_job fy_itemsim_job;
+int fy_itemsim_prepare(fy_context*, const fy_itemsim_params*, const fy_ratings*, fy_itemsim_job** out);
+void fy_itemsim_job_destroy(fy_itemsim_job*);
+typedef struct { int64_t n_items; const int32_t* items; } fy_itemsim_request;   /* HOST, raw item ids, any order */
+int fy_itemsim_rows(fy_itemsim_job*, const fy_itemsim_request*, fy_result** out);
+typedef struct {
+    int64_t items_asked;      /* n_items of the request */
+    int64_t items_known;      /* distinct requested items with a kept preference that this rank answers for */
+    int64_t rows_emitted;     /* of those, the items whose row is not empty */
+    int64_t batches;          /* launches of the row kernel */
+    int64_t pair_contribs;    /* sum over the known items j of sum over the raters v of j of n_v */
+    int64_t chunks;           /* column chunks per row */
+} fy_itemsim_request_stats;
+int fy_result_itemsim_request_stats(fy_result*, fy_itemsim_request_stats* out);   /* FY_ERR_STATE on any other result */
+
 /* ------------------------------------------------------------------ item-based CF recommendation (phases 3-4)
  * Replaces the partialMultiply and aggregateAndRecommend jobs of M/baselinerecommender/BaselineRecommenderJob.java:285-328,
  * 340-393 (reducer M/baselinerecommender/BaselineAggregateAndRecommendReducer.java:97-161, 195-235): prediction(u, i) =
