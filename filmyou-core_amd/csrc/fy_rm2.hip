@@ -1342,7 +1342,7 @@ void launch_topn_rows(Context* ctx, hipStream_t st, const float* S, int64_t ldS,
     if (top_n_hint > TOPN_LONG) k_topn_long<<<n_rows, 256, (size_t)fy_topn_long_cap(top_n_hint) * 8, st>>>(TA, overflow, any_overflow, 0, fy_topn_long_cap(top_n_hint));
     else k_topn_fast<<<n_rows, 256, 0, st>>>(TA, overflow, any_overflow, 0);
     FY_KERNEL_CHECK();
-    k_topn_select<<<n_rows, 256, 0, st>>>(TA, overflow, any_overflow);
+    k_topn_select<<<fy_topn_select_grid(n_rows, ctx->num_cus), 256, 0, st>>>(TA, overflow, any_overflow, n_rows);
     FY_KERNEL_CHECK();
 }
 
@@ -2381,7 +2381,8 @@ static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
                 const size_t ss = X.t_score->begin(st);
                 k_count_heavy_multi<<<(ny + 63) / 64, 64, 0, st>>>(F.d_flat[f].get(), (int32_t)ny);
                 FY_KERNEL_CHECK();
-                if (f) k_score_multi<4, true, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
+                if (f && tune.score_walk) k_score_multi<4, true, 8, 1><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
+                else if (f) k_score_multi<4, true, 8, 0><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
                 else k_score_multi<4, false, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
                 FY_KERNEL_CHECK();
                 X.t_score->end(ss, st);
@@ -2742,7 +2743,8 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
         const int n_slices = score_slices(ctx->num_cus, tune, nb, n_chunks);
         ScoreArgs SA = score_args(L.M.get(), ldm, Ic, X.a_rank + pbase, s0, nb, Sx, ldS, n_slices, n_chunks);
         const size_t ss = X.t_score->begin(ls);
-        if (pack24) k_score<4, true, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+        if (pack24 && tune.score_walk) k_score<4, true, 8, 1><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+        else if (pack24) k_score<4, true, 8, 0><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
         else k_score<4, false, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
         FY_KERNEL_CHECK();
         X.t_score->end(ss, ls);
@@ -2756,7 +2758,7 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
                                                                                                  fy_topn_long_cap(prm.number_of_recommendations));
         else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
         FY_KERNEL_CHECK();
-        k_topn_select<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), X.prune_counters + 2);
+        k_topn_select<<<fy_topn_select_grid(nb, ctx->num_cus), 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), nb, X.prune_counters + 2);
         FY_KERNEL_CHECK();
         X.t_topn->end(tt, ls);
         refine_rows(s0, nb);
@@ -2793,7 +2795,8 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
             L.UBs.alloc(ctx, (size_t)nb * 64);
             SU.Bsup = L.Bsup.get(); SU.asup = L.asup.get(); SU.bsup_b = L.bsupb.get(); SU.UBsup = L.UBs.get();
             SU.n_sup = std::min(64, std::max(0, p.nblk - seed_chunks));
-            k_score_sup<<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
+            if (tune.score_walk) k_score_sup<1><<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
+            else k_score_sup<0><<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
             FY_KERNEL_CHECK();
         }
         ScoreArgs SA = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks + bchunks);
@@ -2807,7 +2810,8 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
         SA.ldS2 = bld;
         SA.no_mask2 = 1;
         if (!use_sup) {
-            k_score<4, true, 8><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+            if (tune.score_walk) k_score<4, true, 8, 1><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+            else k_score<4, true, 8, 0><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
             FY_KERNEL_CHECK();
         }
         // (2) tau_u = N-th best seed score; the sorted seed head is also the user's list unless a block survives
@@ -2918,7 +2922,10 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
         if (n_surv_total > 0) {
             ScoreArgs SQ = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.Ssurv.get(), 0, n_slices, n_chunks);
             const int panel_blocks = p.panel ? p.panel_cols / 256 : 0x7FFFFFFF;
-            k_score_blocks<8><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
+            if (tune.score_walk) k_score_blocks<8, 1><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
+                                                                L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, bld, X.prune_counters, panel_blocks,
+                                                                p.panel ? L.surv_mask.get() : nullptr);
+            else k_score_blocks<8, 0><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
                                                                 L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, bld, X.prune_counters, panel_blocks,
                                                                 p.panel ? L.surv_mask.get() : nullptr);
             FY_KERNEL_CHECK();
@@ -2956,7 +2963,7 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
                                                                                                  fy_topn_long_cap(prm.number_of_recommendations));
         else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
         FY_KERNEL_CHECK();
-        k_topn_select<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), X.prune_counters + 2);
+        k_topn_select<<<fy_topn_select_grid(nb, ctx->num_cus), 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), nb, X.prune_counters + 2);
         FY_KERNEL_CHECK();
         X.t_topn->end(tt, ls);
         refine_rows(s0, nb);

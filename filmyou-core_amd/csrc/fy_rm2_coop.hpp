@@ -169,7 +169,8 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
         SA.S2 = ub_send.get() + (int64_t)k * Umax * ldb;
         SA.ldS2 = ldb;
         SA.no_mask2 = 1;
-        k_score<4, true, 8><<<(seed_chunks + bchunks) * ns, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+        if (tune.score_walk) k_score<4, true, 8, 1><<<(seed_chunks + bchunks) * ns, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
+        else k_score<4, true, 8, 0><<<(seed_chunks + bchunks) * ns, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
         FY_KERNEL_CHECK();
         R->st.score_launches += 2;
     }
@@ -236,7 +237,7 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
         FY_HIP(hipMemsetAsync(any_overflow.get(), 0, sizeof(int32_t), ls));
         k_topn_fast<<<n_mine, 256, 0, ls>>>(TA, overflow.get(), any_overflow.get(), tune.force_select);
         FY_KERNEL_CHECK();
-        k_topn_select<<<n_mine, 256, 0, ls>>>(TA, overflow.get(), any_overflow.get(), X.prune_counters + 2);
+        k_topn_select<<<fy_topn_select_grid(n_mine, ctx->num_cus), 256, 0, ls>>>(TA, overflow.get(), any_overflow.get(), n_mine, X.prune_counters + 2);
         FY_KERNEL_CHECK();
         X.t_topn->end(tt, ls);
     }

@@ -105,6 +105,135 @@ __device__ __forceinline__ void fy_unpack24(const U3& d, float* f) {
     f[3] = __uint_as_float(__builtin_amdgcn_perm(0u, d.c, 0x0302010cu) >> (8 - FY_P24_SHIFT));
 }
 
+// ---------------------------------------------------------------- the row walk of the 24-bit scoring kernels (WALK = 1, FY_SCORE_WALK)
+// The arithmetic of a log term is the one above, to the bit; what differs from the first walk (WALK = 0, kept: the short last batch of
+// a list still takes it) is the bookkeeping around it, which cost a third of the loop's VALU instructions:
+//   * (idx, e, q) of a FULL batch of eight rows are wave-uniform loads of eight consecutive dwords each (s_load_dwordx8), fetched one
+//     batch ahead by the caller -- no vector load + three v_readlane per row.  A full batch lies inside the list, so nothing is read
+//     behind `end` (a list may end the arrays);
+//   * the row's address (base + j * pitch) is scalar arithmetic, the lane adds its constant 32-bit byte offset -- no v_mad_u64_u32;
+//   * the "already rated" mask is found once per list (fy_rated_mask), not tested in every row;
+//   * x = G + a e + q b for two columns at a time (v_pk_fma_f32: the same two fused multiply-adds).
+typedef float fy_v2f __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(1))) unsigned char* fy_gbytes;      // global, not flat
+typedef const __attribute__((address_space(1))) uint32_t* fy_gwords;
+// wave-uniform address of row j of a matrix with `pitch` bytes per row (pitch < 2^32: a row of the dense matrix)
+__device__ __forceinline__ fy_gbytes fy_row_base(const void* M, int j, uint32_t pitch) {
+    const unsigned long long rb = (unsigned long long)M + (unsigned long long)(uint32_t)j * (unsigned long long)pitch;
+    const unsigned long long rs = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rb >> 32)) << 32) |
+                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rb);
+    return reinterpret_cast<fy_gbytes>(rs);
+}
+// Which of the lane's four columns [col0 + 4 lane, col0 + 4 lane + 4) do the rows [beg, end) of a list stand for?  Bit v = column
+// col0 + 4 lane + v, exactly the bits the per-row test of the first walk sets.  `bm` = eight words of LDS that belong to this wave
+// alone: the 256 columns of the chunk as a bitmap, filled by the lanes that hold a hit (ds_or_b32) -- a wave's LDS operations complete
+// in order, so no barrier is needed, only that the compiler keeps the three steps apart.
+__device__ __forceinline__ unsigned fy_rated_mask(const int32_t* __restrict__ csr_idx_, int beg, int end, int row_mul, int row_add, int col0,
+                                                  unsigned* bm, int lane) {
+    if (lane < 8) bm[lane] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    for (int k0 = beg; k0 < end; k0 += 64) {
+        const int k = k0 + lane;
+        if (k < end) {
+            const unsigned d = (unsigned)(csr_idx_[k] * row_mul + row_add - col0);
+            if (d < 256u) atomicOr(&bm[d >> 5], 1u << (d & 31u));
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const unsigned m = (bm[lane >> 3] >> ((lane & 7) * 4)) & 15u;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the next list's zeroes stay behind this read)
+    return m;
+}
+// One FULL batch of eight rows: t[v] += log2 of the product of the eight terms of column v (fy_logprod_step / fy_logprod_fold: one
+// frexp pair per term, the mantissas multiplied in row order, one v_log_f32 per column, folded in fp64).  jj / e / qq are wave-uniform
+// (SGPRs).  live = false: the lane loads nothing and its terms are those of a zero entry (k_score_blocks' dead sub-blocks).
+// SUP && sup_here: the super-block term of the lane rides along (score_body).
+template <bool SUP>
+__device__ __forceinline__ void fy_batch8_p24(const void* M, uint32_t pitch, uint32_t lane_off, bool live, const int (&jj)[8],
+                                              const float (&e)[8], const float (&qq)[8], fy_v2f a01, fy_v2f a23, fy_v2f b01, fy_v2f b23,
+                                              double* t, bool sup_here, const void* Bsup, uint32_t sup_off, float as_, float bs_, double& ts) {
+    U3 g[8];
+    float gs[SUP ? 8 : 1];
+#pragma unroll
+    for (int r = 0; r < 8; r++) g[r] = U3{0u, 0u, 0u};
+    if (live) {      // (one divergent region for the eight loads; score_body passes a constant)
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const fy_gwords gw = reinterpret_cast<fy_gwords>(fy_row_base(M, jj[r], pitch) + lane_off);
+            g[r].a = gw[0]; g[r].b = gw[1]; g[r].c = gw[2];      // one global_load_dwordx3
+        }
+    }
+    if constexpr (SUP) {
+        if (sup_here) {      // (wave-uniform branch)
+#pragma unroll
+            for (int r = 0; r < 8; r++) gs[r] = __uint_as_float(*reinterpret_cast<fy_gwords>(fy_row_base(Bsup, jj[r], 256u) + sup_off));
+        }
+    }
+    fy_v2f p01 = fy_v2f{1.f, 1.f}, p23 = fy_v2f{1.f, 1.f};
+    int pe[4] = {0, 0, 0, 0};
+    float ps = 1.f;
+    int pes = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        if constexpr (SUP) {
+            if (sup_here) fy_logprod_step(fmaf(qq[r], bs_, fmaf(as_, e[r], gs[r])), ps, pes);
+        }
+        float gv[4];
+        fy_unpack24(g[r], gv);
+        const fy_v2f e2 = fy_v2f{e[r], e[r]}, q2 = fy_v2f{qq[r], qq[r]};
+        const fy_v2f x01 = __builtin_elementwise_fma(q2, b01, __builtin_elementwise_fma(a01, e2, fy_v2f{gv[0], gv[1]}));
+        const fy_v2f x23 = __builtin_elementwise_fma(q2, b23, __builtin_elementwise_fma(a23, e2, fy_v2f{gv[2], gv[3]}));
+        p01 *= fy_v2f{__builtin_amdgcn_frexp_mantf(x01.x), __builtin_amdgcn_frexp_mantf(x01.y)};
+        p23 *= fy_v2f{__builtin_amdgcn_frexp_mantf(x23.x), __builtin_amdgcn_frexp_mantf(x23.y)};
+        pe[0] += __builtin_amdgcn_frexp_expf(x01.x);
+        pe[1] += __builtin_amdgcn_frexp_expf(x01.y);
+        pe[2] += __builtin_amdgcn_frexp_expf(x23.x);
+        pe[3] += __builtin_amdgcn_frexp_expf(x23.y);
+    }
+    t[0] += fy_logprod_fold(p01.x, pe[0]);
+    t[1] += fy_logprod_fold(p01.y, pe[1]);
+    t[2] += fy_logprod_fold(p23.x, pe[2]);
+    t[3] += fy_logprod_fold(p23.y, pe[3]);
+    if constexpr (SUP) {
+        if (sup_here) ts += fy_logprod_fold(ps, pes);
+    }
+}
+// The full batches of the rows [beg, end): triplets by scalar loads, one batch ahead.  Returns the first row that is left over (the
+// short last batch, < 8 rows, or `end`): the caller walks it the first way.
+template <bool SUP>
+__device__ __forceinline__ int fy_walk_full_p24(const void* M, uint32_t pitch, uint32_t lane_off, bool live, const int32_t* __restrict__ csr_idx_,
+                                                const float* __restrict__ csr_e_, const float* __restrict__ csr_q_, int beg, int end, fy_v2f a01,
+                                                fy_v2f a23, fy_v2f b01, fy_v2f b23, double* t, bool sup_here, const void* Bsup, uint32_t sup_off,
+                                                float as_, float bs_, double& ts) {
+    int k = __builtin_amdgcn_readfirstlane(beg);      // (wave-uniform by contract; said so where the list's bounds came through a vector load)
+    end = __builtin_amdgcn_readfirstlane(end);
+    if (k + 8 > end) return k;
+    // the three arrays through the constant address space (nothing writes them while a scoring kernel runs): a wave-uniform load from
+    // it is a scalar load wherever it stands -- inside a long loop hipcc otherwise gives up proving that no store reaches the load
+    // and fetches the eight dwords with vector loads
+    typedef const __attribute__((address_space(4))) int32_t* cints;
+    typedef const __attribute__((address_space(4))) float* cfloats;
+    const cints ci = reinterpret_cast<cints>(reinterpret_cast<unsigned long long>(csr_idx_));
+    const cfloats ce = reinterpret_cast<cfloats>(reinterpret_cast<unsigned long long>(csr_e_));
+    const cfloats cq = reinterpret_cast<cfloats>(reinterpret_cast<unsigned long long>(csr_q_));
+    int jj[8], jn[8];
+    float e[8], en[8], qq[8], qn[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) { jj[r] = ci[k + r]; e[r] = ce[k + r]; qq[r] = cq[k + r]; }
+    for (;;) {
+        const bool more = k + 16 <= end;      // (wave-uniform) the next batch is a full one too: it lies inside the list
+        if (more) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) { jn[r] = ci[k + 8 + r]; en[r] = ce[k + 8 + r]; qn[r] = cq[k + 8 + r]; }
+        }
+        fy_batch8_p24<SUP>(M, pitch, lane_off, live, jj, e, qq, a01, a23, b01, b23, t, sup_here, Bsup, sup_off, as_, bs_, ts);
+        k += 8;
+        if (!more) break;
+        for (int r = 0; r < 8; r++) { jj[r] = jn[r]; e[r] = en[r]; qq[r] = qn[r]; }
+    }
+    return k;
+}
+
 // Does a block with upper bound `ub` have to be scored exactly for a user whose N-th best seed score is `tau`?
 // tau = +inf: the user emits nothing; tau = -inf: fewer than N finite seed scores, nothing can be excluded (ties at -inf
 // are broken by item id, so even a block of -inf scores may contribute).
@@ -121,7 +250,7 @@ __device__ __forceinline__ bool fy_bound_keeps(float ub, float tau, float pvpi) 
     return ub + (4e-6f * S + 1e-4f) >= tau;
 }
 
-template <int VEC, bool P24, int SB, bool SUP = false>
+template <int VEC, bool P24, int SB, bool SUP = false, int WALK = 0>
 __device__ __forceinline__ void score_body(const float* __restrict__ M_, const float* __restrict__ a_rank_,
                                            const int32_t* __restrict__ rb_off_, const int32_t* __restrict__ csr_idx_,
                                            const float* __restrict__ csr_e_, const float* __restrict__ csr_q_,
@@ -130,6 +259,7 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
     using V = typename VecT<VEC>::type;
     using G = typename std::conditional<P24, U3, V>::type;   // what one lane loads per row
     static_assert(!P24 || VEC == 4, "24-bit rows are packed four columns to three dwords");
+    static_assert(WALK == 0 || (P24 && SB == 8), "the second walk is that of the 24-bit rows, in batches of eight");
     constexpr int CW = 64 * VEC;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -174,7 +304,7 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
     // logs -- 24 dependent scalar round trips per batch of 8 rows, which is what "bound by scalar-load latency" meant.)
     // All SB row-segment loads are issued before the first use, also for a short tail (out-of-range slots re-load the last valid
     // row -- an L1 hit -- and are skipped by a wave-uniform test).
-    auto walk = [&](int beg, int end, double* t, unsigned& mask, double& ts) __attribute__((always_inline)) {
+    auto walk = [&](int beg, int end, double* t, unsigned& mask, double& ts, const bool do_mask) __attribute__((always_inline)) {
         if (beg >= end) return;
         static_assert(SB <= 64, "one lane per row of a batch");
         const int sub = lane & (SB - 1);     // (SB is a power of two)
@@ -229,7 +359,7 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
 #pragma unroll
                     for (int v = 0; v < VEC; v++) fy_logprod_step(fmaf(qq[q], bb[v], fmaf(a[v], e[q], gv[v])), p[v], pe[v]);
                     const unsigned d = (unsigned)(jj[q] * row_mul + A.row_add - col0);
-                    if (!no_mask && d < (unsigned)CW && (int)(d / VEC) == lane) mask |= 1u << (d % VEC);
+                    if (do_mask && !no_mask && d < (unsigned)CW && (int)(d / VEC) == lane) mask |= 1u << (d % VEC);
                 }
             }
 #pragma unroll
@@ -238,6 +368,21 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
                 if (sup_here) ts += fy_logprod_fold(ps, pes);
             }
             vi = vi_n; ve = ve_n; vq = vq_n;
+        }
+    };
+    // WALK = 1 (see fy_batch8_p24): the mask once per list, the full batches from scalar loads, the short last batch as above
+    __shared__ unsigned sh_bm[WALK ? 4 : 1][8];
+    auto walk_rows = [&](int beg, int end, double* t, unsigned& mask, double& ts) __attribute__((always_inline)) {
+        if constexpr (WALK == 0) walk(beg, end, t, mask, ts, true);
+        else {
+            if (beg >= end) return;
+            if (!no_mask) mask |= fy_rated_mask(csr_idx_, beg, end, row_mul, A.row_add, col0, sh_bm[wave], lane);
+            fy_v2f a01, a23, b01, b23;
+            a01.x = a[0]; a01.y = a[1]; a23.x = a[2]; a23.y = a[3];
+            b01.x = bb[0]; b01.y = bb[1]; b23.x = bb[2]; b23.y = bb[3];
+            const int k = fy_walk_full_p24<SUP>(Msel, (uint32_t)pitch, (uint32_t)col * 3u, true, csr_idx_, csr_e_, csr_q_, beg, end, a01, a23, b01, b23, t,
+                                                sup_here, A.Bsup, (uint32_t)lane * 4u, as_, bs_, ts);
+            walk(k, end, t, mask, ts, false);
         }
     };
     auto store = [&](int u, int slot, const double* t, unsigned mask) __attribute__((always_inline)) {
@@ -275,7 +420,7 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
         for (int v = 0; v < VEC; v++) t[v] = 0.0;
         unsigned mask = 0;
         double ts = 0.0;
-        walk(wb, we, t, mask, ts);
+        walk_rows(wb, we, t, mask, ts);
         if (wave > 0) {
 #pragma unroll
             for (int v = 0; v < VEC; v++) sh_t[wave - 1][lane][v] = t[v];
@@ -305,7 +450,7 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
         for (int v = 0; v < VEC; v++) t[v] = 0.0;
         unsigned mask = 0;
         double ts = 0.0;
-        walk(beg, end, t, mask, ts);
+        walk_rows(beg, end, t, mask, ts);
         store(u, slot, t, mask);
         store_sup(u, slot, ts);
     }
@@ -313,22 +458,23 @@ __device__ __forceinline__ void score_body(const float* __restrict__ M_, const f
 // (Round 4 held the register allocator to 64 VGPRs -- eight waves per SIMD instead of the seven that its 68 allow -- with
 // amdgpu_waves_per_eu(8, 8): 6.19 against 6.14 ms for the scoring family, nothing; the kernel sits at the gather rate of the cache
 // hierarchy, not at its occupancy.)
-template <int VEC, bool P24, int SB>
+template <int VEC, bool P24, int SB, int WALK = 0>
 __global__ __launch_bounds__(256) void k_score(const float* __restrict__ M_, const float* __restrict__ a_rank_,
                                                const int32_t* __restrict__ rb_off_, const int32_t* __restrict__ csr_idx_,
                                                const float* __restrict__ csr_e_, const float* __restrict__ csr_q_,
                                                const double* __restrict__ pvpi_,
                                                const int32_t* __restrict__ n_out_, float* __restrict__ S_, ScoreArgs A) {
-    score_body<VEC, P24, SB>(M_, a_rank_, rb_off_, csr_idx_, csr_e_, csr_q_, pvpi_, n_out_, S_, A, (int)blockIdx.x);
+    score_body<VEC, P24, SB, false, WALK>(M_, a_rank_, rb_off_, csr_idx_, csr_e_, csr_q_, pvpi_, n_out_, S_, A, (int)blockIdx.x);
 }
 
 // the seed pass of the one-cluster pruned job with the super-block bounds riding along (score_body<..., SUP = true>)
+template <int WALK>
 __global__ __launch_bounds__(256) void k_score_sup(const float* __restrict__ M_, const float* __restrict__ a_rank_,
                                                    const int32_t* __restrict__ rb_off_, const int32_t* __restrict__ csr_idx_,
                                                    const float* __restrict__ csr_e_, const float* __restrict__ csr_q_,
                                                    const double* __restrict__ pvpi_,
                                                    const int32_t* __restrict__ n_out_, float* __restrict__ S_, ScoreArgs A) {
-    score_body<4, true, 8, true>(M_, a_rank_, rb_off_, csr_idx_, csr_e_, csr_q_, pvpi_, n_out_, S_, A, (int)blockIdx.x);
+    score_body<4, true, 8, true, WALK>(M_, a_rank_, rb_off_, csr_idx_, csr_e_, csr_q_, pvpi_, n_out_, S_, A, (int)blockIdx.x);
 }
 
 // ================================================================ top-N (PriorityQueue + poll loop, AbstractRM2Reducer.java:325, 358-369)
@@ -949,9 +1095,20 @@ __device__ __forceinline__ void topn_select_body(const TopNArgs& A, const int32_
         A.out_cluster[off + i] = A.cluster;
     }
 }
+// A grid of at most fy_topn_select_grid() workgroups that strides over the users.  With one workgroup per user (until round 4) a launch
+// in which NOBODY had overflowed -- the usual case -- still had to place n_rows workgroups of 44 KB of LDS each between another lane's
+// scoring workgroups only to see them leave at once: 8.2 ms per cluster at 50 clusters x N = 1000 (profiles/r4/k50_n1000_summary_trace.txt:
+// 408 ms of lane time per job for 0 selected users).  44 KB never let more than three of them run on a CU, so the users that DO overflow
+// (massive ties) lose nothing.
+inline int fy_topn_select_grid(int n_rows, int num_cus) { return n_rows < 2 * num_cus ? n_rows : 2 * num_cus; }
 __global__ __launch_bounds__(256) void k_topn_select(TopNArgs A, const int32_t* __restrict__ overflow,
-                                                     const int32_t* __restrict__ any_overflow, unsigned long long* __restrict__ n_selected = nullptr) {
-    topn_select_body(A, overflow, any_overflow, n_selected, (int)blockIdx.x);
+                                                     const int32_t* __restrict__ any_overflow, int n_rows,
+                                                     unsigned long long* __restrict__ n_selected = nullptr) {
+    if (*any_overflow == 0) return;                  // (block-uniform, and the same for every workgroup of the launch)
+    for (int u = (int)blockIdx.x; u < n_rows; u += (int)gridDim.x) {
+        topn_select_body(A, overflow, any_overflow, n_selected, u);     // (its early exits are block-uniform)
+        __syncthreads();                             // the body's LDS arrays are free again
+    }
 }
 
 // ================================================================ many small clusters in ONE launch per kernel ("flat batch")
@@ -978,14 +1135,14 @@ __global__ void k_count_heavy_multi(const FlatDesc* __restrict__ D, int32_t n) {
     *d.n_heavy = lo;
     *d.any_overflow = 0;
 }
-template <int VEC, bool P24, int SB>
+template <int VEC, bool P24, int SB, int WALK = 0>
 __global__ __launch_bounds__(256) void k_score_multi(const FlatDesc* __restrict__ D, const int32_t* __restrict__ csr_idx_,
                                                      const float* __restrict__ csr_e_, const float* __restrict__ csr_q_,
                                                      const double* __restrict__ pvpi_, const int32_t* __restrict__ n_out_) {
     const FlatDesc& d = D[blockIdx.y];
     if ((int)blockIdx.x >= d.score_grid) return;
     const ScoreArgs A = d.SA;
-    score_body<VEC, P24, SB>(A.M, A.a_rank, A.rb_off, csr_idx_, csr_e_, csr_q_, pvpi_, n_out_, A.S, A, (int)blockIdx.x);
+    score_body<VEC, P24, SB, false, WALK>(A.M, A.a_rank, A.rb_off, csr_idx_, csr_e_, csr_q_, pvpi_, n_out_, A.S, A, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_topn_fast_multi(const FlatDesc* __restrict__ D, int force_select) {
     const FlatDesc& d = D[blockIdx.y];
@@ -1024,7 +1181,7 @@ __global__ void k_block_amax(int32_t Ic, int32_t ldb, const float* __restrict__ 
 // One WORKGROUP = one (user, surviving block): its four waves split the user's rated items into quarters and their partial
 // log-sums are added in wave order (fixed, so the result is reproducible).  Survivors belong to the heaviest users -- a
 // single wave walked thousands of rows in dependent batches of 8 and the pass ended on a handful of such waves.
-template <int SB>
+template <int SB, int WALK = 0>
 __global__ __launch_bounds__(256) void k_score_blocks(const float* __restrict__ M_, const float* __restrict__ a_rank_,
                                                       const int32_t* __restrict__ rowptr_, const int32_t* __restrict__ csr_idx_,
                                                       const float* __restrict__ csr_e_, const float* __restrict__ csr_q_,
@@ -1035,6 +1192,8 @@ __global__ __launch_bounds__(256) void k_score_blocks(const float* __restrict__ 
                                                       const uint8_t* __restrict__ surv_mask_ = nullptr) {
     __shared__ double sh_t[3][64][4];
     __shared__ unsigned sh_mask[3][64];
+    __shared__ unsigned sh_bm[WALK ? 4 : 1][8];
+    static_assert(WALK == 0 || SB == 8, "the second walk runs in batches of eight");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int total = surv_prefix_[A.n_users];
@@ -1067,9 +1226,21 @@ __global__ __launch_bounds__(256) void k_score_blocks(const float* __restrict__ 
         const char* __restrict__ Mcol = reinterpret_cast<const char*>(M_) + (int64_t)col * 3;
         const int row_beg = rowptr_[slot], row_end = rowptr_[slot + 1];
         const int quarter = (((row_end - row_beg + 3) >> 2) + SB - 1) / SB * SB;   // whole batches per wave
-        const int beg = min(row_end, row_beg + wave * quarter), end = min(row_end, beg + quarter);
+        int beg = min(row_end, row_beg + wave * quarter);
+        const int end = min(row_end, beg + quarter);
         double t[4] = {0.0, 0.0, 0.0, 0.0};
         unsigned mask = 0;
+        if constexpr (WALK != 0) {      // (see fy_batch8_p24) the mask once per quarter, its full batches from scalar loads; the loop below is left the short last batch
+            if (beg < end) {
+                mask = fy_rated_mask(csr_idx_, beg, end, 1, 0, col0, sh_bm[wave], lane);
+                fy_v2f a01, a23, b01, b23;
+                a01.x = a[0]; a01.y = a[1]; a23.x = a[2]; a23.y = a[3];
+                b01.x = bb[0]; b01.y = bb[1]; b23.x = bb[2]; b23.y = bb[3];
+                double ts_unused = 0.0;
+                beg = fy_walk_full_p24<false>(M_, (uint32_t)pitch, (uint32_t)col * 3u, live, csr_idx_, csr_e_, csr_q_, beg, end, a01, a23, b01, b23, t, false,
+                                              nullptr, 0u, 0.f, 0.f, ts_unused);
+            }
+        }
         // (idx, e, q) of a batch by three vector loads, one batch ahead, handed out with v_readlane: see k_score's walk
         const int sub = lane & (SB - 1);
         int vi = 0, vi_n;
@@ -1104,7 +1275,7 @@ __global__ __launch_bounds__(256) void k_score_blocks(const float* __restrict__ 
 #pragma unroll
                     for (int v = 0; v < 4; v++) fy_logprod_step(fmaf(qq[x], bb[v], fmaf(a[v], e[x], gv[v])), p[v], pe[v]);
                     const unsigned d = (unsigned)(jj[x] - col);
-                    if (d < 4u) mask |= 1u << d;
+                    if (WALK == 0 && d < 4u) mask |= 1u << d;
                 }
             }
 #pragma unroll

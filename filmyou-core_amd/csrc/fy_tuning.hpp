@@ -49,6 +49,7 @@ struct Tuning {
     bool bounded_tables = true;        // FY_BOUNDED_TABLES=0: exact table sizes (two host round trips per table)
     bool cooc_planes = true;           // FY_COOC_PLANES=0: linear accumulator layout (measurement only)
     int score_heavy = 512;             // users with more ratings are walked by a whole workgroup of the scoring kernel (0 = off)
+    int score_walk = 1;                // FY_SCORE_WALK=0: the 24-bit scoring kernels walk every batch the first way (v_readlane triplets, a mask test per row); same bits, measurement and parity tests only
     bool panel_repair = true;          // FY_PANEL_REPAIR=0: measurement only
     int panel_lanes = 2;               // job lanes when clusters run in panel mode (measured, 50 clusters: 1 lane 300 ms, 2: 213, 3: 230, 4: 240)
     int64_t flat_budget = 0;           // FY_FLAT_BUDGET_MB: bytes of matrices + score rows one flat batch may hold (0 = a quarter of the HBM, at most the workspace)
