@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp"]  # fy_itemcf.hip uses fy_prep.hpp / fy_rm2.hpp
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -22,7 +22,7 @@ SYMBOLS = [
     "fy_abi_version", "fy_last_error", "fy_context_create", "fy_context_destroy", "fy_context_synchronize", "fy_context_reload_tuning", "fy_context_inject_alloc_failure",
     "fy_context_stream", "fy_ratings_create", "fy_ratings_destroy", "fy_ratings_nnz", "fy_ratings_drop_cache", "fy_ratings_apply", "fy_ratings_copy_out", "fy_rm2_prepare",
     "fy_rm2_partial_stats", "fy_rm2_stats_layout", "fy_rm2_set_global_stats", "fy_rm2_set_collectives", "fy_rccl_unique_id", "fy_rccl_create", "fy_rccl_collectives", "fy_rccl_counters", "fy_rccl_destroy", "fy_rccl_detach_context", "fy_rm2_score", "fy_rm2_score_users", "fy_result_request_stats", "fy_rm2_job_destroy", "fy_rm2_run",
-    "fy_itemsim_build", "fy_itemsim_run", "fy_itemsim_prepare", "fy_itemsim_job_destroy", "fy_itemsim_rows", "fy_result_itemsim_request_stats", "fy_itemcf_recommend", "fy_itemcf_recommend_filtered", "fy_ratings_shifted", "fy_itemsim_pairs",
+    "fy_itemsim_build", "fy_itemsim_run", "fy_itemsim_prepare", "fy_itemsim_job_destroy", "fy_itemsim_rows", "fy_result_itemsim_request_stats", "fy_itemcf_recommend", "fy_itemcf_recommend_filtered", "fy_itemcf_recommend_prepared", "fy_result_itemcf_request_stats", "fy_itemsim_job_drop_rows", "fy_ratings_shifted", "fy_itemsim_pairs",
     "fy_simpairs_write_text", "fy_idfile_read", "fy_cluster_assign", "fy_nmf_factorize", "fy_result_size", "fy_result_key0", "fy_result_key1", "fy_result_value",
     "fy_result_aux", "fy_result_n_users", "fy_result_user_id", "fy_result_user_sum", "fy_result_n_items",
     "fy_result_item_id", "fy_result_item_coll", "fy_result_total_sum", "fy_result_free", "fy_result_stats",
@@ -183,6 +183,14 @@ class ItemSimRequestStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ItemCFRequestStats(C.Structure):
+    _fields_ = [("users_asked", C.c_int64), ("users_known", C.c_int64), ("items_needed", C.c_int64), ("rows_built", C.c_int64),
+                ("rows_from_store", C.c_int64), ("rows_stored", C.c_int64), ("pair_contribs", C.c_int64), ("batches", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RatingsUpdateStats(C.Structure):
     _fields_ = [("n_writes", C.c_int64), ("n_superseded", C.c_int64), ("n_replaced", C.c_int64), ("n_inserted", C.c_int64),
                 ("n_deleted", C.c_int64), ("n_delete_missed", C.c_int64), ("n_source_dropped", C.c_int64), ("nnz_out", C.c_int64)]
@@ -279,6 +287,10 @@ def load():
     L.fy_result_itemsim_request_stats.argtypes = [vp, C.POINTER(ItemSimRequestStats)]
     L.fy_itemcf_recommend.argtypes = [vp, C.POINTER(ItemCFParams), vp, vp, pvp]
     L.fy_itemcf_recommend_filtered.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFFilter), vp, vp, pvp]
+    L.fy_itemcf_recommend_prepared.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFFilter), pvp]
+    L.fy_result_itemcf_request_stats.argtypes = [vp, C.POINTER(ItemCFRequestStats)]
+    L.fy_itemsim_job_drop_rows.argtypes = [vp]
+    L.fy_itemsim_job_drop_rows.restype = None
     L.fy_ratings_shifted.argtypes = [vp, vp, C.c_float, pvp]
     L.fy_itemsim_pairs.argtypes = [vp, vp, pvp]
     for name, rt in (("size", i64), ("key0", vp), ("key1", vp), ("value", vp), ("aux", vp), ("n_users", i64),

@@ -11,6 +11,7 @@
 #include "fy_ratings_update.hpp"
 #include "fy_rm2_request.hpp"
 #include "fy_itemsim_request.hpp"
+#include "fy_itemcf_request.hpp"
 
 namespace fy {
 static thread_local char g_err[512] = "";
@@ -471,6 +472,22 @@ int fy_itemcf_recommend_filtered(fy_context* c, const fy_itemcf_params* p, const
     FY_CATCH
 }
 
+int fy_itemcf_recommend_prepared(fy_itemsim_job* j, const fy_itemcf_params* p, const fy_itemcf_filter* f, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !p) { set_error("job or parameters are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(j->ctx);
+    *out = fy::itemcf_recommend_prepared(j, p, f);
+    FY_CATCH
+}
+
+void fy_itemsim_job_drop_rows(fy_itemsim_job* j) {
+    if (!j) return;
+    if (j->ctx) (void)hipSetDevice(j->ctx->device);
+    fy::itemsim_job_drop_rows(j);
+}
+
 int fy_ratings_shifted(fy_context* c, const fy_ratings* r, float shift, fy_ratings** out) {
     if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
     *out = nullptr;
@@ -555,6 +572,12 @@ int fy_result_itemsim_request_stats(fy_result* r, fy_itemsim_request_stats* out)
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     if (!r->has_itemsim_request_stats) { set_error("not a result of fy_itemsim_rows"); return FY_ERR_STATE; }
     *out = r->irq;
+    return FY_OK;
+}
+int fy_result_itemcf_request_stats(fy_result* r, fy_itemcf_request_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_itemcf_request_stats) { set_error("not a result of fy_itemcf_recommend_prepared"); return FY_ERR_STATE; }
+    *out = r->crq;
     return FY_OK;
 }
 void fy_result_free(fy_result* r) {

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <memory>
 
+#include "fy_itemcf_request.hpp"
 #include "fy_prep.hpp"
 #include "fy_rm2.hpp"
 
@@ -31,16 +32,6 @@ namespace fy {
 static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
     int64_t g = ceil_div(n, block);
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
-// raw item id -> compact column (popularity rank); -1 when the item has no rating
-__device__ __forceinline__ int32_t icf_column(const int32_t* __restrict__ iid, int32_t nI, const int32_t* __restrict__ pair_rank, int32_t raw) {
-    int32_t lo = 0, hi = nI;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (iid[mid] < raw) lo = mid + 1; else hi = mid;
-    }
-    return (lo < nI && iid[lo] == raw) ? pair_rank[lo] : -1;
 }
 
 // similarity rows (grouped by item) -> per-column row start / length, entries re-expressed as columns
@@ -265,15 +256,111 @@ __global__ void k_icf_count_lists(int32_t n, const int32_t* __restrict__ n_out, 
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, mine);
 }
 
-// filt == nullptr: every user of the rank's slot range, every item (fy_itemcf_recommend)
-static fy_result* icf_run(Context* ctx, const fy_itemcf_params* prm, const fy_itemcf_filter* filt, const fy_ratings* R, fy_result* sims) {
+// what the pass refuses before it touches the device (the request pass of fy_itemcf_request.hip refuses the same)
+void icf_check_arguments(const fy_itemcf_params* prm, const fy_itemcf_filter* filt) {
     if (prm->num_recommendations <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "numRecommendations must be > 0");
     if (prm->num_recommendations > 2048) FY_FAIL(FY_ERR_UNSUPPORTED, "numRecommendations %d exceeds the top-N kernel limit 2048", prm->num_recommendations);
     if (prm->max_prefs_per_user <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "maxPrefsPerUser must be > 0");
     if (prm->world <= 0 || prm->rank < 0 || prm->rank >= prm->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", prm->rank, prm->world);
-    const bool by_list = filt != nullptr, by_items = filt && filt->has_items;
+    const bool by_items = filt && filt->has_items;
     if (filt && filt->has_users && (filt->n_users < 0 || (filt->n_users > 0 && !filt->users))) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "users is NULL or n_users < 0");
     if (by_items && (filt->n_items < 0 || (filt->n_items > 0 && !filt->items))) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "items is NULL or n_items < 0");
+}
+
+void icf_allow_bitmap(Context* ctx, const Prepared& P, const fy_itemcf_filter* filt, DevBuf<uint32_t>& allow) {
+    hipStream_t st = ctx->stream;
+    DevBuf<int32_t> ids(ctx, (size_t)filt->n_items);
+    allow.alloc(ctx, (size_t)ceil_div(P.nP, 32));
+    allow.zero();
+    h2d(ctx, ids.get(), filt->items, (size_t)filt->n_items);
+    k_icf_mark_items<<<grid_for(filt->n_items), 256, 0, st>>>(filt->n_items, ids.get(), P.iid.get(), P.nI, P.pair_rank.get(), allow.get());
+    FY_KERNEL_CHECK();
+}
+
+void icf_thresholds(Context* ctx, const Prepared& P, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr) {
+    if (hi <= lo) return;
+    hipStream_t st = ctx->stream;
+    const int g = grid_for((int64_t)(hi - lo) * 64, 256);
+    if (list) k_icf_threshold<true><<<g, 256, 0, st>>>(lo, hi, list, P.rowptr.get(), P.csr_r.get(), max_prefs, thr);
+    else k_icf_threshold<false><<<g, 256, 0, st>>>(lo, hi, nullptr, P.rowptr.get(), P.csr_r.get(), max_prefs, thr);
+    FY_KERNEL_CHECK();
+}
+
+void icf_score_lists(Context* ctx, const fy_itemcf_params* prm, const Prepared& P, const IcfSims& S_, const int32_t* list, const int32_t* list_du,
+                     const uint32_t* allow, int32_t lo, int32_t hi, const float* thr, fy_result* Rs, EventTimer& t_score, EventTimer& t_topn,
+                     DevBuf<int32_t>& n_lists) {
+    hipStream_t st = ctx->stream;
+    const bool by_list = list != nullptr, by_items = allow != nullptr;
+    const int32_t nI = P.nP, N = prm->num_recommendations, nmine = hi - lo;
+    // ---- batches of users with dense accumulators
+    const int64_t ld = round_up(nI, 256);
+    const int64_t per_user = ld * (8 + 8 + 4 + 4);
+    int64_t B = std::max<int64_t>(1, ((int64_t)8 << 30) / per_user);
+    B = std::min<int64_t>(B, std::max<int32_t>(nmine, 1));
+    DevBuf<double> num(ctx, (size_t)(B * ld)), den(ctx, (size_t)(B * ld));
+    DevBuf<int32_t> cnt(ctx, (size_t)(B * ld));
+    DevBuf<float> S(ctx, (size_t)(B * ld));
+    DevBuf<int32_t> n_out(ctx, (size_t)nmine + 1), pad_off(ctx, (size_t)nmine + 1), overflow(ctx, (size_t)B), any_overflow(ctx, 1);
+    DevBuf<int32_t> p_user(ctx, (size_t)nmine * N), p_item(ctx, (size_t)nmine * N);
+    DevBuf<float> p_score(ctx, (size_t)nmine * N);
+    DevBuf<int32_t> p_aux(ctx, (size_t)nmine * N);
+    n_out.zero();
+    if (nmine > 0) {
+        k_icf_offsets<<<grid_for(nmine), 256, 0, st>>>(nmine, N, pad_off.get());
+        FY_KERNEL_CHECK();
+    }
+    for (int32_t s0 = lo; s0 < hi; s0 += (int32_t)B) {
+        const int32_t nb = (int32_t)std::min<int64_t>(B, hi - s0);
+        const size_t sp3 = t_score.begin();
+        FY_HIP(hipMemsetAsync(num.get(), 0, (size_t)nb * ld * 8, st));
+        FY_HIP(hipMemsetAsync(den.get(), 0, (size_t)nb * ld * 8, st));
+        FY_HIP(hipMemsetAsync(cnt.get(), 0, (size_t)nb * ld * 4, st));
+        IcfArgs A{P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), thr, S_.row_start, S_.row_cnt, S_.col_other,
+                  S_.sim, lo, s0, nb, prm->boolean_data, ld, num.get(), den.get(), cnt.get(), list};
+        const int g = grid_for((int64_t)nb * 64, 256, 256 * 32);
+        if (by_list) k_icf_accumulate<true><<<g, 256, 0, st>>>(A);
+        else k_icf_accumulate<false><<<g, 256, 0, st>>>(A);
+        FY_KERNEL_CHECK();
+        if (by_items) k_icf_finalize<true><<<nb, 256, 0, st>>>(nb, nI, ld, num.get(), den.get(), cnt.get(), prm->boolean_data, N, allow, S.get(), n_out.get() + (s0 - lo));
+        else k_icf_finalize<false><<<nb, 256, 0, st>>>(nb, nI, ld, num.get(), den.get(), cnt.get(), prm->boolean_data, N, nullptr, S.get(), n_out.get() + (s0 - lo));
+        FY_KERNEL_CHECK();
+        t_score.end(sp3);
+        const size_t sp4 = t_topn.begin();
+        // (the top-N kernels name row u's user through slot2du[slot0 + u]: with a list that is the list's own dense-index column)
+        launch_topn_rows(ctx, st, S.get(), ld, nI, nb, n_out.get() + (s0 - lo), pad_off.get() + (s0 - lo), P.rank_item_raw.get(),
+                         by_list ? list_du : P.slot2du.get(), P.uid.get(), s0, 0, p_user.get(), p_item.get(), p_score.get(), p_aux.get(),
+                         overflow.get(), any_overflow.get());
+        t_topn.end(sp4);
+    }
+    // ---- compact the padded lists
+    DevBuf<int32_t> off(ctx, (size_t)nmine + 1);
+    n_lists.alloc(ctx, 1);
+    if (by_list) {
+        n_lists.zero();
+        if (nmine > 0) {
+            k_icf_count_lists<<<grid_for(nmine), 256, 0, st>>>(nmine, n_out.get(), n_lists.get());
+            FY_KERNEL_CHECK();
+        }
+    }
+    exclusive_scan_i32(ctx, n_out.get(), off.get(), (size_t)nmine + 1);
+    const int64_t n = nmine > 0 ? (int64_t)fetch(ctx, off.get() + nmine) : 0;
+    Rs->n = n;
+    Rs->d_key0.alloc(ctx, (size_t)n);
+    Rs->d_key1.alloc(ctx, (size_t)n);
+    Rs->d_value.alloc(ctx, (size_t)n);
+    Rs->d_aux.alloc(ctx, (size_t)n);
+    if (n > 0) {
+        k_icf_compact<<<grid_for((int64_t)nmine * 64, 256), 256, 0, st>>>(nmine, N, n_out.get(), off.get(), p_user.get(), p_item.get(),
+                                                                          p_score.get(), Rs->d_key0.get(), Rs->d_key1.get(),
+                                                                          Rs->d_value.get(), Rs->d_aux.get());
+        FY_KERNEL_CHECK();
+    }
+}
+
+// filt == nullptr: every user of the rank's slot range, every item (fy_itemcf_recommend)
+static fy_result* icf_run(Context* ctx, const fy_itemcf_params* prm, const fy_itemcf_filter* filt, const fy_ratings* R, fy_result* sims) {
+    icf_check_arguments(prm, filt);
+    const bool by_list = filt != nullptr, by_items = filt && filt->has_items;
     hipStream_t st = ctx->stream;
     SyncOnUnwind drain(st);   // the caller's id arrays are uploaded asynchronously
     std::unique_ptr<fy_result> Rs(new fy_result);
@@ -299,7 +386,7 @@ static fy_result* icf_run(Context* ctx, const fy_itemcf_params* prm, const fy_it
         Rs->st.ms_total = t_total.total_ms();
         return Rs.release();
     }
-    const int32_t nI = P.nP, N = prm->num_recommendations;
+    const int32_t nI = P.nP;
     const int64_t n_sim = sims->n;
     // ---- similarity rows by column
     const size_t sp2 = t_index.begin();
@@ -333,14 +420,7 @@ static fy_result* icf_run(Context* ctx, const fy_itemcf_params* prm, const fy_it
             FY_KERNEL_CHECK();
         }
     }
-    if (by_items) {
-        DevBuf<int32_t> ids(ctx, (size_t)filt->n_items);
-        allow.alloc(ctx, (size_t)ceil_div(nI, 32));
-        allow.zero();
-        h2d(ctx, ids.get(), filt->items, (size_t)filt->n_items);
-        k_icf_mark_items<<<grid_for(filt->n_items), 256, 0, st>>>(filt->n_items, ids.get(), P.iid.get(), P.nI, P.pair_rank.get(), allow.get());
-        FY_KERNEL_CHECK();
-    }
+    if (by_items) icf_allow_bitmap(ctx, P, filt, allow);
     t_index.end(sp2);
     // ---- this rank's users: a contiguous range of the (degree-sorted) slot order, or of the slot list
     int32_t lo = 0, hi = n_all;
@@ -350,74 +430,12 @@ static fy_result* icf_run(Context* ctx, const fy_itemcf_params* prm, const fy_it
     }
     const int32_t nmine = hi - lo;
     DevBuf<float> thr(ctx, (size_t)nmine + 1);
-    if (nmine > 0) {
-        const int g = grid_for((int64_t)nmine * 64, 256);
-        if (by_list) k_icf_threshold<true><<<g, 256, 0, st>>>(lo, hi, list.get(), P.rowptr.get(), P.csr_r.get(), prm->max_prefs_per_user, thr.get());
-        else k_icf_threshold<false><<<g, 256, 0, st>>>(lo, hi, nullptr, P.rowptr.get(), P.csr_r.get(), prm->max_prefs_per_user, thr.get());
-        FY_KERNEL_CHECK();
-    }
-    // ---- batches of users with dense accumulators
-    const int64_t ld = round_up(nI, 256);
-    const int64_t per_user = ld * (8 + 8 + 4 + 4);
-    int64_t B = std::max<int64_t>(1, ((int64_t)8 << 30) / per_user);
-    B = std::min<int64_t>(B, std::max<int32_t>(nmine, 1));
-    DevBuf<double> num(ctx, (size_t)(B * ld)), den(ctx, (size_t)(B * ld));
-    DevBuf<int32_t> cnt(ctx, (size_t)(B * ld));
-    DevBuf<float> S(ctx, (size_t)(B * ld));
-    DevBuf<int32_t> n_out(ctx, (size_t)nmine + 1), pad_off(ctx, (size_t)nmine + 1), overflow(ctx, (size_t)B), any_overflow(ctx, 1);
-    DevBuf<int32_t> p_user(ctx, (size_t)nmine * N), p_item(ctx, (size_t)nmine * N);
-    DevBuf<float> p_score(ctx, (size_t)nmine * N);
-    DevBuf<int32_t> p_aux(ctx, (size_t)nmine * N);
-    n_out.zero();
-    if (nmine > 0) {
-        k_icf_offsets<<<grid_for(nmine), 256, 0, st>>>(nmine, N, pad_off.get());
-        FY_KERNEL_CHECK();
-    }
-    for (int32_t s0 = lo; s0 < hi; s0 += (int32_t)B) {
-        const int32_t nb = (int32_t)std::min<int64_t>(B, hi - s0);
-        const size_t sp3 = t_score.begin();
-        FY_HIP(hipMemsetAsync(num.get(), 0, (size_t)nb * ld * 8, st));
-        FY_HIP(hipMemsetAsync(den.get(), 0, (size_t)nb * ld * 8, st));
-        FY_HIP(hipMemsetAsync(cnt.get(), 0, (size_t)nb * ld * 4, st));
-        IcfArgs A{P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), thr.get(), row_start.get(), row_cnt.get(), col_other.get(),
-                  sims->d_value.get(), lo, s0, nb, prm->boolean_data, ld, num.get(), den.get(), cnt.get(), list.get()};
-        const int g = grid_for((int64_t)nb * 64, 256, 256 * 32);
-        if (by_list) k_icf_accumulate<true><<<g, 256, 0, st>>>(A);
-        else k_icf_accumulate<false><<<g, 256, 0, st>>>(A);
-        FY_KERNEL_CHECK();
-        if (by_items) k_icf_finalize<true><<<nb, 256, 0, st>>>(nb, nI, ld, num.get(), den.get(), cnt.get(), prm->boolean_data, N, allow.get(), S.get(), n_out.get() + (s0 - lo));
-        else k_icf_finalize<false><<<nb, 256, 0, st>>>(nb, nI, ld, num.get(), den.get(), cnt.get(), prm->boolean_data, N, nullptr, S.get(), n_out.get() + (s0 - lo));
-        FY_KERNEL_CHECK();
-        t_score.end(sp3);
-        const size_t sp4 = t_topn.begin();
-        // (the top-N kernels name row u's user through slot2du[slot0 + u]: with a list that is the list's own dense-index column)
-        launch_topn_rows(ctx, st, S.get(), ld, nI, nb, n_out.get() + (s0 - lo), pad_off.get() + (s0 - lo), P.rank_item_raw.get(),
-                         by_list ? list_du.get() : P.slot2du.get(), P.uid.get(), s0, 0, p_user.get(), p_item.get(), p_score.get(), p_aux.get(),
-                         overflow.get(), any_overflow.get());
-        t_topn.end(sp4);
-    }
-    // ---- compact the padded lists
-    DevBuf<int32_t> off(ctx, (size_t)nmine + 1), n_lists(ctx, 1);
-    if (by_list) {
-        n_lists.zero();
-        if (nmine > 0) {
-            k_icf_count_lists<<<grid_for(nmine), 256, 0, st>>>(nmine, n_out.get(), n_lists.get());
-            FY_KERNEL_CHECK();
-        }
-    }
-    exclusive_scan_i32(ctx, n_out.get(), off.get(), (size_t)nmine + 1);
-    const int64_t n = nmine > 0 ? (int64_t)fetch(ctx, off.get() + nmine) : 0;
-    Rs->n = n;
-    Rs->d_key0.alloc(ctx, (size_t)n);
-    Rs->d_key1.alloc(ctx, (size_t)n);
-    Rs->d_value.alloc(ctx, (size_t)n);
-    Rs->d_aux.alloc(ctx, (size_t)n);
-    if (n > 0) {
-        k_icf_compact<<<grid_for((int64_t)nmine * 64, 256), 256, 0, st>>>(nmine, N, n_out.get(), off.get(), p_user.get(), p_item.get(),
-                                                                          p_score.get(), Rs->d_key0.get(), Rs->d_key1.get(),
-                                                                          Rs->d_value.get(), Rs->d_aux.get());
-        FY_KERNEL_CHECK();
-    }
+    icf_thresholds(ctx, P, by_list ? list.get() : nullptr, lo, hi, prm->max_prefs_per_user, thr.get());
+    DevBuf<int32_t> n_lists;
+    const IcfSims S_{row_start.get(), row_cnt.get(), col_other.get(), sims->d_value.get()};
+    icf_score_lists(ctx, prm, P, S_, by_list ? list.get() : nullptr, by_list ? list_du.get() : nullptr, by_items ? allow.get() : nullptr, lo, hi,
+                    thr.get(), Rs.get(), t_score, t_topn, n_lists);
+    const int64_t n = Rs->n;
     t_total.end(sp0);
     // the unrestricted job reports the users it walked; the restricted one the users that received a list
     const int64_t scored = by_list ? (int64_t)fetch(ctx, n_lists.get()) : nmine;

@@ -169,6 +169,56 @@ RowsKernel rows_kernel(int measure) {
 
 }  // namespace
 
+// The rows of the similarity matrix with the popularity ranks rows[0 .. n) (device, ascending), in batches: the row kernel, then the
+// merge of each row's chunks into cnt[m] / other[m * K ..] / sim[m * K ..] (raw item ids, best first).  Shared by fy_itemsim_rows and
+// the item-CF request pass (fy_itemcf_request.hip).  Returns the number of batches (launches of the row kernel).
+int64_t itemsim_build_rank_rows(fy_itemsim_job* J, const int32_t* rows, int64_t n, int32_t* cnt, int32_t* other, float* sim,
+                                EventTimer& t_cooc, EventTimer& t_topn) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    const fy_itemsim_params& prm = J->prm;
+    hipStream_t st = ctx->stream;
+    const int32_t K = prm.max_similarities_per_item, Ic = P.nP, nch = J->nch, CH = J->CH;
+    // rows per batch: the per-(row, chunk) partial lists fit the workspace default, the grid fits a launch
+    const Tuning& tune = ctx->tune;
+    int64_t per_batch = std::max<int64_t>(1, tune.workspace_default / ((int64_t)nch * K * 8));
+    per_batch = std::min<int64_t>(per_batch, 0x7FFFFFFFll / nch);
+    if (tune.isim_req_rows > 0) per_batch = std::min<int64_t>(per_batch, tune.isim_req_rows);
+    per_batch = std::min(per_batch, n);
+    DevBuf<int32_t> part_cnt(ctx, (size_t)per_batch * nch);
+    DevBuf<uint64_t> part(ctx, (size_t)per_batch * nch * K);
+    SyncOnUnwind drain(st);      // a failure in the loop drains the stream before the partial lists go
+    int64_t batches = 0;
+
+    const int measure = prm.similarity;
+    const bool cosine = measure == FY_SIMILARITY_COSINE, pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
+                          measure == FY_SIMILARITY_CITY_BLOCK || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
+    const int cap = ISIM_CAP;
+    const size_t lds = (size_t)CH * 8 + (size_t)cap * 8;
+    const RowsKernel kernel = rows_kernel(measure);
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int64_t b0 = 0; b0 < n; b0 += per_batch) {
+        const int32_t nb = (int32_t)std::min<int64_t>(per_batch, n - b0);
+        ReqRowsArgs A{rows + b0, Ic, CH, nch, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.csc_r.get(), J->choff.get(),
+                      P.csr_idx.get(), P.csr_r.get(), J->csr_w.get(), J->centre.get(), J->cnorm.get(), J->bound.get()};
+        ISimEpilogue E{P.rank_item_raw.get(), K, prm.exclude_self, prm.has_threshold, (float)prm.threshold, prm.rank, prm.world, nullptr, nullptr,
+                       nullptr, (cosine || pearson) ? J->inv_norm.get() : nullptr, finishes ? J->aux.get() : nullptr, (double)P.nU, part_cnt.get(),
+                       part.get(), 0, 0, cap};
+        const unsigned grid = (unsigned)((int64_t)nb * nch);
+        const size_t sp_c = t_cooc.begin();
+        kernel<<<grid, ROWS_THREADS, lds, st>>>(A, E);
+        FY_KERNEL_CHECK();
+        t_cooc.end(sp_c);
+        const size_t sp_t = t_topn.begin();
+        k_isim_merge<<<std::min(nb, ctx->num_cus * 8), 256, 0, st>>>(nb, nch, K, part_cnt.get(), part.get(), cnt + b0, other + b0 * K, sim + b0 * K);
+        FY_KERNEL_CHECK();
+        t_topn.end(sp_t);
+        batches++;
+    }
+    return batches;
+}
+
 fy_result* itemsim_rows(fy_itemsim_job* J, const fy_itemsim_request* rq) {
     Context* ctx = J->ctx;
     const Prepared& P = J->P;
@@ -210,20 +260,12 @@ fy_result* itemsim_rows(fy_itemsim_job* J, const fy_itemsim_request* rq) {
     R->st.pair_contribs = R->irq.pair_contribs;
     if (n == 0) return R.release();
 
-    const int32_t K = prm.max_similarities_per_item, Ic = P.nP, nch = J->nch, CH = J->CH;
+    const int32_t K = prm.max_similarities_per_item;
     if (n * K > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "the request's result may exceed 2^31 rows");
-    // rows per batch: the per-(row, chunk) partial lists fit the workspace default, the grid fits a launch
-    const Tuning& tune = ctx->tune;
-    int64_t per_batch = std::max<int64_t>(1, tune.workspace_default / ((int64_t)nch * K * 8));
-    per_batch = std::min<int64_t>(per_batch, 0x7FFFFFFFll / nch);
-    if (tune.isim_req_rows > 0) per_batch = std::min<int64_t>(per_batch, tune.isim_req_rows);
-    per_batch = std::min(per_batch, n);
 
     EventTimer t_total(ctx), t_cooc(ctx), t_topn(ctx);
     DevBuf<int32_t> d_rows(ctx, (size_t)n), cnt(ctx, (size_t)n + 1), off(ctx, (size_t)n + 1), other(ctx, (size_t)n * K);
     DevBuf<float> sim(ctx, (size_t)n * K);
-    DevBuf<int32_t> part_cnt(ctx, (size_t)per_batch * nch);
-    DevBuf<uint64_t> part(ctx, (size_t)per_batch * nch * K);
     std::vector<int32_t> h_cnt((size_t)n);
     // behind the host ends of the queued copies (`rows`, `h_cnt`) AND the scratch buffers: a failure drains the stream before any of
     // them goes (objects die in reverse order of declaration)
@@ -231,34 +273,7 @@ fy_result* itemsim_rows(fy_itemsim_job* J, const fy_itemsim_request* rq) {
     const size_t sp_total = t_total.begin();
     h2d(ctx, d_rows.get(), rows.data(), (size_t)n);
     cnt.zero();
-
-    const int measure = prm.similarity;
-    const bool cosine = measure == FY_SIMILARITY_COSINE, pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
-    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
-                          measure == FY_SIMILARITY_CITY_BLOCK || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
-    const int cap = ISIM_CAP;
-    const size_t lds = (size_t)CH * 8 + (size_t)cap * 8;
-    const RowsKernel kernel = rows_kernel(measure);
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    for (int64_t b0 = 0; b0 < n; b0 += per_batch) {
-        const int32_t nb = (int32_t)std::min<int64_t>(per_batch, n - b0);
-        ReqRowsArgs A{d_rows.get() + b0, Ic, CH, nch, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.csc_r.get(), J->choff.get(),
-                      P.csr_idx.get(), P.csr_r.get(), J->csr_w.get(), J->centre.get(), J->cnorm.get(), J->bound.get()};
-        ISimEpilogue E{P.rank_item_raw.get(), K, prm.exclude_self, prm.has_threshold, (float)prm.threshold, prm.rank, prm.world, nullptr, nullptr,
-                       nullptr, (cosine || pearson) ? J->inv_norm.get() : nullptr, finishes ? J->aux.get() : nullptr, (double)P.nU, part_cnt.get(),
-                       part.get(), 0, 0, cap};
-        const unsigned grid = (unsigned)((int64_t)nb * nch);
-        const size_t sp_c = t_cooc.begin();
-        kernel<<<grid, ROWS_THREADS, lds, st>>>(A, E);
-        FY_KERNEL_CHECK();
-        t_cooc.end(sp_c);
-        const size_t sp_t = t_topn.begin();
-        k_isim_merge<<<std::min(nb, ctx->num_cus * 8), 256, 0, st>>>(nb, nch, K, part_cnt.get(), part.get(), cnt.get() + b0, other.get() + b0 * K,
-                                                                     sim.get() + b0 * K);
-        FY_KERNEL_CHECK();
-        t_topn.end(sp_t);
-        R->irq.batches++;
-    }
+    R->irq.batches = itemsim_build_rank_rows(J, d_rows.get(), n, cnt.get(), other.get(), sim.get(), t_cooc, t_topn);
     const size_t sp_t = t_topn.begin();
     exclusive_scan_i32(ctx, cnt.get(), off.get(), (size_t)n + 1);
     d2h(ctx, h_cnt.data(), cnt.get(), (size_t)n);

@@ -23,9 +23,24 @@ struct fy_itemsim_job {
     // host: raw item ids ascending with their popularity rank, and per rank the sum of the raters' degrees
     std::vector<int32_t> raw_sorted, rank_of_sorted;
     std::vector<long long> walk;
+    // Similarity rows kept for the item-CF request pass (fy_itemcf_recommend_prepared: fy_itemcf_request.hip), indexed by popularity
+    // rank, in the layout k_icf_accumulate reads: allocated by the first such call, released by fy_itemsim_job_drop_rows.  A row is
+    // valid only where state is 1 (written after the row is complete); fy_itemsim_rows neither reads nor fills it.
+    struct RowStore {
+        fy::DevBuf<int32_t> state;     // [nP] 1 = the row is here
+        fy::DevBuf<int32_t> cnt;       // [nP] entries of the row
+        fy::DevBuf<int32_t> start;     // [nP] j * K: the row_start of the accumulate kernel
+        fy::DevBuf<int32_t> other;     // [nP * K] the other item as a column (popularity rank; -1 = no column)
+        fy::DevBuf<float> sim;         // [nP * K]
+        int64_t rows = 0;              // rows marked present
+        bool allocated = false;
+    } store;
 };
 
 namespace fy {
 fy_itemsim_job* itemsim_prepare(Context*, const fy_itemsim_params*, const fy_ratings*);
 fy_result* itemsim_rows(fy_itemsim_job*, const fy_itemsim_request*);
+// rows of the given popularity ranks (device, ascending) -> cnt[n], other[n * K] (raw ids), sim[n * K]; returns the batches launched
+int64_t itemsim_build_rank_rows(fy_itemsim_job*, const int32_t* rows, int64_t n, int32_t* cnt, int32_t* other, float* sim,
+                                EventTimer& t_cooc, EventTimer& t_topn);
 }  // namespace fy

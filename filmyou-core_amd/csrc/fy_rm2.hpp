@@ -19,6 +19,8 @@ struct fy_result {
     fy_rm2_request_stats rq{};
     bool has_itemsim_request_stats = false;   // a result of fy_itemsim_rows
     fy_itemsim_request_stats irq{};
+    bool has_itemcf_request_stats = false;    // a result of fy_itemcf_recommend_prepared
+    fy_itemcf_request_stats crq{};
     // host mirrors, filled on first access
     bool rows_on_host = false, sums_on_host = false;
     std::vector<int32_t> h_key0, h_key1, h_aux, h_user_id, h_item_id;

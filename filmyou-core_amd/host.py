@@ -644,11 +644,17 @@ class PreparedRM2:
 class ItemRecommendations(_Result):
     """Rows of the item-based recommender's output table: (user, item, score), grouped by user, best first."""
 
-    def __init__(self, handle, ctx=None):
+    def __init__(self, handle, ctx=None, request=False):
         super().__init__(handle, ctx)
         self.stats = self._stats()
         self.size = self._lib.fy_result_size(handle)
         self._rows = None
+        # request=True (a result of fy_itemcf_recommend_prepared): what the request touched; None on any other result
+        self.request_stats = None
+        if request:
+            rq = _native.ItemCFRequestStats()
+            _check(self._lib.fy_result_itemcf_request_stats(handle, C.byref(rq)))
+            self.request_stats = rq.as_dict()
 
     def rows(self):
         if self._rows is None:
@@ -667,6 +673,33 @@ class BaselineRecommenderJob:
 
     def __init__(self, ctx=None):
         self.ctx = ctx
+
+    def prepare(self, ratings, maxSimilaritiesPerItem=100, similarityClassname=SIMILARITY_COSINE, threshold=None, ratingShift=0.0):
+        """The similarity phase of ``run`` as a prepared job: a ``PreparedItemSimilarity`` whose ``recommend(users)`` answers
+        "these users just rated something" without building the similarity matrix.  The options are those ``run`` passes to
+        phase 2: self-similarity excluded, world 1, no input preparation, ratingShift applied first.  ``ratings`` (a ``Ratings``
+        or a triple of arrays) may be closed afterwards; after a write, prepare again on the new ``Ratings``."""
+        ctx = self.ctx or Context(0)
+        self.ctx = ctx
+        own_ratings = not isinstance(ratings, Ratings)
+        r = Ratings(ctx, *ratings) if own_ratings else ratings
+        if float(ratingShift) != 0.0:
+            try:
+                shifted = r.shifted(ratingShift)
+            finally:
+                if own_ratings:
+                    r.close()
+            r, own_ratings = shifted, True
+        try:
+            try:
+                return RowSimilarityJob(ctx).prepare(r, similarityClassname, maxSimilaritiesPerItem, True, threshold)
+            except RuntimeError as e:      # the similarity phase's failure under this job's name
+                if isinstance(e.__cause__, FilmYouError):
+                    raise RuntimeError("%s failed!: %s" % (self.JOB_NAME, e.__cause__.message)) from e.__cause__
+                raise
+        finally:
+            if own_ratings:
+                r.close()
 
     def run(self, ratings, numRecommendations=100, maxPrefsPerUser=50, maxSimilaritiesPerItem=100,
             similarityClassname=SIMILARITY_COSINE, threshold=None, booleanData=False, rank=0, world=1,
@@ -824,6 +857,30 @@ class PreparedItemSimilarity:
         except FilmYouError as e:
             raise RuntimeError("%s failed!: %s" % (RowSimilarityJob.JOB_NAME, e.message)) from e
         return ItemSimilarities(res, self._ctx, request=True)
+
+    def recommend(self, users, numRecommendations=100, maxPrefsPerUser=50, booleanData=False, itemsFile=None, rank=0, world=1):
+        """fy_itemcf_recommend_prepared: the lists ``BaselineRecommenderJob.run(usersFile=users)`` would emit on the ratings this
+        job was prepared on, from the similarity rows of the users' own strongest preferences alone.  Rows built by a call stay
+        on the job for later calls (``drop_rows`` releases them); they change no result.  ``users`` / ``itemsFile``: a path of
+        one id per line or an integer array.  Returns an ``ItemRecommendations`` with ``request_stats`` beside ``stats``."""
+        if users is None:
+            raise ValueError("recommend() needs the users to recommend for; BaselineRecommenderJob.run serves every user")
+        users, items = _id_list(users), _id_list(itemsFile)
+        p = _native.ItemCFParams(int(numRecommendations), int(maxPrefsPerUser), 1 if booleanData else 0, int(rank), int(world), 0)
+        f = _native.ItemCFFilter(1, int(items is not None), len(users), users.ctypes.data if len(users) else None,
+                                 0 if items is None else len(items), None if items is None or not len(items) else items.ctypes.data)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            _check(self._lib.fy_itemcf_recommend_prepared(self._h, C.byref(p), C.byref(f), C.byref(res)))
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
+        return ItemRecommendations(res, self._ctx, request=True)
+
+    def drop_rows(self):
+        """fy_itemsim_job_drop_rows: releases the similarity rows kept by ``recommend``; the job stays valid."""
+        if getattr(self, "_h", None) and self._ctx._h:
+            self._lib.fy_itemsim_job_drop_rows(self._h)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -395,6 +395,37 @@ class RowSimilarityJob {
     }
 };
 
+// What BaselineRecommenderJob::prepare returns: a prepared similarity job and the context it lives on, owned (move-only).
+class PreparedItemSimilarity {
+   public:
+    PreparedItemSimilarity() = default;
+    PreparedItemSimilarity(const PreparedItemSimilarity&) = delete;
+    PreparedItemSimilarity& operator=(const PreparedItemSimilarity&) = delete;
+    PreparedItemSimilarity(PreparedItemSimilarity&& o) noexcept : ctx_(o.ctx_), job_(o.job_) { o.ctx_ = nullptr; o.job_ = nullptr; }
+    PreparedItemSimilarity& operator=(PreparedItemSimilarity&& o) noexcept {
+        if (this != &o) {
+            close();
+            ctx_ = o.ctx_; job_ = o.job_;
+            o.ctx_ = nullptr; o.job_ = nullptr;
+        }
+        return *this;
+    }
+    ~PreparedItemSimilarity() { close(); }
+    fy_itemsim_job* job() const { return job_; }
+    void dropRows() { fy_itemsim_job_drop_rows(job_); }      // the row store; the job stays valid
+    void close() {
+        if (job_) fy_itemsim_job_destroy(job_);
+        if (ctx_) fy_context_destroy(ctx_);
+        job_ = nullptr;
+        ctx_ = nullptr;
+    }
+
+   private:
+    friend class BaselineRecommenderJob;
+    fy_context* ctx_ = nullptr;
+    fy_itemsim_job* job_ = nullptr;
+};
+
 // Item-based CF from the similarity phase on (M/baselinerecommender/BaselineRecommenderJob.java:179-328), with the job's option
 // names: the similarity build, then the recommendation pass on one context.  usersFile / itemsFile (paths of one id per line; empty
 // = not given, the reference's NULL), ratingShift and outputPathForSimilarityMatrix as in the reference (:74, 189, 259-278, 305-307;
@@ -473,6 +504,74 @@ class BaselineRecommenderJob {
         for (int64_t k = 0; k < n; k++) sink(u[k], i[k], s[k]);
         fy_result_stats(res, &stats);
         release();
+        return 0;
+    }
+
+    // "These users just rated something": prepare() keeps the similarity phase of run() as a prepared job (self-similarity excluded,
+    // world 1, no input preparation, ratingShift applied first) on a context of its own and returns the handle that owns both;
+    // recommendUsers() then answers any number of requests on it with the lists run() with that usersFile would emit
+    // (fy_itemcf_recommend_prepared; itemsFile, numRecommendations, maxPrefsPerUser and booleanData are read at each request).  The
+    // similarity rows a request builds stay on the prepared job for the next one (dropRows releases them).  After a write, prepare
+    // again on the new ratings.
+    fy_itemcf_request_stats requestStats{};
+    PreparedItemSimilarity prepare(const Ratings& r, int device = 0) const {
+        PreparedItemSimilarity p;
+        fy_ratings *rt = nullptr, *shifted = nullptr;
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("BaselineRecommenderJob failed!: ") + what + ": " + fy_last_error();
+            if (shifted) fy_ratings_destroy(shifted);
+            if (rt) fy_ratings_destroy(rt);
+            throw std::runtime_error(msg);      // (p goes with the unwinding)
+        };
+        fy_itemsim_params sp{};
+        sp.similarity = RowSimilarityJob::similarityId(similarityClassname);
+        sp.max_similarities_per_item = maxSimilaritiesPerItem;
+        sp.exclude_self = 1;
+        sp.has_threshold = hasThreshold ? 1 : 0;
+        sp.threshold = threshold;
+        sp.world = 1;
+        sp.min_prefs_per_user = 1;
+        if (fy_context_create(device, &p.ctx_) != FY_OK) fail("context");
+        if (fy_ratings_create(p.ctx_, (int64_t)r.user.size(), r.user.data(), r.item.data(), r.score.data(), FY_HOST, &rt) != FY_OK) fail("ratings");
+        if (ratingShift != 0.0f && fy_ratings_shifted(p.ctx_, rt, ratingShift, &shifted) != FY_OK) fail("ratingShift");
+        if (fy_itemsim_prepare(p.ctx_, &sp, shifted ? shifted : rt, &p.job_) != FY_OK) fail("prepare");
+        if (shifted) fy_ratings_destroy(shifted);      // the prepared job owns what it needs
+        fy_ratings_destroy(rt);
+        return p;
+    }
+    int recommendUsers(PreparedItemSimilarity& prepared, const std::vector<int32_t>& users, const RecommendationSink& sink) {
+        if (!prepared.job()) throw std::runtime_error("BaselineRecommenderJob failed!: recommendUsers on a closed prepared job");
+        fy_result* res = nullptr;
+        int32_t* items = nullptr;
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("BaselineRecommenderJob failed!: ") + what + ": " + fy_last_error();
+            if (res) fy_result_free(res);
+            fy_buffer_free(items);
+            throw std::runtime_error(msg);
+        };
+        fy_itemcf_filter f{};
+        f.has_users = 1;
+        f.n_users = (int64_t)users.size();
+        f.users = users.empty() ? nullptr : users.data();
+        if (!itemsFile.empty()) {
+            f.has_items = 1;
+            if (fy_idfile_read(itemsFile.c_str(), &f.n_items, &items) != FY_OK) fail("itemsFile");
+            f.items = items;
+        }
+        fy_itemcf_params cp{};
+        cp.num_recommendations = numRecommendations;
+        cp.max_prefs_per_user = maxPrefsPerUser;
+        cp.boolean_data = booleanData ? 1 : 0;
+        cp.world = 1;
+        if (fy_itemcf_recommend_prepared(prepared.job(), &cp, &f, &res) != FY_OK) fail("recommend");
+        const int64_t n = fy_result_size(res);
+        const int32_t *u = fy_result_key0(res), *i = fy_result_key1(res);
+        const float* s = fy_result_value(res);
+        for (int64_t k = 0; k < n; k++) sink(u[k], i[k], s[k]);
+        fy_result_stats(res, &stats);
+        fy_result_itemcf_request_stats(res, &requestStats);
+        fy_result_free(res);
+        fy_buffer_free(items);
         return 0;
     }
 };

@@ -52,8 +52,42 @@ static int main_similar_items(char** a) {
     return 0;
 }
 
+// rm2_main --recommend-users <users.txt> <ratings.txt> <similarityClassname> <K> <N> <maxPrefs>
+//   : BaselineRecommenderJob::prepare + recommendUsers, item-based lists for the ids of the users file alone.  Prints "user item score".
+static int main_recommend_users(char** a) {
+    fy::host::Ratings r;
+    FILE* f = fopen(a[1], "r");
+    if (!f) { perror(a[1]); return 2; }
+    int u, i; float s;
+    while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) r.add(u, i, s);
+    fclose(f);
+    int64_t n = 0;
+    int32_t* ids = nullptr;
+    if (fy_idfile_read(a[0], &n, &ids) != FY_OK) { fprintf(stderr, "BaselineRecommenderJob failed!: %s\n", fy_last_error()); return 1; }
+    std::vector<int32_t> users(ids, ids + n);
+    fy_buffer_free(ids);
+    try {
+        fy::host::BaselineRecommenderJob job;
+        job.similarityClassname = a[2];
+        job.maxSimilaritiesPerItem = atoi(a[3]);
+        job.numRecommendations = atoi(a[4]);
+        job.maxPrefsPerUser = atoi(a[5]);
+        fy::host::PreparedItemSimilarity prepared = job.prepare(r);
+        job.recommendUsers(prepared, users, [](int32_t user, int32_t item, float score) { printf("%d %d %.9g\n", user, item, score); });
+        const fy_itemcf_request_stats& q = job.requestStats;
+        fprintf(stderr, "request users_known %lld items_needed %lld rows_built %lld rows_from_store %lld rows_stored %lld batches %lld pair_contribs %lld\n",
+                (long long)q.users_known, (long long)q.items_needed, (long long)q.rows_built, (long long)q.rows_from_store, (long long)q.rows_stored,
+                (long long)q.batches, (long long)q.pair_contribs);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 9 && strcmp(argv[1], "--files") == 0) return main_files(argv + 2);
+    if (argc == 8 && strcmp(argv[1], "--recommend-users") == 0) return main_recommend_users(argv + 2);
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
     bool rccl = false;
     // rm2_main --users <users.txt> <ratings.txt> ... : RM2Job::runUsers, lists for the ids of the usersFile alone

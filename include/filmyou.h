@@ -379,6 +379,47 @@ typedef struct {
 } fy_itemcf_filter;
 int fy_itemcf_recommend_filtered(fy_context*, const fy_itemcf_params*, const fy_itemcf_filter*,
                                  const fy_ratings*, fy_result* similarities, fy_result** out);
+/* ------------------------------------------------------------------ item-based CF on request from a prepared similarity job
+ * fy_itemcf_recommend_prepared is fy_itemcf_recommend_filtered without the similarity matrix as an input: a user's prediction needs
+ * only the similarity rows of that user's own max_prefs_per_user strongest preferences, and the prepared job builds any row on
+ * request.  The result holds exactly the rows fy_itemcf_recommend_filtered would emit with the same fy_itemcf_params, the same
+ * filter, the ratings the job was prepared on and a similarity matrix whose rows are those fy_itemsim_rows of this job returns:
+ * the user order (slot order of the unrestricted job), best first, ties at the cut, the strongest max_prefs_per_user preferences
+ * with ties at the cut kept, the (j, NaN) self entry, at least two contributing preferences, the numerator == 0 skip,
+ * boolean_data, the allow-list applied where a cell becomes a prediction, the 2048 limit, and (rank, world) of fy_itemcf_params
+ * cutting the list of known requested users -- all bit for bit: the per-cell order of additions is still the order of the user's
+ * preferences.  On half-star or integer preferences, for every measure but Pearson, fy_itemsim_rows is bitwise the full build and
+ * the result is bitwise fy_itemcf_recommend_filtered's on the full matrix; for Pearson, and for cosine on preferences that are not
+ * fp16-exact, it is the filtered pass fed with the job's own rows.
+ * The filter must name users: filter == NULL or has_users == 0 is FY_ERR_INVALID_ARGUMENT (lists for everybody are
+ * fy_itemcf_recommend's).  has_users with n_users == 0, has_items with n_items == 0, and a job over an empty preference matrix give
+ * an empty result; unknown ids, negative ids and duplicates are passed over.  A job prepared with world != 1 (every rank needs any
+ * row) or with min_prefs_per_user > 1 or max_prefs_per_user != 0 (its CSR is no longer the users' preference vectors) answers
+ * FY_ERR_UNSUPPORTED.
+ * The row store: rows built by a call stay on the JOB (not on the ratings) for later calls -- per column a state, a count, and
+ * K = max_similarities_per_item entries (the other item as a popularity-rank column, the similarity): 8 K + 12 bytes per rated
+ * item, allocated by the first call (FY_ERR_OUT_OF_MEMORY like any allocation).  A row is marked present only after it is
+ * complete, so a call that fails half way leaves the job answering correctly.  The store changes no result: a cold job, a warm job
+ * and a job after fy_itemsim_job_drop_rows (releases the store; the job stays valid) return the same bits.  There is no eviction,
+ * and the store does not follow a write: prepare again on the new ratings.  fy_itemsim_rows neither reads nor fills it.
+ * Work: sum over the rows BUILT of the row's walk (fy_itemsim_rows), plus the filtered pass's accumulate; nothing runs over all
+ * ratings or all users, the dense accumulators are sized by the request.
+ * fy_result_stats: nnz, n_users, n_items (the job's), users_scored = users that received a list, recs, pair_contribs,
+ * cooc_launches (= batches), score_launches, ms_prepare = 0, ms_tables (request list, thresholds, the set J), ms_cooc (row kernel,
+ * merge, store fill), ms_score, ms_topn, ms_total. */
+typedef struct {
+    int64_t users_asked;      /* n_users of the filter */
+    int64_t users_known;      /* distinct requested users with a kept preference that this rank emits for */
+    int64_t items_needed;     /* |J|: distinct items among the kept (strongest) preferences of those users */
+    int64_t rows_built;       /* rows of J the row kernel had to build in this call */
+    int64_t rows_from_store;  /* rows of J found in the job's row store */
+    int64_t rows_stored;      /* rows in the store when the call returns */
+    int64_t pair_contribs;    /* sum over the rows BUILT of sum over the raters v of the row's item of n_v */
+    int64_t batches;          /* launches of the row kernel */
+} fy_itemcf_request_stats;
+int fy_itemcf_recommend_prepared(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_filter*, fy_result** out);
+int fy_result_itemcf_request_stats(fy_result*, fy_itemcf_request_stats* out);   /* FY_ERR_STATE on any other result */
+void fy_itemsim_job_drop_rows(fy_itemsim_job*);                                  /* releases the row store; the job stays valid */
 /* ratingShift (BaselinePreparePreferenceMatrixJob.java:105-106, 201, 223; BaselineToItemPrefsMapper.java:51, 60): a NEW ratings
  * object whose scores are (float)(score + shift), added in fp32 like the mapper's `float prefValue`; ids as they are.  Nothing
  * the jobs kept on the source object is carried over.  The baseline job feeds it to the similarity build and to the
