@@ -55,18 +55,31 @@ struct PairPass {
     long long* __restrict__ walk_rank; // by rank position: sum of the raters' degrees
     int32_t* __restrict__ cnt_rank;    // by rank position: raters
     float* __restrict__ fx_rank;       // by rank position, 3 floats: sum and maximum of r / s_v^2 over the column, maximum rating
-};                                     // (bounds of the fixed-point scale of the row kernel, fx_exponent)
+                                       // (bounds of the fixed-point scale of the row kernel, fx_exponent)
+    // General smoothing (the GEN instantiations; fy_rm2.hpp: Smoothing): ud_slot holds (d_v, n_v), the weights are taken over
+    // r' = max(r - delta, 0) (delta = 0: Dirichlet) and d_v, and b_rank receives b~_i = sum_v beta_v x_vi instead of b_i = sum_v x_vi:
+    // beta_v x_vi = mu r / d_v^2 (Dirichlet) or delta n_v r' / s_v^2 (absolute discounting), i.e. bt_scale times the sum of the
+    // walk weights r' / d_v^2, each multiplied by n_v when bt_by_n -- summed in the same fixed order as b.  The partial rating
+    // sums stay those of the raw ratings.
+    double delta, bt_scale;
+    int32_t bt_by_n;
+};
 struct PairAcc {   // (no member initialisers: instances live in __shared__ memory too)
     double ps, b, ws;
     long long w;
     float wm, rm;
+    double bt;     // general smoothing only
 };
-__device__ __forceinline__ PairAcc fy_pair_zero() { return PairAcc{0.0, 0.0, 0.0, 0, 0.0f, 0.0f}; }
+__device__ __forceinline__ PairAcc fy_pair_zero() { return PairAcc{0.0, 0.0, 0.0, 0, 0.0f, 0.0f, 0.0}; }
+// r' of a rating under absolute discounting, rounded to fp32 like every stored rating (the prepared CSR / CSC hold the same value)
+__device__ __forceinline__ float fy_discounted(float r, double delta) { return (float)fmax((double)r - delta, 0.0); }
+template <bool GEN>
 __device__ __forceinline__ void fy_pair_entry(const PairPass& A, int32_t q, PairAcc& a) {
     const int32_t slot = A.csc_slot[q];
-    const double r = (double)A.csc_r[q];
+    double r = (double)A.csc_r[q];
     if (slot >= A.lo && slot < A.hi) a.ps += r;
     const double2 ud = A.ud_slot[slot];
+    if constexpr (GEN) r = (double)fy_discounted((float)r, A.delta);
     const double inv = 1.0 / ud.x;                    // ONE fp64 division per entry for the column sums (round 4: r / s and r / (s * s) were two;
     const double x = r * inv;                         // the heavy-column kernel ran with 40 spilled VGPRs around them)
     if (A.csc_x || A.csc_x_over_s) {                  // (kernel-uniform) the stored weights keep their own roundings: r / s, then / s
@@ -78,12 +91,14 @@ __device__ __forceinline__ void fy_pair_entry(const PairPass& A, int32_t q, Pair
     a.w += (long long)ud.y;
     const double wt = x * inv;
     a.ws += wt;
+    if constexpr (GEN) a.bt += A.bt_by_n ? wt * ud.y : wt;
     a.wm = fmaxf(a.wm, (float)wt);
     a.rm = fmaxf(a.rm, (float)r);
 }
-template <int G = 64>
+template <int G = 64, bool GEN = false>
 __device__ __forceinline__ void fy_pair_reduce(PairAcc& a) {      // over groups of G consecutive lanes
     for (int o = G / 2; o > 0; o >>= 1) {
+        if constexpr (GEN) a.bt += __shfl_down(a.bt, o, 64);
         a.ps += __shfl_down(a.ps, o, 64);
         a.b += __shfl_down(a.b, o, 64);
         a.ws += __shfl_down(a.ws, o, 64);
@@ -92,9 +107,10 @@ __device__ __forceinline__ void fy_pair_reduce(PairAcc& a) {      // over groups
         a.rm = fmaxf(a.rm, __shfl_down(a.rm, o, 64));
     }
 }
+template <bool GEN>
 __device__ __forceinline__ void fy_pair_store(const PairPass& A, int32_t pos, int32_t pr, int32_t n, const PairAcc& a) {
     if (a.ps != 0.0) atomicAdd(&A.partial[A.pair_di[pr]], a.ps);
-    A.b_rank[pos] = a.b;
+    A.b_rank[pos] = GEN ? A.bt_scale * a.bt : a.b;
     A.walk_rank[pos] = a.w;
     A.cnt_rank[pos] = n;
     A.fx_rank[3 * (int64_t)pos + 0] = (float)(a.ws * 1.000001);      // rounded up: these are upper bounds
@@ -114,7 +130,7 @@ struct PairHeavy {
     int32_t* __restrict__ counters;   // [0] heavy columns, [1] chunks
     PairAcc* __restrict__ acc;        // [chunk]
 };
-template <int G>
+template <int G, bool GEN>
 __global__ void k_pair_pass(int32_t nP, PairPass A, PairHeavy H) {
     const int lane = threadIdx.x & (G - 1), gpb = blockDim.x / G;
     const int32_t stride = gridDim.x * gpb;
@@ -134,15 +150,18 @@ __global__ void k_pair_pass(int32_t nP, PairPass A, PairHeavy H) {
         }
         PairAcc a = fy_pair_zero();
         if (!is_heavy)
-            for (int32_t q = q0 + lane; q < q1; q += G) fy_pair_entry(A, q, a);
-        fy_pair_reduce<G>(a);
-        if (live && !is_heavy && lane == 0) fy_pair_store(A, pos, pr, q1 - q0, a);
+            for (int32_t q = q0 + lane; q < q1; q += G) fy_pair_entry<GEN>(A, q, a);
+        fy_pair_reduce<G, GEN>(a);
+        if (live && !is_heavy && lane == 0) fy_pair_store<GEN>(A, pos, pr, q1 - q0, a);
     }
 }
+template <bool GEN>
 __device__ __forceinline__ void fy_pair_add(PairAcc& t, const PairAcc& x) {
     t.ps += x.ps; t.b += x.b; t.ws += x.ws; t.w += x.w;
     t.wm = fmaxf(t.wm, x.wm); t.rm = fmaxf(t.rm, x.rm);
+    if constexpr (GEN) t.bt += x.bt;
 }
+template <bool GEN>
 __global__ __launch_bounds__(256) void k_pair_chunks(PairPass A, PairHeavy H) {
     __shared__ PairAcc sh_a[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -153,26 +172,27 @@ __global__ __launch_bounds__(256) void k_pair_chunks(PairPass A, PairHeavy H) {
         const int32_t q0 = A.pair_start[pr] + (c - H.base[k]) * PAIR_CHUNK, q1 = min(A.pair_start[pr + 1], q0 + PAIR_CHUNK);
         PairAcc a = fy_pair_zero();
 #pragma unroll 4
-        for (int32_t q = q0 + (int32_t)threadIdx.x; q < q1; q += 256) fy_pair_entry(A, q, a);
-        fy_pair_reduce(a);
+        for (int32_t q = q0 + (int32_t)threadIdx.x; q < q1; q += 256) fy_pair_entry<GEN>(A, q, a);
+        fy_pair_reduce<64, GEN>(a);
         if (lane == 0) sh_a[wave] = a;
         __syncthreads();
         if (threadIdx.x == 0) {
             PairAcc t = sh_a[0];
-            for (int x = 1; x < 4; x++) fy_pair_add(t, sh_a[x]);
+            for (int x = 1; x < 4; x++) fy_pair_add<GEN>(t, sh_a[x]);
             H.acc[c] = t;
         }
         __syncthreads();
     }
 }
+template <bool GEN>
 __global__ void k_pair_finish(PairPass A, PairHeavy H) {
     const int n = H.counters[0];
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
         const int32_t pos = H.col[k], pr = A.rank_pair[pos];
         const int32_t len = A.pair_start[pr + 1] - A.pair_start[pr], nchk = (len + PAIR_CHUNK - 1) / PAIR_CHUNK;
         PairAcc t = H.acc[H.base[k]];
-        for (int32_t i = 1; i < nchk; i++) fy_pair_add(t, H.acc[H.base[k] + i]);      // chunk order: the same sum in every run
-        fy_pair_store(A, pos, pr, len, t);
+        for (int32_t i = 1; i < nchk; i++) fy_pair_add<GEN>(t, H.acc[H.base[k] + i]);      // chunk order: the same sum in every run
+        fy_pair_store<GEN>(A, pos, pr, len, t);
     }
 }
 // per-slot copies of the user sums and degrees: one gather per CSC entry instead of two dependent ones
@@ -185,6 +205,50 @@ __global__ void k_slot_user_arrays(int32_t nU, const int32_t* __restrict__ slot2
         deg_slot[s] = udeg[du];
         ud_slot[s] = make_double2(usum[du], (double)udeg[du]);
     }
+}
+// general smoothing: (d_v, n_v) and beta_v of every slot; usum_slot then holds d_v, the divisor of every weight of the job
+__global__ void k_slot_user_arrays_gen(int32_t nU, const int32_t* __restrict__ slot2du, const double* __restrict__ usum,
+                                       const int32_t* __restrict__ udeg, int method, double param, double* __restrict__ d_slot,
+                                       int32_t* __restrict__ deg_slot, double2* __restrict__ ud_slot, double* __restrict__ beta_slot) {
+    for (int32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < nU; s += gridDim.x * blockDim.x) {
+        const int32_t du = slot2du[s];
+        const double sv = usum[du], n = (double)udeg[du];
+        const double d = method == 1 ? sv + param : sv;
+        d_slot[s] = d;
+        deg_slot[s] = udeg[du];
+        ud_slot[s] = make_double2(d, n);
+        beta_slot[s] = method == 1 ? param / d : param * n / sv;
+    }
+}
+// S2 = sum of beta_v^2 over the users of a cluster: one workgroup per cluster, a strided sum per thread, then a tree -- a fixed order
+__global__ __launch_bounds__(256) void k_cluster_s2(const int32_t* __restrict__ ucstart, const double* __restrict__ beta_slot, double* __restrict__ s2) {
+    __shared__ double sh[256];
+    const int c = blockIdx.x;
+    double t = 0.0;
+    for (int32_t s = ucstart[c] + (int32_t)threadIdx.x; s < ucstart[c + 1]; s += 256) t += beta_slot[s] * beta_slot[s];
+    sh[threadIdx.x] = t;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) s2[c] = sh[0];
+}
+// absolute discounting: the prepared CSR / CSC of the job hold r' = max(r - delta, 0) once the statistics pass has read the raw ratings
+__global__ void k_discount_inplace(int64_t n, double delta, float* __restrict__ a, float* __restrict__ b) {
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        a[q] = fy_discounted(a[q], delta);
+        b[q] = fy_discounted(b[q], delta);
+    }
+}
+// ... and whether every r' is exactly representable in fp16 (Prepared::ratings_fp16_exact is then judged on r'): flag[0] = 1 if not
+__global__ void k_discount_not_fp16(int64_t n, double delta, const float* __restrict__ r, int32_t* __restrict__ flag) {
+    bool bad = false;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        const float v = fy_discounted(r[q], delta);
+        bad |= __half2float(__float2half(v)) != v;
+    }
+    if (bad) atomicOr(flag, 1);
 }
 
 // per cluster: maxima over its items of (sum of r / s^2, largest r / s^2, largest rating) -> bounds of a Gram entry and of one contribution
@@ -280,6 +344,7 @@ __global__ void k_item_coll(int32_t nI, const double* __restrict__ stats, double
 }
 
 // p(i|C) of every (cluster, item) in rank order, a = l * p, b rounded once to fp32
+template <bool GEN>      // GEN (general smoothing): a = p, and b_rank is b~
 __global__ void k_pair_p(int32_t nP, const int32_t* __restrict__ rank_pair, const int32_t* __restrict__ pair_di,
                          const double* __restrict__ icoll, double lambda, const double* __restrict__ b_rank,
                          double* __restrict__ p_rank, float* __restrict__ a_rank, float* __restrict__ b_rank32, double2* __restrict__ pb_rank) {
@@ -287,7 +352,8 @@ __global__ void k_pair_p(int32_t nP, const int32_t* __restrict__ rank_pair, cons
         const double p = icoll[pair_di[rank_pair[pos]]];
         p_rank[pos] = p;
         pb_rank[pos] = make_double2(p, b_rank[pos]);      // (p, b) side by side: k_csr_values gathers both with one 16-byte load per rating
-        a_rank[pos] = (float)(lambda * p);
+        if constexpr (GEN) a_rank[pos] = (float)p;
+        else a_rank[pos] = (float)(lambda * p);
         b_rank32[pos] = (float)b_rank[pos];
     }
 }
@@ -372,19 +438,22 @@ __global__ __launch_bounds__(256) void k_tail_blocks(int32_t slot_base, int32_t 
 }
 
 // one wave per user row: x = r / s_u and e = (1-l)(b_j - x) + l (U_c - 1) p_j  (all fp64, rounded once)
+// GEN (general smoothing): x = r' / d_u, e = e~_uj (fy_e_general), q = p_j; csr_r holds r', pb_rank (p, b~), usum_slot d by slot
+template <bool GEN>
 __global__ void k_csr_values(int32_t nU, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_idx,
                              const float* __restrict__ csr_r, const int32_t* __restrict__ slot2du,
                              const int32_t* __restrict__ ucluster, const double* __restrict__ usum,
                              const int32_t* __restrict__ csize, const int32_t* __restrict__ pcstart,
                              const double2* __restrict__ pb_rank, double lambda,
                              const float* __restrict__ gscale /* [cluster]: 2^-c of the packed matrix format, 1 for fp32 rows */,
-                             float* __restrict__ csr_x, float* __restrict__ csr_e, float* __restrict__ csr_q) {
+                             float* __restrict__ csr_x, float* __restrict__ csr_e, float* __restrict__ csr_q,
+                             const double* __restrict__ usum_slot, SmoothArgs G) {
     const int lane = threadIdx.x & 63;
     const int wpb = blockDim.x >> 6;
     for (int32_t s = blockIdx.x * wpb + (threadIdx.x >> 6); s < nU; s += gridDim.x * wpb) {
         const int32_t du = slot2du[s];
         const int32_t c = ucluster[du];
-        const double sum = usum[du];
+        const double sum = GEN ? usum_slot[s] : usum[du];
         const double Uc1 = (double)(csize[c] - 1);
         const double gs = (double)gscale[c];
         const int32_t pb = pcstart[c];
@@ -392,6 +461,13 @@ __global__ void k_csr_values(int32_t nU, const int32_t* __restrict__ rowptr, con
             const int32_t j = csr_idx[f];
             const double x = (double)csr_r[f] / sum;
             const double2 pbj = pb_rank[pb + j];       // (p(j|C), b_j)
+            if constexpr (GEN) {
+                const double e = fy_e_general(pbj.y, pbj.x, (double)csr_r[f], sum, (double)G.deg_slot[s], G.beta_slot[s], G.s2_cluster[c], G.bt_scale, G.bt_by_n);
+                csr_x[f] = (float)x;
+                csr_e[f] = (float)(e * gs);
+                csr_q[f] = (float)(pbj.x * gs);
+                continue;
+            }
             double e = (1.0 - lambda) * (pbj.y - x) + lambda * Uc1 * pbj.x;
             if (!(e > 0.0)) e = 0.0;
             csr_x[f] = (float)x;
@@ -1353,7 +1429,9 @@ using namespace fy;
 
 // Everything about a job that depends only on the RATINGS and the CLUSTERING (and the rank's share): the CSR / CSC of fy_prep,
 // the statistics summed per (cluster, item), and -- filled by the first fy_rm2_score -- the row kernel's tables.  None of it
-// depends on lambda, the list length or numberOfItems.  The reference rebuilds all of it in every job (its mappers re-read and
+// depends on lambda, the list length or numberOfItems -- under Jelinek-Mercer.  With a Dirichlet prior or absolute discounting the
+// weights x = r' / d_v, b~, the bounds and the tables depend on (method, parameter), which are then part of the key (RM2Static::smooth):
+// the structure's csr_r / csc_r hold r', usum_slot holds d_v, b_rank holds b~ (PairPass).  The reference rebuilds all of it in every job (its mappers re-read and
 // re-shuffle the ratings, RM2Job.java:130-258); here it is kept on the fy_ratings object (fy_ratings::rm2_cache) and a later
 // job over the same ratings and the same clustering starts from it ("warm": fy_stats::prepared_from_cache).  fy_rm2_params::flags
 // & FY_RM2_NO_CACHE builds it afresh and does not keep it: the "cold" job, which bench.py times as its headline value.
@@ -1377,6 +1455,11 @@ struct RM2Static {
     int32_t max_item = -1;      // largest raw item id of the ratings (fy_ratings::max_item): the refinement pass maps raw ids to columns by table
     bool has_count = false;
     std::vector<int32_t> map_user, map_cluster, cluster_count;
+    Smoothing smooth;           // general smoothing: (method, parameter); Jelinek-Mercer: method 0 and param 0 whatever lambda is
+    // general smoothing: beta_v by slot, S2 per cluster, how b~ was formed (SmoothArgs)
+    DevBuf<double> beta_slot, s2_cluster;
+    double bt_scale = 0.0;
+    int32_t bt_by_n = 0;
     // fy_rm2_prepare
     Prepared P;
     int32_t slot_lo = 0, slot_hi = 0;
@@ -1400,6 +1483,8 @@ struct RM2Static {
     std::shared_ptr<void> request_state;   // what fy_rm2_score_users builds from the ratings and the clustering alone and keeps (fy_rm2_request.hip)
     bool matches(const fy_rm2_params* prm, int64_t n_map, const int32_t* mu, const int32_t* mc, const int32_t* cc) const {
         if (K != prm->number_of_clusters || rank != prm->rank || world != prm->world || (int64_t)map_user.size() != n_map || has_count != (cc != nullptr)) return false;
+        const Smoothing sm = smoothing_of(*prm);
+        if (sm.method != smooth.method || (sm.general() && sm.param != smooth.param)) return false;
         if (n_map && (memcmp(map_user.data(), mu, (size_t)n_map * 4) || memcmp(map_cluster.data(), mc, (size_t)n_map * 4))) return false;
         if (cc && memcmp(cluster_count.data(), cc, (size_t)K * 4)) return false;
         return true;
@@ -1428,6 +1513,7 @@ struct fy_rm2_job {
     DevBuf<float>& fx_rank;
     std::vector<float>& fx_bounds;
     bool count_balanced = false;   // scoring ownership of the users: equal counts instead of equal work (see owner_range)
+    SmoothArgs smooth_args() const { return SmoothArgs{S->beta_slot.get(), S->deg_slot.get(), S->s2_cluster.get(), S->bt_scale, S->bt_by_n}; }
     explicit fy_rm2_job(std::shared_ptr<RM2Static> s)
         : S(std::move(s)), P(S->P), slot_lo(S->slot_lo), slot_hi(S->slot_hi), partial(S->partial), b_rank(S->b_rank), usum_slot(S->usum_slot),
           walk_rank(S->walk_rank), cnt_rank(S->cnt_rank), deg_slot(S->deg_slot), fx_rank(S->fx_rank), fx_bounds(S->fx_bounds) {}
@@ -1649,7 +1735,7 @@ class SideValues {
         if (out) (void)hipEventDestroy(out);
     }
     // queues k_csr_values behind what `main_stream` holds: on the side stream when `beside` (and FY_OVERLAP_VALUES), else on main_stream
-    void launch(hipStream_t main_stream, bool beside, const Prepared& P, double lambda, JobArrays& A) {
+    void launch(hipStream_t main_stream, bool beside, const Prepared& P, double lambda, JobArrays& A, const fy_rm2_job* J) {
         if (launched) return;
         launched = true;
         hipStream_t vs = main_stream;
@@ -1666,9 +1752,16 @@ class SideValues {
             FY_HIP(hipStreamWaitEvent(sv, in, 0));
             vs = sv;
         }
-        k_csr_values<<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
-                                                                         P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
-                                                                         A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get());
+        if (J->S->smooth.general())
+            k_csr_values<true><<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
+                                                                                   P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
+                                                                                   A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get(),
+                                                                                   J->S->usum_slot.get(), J->smooth_args());
+        else
+            k_csr_values<false><<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
+                                                                                    P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
+                                                                                    A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get(),
+                                                                                    nullptr, SmoothArgs{});
         FY_KERNEL_CHECK();
         if (vs != main_stream) {
             FY_HIP(hipEventRecord(out, sv));
@@ -1719,7 +1812,12 @@ static void validate_params(const fy_rm2_params* p) {
     if (!p) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "params is NULL");
     if (p->number_of_clusters <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "numberOfClusters must be > 0 (got %d)", p->number_of_clusters);
     if (p->number_of_items <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "numberOfItems must be > 0 (got %d)", p->number_of_items);
-    if (!(p->lambda >= 0.0 && p->lambda <= 1.0)) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "lambda must be in [0, 1]");
+    const bool dir = p->flags & FY_RM2_SMOOTHING_DIRICHLET, ad = p->flags & FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT;
+    if (dir && ad) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "flags: FY_RM2_SMOOTHING_DIRICHLET and FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT are both set");
+    if (dir || ad) {
+        if (!(std::isfinite(p->lambda) && p->lambda >= 0.0))
+            FY_FAIL(FY_ERR_INVALID_ARGUMENT, "%s must be finite and >= 0 (got %g)", dir ? "mu" : "delta", p->lambda);
+    } else if (!(p->lambda >= 0.0 && p->lambda <= 1.0)) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "lambda must be in [0, 1]");
     if (p->world <= 0 || p->rank < 0 || p->rank >= p->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", p->rank, p->world);
     if (p->number_of_recommendations < 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "numberOfRecommendations must be >= 0");
 }
@@ -1867,6 +1965,11 @@ fy_rm2_job* fy::rm2_prepare(Context* ctx, const fy_rm2_params* prm, const fy_rat
     fresh->world = prm->world;
     fresh->max_item = R->max_item;
     fresh->has_count = cluster_count != nullptr;
+    {
+        const Smoothing sm = smoothing_of(*prm);
+        fresh->smooth.method = sm.method;
+        fresh->smooth.param = sm.general() ? sm.param : 0.0;
+    }
     if (n_map) { fresh->map_user.assign(map_user, map_user + n_map); fresh->map_cluster.assign(map_cluster, map_cluster + n_map); }
     if (cluster_count) fresh->cluster_count.assign(cluster_count, cluster_count + prm->number_of_clusters);
     std::unique_ptr<fy_rm2_job> J(new fy_rm2_job(fresh));
@@ -1924,9 +2027,34 @@ fy_rm2_job* fy::rm2_prepare(Context* ctx, const fy_rm2_params* prm, const fy_rat
         J->usum_slot.alloc(ctx, (size_t)P.nU);
         J->deg_slot.alloc(ctx, (size_t)P.nU);
         DevBuf<double2> ud_slot(ctx, (size_t)P.nU);
-        k_slot_user_arrays<<<grid_for(P.nU), 256, 0, ctx->stream>>>(P.nU, P.slot2du.get(), P.usum.get(), P.udeg.get(), J->usum_slot.get(),
-                                                                    J->deg_slot.get(), ud_slot.get());
-        FY_KERNEL_CHECK();
+        const Smoothing sm = S.smooth;
+        const double delta = sm.method == 2 ? sm.param : 0.0;
+        if (sm.general()) {
+            S.beta_slot.alloc(ctx, (size_t)P.nU);
+            S.s2_cluster.alloc(ctx, (size_t)P.K);
+            S.bt_scale = sm.param;
+            S.bt_by_n = sm.method == 2 ? 1 : 0;
+            k_slot_user_arrays_gen<<<grid_for(P.nU), 256, 0, ctx->stream>>>(P.nU, P.slot2du.get(), P.usum.get(), P.udeg.get(), sm.method, sm.param,
+                                                                            J->usum_slot.get(), J->deg_slot.get(), ud_slot.get(), S.beta_slot.get());
+            FY_KERNEL_CHECK();
+            k_cluster_s2<<<(unsigned)P.K, 256, 0, ctx->stream>>>(P.d_ucstart.get(), S.beta_slot.get(), S.s2_cluster.get());
+            FY_KERNEL_CHECK();
+            if (delta > 0.0) {      // the packed walk needs r' (not r) exactly representable in fp16
+                DevBuf<int32_t> d_flag(ctx, 1);
+                d_flag.zero();
+                k_discount_not_fp16<<<grid_for(P.nnz), 256, 0, ctx->stream>>>(P.nnz, delta, P.csc_r.get(), d_flag.get());
+                FY_KERNEL_CHECK();
+                int32_t flag = 0;
+                d2h(ctx, &flag, d_flag.get(), 1);
+                sync(ctx);
+                P.ratings_fp16_exact = flag == 0;
+                P.ratings_positive = false;      // (r <= delta leaves r' = 0)
+            }
+        } else {
+            k_slot_user_arrays<<<grid_for(P.nU), 256, 0, ctx->stream>>>(P.nU, P.slot2du.get(), P.usum.get(), P.udeg.get(), J->usum_slot.get(),
+                                                                        J->deg_slot.get(), ud_slot.get());
+            FY_KERNEL_CHECK();
+        }
         // the walk's per-rating weights are written by the statistics pass (same gather): x / s_v for the packed walk, x for the plain one
         TableCache& tc0 = S.tables;
         const bool use_pk0 = ctx->tune.cooc_pk && P.ratings_fp16_exact;
@@ -1944,15 +2072,32 @@ fy_rm2_job* fy::rm2_prepare(Context* ctx, const fy_rm2_params* prm, const fy_rat
         heavy_counters.zero();
         const PairPass PA{P.rank_pair.get(), P.pair_start.get(), P.pair_di.get(), P.csc_slot.get(), P.csc_r.get(), ud_slot.get(), J->slot_lo, J->slot_hi,
                           tc0.csc_x.get(), use_pk0 ? tc0.csc_x_over_s.get() : nullptr,
-                          J->partial.get(), J->b_rank.get(), J->walk_rank.get(), J->cnt_rank.get(), J->fx_rank.get()};
+                          J->partial.get(), J->b_rank.get(), J->walk_rank.get(), J->cnt_rank.get(), J->fx_rank.get(),
+                          delta, S.bt_scale, S.bt_by_n};
         const PairHeavy PH{heavy_col.get(), heavy_base.get(), chunk_col.get(), heavy_counters.get(), chunk_acc.get()};
-        if (P.nnz < 24 * (int64_t)P.nP) k_pair_pass<16><<<grid_for((int64_t)P.nP * 16, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
-        else k_pair_pass<64><<<grid_for((int64_t)P.nP * 64, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
-        FY_KERNEL_CHECK();
-        k_pair_chunks<<<(unsigned)std::min<size_t>(max_heavy, (size_t)ctx->num_cus * 32), 256, 0, ctx->stream>>>(PA, PH);
-        FY_KERNEL_CHECK();
-        k_pair_finish<<<(unsigned)std::min<size_t>(ceil_div((int64_t)max_heavy, 64), 1024), 64, 0, ctx->stream>>>(PA, PH);
-        FY_KERNEL_CHECK();
+        const unsigned g_chunks = (unsigned)std::min<size_t>(max_heavy, (size_t)ctx->num_cus * 32);
+        const unsigned g_finish = (unsigned)std::min<size_t>(ceil_div((int64_t)max_heavy, 64), 1024);
+        if (sm.general()) {
+            if (P.nnz < 24 * (int64_t)P.nP) k_pair_pass<16, true><<<grid_for((int64_t)P.nP * 16, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
+            else k_pair_pass<64, true><<<grid_for((int64_t)P.nP * 64, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
+            FY_KERNEL_CHECK();
+            k_pair_chunks<true><<<g_chunks, 256, 0, ctx->stream>>>(PA, PH);
+            FY_KERNEL_CHECK();
+            k_pair_finish<true><<<g_finish, 64, 0, ctx->stream>>>(PA, PH);
+            FY_KERNEL_CHECK();
+            if (delta > 0.0) {      // from here on the structure holds r'
+                k_discount_inplace<<<grid_for(P.nnz), 256, 0, ctx->stream>>>(P.nnz, delta, P.csr_r.get(), P.csc_r.get());
+                FY_KERNEL_CHECK();
+            }
+        } else {
+            if (P.nnz < 24 * (int64_t)P.nP) k_pair_pass<16, false><<<grid_for((int64_t)P.nP * 16, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
+            else k_pair_pass<64, false><<<grid_for((int64_t)P.nP * 64, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
+            FY_KERNEL_CHECK();
+            k_pair_chunks<false><<<g_chunks, 256, 0, ctx->stream>>>(PA, PH);
+            FY_KERNEL_CHECK();
+            k_pair_finish<false><<<g_finish, 64, 0, ctx->stream>>>(PA, PH);
+            FY_KERNEL_CHECK();
+        }
         if (J->slot_hi > J->slot_lo) {
             k_partial_total<<<grid_for(J->slot_hi - J->slot_lo), 256, 0, ctx->stream>>>(J->slot_lo, J->slot_hi, P.slot2du.get(),
                                                                                          P.usum.get(), counter.get());
@@ -2069,8 +2214,12 @@ static void score_preamble(fy_rm2_job* J, fy_result* R, const PackPlan& pack, bo
     A.a_rank.alloc(ctx, nP);
     A.b_rank32.alloc(ctx, nP);
     A.pb_rank.alloc(ctx, nP);
-    k_pair_p<<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
-                                           A.b_rank32.get(), A.pb_rank.get());
+    if (J->S->smooth.general())
+        k_pair_p<true><<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
+                                                     A.b_rank32.get(), A.pb_rank.get());
+    else
+        k_pair_p<false><<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
+                                                      A.b_rank32.get(), A.pb_rank.get());
     FY_KERNEL_CHECK();
     A.csr_x.alloc(ctx, P.nnz);
     A.csr_e.alloc(ctx, P.nnz);
@@ -2095,7 +2244,7 @@ static void score_preamble(fy_rm2_job* J, fy_result* R, const PackPlan& pack, bo
     // (the packed walk reads the packed CSR; the PLAIN walk's row kernel reads x itself: no overlap there.  Measured on one box, ML-25M
     // shape, ms per cold job: side stream from here 20.08, launched right in front of the row kernel 20.15, main stream 20.30 / 20.48 --
     // the table kernels in between wait on the L2's request rate and on dependent loads, and leave more room than the row kernel.)
-    side.launch(st, use_pk, P, lambda, A);
+    side.launch(st, use_pk, P, lambda, A, J);
 }
 
 // ---- 2. per-user meta for this rank's slots [lo, hi), output offsets; returns the number of list entries the rank emits
@@ -2331,7 +2480,7 @@ static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
                             (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
                 const int fxk = fx_exponent(&J->fx_bounds[3 * (size_t)c]);
                 CA.fx_scale = std::ldexp(1.0, fxk);
-                const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale[(size_t)c];
+                const double w2s = J->S->smooth.w2_of(lambda) * (double)X.gscale[(size_t)c];
                 MEpilogue ME{Mc, p.ldm, (float)w2s, std::ldexp(w2s, -fxk), p.pack24 ? 1 : 0, nullptr, p.ldb, 0, 0, nullptr, p.ldb64, nullptr};
                 const int n_items = (int)cooc_item_count(p.Ic, p.CH, p.nch, false);
                 CA.item_seg = F.flat_seg.get() + i_at;
@@ -2508,7 +2657,7 @@ static ClusterNumbers cluster_numbers(const ScoreShared& X, const Plan& p) {
     const int c = p.c;
     ClusterNumbers N{};
     N.fxk = (X.jp->use_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)c]) : -1;
-    N.w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale[(size_t)c];     // (1-l)^2 and the packed format's 2^-c
+    N.w2s = J->S->smooth.w2_of(lambda) * (double)X.gscale[(size_t)c];     // (1-l)^2 (general smoothing: w^2 = 1) and the packed format's 2^-c
     // refinement (k_refine_rows): packed clusters keep the unrounded fp32 values of their first 256 rows (and, in symmetric panel
     // mode, of the first 256 columns of the tail rows)
     N.refine = tune.refine && p.pack24 && !p.coop && N.fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
@@ -2728,6 +2877,7 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
         RA.head32 = H32.get(); RA.ld_head = ld_head; RA.tail32 = p.psym ? T32.get() : nullptr; RA.tail_from = p.p_eff;
         if (!RA.head32 || (p.psym && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", c);
         RA.unscale = 1.0 / (double)X.gscale[(size_t)c];
+        RA.general = J->S->smooth.general() ? 1 : 0; RA.G = J->smooth_args(); RA.cluster = c;
         RA.lambda = lambda; RA.ln_items = std::log((double)prm.number_of_items); RA.ln_users = std::log((double)p.Uc);
         RA.users_minus_1 = (double)(p.Uc - 1);
         RA.refine_c = tune.refine_c;
@@ -3177,6 +3327,7 @@ static PlanInput plan_input(const fy_rm2_job* J) {
     in.rank = prm.rank;
     in.world = prm.world;
     in.lambda = prm.lambda;
+    in.general_smoothing = J->S->smooth.general();
     in.workspace_bytes = prm.workspace_bytes;
     in.tune = J->ctx->tune;
     in.total_mem = J->ctx->total_mem;
@@ -3225,6 +3376,24 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
     }
     const int32_t nU = P.nU, nI = P.nI;
     PlanInput in = plan_input(J);
+    if (J->S->smooth.general()) {
+        // The cooperative path (fy_rm2_coop.hpp) knows Jelinek-Mercer alone.  Whether a cluster would take it is host arithmetic: the
+        // plan is made once ahead with a stand-in for the number of list rows, and such a job is refused before anything is queued.
+        PlanInput dry = in;
+        J->count_balanced = plan_count_balanced(dry);
+        dry.own_lo.resize((size_t)prm.world);
+        dry.own_hi.resize((size_t)prm.world);
+        for (int k = 0; k < prm.world; k++) owner_range(J, k, dry.own_lo[(size_t)k], dry.own_hi[(size_t)k]);
+        dry.n_recs = 1;
+        bool would_coop = false;
+        try {
+            would_coop = plan_job(dry).any_coop;
+        } catch (const PlanError&) {      // (the job's own plan below reports it)
+        }
+        if (would_coop)
+            FY_FAIL(FY_ERR_UNSUPPORTED, "fy_rm2_score: a cluster of this job would be scored cooperatively by all ranks, which supports Jelinek-Mercer "
+                                        "smoothing only (FY_RM2_SMOOTHING_DIRICHLET / FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT: run without collectives)");
+    }
     ScoreTune tune = ctx->tune;
     tune.seed_chunks = plan_seed(tune, prm.number_of_recommendations).seed_chunks;     // (0 = from the list length)
     const bool use_pk = tune.cooc_pk && P.ratings_fp16_exact;   // packed CSR for the row kernel
@@ -3350,6 +3519,8 @@ void fy::rm2_request_view(fy_rm2_job* J, RequestView& V) {
     V.b_rank = J->b_rank.get();
     V.walk_rank = J->walk_rank.get();
     V.usum_slot = J->usum_slot.get();
+    V.general = J->S->smooth.general();
+    if (V.general) { V.G = J->smooth_args(); V.fx_rank = J->fx_rank.get(); V.fx_bounds = J->fx_bounds.data(); }
     V.state = &J->S->request_state;
 }
 

@@ -29,6 +29,46 @@ struct fy_result {
 };
 
 namespace fy {
+// The smoothing of a job (include/filmyou.h, FY_RM2_SMOOTHING_*): c_vi = w x_vi + beta_v p_i with x_vi = r'_vi / d_v.
+// Jelinek-Mercer keeps the code it always had; the two other methods ("general") run the second instantiations of the statistics
+// pass and the table kernels, and the scalar w^2 = 1 wherever Jelinek-Mercer has (1 - lambda)^2.
+struct Smoothing {
+    int method = 0;        // 0 Jelinek-Mercer, 1 Dirichlet prior, 2 absolute discounting
+    double param = 0.0;    // lambda | mu | delta
+    bool general() const { return method != 0; }
+    // the scale of the Gram part of a term: (1 - lambda)^2, or w^2 = 1 (the expression Jelinek-Mercer always had, unchanged)
+    double w2_of(double lambda) const { return method == 0 ? (1.0 - lambda) * (1.0 - lambda) : 1.0; }
+};
+inline Smoothing smoothing_of(const fy_rm2_params& p) {
+    Smoothing s;
+    s.method = (p.flags & FY_RM2_SMOOTHING_DIRICHLET) ? 1 : (p.flags & FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT) ? 2 : 0;
+    s.param = p.lambda;
+    return s;
+}
+#ifdef __HIPCC__
+// What the kernels of a general-smoothing job read besides the arrays every job has: beta_v and n_v by slot (d_v is in the place
+// of s_v), S2 = sum of beta_v^2 per cluster, and how the statistics pass formed b~ (PairPass::bt_scale / bt_by_n, fy_rm2.hip).
+struct SmoothArgs {
+    const double* __restrict__ beta_slot;
+    const int32_t* __restrict__ deg_slot;
+    const double* __restrict__ s2_cluster;
+    double bt_scale;
+    int32_t bt_by_n;
+};
+// e~_uj = (b~_j - beta_u x_uj) + p_j (S2 - beta_u^2) = sum_{v != u} beta_v c_vj, both differences clamped at 0.  beta_u x_uj is
+// formed by the statistics pass's own rounded products, so a column whose only rater is u cancels to exactly 0 (-> ln 0 = -inf,
+// as Jelinek-Mercer's (1 - l)(b_j - x_uj) does).
+__device__ __forceinline__ double fy_e_general(double bt_j, double p_j, double r_uj, double d_u, double n_u, double beta_u, double s2,
+                                               double bt_scale, int32_t bt_by_n) {
+    const double inv = 1.0 / d_u;
+    const double wt = __dmul_rn(__dmul_rn(r_uj, inv), inv);
+    const double bx = __dmul_rn(bt_scale, bt_by_n ? __dmul_rn(wt, n_u) : wt);
+    double e1 = bt_j - bx, e2 = s2 - __dmul_rn(beta_u, beta_u);
+    if (!(e1 > 0.0)) e1 = 0.0;
+    if (!(e2 > 0.0)) e2 = 0.0;
+    return e1 + p_j * e2;
+}
+#endif
 fy_rm2_job* rm2_prepare(Context*, const fy_rm2_params*, const fy_ratings*, int64_t n_map, const int32_t* map_user,
                         const int32_t* map_cluster, const int32_t* cluster_count);
 void rm2_partial_stats(fy_rm2_job*, double** buf, int64_t* len);

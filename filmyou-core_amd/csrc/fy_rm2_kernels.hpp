@@ -1891,6 +1891,9 @@ struct RefineArgs {
     double users_minus_1;
     float refine_c;
     unsigned long long* __restrict__ n_refined;
+    // general smoothing (fy_rm2.hpp): csr_r holds r', usum_slot d_v, b_rank b~; term = G + p_j b~_c + p_c e~_uj
+    int32_t general, cluster;
+    SmoothArgs G;
 };
 __global__ __launch_bounds__(256) void k_refine_rows(RefineArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint64_t fy_refine_keys[];      // [4 waves][lp2]
@@ -1931,6 +1934,12 @@ __global__ __launch_bounds__(256) void k_refine_rows(RefineArgs A) {
                 if (A.tail32 && j >= A.tail_from) g32 = A.tail32[(int64_t)(j - A.tail_from) * A.head_rows + c];
                 else g32 = A.head32[(int64_t)min(j, c) * A.ld_head + max(j, c)];
                 const double pj = A.p_rank[j];
+                if (A.general) {
+                    const double eg = fy_e_general(A.b_rank[j], pj, (double)A.csr_r[beg + k], su, (double)A.G.deg_slot[slot], A.G.beta_slot[slot],
+                                                   A.G.s2_cluster[A.cluster], A.G.bt_scale, A.G.bt_by_n);
+                    sum += log(g32 * A.unscale + pj * bc + pc * eg);
+                    continue;
+                }
                 const double e = (1.0 - l) * (A.b_rank[j] - x) + l * A.users_minus_1 * pj;
                 const double term = g32 * A.unscale + l * (1.0 - l) * pj * bc + l * pc * e;
                 sum += log(term);

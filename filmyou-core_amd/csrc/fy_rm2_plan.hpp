@@ -121,6 +121,7 @@ struct PlanInput {
     // of fy_rm2_params
     int32_t number_of_recommendations = 0, rank = 0, world = 1;
     double lambda = 0.0;
+    bool general_smoothing = false;      // Dirichlet prior / absolute discounting: w^2 = 1 and fx_bounds are taken over r' and d_v
     int64_t workspace_bytes = 0;
     Tuning tune;
     uint64_t total_mem = 0;              // HBM of the device
@@ -174,7 +175,8 @@ inline PackPlan plan_pack24(const PlanInput& in) {
     for (int c = 0; c < K; c++) {
         const int32_t Ic_c = in.pcstart[c + 1] - in.pcstart[c];
         if (!pack24_allowed || Ic_c < tune.pack24_min_items || in.fx_bounds.size() < 3 * (size_t)(c + 1)) continue;
-        const double gmax = (1.0 - lambda) * (1.0 - lambda) * (double)in.fx_bounds[3 * (size_t)c] * (double)in.fx_bounds[3 * (size_t)c + 2];
+        const double w2 = in.general_smoothing ? 1.0 : (1.0 - lambda) * (1.0 - lambda);
+        const double gmax = w2 * (double)in.fx_bounds[3 * (size_t)c] * (double)in.fx_bounds[3 * (size_t)c + 2];
         if (!(gmax >= 0.0) || !std::isfinite(gmax)) continue;                     // unusable bound: fp32 rows
         const int cs = gmax > 0.0 ? std::max(0, std::ilogb(gmax) + 1) : 0;
         if (cs > 64) continue;
@@ -344,9 +346,14 @@ inline JobPlan plan_job(const PlanInput& in) {
         // bound by its pair visits (one cluster of ML-25M shape: 6.5e9 visits, 8 ms; the mirror 2.6 ms); a cluster of many (50
         // clusters: 1.3e8 visits each for 2.6e9 matrix elements) is bound by the rows it WRITES -- 1.65 ms for the half matrix plus 4.3 ms
         // to mirror 7.8 GB, against ~3.3 ms for the full walk: such clusters walk full rows and skip the mirror.
+        // The two walks do not build the same bits below the diagonal: an element is the fixed-point sum of (fp32 weight of the ROW's
+        // rating) x (rating of the column), so the full walk forms G[j][i] from the weights of row j and the symmetric walk mirrors the
+        // sum it formed from the weights of row i -- equal to ~1e-7, not to the bit.  A general-smoothing job keeps the symmetric walk
+        // here, so that the plain full pass and the branch and bound (always symmetric) score one matrix and return the same rows bit
+        // for bit; a Jelinek-Mercer job keeps the plan it always had.
         for (auto& p : plans) {
             const double deg2 = (size_t)p.c < in.cluster_deg2.size() ? (double)in.cluster_deg2[p.c] : (double)in.sum_deg2;
-            if (!p.prune && !p.coop && p.half && tune.full_walk_sparse && deg2 < (double)p.Ic * (double)p.Ic) p.half = false;
+            if (!p.prune && !p.coop && p.half && tune.full_walk_sparse && !in.general_smoothing && deg2 < (double)p.Ic * (double)p.Ic) p.half = false;
         }
         if (n_pruned >= tune.panel_min_clusters)
             for (auto& p : plans)

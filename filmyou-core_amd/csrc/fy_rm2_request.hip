@@ -69,6 +69,8 @@ struct SlabArgs {
     const double* __restrict__ usum_slot;
     const double* __restrict__ b_rank;
     double* __restrict__ slab;
+    const float* __restrict__ fx_rank;      // general smoothing: the row's bound is fx_rank[3 pos] * rmax (null: b_j)
+    double rmax;
 };
 
 // Workgroup = (row j of the slab, column chunk).  The accumulators hold round(x_vj x_vi 2^k) with k per row from b_j = sum_v x_vj, an
@@ -82,7 +84,8 @@ __global__ __launch_bounds__(SLAB_THREADS) void k_req_slab(SlabArgs A) {
     const int32_t pos = A.pbase + A.J[row];
     const int32_t pr = A.rank_pair[pos];
     const int32_t q0 = A.pair_start[pr], q1 = A.pair_start[pr + 1];
-    int ex = ilogb(A.b_rank[pos]);
+    // (general smoothing: G[j][i] = sum_v (r'_vj / d_v^2) r'_vi <= (sum_v r'_vj / d_v^2) * (largest r' of the cluster))
+    int ex = ilogb(A.fx_rank ? (double)A.fx_rank[3 * (int64_t)pos] * A.rmax : A.b_rank[pos]);
     ex = max(-900, min(ex, 60));
     const double scale = ldexp(1.0, 61 - ex), unscale = ldexp(1.0, ex - 61);
     const int g = threadIdx.x / SLAB_GROUP, gl = threadIdx.x % SLAB_GROUP;
@@ -116,6 +119,8 @@ struct ScoreReqArgs {
     double lambda, ln_items, ln_users, users_minus_1;
     float* __restrict__ S;
     int64_t ldS;
+    int32_t general, cluster;               // general smoothing: b_rank is b~, csr_r r', usum_slot d_v
+    SmoothArgs G;
 };
 
 __global__ __launch_bounds__(SCORE_COLS) void k_req_score(ScoreReqArgs A) {
@@ -127,8 +132,10 @@ __global__ __launch_bounds__(SCORE_COLS) void k_req_score(ScoreReqArgs A) {
     const int32_t f0 = A.rowptr[slot], f1 = A.rowptr[slot + 1];
     const double s = A.usum_slot[slot];
     const bool live = i < A.Ic;
-    const double a_i = live ? A.lambda * A.p_rank[i] : 0.0, b_i = live ? A.b_rank[i] : 0.0;
-    const double w2 = (1.0 - A.lambda) * (1.0 - A.lambda), w1 = A.lambda * (1.0 - A.lambda);
+    double a_i = live ? A.lambda * A.p_rank[i] : 0.0;
+    const double b_i = live ? A.b_rank[i] : 0.0;
+    double w2 = (1.0 - A.lambda) * (1.0 - A.lambda), w1 = A.lambda * (1.0 - A.lambda);
+    if (A.general) { a_i = live ? A.p_rank[i] : 0.0; w2 = 1.0; w1 = 1.0; }      // term = G + p_j b~_i + p_i e~_uj
     double acc = 0.0;
     bool rated = false;
     for (int32_t base = f0; base < f1; base += SCORE_COLS) {       // (block-uniform)
@@ -139,6 +146,9 @@ __global__ __launch_bounds__(SCORE_COLS) void k_req_score(ScoreReqArgs A) {
             const double p = A.p_rank[j];
             double e = (1.0 - A.lambda) * (A.b_rank[j] - x) + A.lambda * A.users_minus_1 * p;      // = sum_{v != u} c_vj
             if (!(e > 0.0)) e = 0.0;
+            if (A.general)
+                e = fy_e_general(A.b_rank[j], p, (double)A.csr_r[f], s, (double)A.G.deg_slot[slot], A.G.beta_slot[slot], A.G.s2_cluster[A.cluster],
+                                 A.G.bt_scale, A.G.bt_by_n);
             sh_e[threadIdx.x] = e;
             sh_q[threadIdx.x] = w1 * p;
             sh_j[threadIdx.x] = j;
@@ -379,7 +389,8 @@ fy_result* rm2_score_users(fy_rm2_job* J, const fy_rm2_request* rq) {
             const size_t sp_c = t_cooc.begin();
             if ((int64_t)nJ * nch > 0x7FFFFFFFll) FY_FAIL(FY_ERR_UNSUPPORTED, "fy_rm2_score_users: %d slab rows x %d chunks exceed the launch grid", nJ, nch);
             SlabArgs SA{d_plan.get(), nJ, Ic, CH, nch, pbase, S.stride, ld, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.csc_r.get(),
-                        S.choff.get(), P.csr_idx.get(), P.csr_r.get(), V.usum_slot, V.b_rank, slab.get()};
+                        S.choff.get(), P.csr_idx.get(), P.csr_r.get(), V.usum_slot, V.b_rank, slab.get(),
+                        V.general ? V.fx_rank : nullptr, V.general ? (double)V.fx_bounds[3 * (size_t)c + 2] : 0.0};
             k_req_slab<<<(unsigned)((int64_t)nJ * nch), SLAB_THREADS, (size_t)CH * sizeof(unsigned long long), st>>>(SA);
             FY_KERNEL_CHECK();
             t_cooc.end(sp_c);
@@ -395,7 +406,7 @@ fy_result* rm2_score_users(fy_rm2_job* J, const fy_rm2_request* rq) {
                 const size_t sp_s = t_score.begin();
                 ScoreReqArgs A{d_slot + first, d_plan.get() + nJ, slab.get(), ld, Ic, n_chunks, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), V.usum_slot,
                                p_rank.get() + pbase, V.b_rank + pbase, lambda, std::log((double)prm.number_of_items), std::log((double)Uc),
-                               (double)(Uc - 1), Srows.get(), ldS};
+                               (double)(Uc - 1), Srows.get(), ldS, V.general ? 1 : 0, c, V.G};
                 k_req_score<<<(unsigned)((int64_t)nb * n_chunks), SCORE_COLS, 0, st>>>(A);
                 FY_KERNEL_CHECK();
                 t_score.end(sp_s);

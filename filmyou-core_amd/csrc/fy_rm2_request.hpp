@@ -19,6 +19,12 @@ struct RequestView {
     const double* b_rank = nullptr;          // b_i = sum_v x_vi per (cluster, item), rank order
     const long long* walk_rank = nullptr;    // sum of the raters' degrees per (cluster, item), rank order
     const double* usum_slot = nullptr;       // s_v by slot
+    // general smoothing (fy_rm2.hpp): P holds r', usum_slot d_v, b_rank b~; the slab's fixed-point scale comes from the row kernel's
+    // bounds (fx_rank: per (cluster, item) sum of r' / d_v^2; fx_bounds: per cluster, [3 c + 2] = largest r'), b~ bounds no Gram row
+    bool general = false;
+    SmoothArgs G{};
+    const float* fx_rank = nullptr;          // device, 3 per (cluster, item)
+    const float* fx_bounds = nullptr;        // host, 3 per cluster
     std::shared_ptr<void>* state = nullptr;  // what the first request builds and the job keeps (fy_rm2_request.hip: RequestState)
 };
 void rm2_request_view(fy_rm2_job*, RequestView&);

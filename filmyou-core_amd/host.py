@@ -394,9 +394,15 @@ class RM2Job:
 
     ``conf`` carries the reference's keys: lambda, numberOfItems, numberOfClusters, numberOfRecommendations,
     filterUsers (clusterSplit / splitSize are accepted and ignored: they only partition the reference's reduce groups
-    and never change a score -- M/common/AbstractByClusterAndCountMapper.java:86-102)."""
+    and never change a score -- M/common/AbstractByClusterAndCountMapper.java:86-102).
+
+    Smoothing of the user language model (include/filmyou.h, FY_RM2_SMOOTHING_*): ``smoothing`` = ``jm`` (the default: the
+    reference's Jelinek-Mercer, parameter ``lambda``), ``dirichlet`` (parameter ``mu``) or ``absoluteDiscounting`` (parameter
+    ``delta``), matched without regard to case.  ``mu`` / ``delta`` have no default: the chosen method's parameter must be set."""
 
     JOB_NAME = "RM2"
+    # smoothing name (lower case) -> (flag bit of fy_rm2_params::flags, the Configuration key of the method's parameter)
+    SMOOTHING = {"jm": (0, "lambda"), "dirichlet": (2, "mu"), "absolutediscounting": (4, "delta")}
 
     def __init__(self, conf, ctx=None):
         self.conf = conf
@@ -409,9 +415,15 @@ class RM2Job:
         if n_clusters is None or n_clusters <= 0 or n_items is None or n_items <= 0:
             # AbstractJob.parseArguments rejects a missing required option (TestRMRecommenderJob.java:39-74)
             raise ValueError("numberOfClusters and numberOfItems are required")
-        lam = float(conf.get("lambda"))    # Double.valueOf(conf.get("lambda")), AbstractRM2Reducer.java:108
+        name = str(conf.get("smoothing", "jm"))
+        if name.lower() not in self.SMOOTHING:
+            raise ValueError("smoothing must be jm, dirichlet or absoluteDiscounting (got %r)" % name)
+        flag, key = self.SMOOTHING[name.lower()]
+        if conf.get(key) is None:
+            raise ValueError("smoothing=%s needs %s" % (name, key))
+        lam = float(conf.get(key))    # (jm) Double.valueOf(conf.get("lambda")), AbstractRM2Reducer.java:108
         return _native.RM2Params(lam, n_items, conf.getInt("numberOfRecommendations", 1000),
-                                 conf.getInt("filterUsers", 0), n_clusters, int(rank), int(world), 0,
+                                 conf.getInt("filterUsers", 0), n_clusters, int(rank), int(world), flag,
                                  int(workspace_bytes))
 
     def prepare(self, ratings, clustering=None, clustering_count=None, rank=0, world=1, workspace_bytes=0, cache=True):
@@ -1142,7 +1154,8 @@ class RMRecommenderDriver:
 
     Configuration keys: numberOfUsers, numberOfItems, numberOfClusters (required, :90-92) and the driver's own defaults
     (:93-119) for usersPerSubCluster (-1), numberOfIterations (10), numberOfRecommendations (1000), normalizationFrequency (12),
-    lambda, filterUsers.  One ``Ratings`` object serves every stage.  ``run`` returns ``(recommendations, (users, clusters,
+    lambda, filterUsers, and smoothing / mu / delta, which reach the RM2 stage as they are (``RM2Job``).  One ``Ratings`` object
+    serves every stage.  ``run`` returns ``(recommendations, (users, clusters,
     counts))``: the ``Recommendations`` of ``RM2Job.run`` (None when numberOfRecommendations <= 0) and the clustering the RM2 job
     was -- or would have been -- given.  After refinement the cluster ids are parent * ceil(numberOfUsers / numberOfClusters) +
     sub-cluster, sparse in a long ``counts``; the RM2 job then runs with numberOfClusters = len(counts) (the reference sets the

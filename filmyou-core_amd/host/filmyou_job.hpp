@@ -14,6 +14,7 @@
 // job takes rating triples and hands back rows through a sink callback shaped like writePreference
 // (M/rm/AbstractRM2Reducer.java:404-406).
 #pragma once
+#include <cctype>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -104,6 +105,20 @@ inline Ratings applyWrites(const Ratings& source, const Writes& w, fy_ratings_up
     return out;
 }
 
+// The smoothing of the user language model (include/filmyou.h, FY_RM2_SMOOTHING_*) from the Configuration keys `smoothing` (jm --
+// the default, parameter `lambda` --, dirichlet with `mu`, absoluteDiscounting with `delta`; case does not matter) into
+// fy_rm2_params::flags and ::lambda.  mu / delta have no default; an unknown name or a missing parameter is std::invalid_argument.
+inline void setSmoothing(const Configuration& conf, fy_rm2_params& p) {
+    std::string name = conf.get("smoothing", "jm");
+    for (char& ch : name) ch = (char)std::tolower((unsigned char)ch);
+    const char* key = "lambda";   // Double.valueOf(conf.get("lambda")), AbstractRM2Reducer.java:108
+    if (name == "dirichlet") { p.flags |= FY_RM2_SMOOTHING_DIRICHLET; key = "mu"; }
+    else if (name == "absolutediscounting") { p.flags |= FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT; key = "delta"; }
+    else if (name != "jm") throw std::invalid_argument("smoothing must be jm, dirichlet or absoluteDiscounting (got " + conf.get("smoothing") + ")");
+    if (!conf.has(key)) throw std::invalid_argument("smoothing=" + name + " needs " + key);
+    p.lambda = std::stod(conf.get(key));
+}
+
 // writePreference(context, userId, itemId, score, cluster)
 using PreferenceSink = std::function<void(int32_t user, int32_t item, float score, int32_t cluster)>;
 
@@ -119,7 +134,7 @@ class RM2Job {
 
     int run(const Ratings& r, const Clustering& c, const PreferenceSink& sink) {
         fy_rm2_params p{};
-        p.lambda = std::stod(conf_.get("lambda"));   // Double.valueOf(conf.get("lambda")), AbstractRM2Reducer.java:108
+        setSmoothing(conf_, p);
         p.number_of_items = (int32_t)conf_.getInt("numberOfItems", -1);
         p.number_of_clusters = (int32_t)conf_.getInt("numberOfClusters", -1);
         if (p.number_of_items <= 0 || p.number_of_clusters <= 0)
@@ -273,7 +288,7 @@ class RM2Job {
    private:
     fy_rm2_params params() const {
         fy_rm2_params p{};
-        p.lambda = std::stod(conf_.get("lambda"));
+        setSmoothing(conf_, p);
         p.number_of_items = (int32_t)conf_.getInt("numberOfItems", -1);
         p.number_of_clusters = (int32_t)conf_.getInt("numberOfClusters", -1);
         if (p.number_of_items <= 0 || p.number_of_clusters <= 0) throw std::invalid_argument("numberOfItems and numberOfClusters are required");

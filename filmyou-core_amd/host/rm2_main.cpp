@@ -1,9 +1,13 @@
 // rm2_main.cpp -- a tiny C++ driver over fy::host::RM2Job, used by tests/test_cpp_host_gpu.py.
 //   rm2_main <ratings.txt> <clustering.txt|-> <lambda> <numberOfItems> <numberOfClusters> <numberOfRecommendations>
 // ratings.txt: "user item score" per line; clustering.txt: "user cluster" per line.  Prints "user item score cluster".
+// Trailing key=value arguments (smoothing=dirichlet mu=100) are put into the job's Configuration as they are.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
 
 #include "filmyou_job.hpp"
 
@@ -86,6 +90,12 @@ static int main_recommend_users(char** a) {
 }
 
 int main(int argc, char** argv) {
+    std::vector<std::pair<std::string, std::string>> extra;      // trailing key=value arguments
+    while (argc > 1 && argv[argc - 1][0] != '-' && strchr(argv[argc - 1], '=') && !strchr(argv[argc - 1], '/')) {
+        const char* eq = strchr(argv[argc - 1], '=');
+        extra.emplace_back(std::string((const char*)argv[argc - 1], (size_t)(eq - argv[argc - 1])), std::string(eq + 1));
+        argc--;
+    }
     if (argc == 9 && strcmp(argv[1], "--files") == 0) return main_files(argv + 2);
     if (argc == 8 && strcmp(argv[1], "--recommend-users") == 0) return main_recommend_users(argv + 2);
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
@@ -117,6 +127,7 @@ int main(int argc, char** argv) {
     conf.set("numberOfItems", argv[4]);
     conf.set("numberOfClusters", argv[5]);
     conf.set("numberOfRecommendations", argv[6]);
+    for (const auto& kv : extra) conf.set(kv.first, kv.second);
     try {
         if (writes_file) {
             fy::host::Writes w;

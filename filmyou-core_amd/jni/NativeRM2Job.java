@@ -35,14 +35,38 @@ public class NativeRM2Job extends AbstractJob {
     /** One GPU: fy_rm2_run.  Several: fy_context_create(localDevice) + fy_rm2_prepare + fy_rccl_create + fy_rm2_set_collectives +
      *  fy_rm2_score (the item statistics are all-gathered over xGMI inside the library).  clusterCount = the clusteringCount file
      *  as numberOfClusters ints: the reducer relies on it being exact (AbstractRM2Reducer.java:143-160), the library validates it. */
-    private static native long run(double lambda, int numberOfItems, int numberOfRecommendations, int filterUsers,
+    private static native long run(double lambda, int smoothingFlags, int numberOfItems, int numberOfRecommendations, int filterUsers,
             int numberOfClusters, long nnz, ByteBuffer user, ByteBuffer item, ByteBuffer score, long nMap,
             ByteBuffer mapUser, ByteBuffer mapCluster, ByteBuffer clusterCount, int rank, int world, int localDevice, byte[] rcclId);
 
     /** One GPU, lists for the listed users alone (fy_rm2_prepare + fy_rm2_score_users): the configuration key usersFile. */
-    private static native long runUsers(double lambda, int numberOfItems, int numberOfRecommendations, int filterUsers,
+    private static native long runUsers(double lambda, int smoothingFlags, int numberOfItems, int numberOfRecommendations, int filterUsers,
             int numberOfClusters, long nnz, ByteBuffer user, ByteBuffer item, ByteBuffer score, long nMap,
             ByteBuffer mapUser, ByteBuffer mapCluster, ByteBuffer clusterCount, int localDevice, long nUsers, ByteBuffer users);
+
+    /** Smoothing of the user language model (filmyou.h, FY_RM2_SMOOTHING_*): smoothing = jm (default, parameter lambda), dirichlet
+     *  (parameter mu) or absoluteDiscounting (parameter delta), case-insensitive; mu / delta have no default. */
+    public static final String SMOOTHING_NAME = "smoothing", MU_NAME = "mu", DELTA_NAME = "delta";
+    private static final int SMOOTHING_DIRICHLET = 2, SMOOTHING_ABSOLUTE_DISCOUNT = 4;
+
+    /** {flag bits, the configuration key of the method's parameter} */
+    private static Object[] smoothing(final Configuration conf) {
+        final String name = conf.get(SMOOTHING_NAME, "jm");
+        final Object[] out;
+        if (name.equalsIgnoreCase("jm")) {
+            out = new Object[] { 0, RM2Job.LAMBDA_NAME };
+        } else if (name.equalsIgnoreCase("dirichlet")) {
+            out = new Object[] { SMOOTHING_DIRICHLET, MU_NAME };
+        } else if (name.equalsIgnoreCase("absoluteDiscounting")) {
+            out = new Object[] { SMOOTHING_ABSOLUTE_DISCOUNT, DELTA_NAME };
+        } else {
+            throw new IllegalArgumentException("smoothing must be jm, dirichlet or absoluteDiscounting (got " + name + ")");
+        }
+        if (conf.get((String) out[1]) == null) {
+            throw new IllegalArgumentException("smoothing=" + name + " needs " + out[1]);
+        }
+        return out;
+    }
 
     /** usersFile: one id per line; a line that is not an int is skipped (like the reference's "itemsFile line ignored") */
     public static final String USERS_FILE_NAME = "usersFile";
@@ -137,12 +161,15 @@ public class NativeRM2Job extends AbstractJob {
             throw new IllegalArgumentException("usersFile cannot be combined with filmyou.world > 1 (the collective path serves no requests)");
         }
         final ByteBuffer ids = usersFile != null ? readIds(usersFile) : null;
+        final Object[] smoothing = smoothing(conf);
+        final int smoothingFlags = (Integer) smoothing[0];
+        final double parameter = Double.valueOf(conf.get((String) smoothing[1]));
         final long h = usersFile != null
-                ? runUsers(Double.valueOf(conf.get(RM2Job.LAMBDA_NAME)), conf.getInt(RMRecommenderDriver.numberOfItems, -1),
+                ? runUsers(parameter, smoothingFlags, conf.getInt(RMRecommenderDriver.numberOfItems, -1),
                         conf.getInt(RMRecommenderDriver.numberOfRecommendations, -1), conf.getInt(RMRecommenderDriver.filterUsers, 0),
                         numberOfClusters, nnz, coo[0], coo[1], coo[2], nMap, map[0], map[1], clusterCount,
                         conf.getInt("filmyou.localDevice", 0), ids.limit() / 4, ids)
-                : run(Double.valueOf(conf.get(RM2Job.LAMBDA_NAME)), conf.getInt(RMRecommenderDriver.numberOfItems, -1),
+                : run(parameter, smoothingFlags, conf.getInt(RMRecommenderDriver.numberOfItems, -1),
                 conf.getInt(RMRecommenderDriver.numberOfRecommendations, -1), conf.getInt(RMRecommenderDriver.filterUsers, 0),
                 numberOfClusters, nnz, coo[0], coo[1], coo[2], nMap, map[0], map[1], clusterCount, rank, world,
                 conf.getInt("filmyou.localDevice", rank), world > 1 ? unhex(conf.get(RCCL_ID_NAME)) : null);

@@ -41,10 +41,10 @@ static void release(JniResult* r) {
     delete r;
 }
 
-// private static native long run(double lambda, int numberOfItems, int numberOfRecommendations, int filterUsers,
+// private static native long run(double lambda, int smoothingFlags, int numberOfItems, int numberOfRecommendations, int filterUsers,
 //     int numberOfClusters, long nnz, ByteBuffer user, ByteBuffer item, ByteBuffer score,
 //     long nMap, ByteBuffer mapUser, ByteBuffer mapCluster, ByteBuffer clusterCount, int rank, int world, int localDevice, byte[] rcclId);
-JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_run(JNIEnv* env, jclass, jdouble lambda, jint numberOfItems,
+JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_run(JNIEnv* env, jclass, jdouble lambda, jint smoothingFlags, jint numberOfItems,
                                                                       jint numberOfRecommendations, jint filterUsers,
                                                                       jint numberOfClusters, jlong nnz, jobject user, jobject item,
                                                                       jobject score, jlong nMap, jobject mapUser,
@@ -52,7 +52,8 @@ JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_run(JNIEnv* env,
                                                                       jint localDevice, jbyteArray rcclId) {
     fy_rm2_params p;
     std::memset(&p, 0, sizeof p);
-    p.lambda = lambda;
+    p.lambda = lambda;                       // the chosen method's parameter: lambda, mu or delta
+    p.flags = (uint32_t)smoothingFlags;      // FY_RM2_SMOOTHING_* (0 = Jelinek-Mercer)
     p.number_of_items = numberOfItems;
     p.number_of_recommendations = numberOfRecommendations;
     p.filter_users = filterUsers;
@@ -92,7 +93,7 @@ JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_run(JNIEnv* env,
 }
 
 // private static native long runUsers(... , int localDevice, long nUsers, ByteBuffer users): one GPU, fy_rm2_score_users
-JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_runUsers(JNIEnv* env, jclass, jdouble lambda, jint numberOfItems,
+JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_runUsers(JNIEnv* env, jclass, jdouble lambda, jint smoothingFlags, jint numberOfItems,
                                                                            jint numberOfRecommendations, jint filterUsers,
                                                                            jint numberOfClusters, jlong nnz, jobject user, jobject item,
                                                                            jobject score, jlong nMap, jobject mapUser,
@@ -100,7 +101,8 @@ JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_runUsers(JNIEnv*
                                                                            jlong nUsers, jobject users) {
     fy_rm2_params p;
     std::memset(&p, 0, sizeof p);
-    p.lambda = lambda;
+    p.lambda = lambda;                       // the chosen method's parameter: lambda, mu or delta
+    p.flags = (uint32_t)smoothingFlags;      // FY_RM2_SMOOTHING_* (0 = Jelinek-Mercer)
     p.number_of_items = numberOfItems;
     p.number_of_recommendations = numberOfRecommendations;
     p.filter_users = filterUsers;

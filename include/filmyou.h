@@ -128,7 +128,8 @@ int fy_ratings_copy_out(const fy_ratings*, int32_t* user, int32_t* item, float* 
 /* ------------------------------------------------------------------ RM2 job
  * Field names follow the Hadoop Configuration keys of M/rmrecommender/RMRecommenderDriver.java:49-120. */
 typedef struct {
-    double lambda;                      /* "lambda" (default 0.1), Jelinek-Mercer smoothing */
+    double lambda;                      /* "lambda" (default 0.1), Jelinek-Mercer smoothing; with a FY_RM2_SMOOTHING_* flag: that method's
+                                           parameter ("mu" / "delta"), see below */
     int32_t number_of_items;            /* "numberOfItems": global item count, used only in pvpi (AbstractRM2Reducer.java:327-329) */
     int32_t number_of_recommendations;  /* "numberOfRecommendations" (default 1000) */
     int32_t filter_users;               /* "filterUsers": users with id < this get no list (AbstractRM2Reducer.java:221-223) */
@@ -144,6 +145,29 @@ typedef struct {
  * starts from it -- fy_stats::prepared_from_cache / tables_from_cache.  The reference has no such state: every RM2Job.run re-reads
  * and re-shuffles the ratings (RM2Job.java:130-258).  FY_RM2_NO_CACHE: build everything in this job, keep nothing (the "cold" job). */
 #define FY_RM2_NO_CACHE 1u
+/* Smoothing of the user language model.  The reference has one estimator, c_vi = (1-l) r_vi / s_v + l p(i|C)
+ * (probItemGivenUser, AbstractRM2Reducer.java:384-389: Jelinek-Mercer); the two other standard smoothings have the same shape
+ *     c_vi = w * r'_vi / d_v + beta_v * p(i|C)
+ *
+ *   method                                   r'_vi              d_v        beta_v            w
+ *   (no bit) Jelinek-Mercer, l in [0, 1]     r_vi               s_v        l                 1 - l
+ *   FY_RM2_SMOOTHING_DIRICHLET, mu >= 0      r_vi               s_v + mu   mu / (s_v + mu)   1
+ *   FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT,      max(r_vi - d, 0)   s_v        d * n_v / s_v     1
+ *                          delta = d >= 0
+ *
+ * with s_v the user's rating sum and n_v the number of its kept ratings (score > 0).  The method's parameter travels in
+ * fy_rm2_params::lambda: l (validated to [0, 1] as always), mu or delta (finite and >= 0); anything else, and both bits set, is
+ * FY_ERR_INVALID_ARGUMENT.  Everything else about a job is the same for the three methods: the candidates of a user are the items
+ * of its cluster it has not rated (under absolute discounting a rating <= delta is still a rated item: it is no candidate and
+ * contributes a log term), the side outputs (userSum, itemColl, the total, quirk Q1) are those of the raw ratings, mu = 0 and
+ * delta = 0 give -inf for a candidate never co-rated with a rated item as l = 0 does, and a one-user cluster gives -inf rows.
+ * What a caching job keeps on the fy_ratings object depends on (method, parameter) for the two new methods -- a caching job with
+ * another key releases the kept state and builds its own, as for another clustering -- and on nothing of the kind for
+ * Jelinek-Mercer, whose jobs are bit for bit what they were before these flags existed.
+ * A job that would score a cluster cooperatively (collectives installed, see fy_rm2_set_collectives) answers
+ * FY_ERR_UNSUPPORTED from fy_rm2_score with either flag; the context stays usable. */
+#define FY_RM2_SMOOTHING_DIRICHLET 2u
+#define FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT 4u
 
 /* Stage 1 (jobs RM2-1/RM2-2 up to the exchange): score > 0 filter, CSR/CSC in HBM, cluster routing, user sums,
  * and this rank's PARTIAL per-item rating sums + partial floor-sum total.
