@@ -120,3 +120,26 @@ def seeded_initial(m, kc, seed):
     H0 = [initial_matrix(seed, c, 0, len(m["users"][c]), kc[c]) for c in range(len(kc))]
     W0 = [initial_matrix(seed, c, 1, len(m["items"][c]), kc[c]) for c in range(len(kc))]
     return H0, W0
+
+
+DRIVER_PPC_SEED = 4
+
+
+def driver_initial(n_users, n_items, K, seed):
+    """RMRecommenderDriver.run's draw of the top-level PPC run's initial matrices, restated: H first, then W, both in (0, 1]."""
+    rng = np.random.default_rng(seed)
+    H = 1.0 - rng.random((n_users, K))
+    W = 1.0 - rng.random((n_items, K))
+    return H, W
+
+
+def driver_ppc_stage(case, seed, iterations=10, normalization_frequency=12):
+    """The driver's first stage from the oracles: PPC with the driver's defaults, then the argmax.  Returns (users, clusters,
+    counts, near_tie mask, H0, W0); near_tie as in composed_refinement."""
+    u, i, s = case["coo"]
+    H0, W0 = driver_initial(case["n_users"], case["n_items"], case["K"], seed)
+    H, _ = oracle.nmf(u, i, s, H0, W0, iterations=iterations, ppc=True, normalization_frequency=normalization_frequency)
+    users, clusters, counts = oracle.cluster_assign(H, first_user=1, n_clusters=case["K"])
+    top = np.sort(H, axis=1)[:, ::-1]
+    ties = top[:, 0] - top[:, 1] <= 1e-8 * np.abs(top[:, 0])
+    return users, clusters, counts, ties, H0, W0

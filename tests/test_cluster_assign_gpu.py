@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import factor_edge_inputs as FE
 import oracle
 from util import pkg
 
@@ -44,7 +45,9 @@ def test_reference_sub_clustering(ctx, golden):
     assert counts.sum() == 30 and len(counts) == 2 * 15
 
 
-@pytest.mark.parametrize("n,k,device", [(1000, 5, False), (4097, 50, True), (300, 200, False), (1, 1, False), (513, 64, True), (777, 65, True)])
+@pytest.mark.parametrize("n,k,device", [(1000, 5, False), (4097, 50, True), (300, 200, False), (1, 1, False), (513, 64, True), (777, 65, True),
+                                        (FE.ASSIGN_WIDE_ROWS, 65, True),       # more rows than the wave-per-row launch has waves
+                                        (FE.ASSIGN_THREAD_ROWS, 2, True)])     # more rows than the thread-per-row launch has threads
 def test_random_vs_oracle(ctx, n, k, device):
     rng = np.random.default_rng(n * 131 + k)
     H = rng.random((n, k))
@@ -52,11 +55,17 @@ def test_random_vs_oracle(ctx, n, k, device):
     if n > 10:
         H[3, :] = H[3, 0]                                                          # a row of ties: first index
         H[5, :] = -np.inf                                                          # nothing exceeds -inf: -1
+        H[n - 3, :] = np.arange(k)                                                 # and one of each where a wrapped loop ends:
+        H[n - 3, k - 1] = np.nan                                                   # the would-be maximum is NaN
+        H[n - 2, :] = H[n - 2, 0]
+        H[n - 1, :] = -np.inf
     want_u, want_c = oracle.cluster_assign(H, first_user=7)
     job = pkg().ClusterAssignmentJob(ctx)
     Hd = torch.from_numpy(H).cuda() if device else H
     users, clusters = job._assign(Hd, 7, 0, np.zeros(0, np.int32))
     assert np.array_equal(users, want_u) and np.array_equal(clusters, want_c)
+    if n > 10:
+        assert clusters[n - 3] == max(k - 2, 0) and clusters[n - 2] == 0 and clusters[n - 1] == -1
     if n > 10:
         with pytest.raises(pkg().FilmYouError):      # the -1 row cannot be counted
             job.run(Hd, first_user=7)

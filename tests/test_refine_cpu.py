@@ -175,3 +175,13 @@ def test_oracle_alone_stays_within_the_near_tie_cap():
         assert counts.sum() == case["n_users"] == len(users)
         assert ties.sum() <= 0.001 * len(users), (seed, int(ties.sum()))
         assert len(np.unique(clusters)) > case["K"]              # the sub-runs really split their parents
+
+
+def test_oracle_alone_leaves_the_driver_ppc_stage_without_near_ties():
+    """test_driver_ppc_stage_matches_the_oracle excuses near-tie users under the same cap; with the ML-100K case's 943 users the cap
+    admits none, and seed 4 has none."""
+    case = RR.ml100k_case()
+    users, clusters, counts, ties, _, _ = RR.driver_ppc_stage(case, RR.DRIVER_PPC_SEED)
+    assert len(users) == case["n_users"] == counts.sum()
+    assert ties.sum() <= 0.001 * len(users), int(ties.sum())
+    assert (counts > 0).all()                                    # the PPC stage uses every cluster
