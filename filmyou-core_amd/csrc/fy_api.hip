@@ -56,6 +56,8 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_COOC_PLANES")) t.cooc_planes = atoi(e) != 0;
     if (const char* e = getenv("FY_SCORE_HEAVY")) { int v = atoi(e); if (v >= 0) t.score_heavy = v; }
     if (const char* e = getenv("FY_SCORE_WALK")) t.score_walk = atoi(e) != 0;
+    if (const char* e = getenv("FY_COOC_EPI")) t.cooc_epi = atoi(e) != 0;
+    if (const char* e = getenv("FY_TOPN_SEED_XL")) t.topn_seed_xl = atoi(e) != 0;
     if (const char* e = getenv("FY_PANEL_REPAIR")) t.panel_repair = atoi(e) != 0;
     if (const char* e = getenv("FY_PANEL_MULTI_LAUNCH")) t.panel_multi_launch = atoi(e) != 0;
     if (const char* e = getenv("FY_FLAT")) t.flat_batch = atoi(e) != 0;

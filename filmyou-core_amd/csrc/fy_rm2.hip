@@ -852,17 +852,116 @@ struct MEpilogue {
     int32_t tail_from;
 };
 
+// Cross-lane maxima of the epilogue without an LDS instruction (as ds_bpermute shuffles the six steps of a 64-lane maximum were six
+// dependent LDS round trips per loop trip, a sixth of the kernel's LDS instructions): rotations inside the rows of 16 lanes by DPP, then
+// v_permlane16_swap across the two rows of a half-wave and v_permlane32_swap across the halves.  With both operands the same register a
+// swap leaves "mine" in one result and "the other row's" in the other, whichever way round: their maximum is the maximum of the pair.
+// Every lane of the wave must be active at the swaps (the callers' loops are wave-uniform where they take a maximum).
+#define FY_ROR16(x, n) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), 0x120 + (n), 0xF, 0xF, false))
+__device__ __forceinline__ uint32_t fy_max_half_wave(uint32_t m) {      // maximum over the lanes 0-31 / 32-63, in every lane of the half
+    m = max(m, FY_ROR16(m, 8));
+    m = max(m, FY_ROR16(m, 4));
+    m = max(m, FY_ROR16(m, 2));
+    m = max(m, FY_ROR16(m, 1));
+    const auto r = __builtin_amdgcn_permlane16_swap(m, m, false, false);
+    return max((uint32_t)r[0], (uint32_t)r[1]);
+}
+__device__ __forceinline__ uint32_t fy_max_wave(uint32_t m) {
+    m = fy_max_half_wave(m);
+    const auto r = __builtin_amdgcn_permlane32_swap(m, m, false, false);
+    return max((uint32_t)r[0], (uint32_t)r[1]);
+}
+
 // Epilogue of one (row, chunk) item of the RM2 row kernel: G[i][chunk] = w2 * acc -> 24-bit pack (or fp32), the block maxima, and the
 // accumulators re-zeroed in the same pass.  All threads of the workgroup; `id` = (row of the launch << 8) | chunk.
 // the 24-bit branch of the epilogue; COPY: this item also stores the unrounded fp64 images of its values for the refinement pass
 // (MEpilogue::head32 / tail32) -- a separate instantiation, so that the items that do not (all but the first few hundred rows) run
 // the code of round 3 (with the stores in the one loop the row kernel took 8.3 instead of 8.1 ms)
-template <class ACC, bool COPY>
+// EPI (FY_COOC_EPI): 1 = the plain 24-bit items (no panel, no sub-block maxima, no refinement copy: every item of a one-cluster job but the
+// head rows') take eight columns per lane, and the block maxima of both loops are taken without LDS; 0 = the loop of rounds 3-4 alone,
+// with its __shfl_xor maximum.  Same bytes either way: every element goes through the same roundings, and a maximum has no order.
+template <class ACC, bool COPY, int EPI>
 __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const MEpilogue& E, ACC* __restrict__ acc, int row, int mrow, int c0, int c1, int cb,
                                                        int first_bmax_block) {
-        // four columns -> three dwords (c0 and c1 are multiples of 64)
         const int64_t row_cols = E.pitch ? E.pitch : (E.panel_cols ? E.panel_cols : E.ldm);
         const uint32_t radd = E.ceil24 ? (1u << FY_P24_SHIFT) - 1u : 1u << (FY_P24_SHIFT - 1);
+        if constexpr (EPI && !COPY && sizeof(ACC) == 8) {
+        // Eight columns per lane (planar accumulators; cb, c0 and c1 are multiples of 64): lane L of wave w owns the columns
+        // cb + 512 (w + trip * waves) + 8 L ... + 7.  In plane q these are two adjacent words (the columns + q and + 4 + q): one 16-byte
+        // read and one 16-byte zeroing write per plane; 24 contiguous bytes of the row per lane.  A half-wave is 256 columns: one block
+        // of Bmax when that is requested (cb, c0, c1 are then multiples of 256, pick_chunks), and a half-wave at or behind c1 is masked.
+        // The loop is wave-uniform; the reads of the next trip are issued before the arithmetic of this one.
+        if (A.acc_quarter && !(A.acc_quarter & 1) && !E.Bmax64 && !E.panel_cols && !E.pitch) {
+            // (integral sums as four dwords: low and high halves of the two words, converted from 32 bits each)
+            using Pair = typename std::conditional<std::is_integral<ACC>::value, uint4, double2>::type;
+            const int qz = A.acc_quarter;
+            char* __restrict__ out = reinterpret_cast<char*>(E.M) + (int64_t)mrow * E.ldm * 3;
+            const int l8 = (int)(threadIdx.x & 63) * 8, step = (int)blockDim.x * 8;
+            int cw = cb + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 512;         // first column of the wave's trip
+            // (a masked lane reads what the last lane in front of c1 reads -- a lane of its own wave, c1 - 8 >= the trip's first column -- and
+            // drops it: no branch around the reads, nothing read behind the accumulators)
+            auto fetch = [&](int col, Pair* p) __attribute__((always_inline)) {
+                const Pair* ap = reinterpret_cast<const Pair*>(acc + ((min(col, c1 - 8) - c0) >> 2));
+#pragma unroll
+                for (int q = 0; q < 4; q++) p[q] = ap[(q * qz) >> 1];
+            };
+            auto trip = [&](int col, const Pair* p) __attribute__((always_inline)) {
+                const bool on = col < c1;
+                if (on) {
+                    Pair* ap = reinterpret_cast<Pair*>(acc + ((col - c0) >> 2));
+#pragma unroll
+                    for (int q = 0; q < 4; q++) ap[(q * qz) >> 1] = Pair{};
+                }
+                uint32_t v[8];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        float f;
+                        if constexpr (std::is_integral<ACC>::value) {
+                            // (double)acc in one rounding: hi * 2^32 is exact, the fma rounds the exact sum once, as the conversion does
+                            const double d = __builtin_fma((double)(h ? p[q].w : p[q].y), 4294967296.0, (double)(h ? p[q].z : p[q].x));
+                            f = (float)(d * E.fx_inv);
+                        } else f = E.w2 * (float)(h ? p[q].y : p[q].x);
+                        v[4 * h + q] = (__float_as_uint(f) + radd) >> FY_P24_SHIFT;
+                    }
+                }
+                if (on) {
+                    uint32_t* __restrict__ o = reinterpret_cast<uint32_t*>(out + (int64_t)col * 3);
+                    o[0] = v[0] | (v[1] << 24);
+                    o[1] = (v[1] >> 8) | (v[2] << 16);
+                    o[2] = (v[2] >> 16) | (v[3] << 8);
+                    o[3] = v[4] | (v[5] << 24);
+                    o[4] = (v[5] >> 8) | (v[6] << 16);
+                    o[5] = (v[6] >> 16) | (v[7] << 8);
+                }
+                if (E.Bmax) {
+                    uint32_t m = max(max(max(v[0], v[1]), max(v[2], v[3])), max(max(v[4], v[5]), max(v[6], v[7])));
+                    m = fy_max_half_wave(on ? m : 0u);
+                    if ((threadIdx.x & 31) == 0 && m && (col >> 8) >= first_bmax_block) {
+                        uint8_t* bp = reinterpret_cast<uint8_t*>(E.Bmax) + ((int64_t)mrow * E.ldb + (col >> 8)) * 3;
+                        bp[0] = (uint8_t)m;
+                        bp[1] = (uint8_t)(m >> 8);
+                        bp[2] = (uint8_t)(m >> 16);
+                    }
+                }
+            };
+            // two register sets take turns (the loop is wave-uniform: cw is a scalar)
+            Pair pa[4], pb[4];
+            if (cw < c1) fetch(cw + l8, pa);
+            while (cw < c1) {
+                if (cw + step < c1) fetch(cw + step + l8, pb);
+                trip(cw + l8, pa);
+                cw += step;
+                if (cw >= c1) break;
+                if (cw + step < c1) fetch(cw + step + l8, pa);
+                trip(cw + l8, pb);
+                cw += step;
+            }
+            return;
+        }
+        }
+        // four columns -> three dwords (c0 and c1 are multiples of 64)
         uint32_t* __restrict__ out3 = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(E.M) + (int64_t)mrow * row_cols * 3);
         for (int c4 = (cb >> 2) + threadIdx.x; 4 * c4 < c1; c4 += blockDim.x) {
             uint32_t v[4];
@@ -906,7 +1005,6 @@ __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const 
                 uint32_t t1 = max(a1, b1), t2 = max(min(a1, b1), max(a2, b2));
                 // rotations inside the row of 16 lanes (DPP row_ror: no LDS instruction -- as ds_bpermute shuffles these were a third
                 // of the kernel's LDS instructions in a 50-cluster job): after ror 8, 4, 2, 1 every lane has seen all 16, each once
-#define FY_ROR16(x, n) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), 0x120 + (n), 0xF, 0xF, false))
 #define FY_TOP2_STEP(n)                                         \
     {                                                           \
         const uint32_t p1 = FY_ROR16(t1, n), p2 = FY_ROR16(t2, n); \
@@ -915,7 +1013,6 @@ __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const 
     }
                 FY_TOP2_STEP(8) FY_TOP2_STEP(4) FY_TOP2_STEP(2) FY_TOP2_STEP(1)
 #undef FY_TOP2_STEP
-#undef FY_ROR16
                 const uint32_t m = t1 >> 6;
                 if ((threadIdx.x & 15) == 0 && m) {
                     uint8_t* bp = reinterpret_cast<uint8_t*>(E.Bmax64) + ((int64_t)mrow * E.ldb64 + (c4 >> 4)) * 3;
@@ -929,8 +1026,11 @@ __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const 
                 // maximum of the values exactly as the scoring kernel will unpack them; one wave = one 256-column
                 // block (c0 and c1 are multiples of 256 when the bound matrix is requested, see pick_chunks)
                 uint32_t m = max(max(v[0], v[1]), max(v[2], v[3]));     // non-negative floats order like their bit patterns
+                if constexpr (EPI) m = fy_max_wave(m);      // (c1 - cb is a multiple of 256 here: whole waves)
+                else {
 #pragma unroll
-                for (int o = 1; o < 64; o <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+                    for (int o = 1; o < 64; o <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+                }
                 if ((threadIdx.x & 63) == 0 && m && (c4 >> 6) >= first_bmax_block) {
                     // the maximum of 24-bit values is itself one: Bmax is stored in the same packed format (3 bytes per
                     // block, byte stores: the four blocks of a packed group belong to different waves or chunks), so
@@ -945,7 +1045,7 @@ __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const 
         }
 }
 
-template <class ACC>
+template <class ACC, int EPI>
 __device__ __forceinline__ void cooc_rm2_epilogue(const CoocArgs& A, const MEpilogue& E, ACC* __restrict__ acc, int id) {
     const int lrow = id >> 8;
     const int row = A.row0 + lrow * (A.row_stride ? A.row_stride : 1);
@@ -961,8 +1061,8 @@ __device__ __forceinline__ void cooc_rm2_epilogue(const CoocArgs& A, const MEpil
     if (E.pack24) {
         // (block-uniform) does this item hold values the refinement pass wants?
         const bool copy = E.head32 && (mrow < E.head_rows || (E.tail32 && row >= E.tail_from && c0 < E.head_rows));
-        if (copy) cooc_rm2_epilogue_pack<ACC, true>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
-        else cooc_rm2_epilogue_pack<ACC, false>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
+        if (copy) cooc_rm2_epilogue_pack<ACC, true, EPI>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
+        else cooc_rm2_epilogue_pack<ACC, false, EPI>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
     } else {
         float* __restrict__ out = E.M + (int64_t)mrow * E.ldm;
         for (int col = cb + threadIdx.x; col < c1; col += blockDim.x) {
@@ -986,7 +1086,7 @@ __device__ __forceinline__ void cooc_rm2_epilogue(const CoocArgs& A, const MEpil
 // the load of its first 64 segment descriptors of the NEXT item, and only then runs the epilogue: of the three round
 // trips in front of an item's first slice load none is exposed any more.  (3) The epilogue no longer reads b and p.
 // ROLE only names the instantiation (kernel traces): 0 = matrix rows, 1 = the tail rows' block bounds of panel mode (k_tail_blocks)
-template <bool PK, class ACC>
+template <bool PK, class ACC, int EPI>
 __device__ __forceinline__ void cooc_rm2_body(const CoocArgs& A, const MEpilogue& E, int n_items, int* __restrict__ next_item) {
     ACC* __restrict__ acc = reinterpret_cast<ACC*>(fy_cooc_acc);
     __shared__ int sh_item, sh_s0, sh_s1, sh_id;
@@ -1053,16 +1153,17 @@ __device__ __forceinline__ void cooc_rm2_body(const CoocArgs& A, const MEpilogue
         s1 = sh_s1;
         const int nid = sh_id;
         batch = cooc_first_batch(A, s0, s1);     // in flight during the epilogue
-        cooc_rm2_epilogue<ACC>(A, E, acc, id);
+        cooc_rm2_epilogue<ACC, EPI>(A, E, acc, id);
         item = nitem;
         id = nid;
         if (threadIdx.x == 0) next = next2;
         __syncthreads();   // the accumulators are clean again before the next item's atomics
     }
 }
-template <bool PK, class ACC, int ROLE = 0>
+// EPI: the epilogue's loops (cooc_rm2_epilogue_pack; FY_COOC_EPI)
+template <bool PK, class ACC, int ROLE = 0, int EPI = 1>
 __global__ void k_cooc_rm2(CoocArgs A, MEpilogue E, int n_items, int* __restrict__ next_item) {
-    cooc_rm2_body<PK, ACC>(A, E, n_items, next_item);
+    cooc_rm2_body<PK, ACC, EPI>(A, E, n_items, next_item);
 }
 // The matrix builds of SEVERAL clusters in one launch (panel mode, many clusters): blockIdx.y = cluster; its arguments and its item
 // counter come from device memory.  The workgroups of cluster c + 1 start on the CUs that cluster c's workgroups leave: no launch
@@ -1072,12 +1173,12 @@ struct CoocLaunch {
     MEpilogue E;
     int32_t n_items, pad;
 };
-template <bool PK, class ACC, int ROLE = 0>
+template <bool PK, class ACC, int ROLE = 0, int EPI = 1>
 __global__ void k_cooc_rm2_multi(const CoocLaunch* __restrict__ D, int* __restrict__ counters) {
     const CoocLaunch& d = D[blockIdx.y];
     const CoocArgs A = d.A;
     const MEpilogue E = d.E;
-    cooc_rm2_body<PK, ACC>(A, E, d.n_items, counters + blockIdx.y);
+    cooc_rm2_body<PK, ACC, EPI>(A, E, d.n_items, counters + blockIdx.y);
 }
 // the item lists of all those launches (CoocArgs::item_seg / item_id name the lists to fill)
 __global__ void k_item_list_multi(const CoocLaunch* __restrict__ D) {
@@ -1384,17 +1485,22 @@ static void launch_mirror(Context* ctx, float* M, int64_t ldm, int32_t Ic, float
     }
 }
 
-static void cooc_rm2_allow_lds() {
+template <int EPI>
+static void cooc_rm2_allow_lds_epi() {
     const int bytes = 160 * 1024 - 256;     // everything but the kernel's few static words
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<false, double>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, double>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<false, float>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, float>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, unsigned long long>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, unsigned long long, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2_multi<true, unsigned long long, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2_multi<true, unsigned long long, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<false, double, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, double, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<false, float, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, float, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, unsigned long long, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, uint32_t, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, unsigned long long, 1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2_multi<true, unsigned long long, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2_multi<true, unsigned long long, 1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+}
+static void cooc_rm2_allow_lds(int epi) {    // (Tuning::cooc_epi: the instantiations this context launches)
+    if (epi) cooc_rm2_allow_lds_epi<1>();
+    else cooc_rm2_allow_lds_epi<0>();
 }
 static void stray_allow_lds();
 
@@ -1554,18 +1660,24 @@ static void launch_cooc_rm2(Context* ctx, const ScoreTune& tune, bool use_pk, co
     if (!block) block = by_lds >= 4 ? 256 : (by_lds >= 2 ? 512 : 1024);
     const int per_cu = std::max(1, std::min(by_lds, 2048 / block));
     const int grid = std::min(n_items, ctx->num_cus * per_cu);
-    if (acc32) {
-        k_cooc_rm2<true, uint32_t><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-    } else if (use_pk && CA.fx_scale > 0.0 && !tune.cooc_f32) {
-        if (ME.ceil24) k_cooc_rm2<true, unsigned long long, 1><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        else k_cooc_rm2<true, unsigned long long><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-    } else if (!tune.cooc_f32) {
-        if (use_pk) k_cooc_rm2<true, double><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        else k_cooc_rm2<false, double><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-    } else {
-        if (use_pk) k_cooc_rm2<true, float><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        else k_cooc_rm2<false, float><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-    }
+    // (tune.cooc_epi picks the instantiation: the epilogue's loops are a template argument, not a branch inside them)
+    auto go = [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        if (acc32) {
+            k_cooc_rm2<true, uint32_t, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+        } else if (use_pk && CA.fx_scale > 0.0 && !tune.cooc_f32) {
+            if (ME.ceil24) k_cooc_rm2<true, unsigned long long, 1, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+            else k_cooc_rm2<true, unsigned long long, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+        } else if (!tune.cooc_f32) {
+            if (use_pk) k_cooc_rm2<true, double, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+            else k_cooc_rm2<false, double, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+        } else {
+            if (use_pk) k_cooc_rm2<true, float, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+            else k_cooc_rm2<false, float, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
+        }
+    };
+    if (tune.cooc_epi) go(std::integral_constant<int, 1>{});
+    else go(std::integral_constant<int, 0>{});
     FY_KERNEL_CHECK();
 }
 
@@ -1597,7 +1709,7 @@ bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, co
     pick_chunks(Ic, acc32 && !tune.cooc_max_ch_forced ? 2 * tune.cooc_max_ch : tune.cooc_max_ch, CH, nch);
     if (nch >= 256) return false;                      // (the item ids of the row kernel hold the chunk in 8 bits)
     hipStream_t st = ctx->stream;
-    cooc_rm2_allow_lds();
+    cooc_rm2_allow_lds(tune.cooc_epi);
     EventTimer t_tab(ctx), t_walk(ctx);
     const size_t s0 = t_tab.begin();
     DevBuf<uint32_t> csr_pk(ctx, (size_t)P.nnz);
@@ -1671,8 +1783,13 @@ static void launch_cooc_rm2_multi(Context* ctx, const ScoreTune& tune, std::vect
         k_item_list_multi<<<dim3((unsigned)std::max(1, std::min(grid_for(max_list), 4096)), (unsigned)L.size()), 256, 0, st>>>(d_launch.get());
         FY_KERNEL_CHECK();
     }
-    if (tail_role) k_cooc_rm2_multi<true, unsigned long long, 1><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
-    else k_cooc_rm2_multi<true, unsigned long long, 0><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
+    if (tune.cooc_epi) {
+        if (tail_role) k_cooc_rm2_multi<true, unsigned long long, 1, 1><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
+        else k_cooc_rm2_multi<true, unsigned long long, 0, 1><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
+    } else {
+        if (tail_role) k_cooc_rm2_multi<true, unsigned long long, 1, 0><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
+        else k_cooc_rm2_multi<true, unsigned long long, 0, 0><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
+    }
     FY_KERNEL_CHECK();
 }
 
@@ -2975,11 +3092,16 @@ static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const Clu
             int lp2 = 64;                   // the sort's size: the seed columns, at most TOPN_SAMPLE
             while (lp2 < std::min<int>(std::min<int>(Ic, seed_chunks * 256), TOPN_SAMPLE)) lp2 <<= 1;
             const unsigned sg = (unsigned)((nb + 3) / 4);
-            if (lp2 <= 64) k_topn_seed<1><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-            else if (lp2 == 128) k_topn_seed<2><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-            else if (lp2 == 256) k_topn_seed<4><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-            else if (lp2 == 512) k_topn_seed<8><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-            else k_topn_seed<16><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+            auto seed = [&](auto xl) {      // (tune.topn_seed_xl picks the instantiation)
+                constexpr int XL = decltype(xl)::value;
+                if (lp2 <= 64) k_topn_seed<1, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+                else if (lp2 == 128) k_topn_seed<2, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+                else if (lp2 == 256) k_topn_seed<4, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+                else if (lp2 == 512) k_topn_seed<8, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+                else k_topn_seed<16, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
+            };
+            if (tune.topn_seed_xl) seed(std::integral_constant<int, 1>{});
+            else seed(std::integral_constant<int, 0>{});
         }
         FY_KERNEL_CHECK();
         // (4) the blocks whose bound reaches tau_u, in ascending order
@@ -3426,7 +3548,7 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
     int64_t coop_pair_contribs = 0;
     if (in.n_recs > 0 && jp.max_Ic > 0) {
         const std::vector<Plan>& plans = jp.plans;
-        cooc_rm2_allow_lds();
+        cooc_rm2_allow_lds(tune.cooc_epi);
         stray_allow_lds();
         // (the side stream's per-rating values, see SideValues: only the plain one-cluster flow lets them run beside its row kernel)
         if (!(jp.NS == 1 && plans.size() == 1 && !plans[0].coop && !plans[0].flat && !plans[0].panel)) side.join(st);

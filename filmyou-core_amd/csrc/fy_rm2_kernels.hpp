@@ -685,9 +685,34 @@ __device__ __forceinline__ void fy_wave_fence() {
 // Round 4: the sort lives in REGISTERS -- element i = 64 r + lane is lane's register r; a compare-exchange over a distance of 64 or more
 // is between two registers of one lane, a shorter one between two lanes (two 32-bit cross-lane moves per element), no LDS memory at
 // all.  (The LDS version read and wrote eight 64-bit words per lane and stage behind a fence: 0.74 ms per job for 162 541 users.)
-template <int R>
+// XL (FY_TOPN_SEED_XL): 1 = the cross-lane moves bypass the LDS pipe (as __shfl_xor each is a ds_bpermute_b32 behind a wait of its own: 33 dependent
+// steps, 271 of them in k_topn_seed<4>): lane ^ 1 and ^ 2 by a DPP quad permutation, ^ 8 by a rotation of the row of 16, ^ 4 by two bank-masked
+// row shifts (banks 0 and 2 read four lanes up, banks 1 and 3 four lanes down), ^ 16 and ^ 32 by v_permlane16_swap / v_permlane32_swap
+// of the register with itself (one result holds the lower row's / half's values in both, the other the upper's).  Every lane is active.
+__device__ __forceinline__ uint32_t fy_lane_xor32(uint32_t x, int j, int lane) {
+    switch (j) {
+    // (mov_dpp: no value for lanes the move does not write -- every lane is written, by the one move or by the second of the two)
+    case 1: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, false);      // quad_perm:[1,0,3,2]
+    case 2: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, false);      // quad_perm:[2,3,0,1]
+    case 4: {
+        const int t = __builtin_amdgcn_mov_dpp((int)x, 0x104, 0xF, 0x5, false);              // row_shl:4 into banks 0, 2: lane i reads lane i + 4
+        return (uint32_t)__builtin_amdgcn_update_dpp(t, (int)x, 0x114, 0xF, 0xA, false);     // row_shr:4 into banks 1, 3: lane i reads lane i - 4
+    }
+    case 8: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, false);     // row_ror:8
+    case 16: {
+        const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+        return (lane & 16) ? (uint32_t)r[0] : (uint32_t)r[1];
+    }
+    default: {
+        const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+        return (lane & 32) ? (uint32_t)r[0] : (uint32_t)r[1];
+    }
+    }
+}
+template <int R, int XL = 1>
 __global__ __launch_bounds__(256) void k_topn_seed(TopNArgs A, int32_t n_users, int32_t* __restrict__ overflow) {
-    constexpr int LP2 = 64 * R;
+    constexpr int LP2 = 64 * R, LB = R == 1 ? 6 : R == 2 ? 7 : R == 4 ? 8 : R == 8 ? 9 : 10;     // LP2 = 2^LB
+    static_assert(LP2 == 1 << LB, "R is a power of two, at most 16");
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int u = blockIdx.x * 4 + w;
     if (u >= n_users) return;                        // wave-uniform; nothing below synchronises the workgroup
@@ -717,7 +742,9 @@ __global__ __launch_bounds__(256) void k_topn_seed(TopNArgs A, int32_t n_users, 
 #pragma unroll
     for (int k = 2; k <= LP2; k <<= 1) {
 #pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int jb = LB - 1; jb >= 0; jb--) {      // j = k / 2 ... 1 (a trip count of its own: the loop unrolls before the k loop does)
+            const int j = 1 << jb;
+            if (j >= k) continue;
             if (j >= 64) {
 #pragma unroll
                 for (int r = 0; r < R; r++) {
@@ -736,7 +763,9 @@ __global__ __launch_bounds__(256) void k_topn_seed(TopNArgs A, int32_t n_users, 
                 for (int r = 0; r < R; r++) {
                     const int i = 64 * r + lane;
                     const unsigned long long x = v[r];
-                    const unsigned long long y = __shfl_xor(x, j, 64);
+                    unsigned long long y;
+                    if constexpr (XL) y = ((unsigned long long)fy_lane_xor32((uint32_t)(x >> 32), j, lane) << 32) | fy_lane_xor32((uint32_t)x, j, lane);
+                    else y = __shfl_xor(x, j, 64);
                     const bool lower = (lane & j) == 0, desc = (i & k) == 0;
                     const bool keep_max = lower == desc;
                     v[r] = keep_max ? (x > y ? x : y) : (x < y ? x : y);

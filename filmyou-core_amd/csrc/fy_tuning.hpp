@@ -50,6 +50,8 @@ struct Tuning {
     bool cooc_planes = true;           // FY_COOC_PLANES=0: linear accumulator layout (measurement only)
     int score_heavy = 512;             // users with more ratings are walked by a whole workgroup of the scoring kernel (0 = off)
     int score_walk = 1;                // FY_SCORE_WALK=0: the 24-bit scoring kernels walk every batch the first way (v_readlane triplets, a mask test per row); same bits, measurement and parity tests only
+    int cooc_epi = 1;                  // FY_COOC_EPI=0: the row kernel's epilogue as before DESIGN.md section 7f (four columns per lane everywhere, block maxima by __shfl_xor); same bits, measurement and parity tests only
+    int topn_seed_xl = 1;              // FY_TOPN_SEED_XL=0: k_topn_seed's register sort exchanges lanes by __shfl_xor (ds_bpermute) instead of DPP / v_permlane swaps; same lists, measurement and parity tests only
     bool panel_repair = true;          // FY_PANEL_REPAIR=0: measurement only
     int panel_lanes = 2;               // job lanes when clusters run in panel mode (measured, 50 clusters: 1 lane 300 ms, 2: 213, 3: 230, 4: 240)
     int64_t flat_budget = 0;           // FY_FLAT_BUDGET_MB: bytes of matrices + score rows one flat batch may hold (0 = a quarter of the HBM, at most the workspace)
