@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "fy_common.hpp"
+#include "fy_prep.hpp"
 #include "fy_rm2_plan.hpp"   // pick_chunks
 
 namespace fy {
@@ -67,7 +68,7 @@ struct CoocArgs {
     // column-panel mode (fy_rm2.hip): the rows from tail_row0 on have items only for their first tail_chunks chunks
     // (tail_chunks = 0: every row has all its chunks)
     int32_t tail_row0, tail_chunks;
-    // RM2 row kernel: consecutive items a workgroup takes from the item counter per atomic (0 = 1; fy_rm2.hip: cooc_item_grab)
+    // RM2 row kernel: consecutive items a workgroup takes from the item counter per atomic (0 = 1; fy_rm2_launch.hpp: cooc_item_grab)
     int32_t item_grab;
     // RM2 row kernel: the accumulators of a chunk are stored in four PLANES, column c at (c & 3) * acc_quarter + (c >> 2), so that
     // the epilogue -- every lane packs four consecutive columns -- reads consecutive 8-byte words from consecutive lanes (with
@@ -404,6 +405,23 @@ struct SegTable {
     const int2* seg_() const { return v_seg ? v_seg : seg.get(); }
     const float* w_() const { return v_w ? v_w : w.get(); }
 };
+// What every launch of a row kernel says the same way: the CSC of the structure, a segment table, where the cluster lies and how its
+// rows are cut into chunks, all Ic rows in one launch, the CSR operands (csr_w: the weights of the unpacked walk; csr_pk: the packed
+// CSR, or null).  What differs -- row0 / nrows / row_stride / local_start of a partial launch, half, tail_*, item_*, fx_scale, acc32 --
+// is set by member name by the caller; everything not named here is zero.
+struct CoocGeometry {
+    int32_t pbase, slot_base;   // pcstart[c], ucstart[c]
+    int32_t Ic, CH, nch;        // items of the cluster, columns per chunk, chunks per row
+    int32_t q0, nq;             // the cluster's CSC entries
+};
+inline CoocGeometry cooc_geometry(const Plan& p) { return CoocGeometry{p.pbase, p.sbase, p.Ic, p.CH, p.nch, p.q0, p.nq}; }
+inline CoocArgs cooc_args(const Prepared& P, const SegTable& T, const CoocGeometry& g, const float* csr_w, const uint32_t* csr_pk) {
+    CoocArgs A{};
+    A.rank_pair = P.rank_pair.get(); A.pair_start = P.pair_start.get(); A.seg_ptr = T.ptr_(); A.seg = T.seg_(); A.seg_w = T.w_();
+    A.csr_idx = P.csr_idx.get(); A.csr_w = csr_w; A.csr_pk = csr_pk; A.pk_bytes = (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll);
+    A.pbase = g.pbase; A.slot_base = g.slot_base; A.Ic = g.Ic; A.CH = g.CH; A.nch = g.nch; A.nrows = g.Ic; A.q0 = g.q0; A.nq = g.nq;
+    return A;
+}
 // half_row_of_entry != nullptr: symmetric walk (only the columns behind the entry's own row; fy_rm2.hip, struct Half)
 // only_rows_of_entry != nullptr: CSC entries of the rows in front of only_rows_from get no segments (tail-row launches)
 // max_segments > 0: an upper bound of the number of segments -- the table is allocated for it and the call does not wait for

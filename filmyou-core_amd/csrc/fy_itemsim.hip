@@ -1090,9 +1090,8 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
             k_isim_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), measure, csr_pk.get());
             FY_KERNEL_CHECK();
         }
-        CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), segs.ptr.get(), segs.seg.get(), segs.w.get(), P.csr_idx.get(),
-                    csr_w.get(), 0, 0, Ic, CH, nch, prm->rank, rows_mine, 0, (int32_t)P.nnz, nullptr, prm->world,
-                    use_pk ? csr_pk.get() : nullptr, nullptr, (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
+        CoocArgs CA = cooc_args(P, segs, CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, csr_w.get(), use_pk ? csr_pk.get() : nullptr);
+        CA.row0 = prm->rank; CA.nrows = rows_mine; CA.row_stride = prm->world;      // this rank's rows: rank, rank + world, ...
         DevBuf<int2> item_seg(ctx, (size_t)rows_mine * nch);
         DevBuf<int32_t> part_cnt(ctx, (size_t)rows_mine * nch);
         part_cnt.zero();

@@ -1080,8 +1080,9 @@ __device__ __forceinline__ void cooc_rm2_epilogue(const CoocArgs& A, const MEpil
 //
 // Round 2: (1) accumulators in fp32 (ds_add_f32, ACC = float): half the LDS per column, so TWO workgroups share a CU and
 // one streams rater slices while the other sits in its barrier / epilogue (one 16-wave workgroup per CU spent half of
-// every item's 25 us waiting: three dependent round trips in front of the first slice load, then the epilogue); ACC =
-// double keeps the round-1 arithmetic (FY_COOC_F64=1).  (2) The item counter is read TWO items ahead by thread 0, which
+// every item's 25 us waiting: three dependent round trips in front of the first slice load, then the epilogue).  Today
+// (launch_cooc_rm2) ACC is 64-bit fixed point in the packed walk, 32-bit where the sums of the item-similarity Gram fit,
+// double otherwise, float only with FY_COOC_F32=1.  (2) The item counter is read TWO items ahead by thread 0, which
 // also fetches the segment range of the next item while the current one is accumulated; after the barrier every wave issues
 // the load of its first 64 segment descriptors of the NEXT item, and only then runs the epilogue: of the three round
 // trips in front of an item's first slice load none is exposed any more.  (3) The epilogue no longer reads b and p.
@@ -1485,26 +1486,8 @@ static void launch_mirror(Context* ctx, float* M, int64_t ldm, int32_t Ic, float
     }
 }
 
-template <int EPI>
-static void cooc_rm2_allow_lds_epi() {
-    const int bytes = 160 * 1024 - 256;     // everything but the kernel's few static words
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<false, double, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, double, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<false, float, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, float, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, unsigned long long, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, uint32_t, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2<true, unsigned long long, 1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2_multi<true, unsigned long long, 0, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_rm2_multi<true, unsigned long long, 1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-}
-static void cooc_rm2_allow_lds(int epi) {    // (Tuning::cooc_epi: the instantiations this context launches)
-    if (epi) cooc_rm2_allow_lds_epi<1>();
-    else cooc_rm2_allow_lds_epi<0>();
-}
-static void stray_allow_lds();
-
 #include "fy_rm2_kernels.hpp"   // scoring, top-N, branch-and-bound and cooperative-rank kernels (part of this translation unit)
+#include "fy_rm2_launch.hpp"    // the kernel selectors and the one launcher per kernel family (part of this translation unit)
 
 static_assert(TOPN_MAX == fy::TOPN_LIST_MAX, "fy_rm2.hpp states the top-N kernels' limit for the other translation units");
 static void stray_allow_lds() {   // k_score_stray: (Uc + 1) rater offsets of dynamic LDS, up to 128 KB
@@ -1517,15 +1500,11 @@ void launch_topn_rows(Context* ctx, hipStream_t st, const float* S, int64_t ldS,
                       float* out_score, int32_t* out_aux, int32_t* overflow, int32_t* any_overflow, int32_t top_n_hint) {
     if (n_rows <= 0) return;
     if (!st) st = ctx->stream;
-    // n_out / out_off are indexed by (slot - slot_lo): pass slot_lo = slot0 so that row u reads entry u
-    TopNArgs TA{S, ldS, n_cols, n_out, out_off, rank_item_raw, slot2du, uid, slot0, slot0, aux_value, out_user, out_item, out_score, out_aux,
-                0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-    FY_HIP(hipMemsetAsync(any_overflow, 0, sizeof(int32_t), st));
-    if (top_n_hint > TOPN_LONG) k_topn_long<<<n_rows, 256, (size_t)fy_topn_long_cap(top_n_hint) * 8, st>>>(TA, overflow, any_overflow, 0, fy_topn_long_cap(top_n_hint));
-    else k_topn_fast<<<n_rows, 256, 0, st>>>(TA, overflow, any_overflow, 0);
-    FY_KERNEL_CHECK();
-    k_topn_select<<<fy_topn_select_grid(n_rows, ctx->num_cus), 256, 0, st>>>(TA, overflow, any_overflow, n_rows);
-    FY_KERNEL_CHECK();
+    TopNArgs TA{};
+    TA.S = S; TA.ldS = ldS; TA.Ic = n_cols; TA.n_out = n_out; TA.out_off = out_off; TA.rank_item_raw = rank_item_raw; TA.slot2du = slot2du; TA.uid = uid;
+    TA.slot_lo = TA.slot0 = slot0;      // n_out / out_off are indexed by (slot - slot_lo): row u reads entry u
+    TA.cluster = aux_value; TA.out_user = out_user; TA.out_item = out_item; TA.out_score = out_score; TA.out_cluster = out_aux;
+    launch_topn(ctx, st, TA, n_rows, overflow, any_overflow, 0, top_n_hint > TOPN_LONG, top_n_hint, nullptr);
 }
 
 }  // namespace fy
@@ -1641,46 +1620,6 @@ static void owner_range(const fy_rm2_job* J, int k, int32_t& lo, int32_t& hi) {
 // (fy_context_create / fy_context_reload_tuning in fy_api.hip) -- no job reads the environment.
 using ScoreTune = fy::Tuning;
 
-
-// launch shape of the RM2 row kernel: as many workgroups per CU as the LDS accumulators allow (fp32: two for ML-25M's
-// 19 712-column chunks), 2048 threads per CU at most
-// items per atomic of the row kernel's work counter: 8 where an item is short (fewer than ~12 000 co-rating contributions, i.e.
-// < 256 segments on average; `visits` = the cluster's sum of n_u^2, an upper bound of the launch's contributions), else 1
-static int cooc_item_grab(int64_t visits, int64_t n_items) { return n_items > 0 && visits / n_items < 12000 ? 8 : 1; }
-
-static void launch_cooc_rm2(Context* ctx, const ScoreTune& tune, bool use_pk, const CoocArgs& CA_, const MEpilogue& ME, int n_items,
-                            int32_t* counter, hipStream_t st) {
-    if (n_items <= 0) return;
-    CoocArgs CA = CA_;
-    CA.acc_quarter = tune.cooc_planes ? cooc_lds_columns(CA.CH) / 4 : 0;
-    const bool acc32 = CA.acc32 && use_pk && CA.fx_scale > 0.0 && !tune.cooc_f32;
-    const size_t lds = (size_t)cooc_lds_columns(CA.CH) * ((tune.cooc_f32 || acc32) ? 4 : 8);
-    const int by_lds = (int)std::max<size_t>(1, (160 * 1024 - 512) / (lds + 64));
-    int block = tune.cooc_block;
-    if (!block) block = by_lds >= 4 ? 256 : (by_lds >= 2 ? 512 : 1024);
-    const int per_cu = std::max(1, std::min(by_lds, 2048 / block));
-    const int grid = std::min(n_items, ctx->num_cus * per_cu);
-    // (tune.cooc_epi picks the instantiation: the epilogue's loops are a template argument, not a branch inside them)
-    auto go = [&](auto epi) {
-        constexpr int EPI = decltype(epi)::value;
-        if (acc32) {
-            k_cooc_rm2<true, uint32_t, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        } else if (use_pk && CA.fx_scale > 0.0 && !tune.cooc_f32) {
-            if (ME.ceil24) k_cooc_rm2<true, unsigned long long, 1, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-            else k_cooc_rm2<true, unsigned long long, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        } else if (!tune.cooc_f32) {
-            if (use_pk) k_cooc_rm2<true, double, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-            else k_cooc_rm2<false, double, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        } else {
-            if (use_pk) k_cooc_rm2<true, float, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-            else k_cooc_rm2<false, float, 0, EPI><<<grid, block, lds, st>>>(CA, ME, n_items, counter);
-        }
-    };
-    if (tune.cooc_epi) go(std::integral_constant<int, 1>{});
-    else go(std::integral_constant<int, 0>{});
-    FY_KERNEL_CHECK();
-}
-
 // The upper triangle of the co-rating Gram of a ONE-cluster structure with caller-chosen weights, as fp32 (the item-item
 // similarity build, fy_itemsim.hip): G[i][j] = sum_v w_vi r_vj for j > i, zero for (i & ~255) <= j <= i, rows `ldm` floats
 // apart; nothing in front of a row's diagonal 256-column block is written.  The same symmetric walk, segment table, item
@@ -1723,8 +1662,7 @@ bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, co
     DevBuf<int32_t> samples;
     build_csr_samples(ctx, P.nnz, P.csr_idx.get(), samples, st);
     build_segments(ctx, P.csc_slot.get(), csc_w, co.get(), 0, 0, (int32_t)P.nnz, nch, segs, st, csc_rank.get(), P.csr_idx.get(), CH, nullptr, 0, 0, samples.get());
-    CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), segs.ptr.get(), segs.seg.get(), segs.w.get(), P.csr_idx.get(), nullptr, 0, 0, Ic, CH, nch,
-                0, Ic, 0, (int32_t)P.nnz, nullptr, 0, csr_pk.get(), nullptr, (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
+    CoocArgs CA = cooc_args(P, segs, CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, nullptr, csr_pk.get());
     CA.half = 1;
     CA.fx_scale = std::ldexp(1.0, fxk);
     CA.acc32 = acc32 ? 1 : 0;
@@ -1750,47 +1688,6 @@ bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, co
     if (ms_tables) *ms_tables = t_tab.total_ms();
     if (ms_walk) *ms_walk = t_walk.total_ms();
     return true;
-}
-
-// one launch for the row kernels of several clusters (two-phase panel mode; fixed-point packed walk only): `L` = one CoocLaunch per
-// cluster on the host, uploaded here; the launch shape (workgroup size, LDS) is that of the widest chunk among them
-static void launch_cooc_rm2_multi(Context* ctx, const ScoreTune& tune, std::vector<CoocLaunch>& L, bool tail_role, DevBuf<CoocLaunch>& d_launch,
-                                  DevBuf<int32_t>& d_counters, hipStream_t st, bool item_lists = false /* fill the item lists first */) {
-    if (L.empty()) return;
-    int max_chp = 0, max_items = 0, max_list = 0;
-    for (size_t k = 0; k < L.size(); k++)      // (a null operand here is a fault on the GPU a moment later)
-        if (!L[k].A.item_seg || !L[k].A.item_id || !L[k].E.M || !L[k].A.seg || !L[k].A.seg_ptr || (L[k].E.panel_cols && !L[k].E.Bmax64))
-            FY_FAIL(FY_ERR_STATE, "internal: launch %zu of %zu of a batched row kernel has a null operand (item_seg %p item_id %p M %p seg %p ptr %p Bmax64 %p)", k, L.size(),
-                    (const void*)L[k].A.item_seg, (const void*)L[k].A.item_id, (const void*)L[k].E.M, (const void*)L[k].A.seg, (const void*)L[k].A.seg_ptr, (const void*)L[k].E.Bmax64);
-    for (auto& x : L) {
-        x.A.acc_quarter = tune.cooc_planes ? cooc_lds_columns(x.A.CH) / 4 : 0;
-        max_chp = std::max(max_chp, cooc_lds_columns(x.A.CH));
-        max_items = std::max(max_items, x.n_items);
-        max_list = std::max(max_list, x.A.nrows * x.A.nch);
-    }
-    const size_t lds = (size_t)max_chp * 8;
-    const int by_lds = (int)std::max<size_t>(1, (160 * 1024 - 512) / (lds + 64));
-    int block = tune.cooc_block;
-    if (!block) block = by_lds >= 4 ? 256 : (by_lds >= 2 ? 512 : 1024);
-    const int per_cu = std::max(1, std::min(by_lds, 2048 / block));
-    const int gx = std::max(1, std::min(max_items, ctx->num_cus * per_cu));
-    d_launch.alloc(ctx, L.size());
-    d_counters.alloc(ctx, L.size());
-    FY_HIP(hipMemcpyAsync(d_launch.get(), L.data(), L.size() * sizeof(CoocLaunch), hipMemcpyHostToDevice, st));
-    FY_HIP(hipMemsetAsync(d_counters.get(), 0, L.size() * sizeof(int32_t), st));
-    const dim3 grid((unsigned)gx, (unsigned)L.size());
-    if (item_lists) {
-        k_item_list_multi<<<dim3((unsigned)std::max(1, std::min(grid_for(max_list), 4096)), (unsigned)L.size()), 256, 0, st>>>(d_launch.get());
-        FY_KERNEL_CHECK();
-    }
-    if (tune.cooc_epi) {
-        if (tail_role) k_cooc_rm2_multi<true, unsigned long long, 1, 1><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
-        else k_cooc_rm2_multi<true, unsigned long long, 0, 1><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
-    } else {
-        if (tail_role) k_cooc_rm2_multi<true, unsigned long long, 1, 0><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
-        else k_cooc_rm2_multi<true, unsigned long long, 0, 0><<<grid, block, lds, st>>>(d_launch.get(), d_counters.get());
-    }
-    FY_KERNEL_CHECK();
 }
 
 // the host-side plan (fy_rm2_plan.hpp) states the kernels' limits for itself: the two sides must agree
@@ -1869,16 +1766,11 @@ class SideValues {
             FY_HIP(hipStreamWaitEvent(sv, in, 0));
             vs = sv;
         }
-        if (J->S->smooth.general())
-            k_csr_values<true><<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
-                                                                                   P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
-                                                                                   A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get(),
-                                                                                   J->S->usum_slot.get(), J->smooth_args());
-        else
-            k_csr_values<false><<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(),
-                                                                                    P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
-                                                                                    A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get(),
-                                                                                    nullptr, SmoothArgs{});
+        const bool general = J->S->smooth.general();
+        (general ? k_csr_values<true> : k_csr_values<false>)<<<grid_for((int64_t)P.nU * 64, 256), 256, 0, vs>>>(
+            P.nU, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.slot2du.get(), P.ucluster.get(), P.usum.get(), P.d_csize.get(), P.d_pcstart.get(),
+            A.pb_rank.get(), lambda, A.d_gscale.get(), A.csr_x.get(), A.csr_e.get(), A.csr_q.get(), general ? J->S->usum_slot.get() : nullptr,
+            general ? J->smooth_args() : SmoothArgs{});
         FY_KERNEL_CHECK();
         if (vs != main_stream) {
             FY_HIP(hipEventRecord(out, sv));
@@ -1922,6 +1814,43 @@ struct ScoreShared {
     const int32_t* cshift;            // [cluster]: c of the packed matrix format (k_user_meta)
     const float* gscale;              // [cluster], host: 2^-c
 };
+
+// Scoring arguments of the users [slot0, slot0 + n_users) of cluster `p` against the matrix M (pitch ldm), scores to S (pitch ldS): the
+// job's own CSR and per-rating values.  A second matrix (score_args_bounds), n_heavy, the super-block bounds and the cooperative
+// ranks' own CSR are set by member name by the caller.
+static ScoreArgs score_args(const ScoreShared& X, const Plan& p, const float* M, int64_t ldm, int32_t slot0, int32_t n_users, float* S, int64_t ldS,
+                            int n_slices, int n_chunks) {
+    const Prepared& P = X.J->P;
+    ScoreArgs SA{};
+    SA.M = M; SA.ldm = ldm; SA.Ic = p.Ic; SA.a_rank = X.a_rank + p.pbase; SA.b_rank = X.b_rank + p.pbase;
+    SA.rb_off = P.rowptr.get() + p.sbase;     // the users' CSR rows: [slot - sbase], [slot - sbase + 1]
+    SA.csr_idx = P.csr_idx.get(); SA.csr_e = X.csr_e; SA.csr_q = X.csr_q;
+    SA.pvpi = X.pvpi; SA.n_out = X.n_out; SA.slot_lo = X.lo; SA.slot_base = p.sbase; SA.slot0 = slot0; SA.n_users = n_users;
+    SA.S = S; SA.ldS = ldS; SA.n_slices = n_slices; SA.n_chunks = n_chunks;
+    return SA;
+}
+// the fused seed + bound launch: the chunks from `seed_chunks` on work on the block maxima M2 (pitch ld2, n2 columns, the blocks' maxima
+// a2 / b2 of a and b), the bounds go to S2 at the same pitch; no "already rated" mask there
+static void score_args_bounds(ScoreArgs& SA, int seed_chunks, const float* M2, int64_t ld2, int32_t n2, const float* a2, const float* b2, float* S2) {
+    SA.chunks1 = seed_chunks;
+    SA.M2 = M2; SA.ldm2 = ld2; SA.Ic2 = n2; SA.a2 = a2; SA.b2 = b2; SA.S2 = S2; SA.ldS2 = ld2; SA.no_mask2 = 1;
+}
+// Top-N arguments of the users of cluster `p` from slot0 on, score rows S (pitch ldS), lists into the result: mode 0, the whole row is
+// live.  The branch and bound sets its fields (topn_pruned) for modes 1 and 2.
+static TopNArgs topn_args(const ScoreShared& X, const Plan& p, const float* S, int64_t ldS, int32_t slot0) {
+    const Prepared& P = X.J->P;
+    TopNArgs TA{};
+    TA.S = S; TA.ldS = ldS; TA.Ic = p.Ic; TA.n_out = X.n_out; TA.out_off = X.out_off; TA.rank_item_raw = P.rank_item_raw.get() + p.pbase;
+    TA.slot2du = P.slot2du.get(); TA.uid = P.uid.get(); TA.slot_lo = X.lo; TA.slot0 = slot0; TA.cluster = p.c;
+    TA.out_user = X.R->d_key0.get(); TA.out_item = X.R->d_key1.get(); TA.out_score = X.R->d_value.get(); TA.out_cluster = X.R->d_aux.get();
+    return TA;
+}
+// mode 1 (seed phase) / mode 2 (merge phase: Ssurv and quad_prefix name the packed scores of the survivors)
+static void topn_pruned(TopNArgs& TA, int mode, int32_t seed_cols, const uint16_t* surv, const int32_t* n_quads, int64_t ldb, float* tau,
+                        const float* Ssurv = nullptr, const int32_t* quad_prefix = nullptr) {
+    TA.mode = mode; TA.seed_cols = seed_cols; TA.surv = surv; TA.n_quads = n_quads; TA.ldb = ldb; TA.tau = tau;
+    TA.Ssurv = Ssurv; TA.quad_prefix = quad_prefix;
+}
 
 #include "fy_rm2_coop.hpp"   // score_cluster_coop: a cluster scored by all ranks together (part of this translation unit)
 
@@ -2194,25 +2123,16 @@ fy_rm2_job* fy::rm2_prepare(Context* ctx, const fy_rm2_params* prm, const fy_rat
         const PairHeavy PH{heavy_col.get(), heavy_base.get(), chunk_col.get(), heavy_counters.get(), chunk_acc.get()};
         const unsigned g_chunks = (unsigned)std::min<size_t>(max_heavy, (size_t)ctx->num_cus * 32);
         const unsigned g_finish = (unsigned)std::min<size_t>(ceil_div((int64_t)max_heavy, 64), 1024);
-        if (sm.general()) {
-            if (P.nnz < 24 * (int64_t)P.nP) k_pair_pass<16, true><<<grid_for((int64_t)P.nP * 16, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
-            else k_pair_pass<64, true><<<grid_for((int64_t)P.nP * 64, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
-            FY_KERNEL_CHECK();
-            k_pair_chunks<true><<<g_chunks, 256, 0, ctx->stream>>>(PA, PH);
-            FY_KERNEL_CHECK();
-            k_pair_finish<true><<<g_finish, 64, 0, ctx->stream>>>(PA, PH);
-            FY_KERNEL_CHECK();
-            if (delta > 0.0) {      // from here on the structure holds r'
-                k_discount_inplace<<<grid_for(P.nnz), 256, 0, ctx->stream>>>(P.nnz, delta, P.csr_r.get(), P.csc_r.get());
-                FY_KERNEL_CHECK();
-            }
-        } else {
-            if (P.nnz < 24 * (int64_t)P.nP) k_pair_pass<16, false><<<grid_for((int64_t)P.nP * 16, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
-            else k_pair_pass<64, false><<<grid_for((int64_t)P.nP * 64, 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
-            FY_KERNEL_CHECK();
-            k_pair_chunks<false><<<g_chunks, 256, 0, ctx->stream>>>(PA, PH);
-            FY_KERNEL_CHECK();
-            k_pair_finish<false><<<g_finish, 64, 0, ctx->stream>>>(PA, PH);
+        const bool gen = sm.general(), narrow = P.nnz < 24 * (int64_t)P.nP;      // (narrow: 16 lanes per column instead of a wave)
+        (gen ? (narrow ? k_pair_pass<16, true> : k_pair_pass<64, true>) : (narrow ? k_pair_pass<16, false> : k_pair_pass<64, false>))
+            <<<grid_for((int64_t)P.nP * (narrow ? 16 : 64), 256), 256, 0, ctx->stream>>>(P.nP, PA, PH);
+        FY_KERNEL_CHECK();
+        (gen ? k_pair_chunks<true> : k_pair_chunks<false>)<<<g_chunks, 256, 0, ctx->stream>>>(PA, PH);
+        FY_KERNEL_CHECK();
+        (gen ? k_pair_finish<true> : k_pair_finish<false>)<<<g_finish, 64, 0, ctx->stream>>>(PA, PH);
+        FY_KERNEL_CHECK();
+        if (gen && delta > 0.0) {      // from here on the structure holds r'
+            k_discount_inplace<<<grid_for(P.nnz), 256, 0, ctx->stream>>>(P.nnz, delta, P.csr_r.get(), P.csc_r.get());
             FY_KERNEL_CHECK();
         }
         if (J->slot_hi > J->slot_lo) {
@@ -2331,12 +2251,8 @@ static void score_preamble(fy_rm2_job* J, fy_result* R, const PackPlan& pack, bo
     A.a_rank.alloc(ctx, nP);
     A.b_rank32.alloc(ctx, nP);
     A.pb_rank.alloc(ctx, nP);
-    if (J->S->smooth.general())
-        k_pair_p<true><<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
-                                                     A.b_rank32.get(), A.pb_rank.get());
-    else
-        k_pair_p<false><<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
-                                                      A.b_rank32.get(), A.pb_rank.get());
+    (J->S->smooth.general() ? k_pair_p<true> : k_pair_p<false>)<<<grid_for(nP), 256, 0, st>>>(nP, P.rank_pair.get(), P.pair_di.get(), d_icoll, lambda, J->b_rank.get(),
+                                                                                            A.p_rank.get(), A.a_rank.get(), A.b_rank32.get(), A.pb_rank.get());
     FY_KERNEL_CHECK();
     A.csr_x.alloc(ctx, P.nnz);
     A.csr_e.alloc(ctx, P.nnz);
@@ -2552,12 +2468,10 @@ static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
     const Prepared& P = X.J->P;
     fy_result* R = X.R;
     const ScoreTune& tune = *X.tune;
-    const fy_rm2_params& prm = X.J->prm;
     const JobPlan& jp = *X.jp;
     hipStream_t st = ctx->stream;
     TableCache& tc = J->S->tables;
-    const int32_t lo = X.lo;
-    const double lambda = prm.lambda;
+    const double lambda = J->prm.lambda;
     constexpr int VEC = 4;   // floats per lane of the scoring kernel: column chunk = 256 items
     for (size_t first = 0; first < jp.plans.size();) {
         std::vector<CoocLaunch> fb;
@@ -2592,9 +2506,7 @@ static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
                 const int32_t nb = p.b - p.a;
                 float* const Mc = reinterpret_cast<float*>(F.flatM.get() + m_at);
                 float* const Sc = F.flatS.get() + s_at;
-                CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), tc.segs[pi].ptr_(), tc.segs[pi].seg_(), tc.segs[pi].w_(), P.csr_idx.get(),
-                            X.csr_x, p.pbase, p.sbase, p.Ic, p.CH, p.nch, 0, p.Ic, p.q0, p.nq, nullptr, 0, X.csr_pk, nullptr,
-                            (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
+                CoocArgs CA = cooc_args(P, tc.segs[pi], cooc_geometry(p), X.csr_x, X.csr_pk);
                 const int fxk = fx_exponent(&J->fx_bounds[3 * (size_t)c]);
                 CA.fx_scale = std::ldexp(1.0, fxk);
                 const double w2s = J->S->smooth.w2_of(lambda) * (double)X.gscale[(size_t)c];
@@ -2610,18 +2522,12 @@ static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
                 const int64_t fill = ceil_div(8 * (int64_t)ctx->num_cus, (int64_t)std::max(1, n_chunks) * (int64_t)n_flat);
                 const int n_slices = (int)std::max<int64_t>(1, std::min<int64_t>(tune.max_slices, std::min<int64_t>(ceil_div(nb, 4), std::max<int64_t>(ceil_div(nb, 4 * (int64_t)tune.users_per_wave), fill))));
                 FlatDesc d{};
-                ScoreArgs& SA = d.SA;
-                SA.M = Mc; SA.ldm = p.ldm; SA.Ic = p.Ic; SA.a_rank = X.a_rank + p.pbase; SA.b_rank = X.b_rank + p.pbase;
-                SA.rb_off = P.rowptr.get() + p.sbase;
-                SA.csr_idx = P.csr_idx.get(); SA.csr_e = X.csr_e; SA.csr_q = X.csr_q;
-                SA.pvpi = X.pvpi; SA.n_out = X.n_out; SA.slot_lo = lo; SA.slot_base = p.sbase; SA.slot0 = p.a; SA.n_users = nb;
-                SA.S = Sc; SA.ldS = p.ldm; SA.n_slices = n_slices; SA.n_chunks = n_chunks;
+                d.SA = score_args(X, p, Mc, p.ldm, p.a, nb, Sc, p.ldm, n_slices, n_chunks);
                 d.n_heavy = F.flat_flags.get() + 2 * k;
                 d.any_overflow = F.flat_flags.get() + 2 * k + 1;
-                SA.n_heavy = tune.score_heavy > 0 ? d.n_heavy : nullptr;
+                d.SA.n_heavy = tune.score_heavy > 0 ? d.n_heavy : nullptr;
                 d.heavy_thresh = tune.score_heavy > 0 ? std::min(tune.score_heavy, 32) : 0x7FFFFFFF;
-                d.TA = TopNArgs{Sc, p.ldm, p.Ic, X.n_out, X.out_off, P.rank_item_raw.get() + p.pbase, P.slot2du.get(), P.uid.get(), lo, p.a, c,
-                                R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(), 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+                d.TA = topn_args(X, p, Sc, p.ldm, p.a);
                 d.overflow = F.flat_ov.get() + u_at;
                 d.score_grid = n_chunks * n_slices;
                 d.n_users = nb;
@@ -2647,9 +2553,7 @@ static void score_flat_batches(const ScoreShared& X, FlatBuffers& F) {
                 const size_t ss = X.t_score->begin(st);
                 k_count_heavy_multi<<<(ny + 63) / 64, 64, 0, st>>>(F.d_flat[f].get(), (int32_t)ny);
                 FY_KERNEL_CHECK();
-                if (f && tune.score_walk) k_score_multi<4, true, 8, 1><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
-                else if (f) k_score_multi<4, true, 8, 0><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
-                else k_score_multi<4, false, 8><<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
+                score_multi_kernel(f != 0, tune.score_walk)<<<dim3((unsigned)max_grid[f], ny), 256, 0, st>>>(F.d_flat[f].get(), P.csr_idx.get(), X.csr_e, X.csr_q, X.pvpi, X.n_out);
                 FY_KERNEL_CHECK();
                 X.t_score->end(ss, st);
                 R->st.score_launches++;
@@ -2759,29 +2663,46 @@ struct ClusterVisit {
     PanelSet* PS;
     int32_t* pinned;             // two-phase panel mode: [plan] survivor counts, read by the host between phases 2 and 3
 };
-// numbers the matrix build and the scoring of one cluster agree on
-struct ClusterNumbers {
-    int fxk;                     // exponent of the fixed-point walk, < 0: fp64 accumulators
-    double w2s;                  // (1-l)^2 and the packed format's 2^-c
-    bool refine;
-    int32_t head_rows;
+// What the matrix build and the scoring passes of one cluster share.  The pruned passes write and read only the seed columns and the
+// surviving blocks of a score row.
+struct ClusterPass {
+    const ScoreShared& X;
+    const ClusterVisit& V;
+    const Plan& p;
+    Lane& L;                 // = *V.L, and its stream
+    hipStream_t ls;
+    Context* ctx;            // X.J's context, structure and the job's knobs
+    const Prepared& P;
+    const ScoreTune& tune;
+    int fxk;                 // exponent of the fixed-point walk, < 0: fp64 accumulators
+    double w2s;              // (1-l)^2 (general smoothing: w^2 = 1) and the packed format's 2^-c
+    bool refine;             // k_refine_rows: the cluster keeps the unrounded values of its head rows (symmetric panel mode: and of the tail rows' head columns)
+    int32_t head_rows;       // ... as many as the seed is wide, 256 .. 1024: N = 50 -> 256, N = 100 -> 512; a multiple of 4
     int64_t ld_head;
-};
-static ClusterNumbers cluster_numbers(const ScoreShared& X, const Plan& p) {
+    int n_chunks;            // 256-column chunks of a score row
+    int seed_chunks;         // ... of them scored exactly in front of the bound pass (= the seed blocks)
+    bool use_sup;            // bounds over super-blocks, evaluated by the seed chunk's own waves
+    const float* Gmat;       // the stored rows: the matrix, or (panel mode) the panel_cols wide panel; gld = their pitch
+    int64_t gld, bld, SC;    // bld = pitch of the bound matrix (panel mode: a column per 64-column sub-block), of UB and of the survivor lists;
+};                           // SC = pitch of the compact score rows: seed columns only
+static ClusterPass cluster_pass(const ScoreShared& X, const ClusterVisit& V) {
     const fy_rm2_job* J = X.J;
     const ScoreTune& tune = *X.tune;
-    const double lambda = J->prm.lambda;
-    const int c = p.c;
-    ClusterNumbers N{};
-    N.fxk = (X.jp->use_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)c]) : -1;
-    N.w2s = J->S->smooth.w2_of(lambda) * (double)X.gscale[(size_t)c];     // (1-l)^2 (general smoothing: w^2 = 1) and the packed format's 2^-c
-    // refinement (k_refine_rows): packed clusters keep the unrounded fp32 values of their first 256 rows (and, in symmetric panel
-    // mode, of the first 256 columns of the tail rows)
-    N.refine = tune.refine && p.pack24 && !p.coop && N.fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
-    // (as many head rows / columns as the seed is wide, 256 .. 1024: N = 50 -> 256, N = 100 -> 512; a multiple of 4)
-    N.head_rows = (int32_t)std::min<int64_t>(p.Ic & ~3, std::max<int64_t>(256, std::min<int64_t>(1024, (int64_t)tune.seed_chunks * 256)));
-    N.ld_head = p.psym ? (int64_t)p.p_eff : p.ldm;
-    return N;
+    const Plan& p = X.jp->plans[V.pi];
+    ClusterPass C{X, V, p, *V.L, V.ls, J->ctx, J->P, tune};
+    C.fxk = (X.jp->use_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) : -1;
+    C.w2s = J->S->smooth.w2_of(J->prm.lambda) * (double)X.gscale[(size_t)p.c];
+    C.refine = tune.refine && p.pack24 && !p.coop && C.fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
+    C.head_rows = (int32_t)std::min<int64_t>(p.Ic & ~3, std::max<int64_t>(256, std::min<int64_t>(1024, (int64_t)tune.seed_chunks * 256)));
+    C.ld_head = p.psym ? (int64_t)p.p_eff : p.ldm;
+    C.n_chunks = (int)ceil_div(p.Ic, 256);
+    C.seed_chunks = std::min(C.n_chunks, tune.seed_chunks);
+    C.use_sup = tune.sup_bounds && !p.panel && !X.jp->long_seed;
+    C.Gmat = p.panel ? V.PP.Gp : V.L->M.get();
+    C.gld = p.panel ? (int64_t)p.panel_cols : p.ldm;
+    C.bld = p.panel ? p.ldb64 : p.ldb;
+    C.SC = (int64_t)C.seed_chunks * 256;
+    return C;
 }
 // FY_DEBUG_SYNC=1: drain the device and say where the job is
 static void checkpoint(const ScoreShared& X, const ClusterVisit& V, const char* what) {
@@ -2793,127 +2714,101 @@ static void checkpoint(const ScoreShared& X, const ClusterVisit& V, const char* 
 
 // -- M build: the cluster's matrix (or panel), its block maxima, mirror pass and super-block bounds.  In phase 1 with batched row
 // kernels the launches are only collected (PanelSet::batch_main / batch_tail; launch_panel_batch queues them for the whole group).
-static void build_cluster_matrix(const ScoreShared& X, const ClusterVisit& V, const ClusterNumbers& N) {
-    fy_rm2_job* J = X.J;
-    Context* ctx = X.J->ctx;
-    const Prepared& P = X.J->P;
-    fy_result* R = X.R;
-    const ScoreTune& tune = *X.tune;
-    const JobPlan& jp = *X.jp;
-    TableCache& tc = J->S->tables;
-    const size_t pi = V.pi;
-    const int phase = V.phase;
-    const Plan& p = jp.plans[pi];
+
+// one row kernel of the cluster: its item list, then the launch on the lane -- or, batched, its descriptor for the group's launch
+// (k_item_list_multi fills the lists in front of it).  `tail`: the tail rows' bound launch.
+static void queue_row_kernel(const ScoreShared& X, const ClusterVisit& V, bool batched, bool tail, CoocArgs CA, const MEpilogue& ME, int64_t list_len,
+                             int n_items, int item_grab) {
     Lane& L = *V.L;
-    hipStream_t ls = V.ls;
+    int2* const seg = !batched ? L.item_seg.get() : tail ? V.own->item_seg_t.get() : V.own->item_seg.get();
+    int32_t* const id = !batched ? L.item_id.get() : tail ? V.own->item_id_t.get() : V.own->item_id.get();
+    if (!batched) {
+        k_item_list<<<grid_for(list_len), 256, 0, V.ls>>>(CA, seg, id);
+        FY_KERNEL_CHECK();
+    }
+    CA.item_seg = seg; CA.item_id = id; CA.item_grab = item_grab;
+    if (batched) {
+        (tail ? V.PS->batch_tail : V.PS->batch_main).push_back(CoocLaunch{CA, ME, n_items, 0});
+        return;
+    }
+    FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), V.ls));   // reused as the item counter
+    launch_cooc_rm2(X.J->ctx, *X.tune, X.jp->use_pk, CA, ME, n_items, L.any_overflow.get(), V.ls);
+    X.R->st.cooc_launches++;
+}
+
+static void build_cluster_matrix(const ClusterPass& C) {
+    const ScoreShared& X = C.X; const ClusterVisit& V = C.V; const Prepared& P = C.P; const ScoreTune& tune = C.tune; const Plan& p = C.p; Lane& L = C.L;
+    Context* ctx = C.ctx;
+    hipStream_t ls = C.ls;
+    const TableCache& tc = X.J->S->tables;
+    const JobPlan& jp = *X.jp;
     const PanelPtrs& PP = V.PP;
-    const int c = p.c;
-    const int32_t sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, CH = p.CH, nch = p.nch;
-    const int64_t ldm = p.ldm;
-    const bool pack24 = p.pack24;
-    const int fxk = N.fxk;
-    const double w2s = N.w2s;
-    CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), tc.segs[pi].ptr_(), tc.segs[pi].seg_(), tc.segs[pi].w_(), P.csr_idx.get(),
-                X.csr_x, pbase, sbase, Ic, CH, nch, 0, Ic, p.q0, p.nq, nullptr, 0, X.csr_pk, nullptr,
-                (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
+    const int32_t pbase = p.pbase, Ic = p.Ic;
+    const int fxk = C.fxk;
+    const double w2s = C.w2s;
+    CoocArgs CA = cooc_args(P, tc.segs[V.pi], cooc_geometry(p), X.csr_x, X.csr_pk);
     CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;
-    MEpilogue ME{L.M.get(), ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0,
-                 pack24 ? 1 : 0, (p.prune && !p.panel) ? L.Bmax.get() : nullptr, p.ldb, 0,
+    MEpilogue ME{L.M.get(), p.ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0,
+                 p.pack24 ? 1 : 0, (p.prune && !p.panel) ? L.Bmax.get() : nullptr, p.ldb, 0,
                  p.panel ? p.panel_cols : 0, p.panel ? PP.Bmax64 : nullptr, p.ldb64, p.panel ? PP.Brep : nullptr};
     if (p.panel) ME.M = PP.Gp;
-    if (N.refine) {
-        V.H32->alloc(ctx, (size_t)N.head_rows * N.ld_head + 4);
-        if (p.psym) V.T32->alloc(ctx, (size_t)std::max(1, Ic - p.p_eff) * N.head_rows + 4);
-        ME.head32 = V.H32->get();
-        ME.ld_head = N.ld_head;
-        ME.head_rows = N.head_rows;
-        ME.tail32 = p.psym ? V.T32->get() : nullptr;
-        ME.tail_from = p.p_eff;
+    if (C.refine) {
+        V.H32->alloc(ctx, (size_t)C.head_rows * C.ld_head + 4);
+        if (p.psym) V.T32->alloc(ctx, (size_t)std::max(1, Ic - p.p_eff) * C.head_rows + 4);
+        ME.head32 = V.H32->get(); ME.ld_head = C.ld_head; ME.head_rows = C.head_rows;
+        ME.tail32 = p.psym ? V.T32->get() : nullptr; ME.tail_from = p.p_eff;
     }
-    if (p.panel) {
-        R->st.panel_clusters++;
-        FY_HIP(hipMemsetAsync(PP.Bmax64, 0, (size_t)Ic * p.ldb64 * 3, ls));
-        k_block_amax<<<grid_for(p.ldb64), 256, 0, ls>>>(Ic, (int32_t)p.ldb64, X.a_rank + pbase, X.b_rank + pbase, PP.amax64,
-                                                       PP.bmax64, 64);
-        FY_KERNEL_CHECK();
-    } else if (p.prune) {
-        FY_HIP(hipMemsetAsync(L.Bmax.get(), 0, (size_t)Ic * p.ldb * 3, ls));
-        k_block_amax<<<grid_for(p.ldb), 256, 0, ls>>>(Ic, (int32_t)p.ldb, X.a_rank + pbase, X.b_rank + pbase, L.amax.get(), L.bmax.get());
+    if (p.panel) X.R->st.panel_clusters++;
+    if (p.panel || p.prune) {     // the bound matrix starts at zero; the maxima of a and b over its blocks (panel mode: 64-column sub-blocks)
+        const int64_t bld = p.panel ? p.ldb64 : p.ldb;
+        FY_HIP(hipMemsetAsync(p.panel ? PP.Bmax64 : L.Bmax.get(), 0, (size_t)Ic * bld * 3, ls));
+        k_block_amax<<<grid_for(bld), 256, 0, ls>>>(Ic, (int32_t)bld, X.a_rank + pbase, X.b_rank + pbase, p.panel ? PP.amax64 : L.amax.get(),
+                                                   p.panel ? PP.bmax64 : L.bmax.get(), p.panel ? 64 : PRUNE_BLOCK);
         FY_KERNEL_CHECK();
     }
     const size_t sp = X.t_cooc->begin(ls);
-    const bool batched = phase == 1 && tune.panel_multi_launch && jp.use_pk && fxk >= 0 && !tune.cooc_f32;     // (k_cooc_rm2_multi)
+    const bool batched = V.phase == 1 && tune.panel_multi_launch && jp.use_pk && fxk >= 0 && !tune.cooc_f32;     // (k_cooc_rm2_multi)
     if (p.p_eff < Ic) {   // panel mode: bounds of the tail rows behind p_eff (one item per row, see k_tail_blocks)
-        CoocArgs CB{P.rank_pair.get(), P.pair_start.get(), tc.segs_tail[pi].ptr_(), tc.segs_tail[pi].seg_(), tc.segs_tail[pi].w_(), P.csr_idx.get(),
-                    X.csr_x, pbase, sbase, Ic, p.tail_width, 1, p.p_eff, Ic - p.p_eff, p.q0, p.nq, nullptr, 0, tc.y_pk.get(), nullptr, CA.pk_bytes};
-        CB.fx_scale = CA.fx_scale;
+        CoocGeometry g = cooc_geometry(p);
+        g.CH = p.tail_width; g.nch = 1;
+        CoocArgs CB = cooc_args(P, tc.segs_tail[V.pi], g, X.csr_x, tc.y_pk.get());
+        CB.row0 = p.p_eff; CB.nrows = Ic - p.p_eff; CB.fx_scale = CA.fx_scale;
         MEpilogue MB{reinterpret_cast<float*>(reinterpret_cast<char*>(PP.Bmax64) + (size_t)(p.p_eff / 64) * 3), p.tail_width, ME.w2, ME.fx_inv, 1,
                      nullptr, 0, 0, 0, nullptr, 0, nullptr, p.ldb64, 1};
-        int2* const tseg = batched ? V.own->item_seg_t.get() : L.item_seg.get();
-        int32_t* const tid = batched ? V.own->item_id_t.get() : L.item_id.get();
-        if (!batched) {      // (batched: k_item_list_multi, in front of the launch)
-            k_item_list<<<grid_for((int64_t)(Ic - p.p_eff)), 256, 0, ls>>>(CB, tseg, tid);
-            FY_KERNEL_CHECK();
-        }
-        CB.item_seg = tseg;
-        CB.item_id = tid;
-        CB.item_grab = 8;      // a tail row's bound item is a handful of segments
-        if (batched) V.PS->batch_tail.push_back(CoocLaunch{CB, MB, Ic - p.p_eff, 0});
-        else {
-            FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
-            launch_cooc_rm2(ctx, tune, jp.use_pk, CB, MB, Ic - p.p_eff, L.any_overflow.get(), ls);
-            R->st.cooc_launches++;
-        }
+        queue_row_kernel(X, V, batched, true, CB, MB, Ic - p.p_eff, Ic - p.p_eff, 8);      // (a tail row's bound item is a handful of segments)
         CA.tail_row0 = p.p_eff;
         CA.tail_chunks = p.tail_chunks;
     }
-    {
-        CA.half = (p.half || p.psym) ? 1 : 0;
-        if (p.psym) { CA.half_rows = p.p_eff; CA.head_chunks = p.tail_chunks; }
-        const int n_items = p.psym ? (int)(cooc_half_item_index(p.p_eff - 1, p.tail_chunks - 1, CH, p.tail_chunks) + 1 + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
-                            : CA.tail_chunks > 0 ? (int)((int64_t)p.p_eff * nch + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
-                                                 : (int)cooc_item_count(Ic, CH, nch, p.half);
-        int2* const mseg = batched ? V.own->item_seg.get() : L.item_seg.get();
-        int32_t* const mid = batched ? V.own->item_id.get() : L.item_id.get();
-        if (!batched) {
-            k_item_list<<<grid_for((int64_t)Ic * nch), 256, 0, ls>>>(CA, mseg, mid);
-            FY_KERNEL_CHECK();
-        }
-        CA.item_seg = mseg;
-        CA.item_id = mid;
-        CA.item_grab = cooc_item_grab(((size_t)c < P.cluster_deg2.size() ? P.cluster_deg2[c] : P.sum_deg2) / (p.half ? 2 : 1), n_items);
-        if (batched) V.PS->batch_main.push_back(CoocLaunch{CA, ME, n_items, 0});
-        else {
-            FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
-            launch_cooc_rm2(ctx, tune, jp.use_pk, CA, ME, n_items, L.any_overflow.get(), ls);
-        }
-    }
+    CA.half = (p.half || p.psym) ? 1 : 0;
+    if (p.psym) { CA.half_rows = p.p_eff; CA.head_chunks = p.tail_chunks; }
+    const int n_items = p.psym ? (int)(cooc_half_item_index(p.p_eff - 1, p.tail_chunks - 1, p.CH, p.tail_chunks) + 1 + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
+                        : CA.tail_chunks > 0 ? (int)((int64_t)p.p_eff * p.nch + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
+                                             : (int)cooc_item_count(Ic, p.CH, p.nch, p.half);
+    const int64_t visits = (size_t)p.c < P.cluster_deg2.size() ? P.cluster_deg2[p.c] : P.sum_deg2;
+    queue_row_kernel(X, V, batched, false, CA, ME, (int64_t)Ic * p.nch, n_items, cooc_item_grab(visits / (p.half ? 2 : 1), n_items));
     X.t_cooc->end(sp, ls);
     X.side->join(ls);      // (the scoring kernels behind this point read the per-rating values)
     checkpoint(X, V, "row kernel queued / run");
-    if (!batched) R->st.cooc_launches++;
     if (p.half) {    // lower triangle + the block maxima in front of / on the diagonal
         const size_t sm = X.t_mirror->begin(ls);
         // pruned flow: LAZY mirror -- the seed pass reads the seed columns of every row, the bound pass the block maxima, the
         // survivor pass the surviving column blocks (mirrored below, once they are known); nothing else of the lower triangle
         // is ever read, so it is not written (round 3 moved 10.7 GB here to fill a triangle of which a few per cent were read)
         const bool lazy = p.prune && tune.lazy_mirror;
-        launch_mirror(ctx, L.M.get(), ldm, Ic, p.prune ? L.Bmax.get() : nullptr, p.ldb, ls, nullptr, lazy ? std::min(tune.seed_chunks, p.nblk) : 0x7FFFFFFF);
+        launch_mirror(ctx, L.M.get(), p.ldm, Ic, p.prune ? L.Bmax.get() : nullptr, p.ldb, ls, nullptr, lazy ? std::min(tune.seed_chunks, p.nblk) : 0x7FFFFFFF);
         X.t_mirror->end(sm, ls);
     }
     // (not for long lists: their survivors -- 14 % of the blocks at N = 1000 -- spread over the whole popularity order, the 16 wide
     // groups behind the first 48 blocks all survive and hand every block to the survivor pass: measured, the batch falls back to
     // the full pass, 261 -> 471 ms)
     if (p.prune && !p.panel && tune.sup_bounds && !jp.long_seed) {      // super-block bounds for the seed pass (k_score_sup)
-        const int seed_b = std::min(tune.seed_chunks, p.nblk);
         std::vector<int32_t> first;
-        sup_block_map(seed_b, p.nblk, first);
+        sup_block_map(std::min(tune.seed_chunks, p.nblk), p.nblk, first);
         const int n_sup = (int)first.size() - 1;
         first.resize(65, first.back());
         L.sup_first.alloc(ctx, 65);
         L.Bsup.alloc(ctx, (size_t)Ic * 64);
-        L.asup.alloc(ctx, 64);
-        L.bsupb.alloc(ctx, 64);
+        L.asup.alloc(ctx, 64); L.bsupb.alloc(ctx, 64);
         FY_HIP(hipMemcpyAsync(L.sup_first.get(), first.data(), 65 * sizeof(int32_t), hipMemcpyHostToDevice, ls));
         FY_HIP(hipStreamSynchronize(ls));      // (`first` is a host temporary; one cluster: no other lane is waiting)
         const size_t sb = X.t_score->begin(ls);
@@ -2927,319 +2822,269 @@ static void build_cluster_matrix(const ScoreShared& X, const ClusterVisit& V, co
 
 // -- scoring + top-N of the cluster's users of this rank, in user batches that fit the score scratch: the plain full pass, or the
 // three pruned passes (seed + bounds, survivor selection, survivors) with the full pass as their fallback.  A two-phase panel
-// cluster is visited twice: phase 2 queues the front up to the survivor count, phase 3 the rest.
-static void score_cluster(const ScoreShared& X, const ClusterVisit& V, const ClusterNumbers& N) {
+// cluster is visited twice: phase 2 queues the front up to the survivor count, phase 3 the back.
+
+struct UserBatch {           // one batch of the cluster's users
+    int32_t s0, nb;
+    int n_slices;
+    bool whole, split;       // the whole cluster (its CSR range is on the host already); two-phase panel mode: front in phase 2, back in phase 3
+};
+
+// scoring arguments of a batch; with FY_SCORE_HEAVY the count of its heavy users is queued in front of the scoring launches
+static ScoreArgs batch_score_args(const ClusterPass& C, int32_t s0, int32_t nb, const float* M, int64_t ldm, float* S, int64_t ldS, int n_slices, int n_chunks) {
+    ScoreArgs SA = score_args(C.X, C.p, M, ldm, s0, nb, S, ldS, n_slices, n_chunks);
+    if (C.tune.score_heavy > 0) {     // (stream order: every scoring launch of the batch follows)
+        // a small batch (one cluster of many) cannot fill the chip with a wave per user and its launch lasts as long as its
+        // longest list on ONE wave (ML-1M shape in 50 clusters: 0.14 ms per cluster for 120 users): there every user with
+        // more than a few batches is walked by a whole workgroup
+        const int heavy = (int64_t)nb * n_chunks < 8 * (int64_t)C.ctx->num_cus ? std::min(C.tune.score_heavy, 32) : C.tune.score_heavy;
+        k_count_heavy<<<1, 64, 0, C.ls>>>(C.P.rowptr.get() + s0, nb, heavy, C.L.n_heavy.get());
+        SA.n_heavy = C.L.n_heavy.get();
+    }
+    return SA;
+}
+
+// ill-conditioned list rows of a range of users, scored again in fp64 from the fp32 head rows (k_refine_rows); after the lists stand
+static void refine_rows(const ClusterPass& C, int32_t s0, int32_t nb) {
+    if (!C.refine || nb <= 0) return;
+    const ScoreShared& X = C.X; const Prepared& P = C.P; const Plan& p = C.p; Lane& L = C.L; hipStream_t ls = C.ls;
     fy_rm2_job* J = X.J;
-    Context* ctx = X.J->ctx;
-    const Prepared& P = X.J->P;
-    fy_result* R = X.R;
-    const ScoreTune& tune = *X.tune;
-    const fy_rm2_params& prm = X.J->prm;
-    const JobPlan& jp = *X.jp;
-    TableCache& tc = J->S->tables;
-    const size_t pi = V.pi;
-    const int phase = V.phase;
-    const Plan& p = jp.plans[pi];
-    Lane& L = *V.L;
-    hipStream_t ls = V.ls;
-    const PanelPtrs& PP = V.PP;
-    const int c = p.c;
-    const int32_t sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, a = p.a, b = p.b;
-    const int64_t ldm = p.ldm;
-    const bool pack24 = p.pack24;
-    const int32_t lo = X.lo;
-    const double lambda = prm.lambda;
-    const double w2s = N.w2s;
-    const bool refine = N.refine;
-    const int32_t head_rows = N.head_rows;
-    const int64_t ld_head = N.ld_head;
-    const DevBuf<double>&H32 = *V.H32, &T32 = *V.T32;
-    constexpr int VEC = 4;   // floats per lane of the scoring kernel: column chunk = 256 items
-    const int64_t ldS = ldm, B = p.B;
-    const int n_chunks = (int)ceil_div(Ic, 64 * VEC);
-    const int32_t* row_off = P.rowptr.get() + sbase;   // the users' CSR rows: [slot - sbase], [slot - sbase + 1]
-    auto score_args = [&](const float* Mx, int64_t ldmx, int32_t Icx, const float* ax, int32_t s0, int32_t nb, float* Sx, int64_t ldSx,
-                          int n_slices, int nchunks) {
-        ScoreArgs SA{};
-        SA.M = Mx; SA.ldm = ldmx; SA.Ic = Icx; SA.a_rank = ax; SA.b_rank = X.b_rank + pbase; SA.rb_off = row_off;
-        SA.csr_idx = P.csr_idx.get(); SA.csr_e = X.csr_e; SA.csr_q = X.csr_q;
-        SA.pvpi = X.pvpi; SA.n_out = X.n_out; SA.slot_lo = lo; SA.slot_base = sbase; SA.slot0 = s0; SA.n_users = nb;
-        SA.S = Sx; SA.ldS = ldSx; SA.n_slices = n_slices; SA.n_chunks = nchunks;
-        if (tune.score_heavy > 0) {     // (stream order: every scoring launch of the batch follows)
-            // a small batch (one cluster of many) cannot fill the chip with a wave per user and its launch lasts as long as its
-            // longest list on ONE wave (ML-1M shape in 50 clusters: 0.14 ms per cluster for 120 users): there every user with
-            // more than a few batches is walked by a whole workgroup
-            const int heavy = (int64_t)nb * nchunks < 8 * (int64_t)ctx->num_cus ? std::min(tune.score_heavy, 32) : tune.score_heavy;
-            k_count_heavy<<<1, 64, 0, ls>>>(P.rowptr.get() + s0, nb, heavy, L.n_heavy.get());
-            SA.n_heavy = L.n_heavy.get();
+    const fy_rm2_params& prm = J->prm;
+    const size_t tt = X.t_topn->begin(ls);
+    const int32_t n_ids = J->S->max_item + 1, head_rows = C.head_rows;
+    L.colmap.alloc(C.ctx, (size_t)n_ids);
+    FY_HIP(hipMemsetAsync(L.colmap.get(), 0xFF, (size_t)n_ids * sizeof(int32_t), ls));
+    k_refine_colmap<<<(head_rows + 255) / 256, 256, 0, ls>>>(head_rows, P.rank_item_raw.get() + p.pbase, L.colmap.get());
+    FY_KERNEL_CHECK();
+    RefineArgs RA{};
+    RA.slot0 = s0; RA.n_users = nb; RA.slot_lo = X.lo; RA.slot_base = p.sbase;
+    RA.n_out = X.n_out; RA.out_off = X.out_off; RA.out_item = X.R->d_key1.get(); RA.out_score = X.R->d_value.get(); RA.out_item_w = X.R->d_key1.get();
+    RA.rowptr = P.rowptr.get(); RA.csr_idx = P.csr_idx.get(); RA.csr_r = P.csr_r.get(); RA.usum_slot = J->usum_slot.get();
+    RA.p_rank = X.p_rank + p.pbase; RA.b_rank = X.b_rank64 + p.pbase;
+    RA.colmap = L.colmap.get(); RA.max_item = J->S->max_item; RA.head_rows = head_rows;
+    RA.head32 = C.V.H32->get(); RA.ld_head = C.ld_head; RA.tail32 = p.psym ? C.V.T32->get() : nullptr; RA.tail_from = p.p_eff;
+    if (!RA.head32 || (p.psym && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", p.c);
+    RA.unscale = 1.0 / (double)X.gscale[(size_t)p.c];
+    RA.general = J->S->smooth.general() ? 1 : 0; RA.G = J->smooth_args(); RA.cluster = p.c;
+    RA.lambda = prm.lambda; RA.ln_items = std::log((double)prm.number_of_items); RA.ln_users = std::log((double)p.Uc);
+    RA.users_minus_1 = (double)(p.Uc - 1); RA.refine_c = C.tune.refine_c; RA.n_refined = X.prune_counters + 5;
+    int lp2 = 64;
+    while (lp2 < std::min<int>(prm.number_of_recommendations, p.Ic)) lp2 <<= 1;
+    k_refine_rows<<<(nb + 3) / 4, 256, (size_t)4 * lp2 * sizeof(uint64_t), ls>>>(RA);
+    FY_KERNEL_CHECK();
+    X.t_topn->end(tt, ls);
+}
+
+// the lists of a batch from its score rows (TA), then the refinement
+static void batch_lists(const ClusterPass& C, int32_t s0, int32_t nb, const TopNArgs& TA, bool long_list) {
+    const ScoreShared& X = C.X;
+    const size_t tt = X.t_topn->begin(C.ls);
+    launch_topn(C.ctx, C.ls, TA, nb, C.L.overflow.get(), C.L.any_overflow.get(), C.tune.force_select, long_list, X.J->prm.number_of_recommendations,
+                X.prune_counters + 2);
+    X.t_topn->end(tt, C.ls);
+    refine_rows(C, s0, nb);
+}
+
+// the plain full pass over a range of users: every log term, like the reference's loop (AbstractRM2Reducer.java:332-356)
+static void full_pass(const ClusterPass& C, int32_t s0, int32_t nb, float* Sx) {
+    const ScoreShared& X = C.X; const Plan& p = C.p;
+    const int n_slices = score_slices(C.ctx->num_cus, C.tune, nb, C.n_chunks);
+    const ScoreArgs SA = batch_score_args(C, s0, nb, C.L.M.get(), p.ldm, Sx, p.ldm, n_slices, C.n_chunks);
+    const size_t ss = X.t_score->begin(C.ls);
+    launch_score(score_kernel(p.pack24, C.tune.score_walk), C.n_chunks * n_slices, C.ls, SA);
+    X.t_score->end(ss, C.ls);
+    X.R->st.score_launches++;
+    batch_lists(C, s0, nb, topn_args(X, p, Sx, p.ldm, s0), X.J->prm.number_of_recommendations > TOPN_LONG);
+}
+
+// FY_DEBUG_SYNC=3: which blocks survive, and for how many users
+static void dump_survivors(const ClusterPass& C, const UserBatch& B) {
+    const Plan& p = C.p; Lane& L = C.L;
+    DevBuf<int32_t> cnt(C.ctx, (size_t)p.nblk + 1);
+    FY_HIP(hipMemsetAsync(cnt.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), C.ls));
+    k_surv_block_counts<<<std::min<int>(B.nb, 4096), 64, 0, C.ls>>>(B.nb, L.n_quads.get(), L.surv.get(), p.ldb, cnt.get());
+    std::vector<int32_t> hc((size_t)p.nblk + 1);
+    FY_HIP(hipMemcpyAsync(hc.data(), cnt.get(), hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, C.ls));
+    FY_HIP(hipStreamSynchronize(C.ls));
+    int distinct = 0;
+    long long total = 0;
+    for (int b2 = 0; b2 < p.nblk; b2++) { distinct += hc[b2] > 0; total += hc[b2]; }
+    fprintf(stderr, "[fy] cluster %d: %lld surviving (user, block) pairs in %d distinct blocks of %d:", p.c, total, distinct, p.nblk);
+    for (int b2 = 0; b2 < p.nblk; b2++)
+        if (hc[b2]) fprintf(stderr, " %d:%d", b2, hc[b2]);
+    fprintf(stderr, "\n");
+}
+
+// the pruned front: seed + bound launch, tau, block selection, repair, lazy mirror, the scan of the survivor counts
+static void pruned_front(const ClusterPass& C, const UserBatch& B) {
+    const ScoreShared& X = C.X; const Prepared& P = C.P; const ScoreTune& tune = C.tune; const Plan& p = C.p; Lane& L = C.L; hipStream_t ls = C.ls;
+    Context* ctx = C.ctx;
+    const PanelPtrs& PP = C.V.PP;
+    const int32_t s0 = B.s0, nb = B.nb;
+    // (1) + (3) ONE launch: exact scores of the seed columns (the most popular candidates) and the upper bounds of all 256-column
+    // blocks (the same kernel on the block-maximum matrix); the grid's tail -- the waves that walk the heaviest users -- is paid once
+    // instead of twice.  With super-block bounds the seed chunks' own waves evaluate them and the bound chunks are not launched.
+    // (A two-level bound -- 256-column block maxima first, the 64-column sub-block bounds only for the surviving blocks -- was
+    // built and measured in round 3: the first level reads a quarter of the bytes, but five times as many blocks reach the
+    // second level, whose per-(user, block) gathers of Bmax64 rows cost more than the streamed pass saved: 113 -> 129 ms at 50
+    // clusters.  Removed.)
+    const int bchunks = (int)(C.bld / 256);
+    if (C.use_sup) {
+        ScoreArgs SU = batch_score_args(C, s0, nb, C.Gmat, C.gld, L.S.get(), C.SC, B.n_slices, C.seed_chunks);
+        L.UBs.alloc(ctx, (size_t)nb * 64);
+        SU.Bsup = L.Bsup.get(); SU.asup = L.asup.get(); SU.bsup_b = L.bsupb.get(); SU.UBsup = L.UBs.get();
+        SU.n_sup = std::min(64, std::max(0, p.nblk - C.seed_chunks));
+        launch_score(score_sup_kernel(tune.score_walk), C.seed_chunks * B.n_slices, ls, SU);
+    }
+    ScoreArgs SA = batch_score_args(C, s0, nb, C.Gmat, C.gld, L.S.get(), C.SC, B.n_slices, C.seed_chunks + bchunks);
+    score_args_bounds(SA, C.seed_chunks, p.panel ? PP.Bmax64 : L.Bmax.get(), C.bld, p.panel ? p.nsub : p.nblk, p.panel ? PP.amax64 : L.amax.get(),
+                      p.panel ? PP.bmax64 : L.bmax.get(), L.UB.get());
+    if (!C.use_sup) launch_score(score_kernel(true, tune.score_walk), (C.seed_chunks + bchunks) * B.n_slices, ls, SA);
+    // (2) tau_u = N-th best seed score; the sorted seed head is also the user's list unless a block survives
+    TopNArgs T1 = topn_args(X, p, L.S.get(), C.SC, s0);
+    topn_pruned(T1, 1, C.seed_chunks * 256, L.surv.get(), L.n_quads.get(), C.bld, L.tau.get());
+    if (X.jp->long_seed) {
+        launch_topn_pass(ls, T1, nb, L.overflow.get(), L.any_overflow.get(), 0, true, X.J->prm.number_of_recommendations);
+    } else {
+        int lp2 = 64;                   // the sort's size: the seed columns, at most TOPN_SAMPLE
+        while (lp2 < std::min<int>(std::min<int>(p.Ic, C.seed_chunks * 256), TOPN_SAMPLE)) lp2 <<= 1;
+        topn_seed_kernel(lp2, tune.topn_seed_xl)<<<(unsigned)((nb + 3) / 4), 256, 0, ls>>>(T1, nb, L.overflow.get());
+        FY_KERNEL_CHECK();
+    }
+    // (4) the blocks whose bound reaches tau_u, in ascending order
+    FY_HIP(hipMemsetAsync(L.n_quads.get(), 0, ((size_t)nb + 1) * sizeof(int32_t), ls));
+    if (p.panel)
+        k_bound_select_sub<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), C.bld, p.nsub, p.nblk, C.seed_chunks, L.tau.get(),
+                                                                           X.pvpi + (s0 - X.lo), nb, C.bld, L.surv.get(), L.surv_mask.get(), L.n_quads.get());
+    else if (C.use_sup)
+        k_bound_select_sup<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UBs.get(), std::min(64, std::max(0, p.nblk - C.seed_chunks)), L.sup_first.get(), L.tau.get(),
+                                                                           X.pvpi + (s0 - X.lo), nb, p.ldb, L.surv.get(), L.n_quads.get());
+    else
+        k_bound_select<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), p.ldb, p.nblk, C.seed_chunks, L.tau.get(), X.pvpi + (s0 - X.lo), nb,
+                                                                       L.surv.get(), L.n_quads.get());
+    FY_KERNEL_CHECK();
+    if (tune.debug_sync == 3 && !p.panel) dump_survivors(C, B);
+    if (p.panel && tune.panel_repair) {
+        // (4b) sub-blocks that hold an item the user rated: bound again without the user's own co-ratings
+        RepairArgs RA{L.surv.get(), L.surv_mask.get(), L.n_quads.get(), C.bld, nb, s0, X.lo, p.p_eff, p.Ic, P.rowptr.get(), P.csr_idx.get(),
+                      X.csr_x, X.csr_e, X.csr_q, PP.Bmax64, PP.Brep, p.ldb64, PP.amax64, PP.bmax64,
+                      L.tau.get(), X.pvpi, (float)C.w2s, X.prune_counters};
+        k_bound_repair<<<std::min<int>(nb, ctx->num_cus * 16), 256, 0, ls>>>(RA);
+        FY_KERNEL_CHECK();
+    }
+    if (p.half && !p.panel && tune.lazy_mirror) {      // lazy mirror, second pass: the column blocks with survivors
+        const size_t sm = X.t_mirror->begin(ls);
+        L.need.alloc(ctx, (size_t)p.nblk + 1);
+        FY_HIP(hipMemsetAsync(L.need.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
+        k_flag_surviving_blocks<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, L.need.get());
+        FY_KERNEL_CHECK();
+        launch_mirror(ctx, L.M.get(), p.ldm, p.Ic, nullptr, p.ldb, ls, L.need.get(), 0, false);
+        X.t_mirror->end(sm, ls);
+    }
+    exclusive_scan_i32(ctx, L.n_quads.get(), L.quad_prefix.get(), (size_t)nb + 1, ls, &L.scan_tmp);
+}
+
+// The threshold did not bite (e.g. lambda = 0: a user who rated an item nobody else of the cluster rated has only -inf scores,
+// tau = -inf keeps every block): the survivor pass would cost more than the plain full pass and 1 KB of scratch per survivor.
+// Redo the batch with the full pass, in sub-batches that fit the workspace.
+static void fallback_full_pass(const ClusterPass& C, const UserBatch& B) {
+    const ScoreShared& X = C.X; const Plan& p = C.p; hipStream_t ls = C.ls;
+    if (p.half && C.tune.lazy_mirror) {      // the plain full pass reads every row whole: the rest of the lower triangle now
+        const size_t sm = X.t_mirror->begin(ls);
+        launch_mirror(C.ctx, C.L.M.get(), p.ldm, p.Ic, nullptr, p.ldb, ls, nullptr, 0x7FFFFFFF, false);
+        X.t_mirror->end(sm, ls);
+    }
+    const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((X.jp->ws / X.jp->NS) / (p.ldm * 4), B.nb));
+    DevBuf<float> Sfull(C.ctx, (size_t)(sub * p.ldm));
+    for (int32_t t0 = B.s0; t0 < B.s0 + B.nb; t0 += (int32_t)sub) full_pass(C, t0, (int32_t)std::min<int64_t>(sub, B.s0 + B.nb - t0), Sfull.get());
+    FY_HIP(hipStreamSynchronize(ls));   // Sfull goes back to the allocator
+    X.R->st.prune_fallbacks++;
+    X.R->st.score_launches++;          // the fused seed + bound launch that was thrown away
+}
+
+// the pruned back: the survivor count reaches the host, then the fallback, or survivors, strays and lists.  `ss` = the open span of
+// the scoring timer.
+static void pruned_back(const ClusterPass& C, const UserBatch& B, size_t ss) {
+    const ScoreShared& X = C.X; const Prepared& P = C.P; const Plan& p = C.p; Lane& L = C.L; hipStream_t ls = C.ls;
+    Context* ctx = C.ctx;
+    const int32_t s0 = B.s0, nb = B.nb;
+    int32_t hv[3] = {0, 0, 0};   // survivors, first / last CSR entry of the batch
+    if (!B.split) FY_HIP(hipMemcpyAsync(&hv[0], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+    else hv[0] = C.V.pinned[C.V.pi];
+    if (B.whole) {
+        hv[1] = (*X.csr_range)[2 * C.V.pi];
+        hv[2] = (*X.csr_range)[2 * C.V.pi + 1];
+    } else {
+        FY_HIP(hipMemcpyAsync(&hv[1], P.rowptr.get() + s0, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+        FY_HIP(hipMemcpyAsync(&hv[2], P.rowptr.get() + s0 + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+    }
+    if (!B.split) FY_HIP(hipStreamSynchronize(ls));   // (everything queued on this lane before has finished: Ssurv may be re-sized)
+    const int32_t n_surv_total = hv[0];
+    const int64_t blocks_checked = (int64_t)nb * std::max(0, p.nblk - C.seed_chunks);
+    *X.blocks_total += blocks_checked;
+    if (!p.panel && (double)n_surv_total > C.tune.max_surv_frac * (double)blocks_checked) {     // (panel mode has no full matrix to fall back on)
+        X.t_score->end(ss, ls);
+        fallback_full_pass(C, B);
+        *X.fallback_survived += n_surv_total;
+        *X.seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (C.seed_chunks * 256 + p.ldb + p.ldm);
+        return;
+    }
+    L.Ssurv.alloc(ctx, (size_t)std::max(1, n_surv_total) * PRUNE_BLOCK);
+    if (n_surv_total > 0) {     // (5) exact scores of the survivors, packed: 256 floats per surviving block at entry quad_prefix[u] + k
+        const ScoreArgs SQ = batch_score_args(C, s0, nb, C.Gmat, C.gld, L.Ssurv.get(), 0, B.n_slices, C.n_chunks);
+        const int panel_blocks = p.panel ? p.panel_cols / 256 : 0x7FFFFFFF;
+        score_blocks_kernel(C.tune.score_walk)<<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(
+            SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi, L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, C.bld, X.prune_counters,
+            panel_blocks, p.panel ? L.surv_mask.get() : nullptr);
+        FY_KERNEL_CHECK();
+        if (p.panel && panel_blocks < p.nblk) {     // survivors behind the panel: exact, from the sparse data
+            const size_t slds = ((size_t)p.Uc + 1) * sizeof(int32_t);
+            const int sgrid = std::min<int>(n_surv_total, ctx->num_cus * (int)std::max<size_t>(1, std::min<size_t>(6, (150 * 1024) / (slds + 34 * 1024))));
+            L.strayT.alloc(ctx, (size_t)sgrid * STRAY_TCAP);
+            L.stray_items.alloc(ctx, (size_t)n_surv_total + 1);      // (a group holds at least one surviving block)
+            FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
+            k_stray_items<<<grid_for(nb), 256, 0, ls>>>(L.quad_prefix.get(), L.surv.get(), C.bld, nb, panel_blocks, L.stray_items.get(),
+                                                       L.any_overflow.get());
+            FY_KERNEL_CHECK();
+            StrayArgs ST{L.quad_prefix.get(), L.surv.get(), L.surv_mask.get(), C.bld, nb, s0, X.lo, p.sbase, p.Uc, panel_blocks, p.Ic, p.pbase,
+                         P.rowptr.get(), P.csr_idx.get(), X.csr_e, X.csr_q, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(),
+                         X.J->S->tables.csc_x.get(), X.a_rank + p.pbase, X.b_rank + p.pbase, X.pvpi,
+                         (float)C.w2s, L.Ssurv.get(), L.strayT.get(), X.prune_counters, L.stray_items.get(),
+                         L.any_overflow.get()};
+            k_score_stray<<<sgrid, 256, slds, ls>>>(ST);
+            FY_KERNEL_CHECK();
         }
-        return SA;
-    };
-    // ill-conditioned list rows of a range of users, scored again in fp64 from the fp32 head rows (k_refine_rows); after the lists stand
-    auto refine_rows = [&](int32_t s0, int32_t nb) {
-        if (!refine || nb <= 0) return;
-        const size_t tt = X.t_topn->begin(ls);
-        const int32_t n_ids = J->S->max_item + 1;
-        L.colmap.alloc(ctx, (size_t)n_ids);
-        FY_HIP(hipMemsetAsync(L.colmap.get(), 0xFF, (size_t)n_ids * sizeof(int32_t), ls));
-        k_refine_colmap<<<(head_rows + 255) / 256, 256, 0, ls>>>(head_rows, P.rank_item_raw.get() + pbase, L.colmap.get());
-        FY_KERNEL_CHECK();
-        RefineArgs RA{};
-        RA.slot0 = s0; RA.n_users = nb; RA.slot_lo = lo; RA.slot_base = sbase;
-        RA.n_out = X.n_out; RA.out_off = X.out_off; RA.out_item = R->d_key1.get(); RA.out_score = R->d_value.get(); RA.out_item_w = R->d_key1.get();
-        RA.rowptr = P.rowptr.get(); RA.csr_idx = P.csr_idx.get(); RA.csr_r = P.csr_r.get(); RA.usum_slot = J->usum_slot.get();
-        RA.p_rank = X.p_rank + pbase; RA.b_rank = X.b_rank64 + pbase;
-        RA.colmap = L.colmap.get(); RA.max_item = J->S->max_item;
-        RA.head_rows = head_rows;
-        RA.head32 = H32.get(); RA.ld_head = ld_head; RA.tail32 = p.psym ? T32.get() : nullptr; RA.tail_from = p.p_eff;
-        if (!RA.head32 || (p.psym && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", c);
-        RA.unscale = 1.0 / (double)X.gscale[(size_t)c];
-        RA.general = J->S->smooth.general() ? 1 : 0; RA.G = J->smooth_args(); RA.cluster = c;
-        RA.lambda = lambda; RA.ln_items = std::log((double)prm.number_of_items); RA.ln_users = std::log((double)p.Uc);
-        RA.users_minus_1 = (double)(p.Uc - 1);
-        RA.refine_c = tune.refine_c;
-        RA.n_refined = X.prune_counters + 5;
-        int lp2 = 64;
-        while (lp2 < std::min<int>(prm.number_of_recommendations, Ic)) lp2 <<= 1;
-        k_refine_rows<<<(nb + 3) / 4, 256, (size_t)4 * lp2 * sizeof(uint64_t), ls>>>(RA);
-        FY_KERNEL_CHECK();
-        X.t_topn->end(tt, ls);
-    };
-    // the plain full pass over a range of users: every log term, like the reference's loop (AbstractRM2Reducer.java:332-356)
-    auto full_pass = [&](int32_t s0, int32_t nb, float* Sx) {
-        const int n_slices = score_slices(ctx->num_cus, tune, nb, n_chunks);
-        ScoreArgs SA = score_args(L.M.get(), ldm, Ic, X.a_rank + pbase, s0, nb, Sx, ldS, n_slices, n_chunks);
+    }
+    X.t_score->end(ss, ls);
+    X.R->st.score_launches += 2;   // the fused seed + bound launch and the survivor pass
+    // log terms of the seed and bound passes of this batch: (ratings of its users) x (columns walked)
+    *X.seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (C.seed_chunks * 256 + (C.use_sup ? 64 : C.bld));
+    TopNArgs TA = topn_args(X, p, L.S.get(), C.SC, s0);
+    topn_pruned(TA, 2, C.seed_chunks * 256, L.surv.get(), L.n_quads.get(), C.bld, L.tau.get(), L.Ssurv.get(), L.quad_prefix.get());
+    batch_lists(C, s0, nb, TA, X.jp->long_seed);
+    checkpoint(X, C.V, "back (survivors, strays, lists)");
+}
+
+static void score_cluster(const ClusterPass& C) {
+    const ScoreShared& X = C.X; const ClusterVisit& V = C.V; const Plan& p = C.p; hipStream_t ls = C.ls;
+    for (int32_t s0 = p.a; s0 < p.b; s0 += (int32_t)p.B) {
+        const int32_t nb = (int32_t)std::min<int64_t>(p.B, p.b - s0);
+        if (!p.prune) { full_pass(C, s0, nb, V.L->S.get()); continue; }
+        UserBatch B{s0, nb, score_slices(C.ctx->num_cus, C.tune, nb, C.seed_chunks + (C.use_sup ? 0 : (int)(p.ldb / 256)))};
+        B.whole = s0 == p.sbase && nb == p.Uc;
+        B.split = X.jp->two_phase && p.panel && B.whole;
+        if (V.phase == 3 && !B.split) continue;
         const size_t ss = X.t_score->begin(ls);
-        if (pack24 && tune.score_walk) k_score<4, true, 8, 1><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-        else if (pack24) k_score<4, true, 8, 0><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-        else k_score<4, false, 8><<<n_chunks * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-        FY_KERNEL_CHECK();
-        X.t_score->end(ss, ls);
-        R->st.score_launches++;
-        TopNArgs TA{Sx, ldS, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(), lo, s0, c,
-                    R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(), 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-        const size_t tt = X.t_topn->begin(ls);
-        FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
-        if (prm.number_of_recommendations > TOPN_LONG)
-            k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select,
-                                                                                                 fy_topn_long_cap(prm.number_of_recommendations));
-        else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
-        FY_KERNEL_CHECK();
-        k_topn_select<<<fy_topn_select_grid(nb, ctx->num_cus), 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), nb, X.prune_counters + 2);
-        FY_KERNEL_CHECK();
-        X.t_topn->end(tt, ls);
-        refine_rows(s0, nb);
-    };
-    for (int32_t s0 = a; s0 < b; s0 += (int32_t)B) {
-        const int32_t nb = (int32_t)std::min<int64_t>(B, b - s0);
-        if (!p.prune) { full_pass(s0, nb, L.S.get()); continue; }
-        const int seed_chunks = std::min(n_chunks, tune.seed_chunks);
-        const bool use_sup = tune.sup_bounds && !p.panel && !jp.long_seed;      // bounds over super-blocks, evaluated by the seed chunk's own waves
-        const int n_slices = score_slices(ctx->num_cus, tune, nb, seed_chunks + (use_sup ? 0 : (int)(p.ldb / 256)));
-        // front in phase 2, back in phase 3 (the whole cluster in one batch: its CSR range is on the host already)
-        const bool split = jp.two_phase && p.panel && s0 == sbase && nb == p.Uc;
-        if (phase == 3 && !split) continue;
-        size_t ss = X.t_score->begin(ls);
-        const int seed_blocks = seed_chunks;
-        const int64_t SC = (int64_t)seed_chunks * 256;   // pitch of the compact score rows: seed columns only
-        // only the seed columns and the surviving blocks of a score row are ever written or read
-        // (1) + (3) ONE launch: exact scores of the seed columns (the most popular candidates) and the upper bounds
-        // of all 256-column blocks (the same kernel on the block-maximum matrix); the grid's tail -- the waves
-        // that walk the heaviest users -- is paid once instead of twice
-        // panel mode: the stored rows are panel_cols wide and the bound matrix has one column per 64-column sub-block
-        const float* Gmat = p.panel ? PP.Gp : L.M.get();
-        const int64_t gld = p.panel ? (int64_t)p.panel_cols : ldm;
-        // (A two-level bound -- 256-column block maxima first, the 64-column sub-block bounds only for the surviving blocks -- was
-        // built and measured in round 3: the first level reads a quarter of the bytes, but five times as many blocks reach the
-        // second level, whose per-(user, block) gathers of Bmax64 rows cost more than the streamed pass saved: 113 -> 129 ms at 50
-        // clusters.  Removed.)
-        const int64_t bld = p.panel ? p.ldb64 : p.ldb;           // pitch of the bound matrix, of UB and of the survivor lists
-        const int bchunks = (int)(bld / 256);
-        int32_t hv[3] = {0, 0, 0};   // survivors, first / last CSR entry of the batch
-        if (phase != 3) {
-        if (use_sup) {
-            ScoreArgs SU = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks);
-            L.UBs.alloc(ctx, (size_t)nb * 64);
-            SU.Bsup = L.Bsup.get(); SU.asup = L.asup.get(); SU.bsup_b = L.bsupb.get(); SU.UBsup = L.UBs.get();
-            SU.n_sup = std::min(64, std::max(0, p.nblk - seed_chunks));
-            if (tune.score_walk) k_score_sup<1><<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
-            else k_score_sup<0><<<seed_chunks * n_slices, 256, 0, ls>>>(SU.M, SU.a_rank, SU.rb_off, SU.csr_idx, SU.csr_e, SU.csr_q, SU.pvpi, SU.n_out, SU.S, SU);
-            FY_KERNEL_CHECK();
-        }
-        ScoreArgs SA = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.S.get(), SC, n_slices, seed_chunks + bchunks);
-        SA.chunks1 = seed_chunks;
-        SA.M2 = p.panel ? PP.Bmax64 : L.Bmax.get();
-        SA.ldm2 = bld;
-        SA.Ic2 = p.panel ? p.nsub : p.nblk;
-        SA.a2 = p.panel ? PP.amax64 : L.amax.get();
-        SA.b2 = p.panel ? PP.bmax64 : L.bmax.get();
-        SA.S2 = L.UB.get();
-        SA.ldS2 = bld;
-        SA.no_mask2 = 1;
-        if (!use_sup) {
-            if (tune.score_walk) k_score<4, true, 8, 1><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-            else k_score<4, true, 8, 0><<<(seed_chunks + bchunks) * n_slices, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-            FY_KERNEL_CHECK();
-        }
-        // (2) tau_u = N-th best seed score; the sorted seed head is also the user's list unless a block survives
-        TopNArgs T1{L.S.get(), SC, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(),
-                    lo, s0, c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
-                    1, seed_chunks * 256, L.surv.get(), L.n_quads.get(), bld, L.tau.get()};
-        if (jp.long_seed) {
-            k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(T1, L.overflow.get(), L.any_overflow.get(), 0,
-                                                                                                 fy_topn_long_cap(prm.number_of_recommendations));
-        } else {
-            int lp2 = 64;                   // the sort's size: the seed columns, at most TOPN_SAMPLE
-            while (lp2 < std::min<int>(std::min<int>(Ic, seed_chunks * 256), TOPN_SAMPLE)) lp2 <<= 1;
-            const unsigned sg = (unsigned)((nb + 3) / 4);
-            auto seed = [&](auto xl) {      // (tune.topn_seed_xl picks the instantiation)
-                constexpr int XL = decltype(xl)::value;
-                if (lp2 <= 64) k_topn_seed<1, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                else if (lp2 == 128) k_topn_seed<2, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                else if (lp2 == 256) k_topn_seed<4, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                else if (lp2 == 512) k_topn_seed<8, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-                else k_topn_seed<16, XL><<<sg, 256, 0, ls>>>(T1, nb, L.overflow.get());
-            };
-            if (tune.topn_seed_xl) seed(std::integral_constant<int, 1>{});
-            else seed(std::integral_constant<int, 0>{});
-        }
-        FY_KERNEL_CHECK();
-        // (4) the blocks whose bound reaches tau_u, in ascending order
-        FY_HIP(hipMemsetAsync(L.n_quads.get(), 0, ((size_t)nb + 1) * sizeof(int32_t), ls));
-        if (p.panel)
-            k_bound_select_sub<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), bld, p.nsub, p.nblk, seed_blocks, L.tau.get(),
-                                                                               X.pvpi + (s0 - lo), nb, bld, L.surv.get(), L.surv_mask.get(), L.n_quads.get());
-        else if (use_sup)
-            k_bound_select_sup<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UBs.get(), std::min(64, std::max(0, p.nblk - seed_chunks)), L.sup_first.get(), L.tau.get(),
-                                                                               X.pvpi + (s0 - lo), nb, p.ldb, L.surv.get(), L.n_quads.get());
-        else
-            k_bound_select<<<grid_for((int64_t)nb * 64, 256), 256, 0, ls>>>(L.UB.get(), p.ldb, p.nblk, seed_blocks, L.tau.get(), X.pvpi + (s0 - lo), nb,
-                                                                           L.surv.get(), L.n_quads.get());
-        FY_KERNEL_CHECK();
-        if (tune.debug_sync == 3 && !p.panel) {      // which blocks survive, and for how many users
-            DevBuf<int32_t> cnt(ctx, (size_t)p.nblk + 1);
-            FY_HIP(hipMemsetAsync(cnt.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
-            k_surv_block_counts<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, cnt.get());
-            std::vector<int32_t> hc((size_t)p.nblk + 1);
-            FY_HIP(hipMemcpyAsync(hc.data(), cnt.get(), hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-            FY_HIP(hipStreamSynchronize(ls));
-            int distinct = 0;
-            long long total = 0;
-            for (int b2 = 0; b2 < p.nblk; b2++) { distinct += hc[b2] > 0; total += hc[b2]; }
-            fprintf(stderr, "[fy] cluster %d: %lld surviving (user, block) pairs in %d distinct blocks of %d:", c, total, distinct, p.nblk);
-            for (int b2 = 0; b2 < p.nblk; b2++)
-                if (hc[b2]) fprintf(stderr, " %d:%d", b2, hc[b2]);
-            fprintf(stderr, "\n");
-        }
-        if (p.panel && tune.panel_repair) {
-            // (4b) sub-blocks that hold an item the user rated: bound again without the user's own co-ratings
-            RepairArgs RA{L.surv.get(), L.surv_mask.get(), L.n_quads.get(), bld, nb, s0, lo, p.p_eff, Ic, P.rowptr.get(), P.csr_idx.get(),
-                          X.csr_x, X.csr_e, X.csr_q, PP.Bmax64, PP.Brep, p.ldb64, PP.amax64, PP.bmax64,
-                          L.tau.get(), X.pvpi, (float)w2s, X.prune_counters};
-            k_bound_repair<<<std::min<int>(nb, ctx->num_cus * 16), 256, 0, ls>>>(RA);
-            FY_KERNEL_CHECK();
-        }
-        if (p.half && !p.panel && tune.lazy_mirror) {      // lazy mirror, second pass: the column blocks with survivors
-            const size_t sm = X.t_mirror->begin(ls);
-            L.need.alloc(ctx, (size_t)p.nblk + 1);
-            FY_HIP(hipMemsetAsync(L.need.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
-            k_flag_surviving_blocks<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, L.need.get());
-            FY_KERNEL_CHECK();
-            launch_mirror(ctx, L.M.get(), ldm, Ic, nullptr, p.ldb, ls, L.need.get(), 0, false);
-            X.t_mirror->end(sm, ls);
-        }
-        exclusive_scan_i32(ctx, L.n_quads.get(), L.quad_prefix.get(), (size_t)nb + 1, ls, &L.scan_tmp);
-        if (split) {      // the count goes to pinned memory; the host does not wait here
-            FY_HIP(hipMemcpyAsync(&V.pinned[pi], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-            X.t_score->end(ss, ls);
-            checkpoint(X, V, "front (seed + bound, select, second bound)");
-            continue;
-        }
-        }      // phase != 3
-        // (5) exact scores of the survivors, packed: 256 floats per surviving block at entry quad_prefix[u] + k
-        if (!split) FY_HIP(hipMemcpyAsync(&hv[0], L.quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-        else hv[0] = V.pinned[pi];
-        if (s0 == sbase && nb == p.Uc) {      // the whole cluster: its CSR range is on the host already
-            hv[1] = (*X.csr_range)[2 * pi];
-            hv[2] = (*X.csr_range)[2 * pi + 1];
-        } else {
-            FY_HIP(hipMemcpyAsync(&hv[1], P.rowptr.get() + s0, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-            FY_HIP(hipMemcpyAsync(&hv[2], P.rowptr.get() + s0 + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-        }
-        if (!split) FY_HIP(hipStreamSynchronize(ls));   // (everything queued on this lane before has finished: Ssurv may be re-sized)
-        const int32_t n_surv_total = hv[0];
-        const int64_t blocks_checked = (int64_t)nb * std::max(0, p.nblk - seed_blocks);
-        if (!p.panel && (double)n_surv_total > tune.max_surv_frac * (double)blocks_checked) {     // (panel mode has no full matrix to fall back on)
-            // The threshold did not bite (e.g. lambda = 0: a user who rated an item nobody else of the cluster rated has
-            // only -inf scores, tau = -inf keeps every block): the survivor pass would cost more than the plain full pass
-            // and 1 KB of scratch per survivor.  Redo the batch with the full pass, in sub-batches that fit the workspace.
-            X.t_score->end(ss, ls);
-            if (p.half && tune.lazy_mirror) {      // the plain full pass reads every row whole: the rest of the lower triangle now
-                const size_t sm = X.t_mirror->begin(ls);
-                launch_mirror(ctx, L.M.get(), ldm, Ic, nullptr, p.ldb, ls, nullptr, 0x7FFFFFFF, false);
-                X.t_mirror->end(sm, ls);
-            }
-            const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((jp.ws / jp.NS) / (ldm * 4), nb));
-            DevBuf<float> Sfull(ctx, (size_t)(sub * ldm));
-            for (int32_t t0 = s0; t0 < s0 + nb; t0 += (int32_t)sub) full_pass(t0, (int32_t)std::min<int64_t>(sub, s0 + nb - t0), Sfull.get());
-            FY_HIP(hipStreamSynchronize(ls));   // Sfull goes back to the allocator
-            R->st.prune_fallbacks++;
-            R->st.score_launches++;          // the fused seed + bound launch that was thrown away
-            *X.blocks_total += blocks_checked;
-            *X.fallback_survived += n_surv_total;
-            *X.seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (seed_chunks * 256 + p.ldb + ldm);
-            continue;
-        }
-        L.Ssurv.alloc(ctx, (size_t)std::max(1, n_surv_total) * PRUNE_BLOCK);
-        if (n_surv_total > 0) {
-            ScoreArgs SQ = score_args(Gmat, gld, Ic, X.a_rank + pbase, s0, nb, L.Ssurv.get(), 0, n_slices, n_chunks);
-            const int panel_blocks = p.panel ? p.panel_cols / 256 : 0x7FFFFFFF;
-            if (tune.score_walk) k_score_blocks<8, 1><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
-                                                                L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, bld, X.prune_counters, panel_blocks,
-                                                                p.panel ? L.surv_mask.get() : nullptr);
-            else k_score_blocks<8, 0><<<std::min(n_surv_total, ctx->num_cus * 16), 256, 0, ls>>>(SQ.M, SQ.a_rank, P.rowptr.get(), SQ.csr_idx, SQ.csr_e, SQ.csr_q, SQ.pvpi,
-                                                                L.quad_prefix.get(), L.surv.get(), SQ.S, SQ, bld, X.prune_counters, panel_blocks,
-                                                                p.panel ? L.surv_mask.get() : nullptr);
-            FY_KERNEL_CHECK();
-            if (p.panel && panel_blocks < p.nblk) {     // survivors behind the panel: exact, from the sparse data
-                const size_t slds = ((size_t)p.Uc + 1) * sizeof(int32_t);
-                const int sgrid = std::min<int>(n_surv_total, ctx->num_cus * (int)std::max<size_t>(1, std::min<size_t>(6, (150 * 1024) / (slds + 34 * 1024))));
-                L.strayT.alloc(ctx, (size_t)sgrid * STRAY_TCAP);
-                L.stray_items.alloc(ctx, (size_t)n_surv_total + 1);      // (a group holds at least one surviving block)
-                FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));   // reused as the item counter
-                k_stray_items<<<grid_for(nb), 256, 0, ls>>>(L.quad_prefix.get(), L.surv.get(), bld, nb, panel_blocks, L.stray_items.get(),
-                                                           L.any_overflow.get());
-                FY_KERNEL_CHECK();
-                StrayArgs ST{L.quad_prefix.get(), L.surv.get(), L.surv_mask.get(), bld, nb, s0, lo, sbase, p.Uc, panel_blocks, Ic, pbase,
-                             P.rowptr.get(), P.csr_idx.get(), X.csr_e, X.csr_q, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(),
-                             tc.csc_x.get(), X.a_rank + pbase, X.b_rank + pbase, X.pvpi,
-                             (float)w2s, L.Ssurv.get(), L.strayT.get(), X.prune_counters, L.stray_items.get(),
-                             L.any_overflow.get()};
-                k_score_stray<<<sgrid, 256, slds, ls>>>(ST);
-                FY_KERNEL_CHECK();
+        if (V.phase != 3) {
+            pruned_front(C, B);
+            if (B.split) {      // the count goes to pinned memory; the host does not wait here
+                FY_HIP(hipMemcpyAsync(&V.pinned[V.pi], V.L->quad_prefix.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
+                X.t_score->end(ss, ls);
+                checkpoint(X, V, "front (seed + bound, select, second bound)");
+                continue;
             }
         }
-        X.t_score->end(ss, ls);
-        R->st.score_launches += 2;   // the fused seed + bound launch and the survivor pass
-        *X.blocks_total += blocks_checked;
-        // log terms of the seed and bound passes of this batch: (ratings of its users) x (columns walked)
-        *X.seed_terms_cols += (int64_t)(hv[2] - hv[1]) * (seed_chunks * 256 + (use_sup ? 64 : bld));
-        const int32_t seed_cols_p = seed_chunks * 256;
-        TopNArgs TA{L.S.get(), (int64_t)seed_cols_p, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase,
-                    P.slot2du.get(), P.uid.get(), lo, s0, c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
-                    2, seed_cols_p, L.surv.get(), L.n_quads.get(), bld, L.tau.get(), L.Ssurv.get(), L.quad_prefix.get()};
-        const size_t tt = X.t_topn->begin(ls);
-        FY_HIP(hipMemsetAsync(L.any_overflow.get(), 0, sizeof(int32_t), ls));
-        if (jp.long_seed)
-            k_topn_long<<<nb, 256, (size_t)fy_topn_long_cap(prm.number_of_recommendations) * 8, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select,
-                                                                                                 fy_topn_long_cap(prm.number_of_recommendations));
-        else k_topn_fast<<<nb, 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), tune.force_select);
-        FY_KERNEL_CHECK();
-        k_topn_select<<<fy_topn_select_grid(nb, ctx->num_cus), 256, 0, ls>>>(TA, L.overflow.get(), L.any_overflow.get(), nb, X.prune_counters + 2);
-        FY_KERNEL_CHECK();
-        X.t_topn->end(tt, ls);
-        refine_rows(s0, nb);
-        checkpoint(X, V, "back (survivors, strays, lists)");
+        pruned_back(C, B, ss);
     }
 }
 
@@ -3255,10 +3100,10 @@ static void visit_cluster(const ScoreShared& X, const ClusterVisit& V) {
         score_cluster_coop(X, p, V.ls);
         return;
     }
-    const ClusterNumbers N = cluster_numbers(X, p);
+    const ClusterPass C = cluster_pass(X, V);
     const bool do_build = !(V.phase >= 2 && p.panel), do_score = V.phase != 1;
-    if (do_build) build_cluster_matrix(X, V, N);
-    if (do_score) score_cluster(X, V, N);
+    if (do_build) build_cluster_matrix(C);
+    if (do_score) score_cluster(C);
 }
 
 // phase 1 of a group: the row kernels of all its panel clusters in two launches, then (symmetric panel mode) the lower triangle of

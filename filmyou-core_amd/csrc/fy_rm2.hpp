@@ -91,7 +91,7 @@ fy_ratings* ratings_shifted(Context*, const fy_ratings*, float shift);
 fy_result* itemsim_pairs(Context*, fy_result* similarities);
 
 constexpr int TOPN_LIST_MAX = 2048;   // longest list of the top-N kernels (TOPN_MAX of fy_rm2_kernels.hpp)
-// top-N over rows of a dense score matrix (NaN = not a candidate): k_topn_fast + k_topn_select of fy_rm2.hip.
+// top-N over rows of a dense score matrix (NaN = not a candidate): launch_topn (fy_rm2_launch.hpp): k_topn_fast or k_topn_long, then k_topn_select.
 // n_out[u] rows are written at out_off[u] for u in [0, n_rows); item ids come from rank_item_raw[column].
 void launch_topn_rows(Context* ctx, hipStream_t st, const float* S, int64_t ldS, int32_t n_cols, int32_t n_rows,
                       const int32_t* n_out, const int32_t* out_off, const int32_t* rank_item_raw, const int32_t* slot2du,

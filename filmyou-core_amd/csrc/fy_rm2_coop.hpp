@@ -1,6 +1,6 @@
 // fy_rm2_coop.hpp -- host orchestration of the cooperative multi-rank path (fy_collectives, include/filmyou.h).
 // NOT a standalone header: one section of fy_rm2.hip's translation unit (needs fy_rm2_job, ScoreShared, Plan and the kernels),
-// split out for size.  score_cluster_coop is the cooperative counterpart of build_cluster_matrix + score_cluster (fy_rm2.hip): visit_cluster
+// split out for size.  score_cluster_coop is the cooperative counterpart of build_cluster_matrix + score_cluster (fy_rm2.hip) and launches through the same launchers (fy_rm2_launch.hpp): visit_cluster
 // hands it the same ScoreShared and the cluster's Plan (Plan::coop, decided by plan_job, fy_rm2_plan.hpp).
 #pragma once
 
@@ -28,6 +28,57 @@ static void coll_reduce_scatter(fy_rm2_job* J, const float* send, float* recv, i
     if (rc) FY_FAIL(FY_ERR_COLLECTIVE, "reduce_scatter callback returned %d", rc);
 }
 
+// ---- the rows r, r + world, ... of the cluster's matrix and of its block maxima on this rank: segment table of my rows (over a compact
+// copy of their CSC entries), then the row kernel.  hcnt = the raters of every row (host), my_ratings = their sum over my rows.
+static void coop_build_rows(const ScoreShared& X, const Plan& p, hipStream_t ls, const std::vector<int32_t>& hcnt, int64_t my_ratings, float* Mloc, float* Bloc,
+                            float* amax, float* bmax) {
+    fy_rm2_job* J = X.J;
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    const ScoreTune& tune = *X.tune;
+    const int W = J->prm.world, r0 = J->prm.rank;
+    const int32_t Uc = p.Uc, sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, CH = p.CH, nch = p.nch, nrows = Ic > r0 ? (Ic - r0 + W - 1) / W : 0;
+    const int64_t ldm = p.ldm, ldb = p.ldb;
+    DevBuf<int32_t> co_tmp(ctx, (size_t)Uc * (nch + 1));
+    SegTable seg;
+    DevBuf<int2> item_seg(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * nch));
+    DevBuf<int32_t> item_id(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * nch)), item_counter(ctx, 1);
+    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), sbase, Uc, CH, nch, co_tmp.get(), ls);
+    std::vector<int32_t> hls((size_t)nrows + 1, 0);
+    for (int32_t i = 0; i < nrows; i++) hls[i + 1] = hls[i] + hcnt[r0 + (int64_t)i * W];
+    DevBuf<int32_t> local_start(ctx, (size_t)nrows + 1), my_slot(ctx, (size_t)std::max<int64_t>(1, my_ratings));
+    DevBuf<float> my_w(ctx, (size_t)std::max<int64_t>(1, my_ratings));
+    FY_HIP(hipMemcpyAsync(local_start.get(), hls.data(), ((size_t)nrows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ls));
+    if (nrows > 0) {
+        k_gather_rows<<<grid_for((int64_t)nrows * 64, 256), 256, 0, ls>>>(r0, W, nrows, P.rank_pair.get() + pbase, P.pair_start.get(),
+                                                                          local_start.get(), P.csc_slot.get(), X.csc_x, my_slot.get(), my_w.get());
+        FY_KERNEL_CHECK();
+    }
+    build_segments(ctx, my_slot.get(), my_w.get(), co_tmp.get(), sbase, 0, (int32_t)my_ratings, nch, seg, ls);
+    FY_HIP(hipMemsetAsync(Bloc, 0, (size_t)std::max<int64_t>(1, (int64_t)nrows * ldb) * 3, ls));
+    k_block_amax<<<grid_for(ldb), 256, 0, ls>>>(Ic, (int32_t)ldb, X.a_rank + pbase, X.b_rank + pbase, amax, bmax);
+    FY_KERNEL_CHECK();
+    if (nrows > 0) {
+        // (the segment table covers my rows' CSC entries alone, renumbered row by row: q0 = 0, nq = local entries)
+        CoocArgs CA = cooc_args(P, seg, CoocGeometry{pbase, sbase, Ic, CH, nch, 0, (int32_t)my_ratings}, X.csr_x, X.csr_pk);
+        CA.row0 = r0; CA.nrows = nrows; CA.row_stride = W; CA.local_start = local_start.get();
+        const int fxk = (X.csr_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) : -1;
+        CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;
+        const double w2s = (1.0 - J->prm.lambda) * (1.0 - J->prm.lambda) * (double)X.gscale[(size_t)p.c];      // (1-l)^2 and the packed format's 2^-c
+        MEpilogue ME{Mloc, ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0, 1, Bloc, ldb, 1};
+        const size_t sp = X.t_cooc->begin(ls);
+        const int n_items = nrows * nch;
+        k_item_list<<<grid_for(n_items), 256, 0, ls>>>(CA, item_seg.get(), item_id.get());
+        FY_KERNEL_CHECK();
+        CA.item_seg = item_seg.get(); CA.item_id = item_id.get();
+        FY_HIP(hipMemsetAsync(item_counter.get(), 0, sizeof(int32_t), ls));
+        launch_cooc_rm2(ctx, tune, X.csr_pk != nullptr, CA, ME, n_items, item_counter.get(), ls);
+        X.t_cooc->end(sp, ls);
+        X.R->st.cooc_launches++;
+    }
+    FY_HIP(hipStreamSynchronize(ls));   // the segment table is released here
+}
+
 static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t ls) {
     fy_rm2_job* J = X.J;
     Context* ctx = J->ctx;
@@ -36,9 +87,8 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
     const ScoreTune& tune = *X.tune;
     const fy_rm2_params& prm = J->prm;
     const int W = prm.world, me = prm.rank;
-    const int32_t Uc = p.Uc, sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, CH = p.CH, nch = p.nch;
+    const int32_t Uc = p.Uc, sbase = p.sbase, pbase = p.pbase, Ic = p.Ic;
     const int64_t ldm = p.ldm, ldb = p.ldb;
-    const double lambda = prm.lambda;
 
     // ---- who owns which users of this cluster (identical on every rank)
     std::vector<int32_t> ua(W), ub(W);
@@ -67,13 +117,12 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
 
     // ---- buffers
     const int n_chunks = (int)ceil_div(Ic, 256);
-    const int seed_chunks = std::min(n_chunks, tune.seed_chunks);
-    const int seed_blocks = seed_chunks;
+    const int seed_chunks = std::min(n_chunks, tune.seed_chunks);     // (= the seed blocks)
     const int64_t SC = (int64_t)seed_chunks * 256;
     const int bchunks = (int)(ldb / 256);
     DevBuf<float> Mloc(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * ldm * 3 / 4 + 4)), Bloc(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * ldb));
     DevBuf<float> amax(ctx, (size_t)ldb), bmax(ctx, (size_t)ldb);
-    DevBuf<int32_t> n_out_all(ctx, (size_t)Uc), item_counter(ctx, 1);
+    DevBuf<int32_t> n_out_all(ctx, (size_t)Uc);
     // my compact CSR over all users of the cluster (local row indices); its size is not known on the host: room for all
     const int64_t nnz_c = (int64_t)p.nq;
     DevBuf<int32_t> my_cnt(ctx, (size_t)Uc + 1), my_rowptr(ctx, (size_t)Uc + 1), my_idx(ctx, (size_t)std::max<int64_t>(1, nnz_c));
@@ -86,52 +135,8 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
     DevBuf<uint16_t> surv(ctx, (size_t)((int64_t)Umax * ldb));
     DevBuf<int32_t> n_quads(ctx, (size_t)Umax + 1), quad_prefix(ctx, (size_t)Umax + 1), overflow(ctx, (size_t)Umax), any_overflow(ctx, 1);
     DevBuf<int32_t> counts(ctx, (size_t)W);
-    const float* Mshift = Mloc.get();    // M / Bmax are indexed by the LOCAL row (k-th row of this rank)
-    const float* Bshift = Bloc.get();
 
-    // ---- segment table of my rows (over a compact copy of their CSC entries), M build
-    {
-        DevBuf<int32_t> co_tmp(ctx, (size_t)Uc * (nch + 1));
-        SegTable seg;
-        DevBuf<int2> item_seg(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * nch));
-        DevBuf<int32_t> item_id(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * nch));
-        build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), sbase, Uc, CH, nch, co_tmp.get(), ls);
-        std::vector<int32_t> hls((size_t)nrows + 1, 0);
-        for (int32_t i = 0; i < nrows; i++) hls[i + 1] = hls[i] + hcnt[r0 + (int64_t)i * W];
-        DevBuf<int32_t> local_start(ctx, (size_t)nrows + 1), my_slot(ctx, (size_t)std::max<int64_t>(1, my_ratings));
-        DevBuf<float> my_w(ctx, (size_t)std::max<int64_t>(1, my_ratings));
-        FY_HIP(hipMemcpyAsync(local_start.get(), hls.data(), ((size_t)nrows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ls));
-        if (nrows > 0) {
-            k_gather_rows<<<grid_for((int64_t)nrows * 64, 256), 256, 0, ls>>>(r0, W, nrows, P.rank_pair.get() + pbase, P.pair_start.get(),
-                                                                              local_start.get(), P.csc_slot.get(), X.csc_x, my_slot.get(), my_w.get());
-            FY_KERNEL_CHECK();
-        }
-        build_segments(ctx, my_slot.get(), my_w.get(), co_tmp.get(), sbase, 0, (int32_t)my_ratings, nch, seg, ls);
-        FY_HIP(hipMemsetAsync(Bloc.get(), 0, (size_t)std::max<int64_t>(1, (int64_t)nrows * ldb) * 3, ls));
-        k_block_amax<<<grid_for(ldb), 256, 0, ls>>>(Ic, (int32_t)ldb, X.a_rank + pbase, X.b_rank + pbase, amax.get(), bmax.get());
-        FY_KERNEL_CHECK();
-        if (nrows > 0) {
-            CoocArgs CA{P.rank_pair.get(), P.pair_start.get(), seg.ptr.get(), seg.seg.get(), seg.w.get(), P.csr_idx.get(),
-                        X.csr_x, pbase, sbase, Ic, CH, nch, r0, nrows, 0, (int32_t)my_ratings, local_start.get(), W, X.csr_pk, nullptr,
-                        (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll)};
-            const int fxk = (X.csr_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) : -1;
-            CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;
-            const double w2s = (1.0 - lambda) * (1.0 - lambda) * (double)X.gscale[(size_t)p.c];      // (1-l)^2 and the packed format's 2^-c
-            MEpilogue ME{const_cast<float*>(Mshift), ldm, (float)w2s, fxk >= 0 ? std::ldexp(w2s, -fxk) : 0.0,
-                         1, const_cast<float*>(Bshift), ldb, 1};
-            const size_t sp = X.t_cooc->begin(ls);
-            const int n_items = nrows * nch;
-            k_item_list<<<grid_for(n_items), 256, 0, ls>>>(CA, item_seg.get(), item_id.get());
-            FY_KERNEL_CHECK();
-            CA.item_seg = item_seg.get();
-            CA.item_id = item_id.get();
-            FY_HIP(hipMemsetAsync(item_counter.get(), 0, sizeof(int32_t), ls));
-            launch_cooc_rm2(ctx, tune, X.csr_pk != nullptr, CA, ME, n_items, item_counter.get(), ls);
-            X.t_cooc->end(sp, ls);
-            R->st.cooc_launches++;
-        }
-        FY_HIP(hipStreamSynchronize(ls));   // the segment table is released here
-    }
+    coop_build_rows(X, p, ls, hcnt, my_ratings, Mloc.get(), Bloc.get(), amax.get(), bmax.get());
 
     // ---- per-user tables over the whole cluster
     k_my_csr_count<<<grid_for(((int64_t)Uc + 1) * 64, 256), 256, 0, ls>>>(Uc, sbase, P.rowptr.get(), P.csr_idx.get(), W, me, my_cnt.get());
@@ -148,30 +153,19 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
     if (me != 0) FY_HIP(hipMemsetAsync(pv_all.get(), 0, (size_t)Uc * sizeof(double), ls));   // pvpi enters the sum once
 
     size_t ss = X.t_score->begin(ls);   // the spans of ms_score cover this rank's kernels, not the waits inside the collectives
-    auto slices_for = [&](int32_t nb) { return score_slices(ctx->num_cus, tune, nb, seed_chunks + bchunks); };
     // ---- (1) partial seed scores AND partial block bounds of every user in one launch per owner (one grid tail, see
     // rm2_score); (2) two reduce-scatters; (3) tau + the speculative lists; (5) the owner keeps the blocks that reach tau
     for (int k = 0; k < W; k++) {
         const int32_t nk = ub[k] - ua[k];
         if (nk <= 0) continue;
-        const int ns = slices_for(nk);
-        ScoreArgs SA{};
-        SA.M = Mshift; SA.ldm = ldm; SA.Ic = Ic; SA.a_rank = X.a_rank + pbase; SA.b_rank = X.b_rank + pbase; SA.rb_off = my_rowptr.get();
-        SA.csr_idx = my_idx.get(); SA.csr_e = my_e.get(); SA.csr_q = my_q.get(); SA.pvpi = pv_all.get(); SA.n_out = n_out_all.get(); SA.slot_lo = sbase; SA.slot_base = sbase; SA.slot0 = ua[k];
-        SA.n_users = nk; SA.S = seed_send.get() + (int64_t)k * Umax * SC; SA.ldS = SC; SA.n_slices = ns; SA.n_chunks = seed_chunks + bchunks;
+        const int ns = score_slices(ctx->num_cus, tune, nk, seed_chunks + bchunks);
+        ScoreArgs SA = score_args(X, p, Mloc.get(), ldm, ua[k], nk, seed_send.get() + (int64_t)k * Umax * SC, SC, ns, seed_chunks + bchunks);
+        // my compact CSR over all users of the cluster: M / Bmax are indexed by the LOCAL row (k-th row of this rank); pvpi and n_out by slot - sbase
+        SA.rb_off = my_rowptr.get(); SA.csr_idx = my_idx.get(); SA.csr_e = my_e.get(); SA.csr_q = my_q.get();
+        SA.pvpi = pv_all.get(); SA.n_out = n_out_all.get(); SA.slot_lo = sbase;
         SA.row_mul = W; SA.row_add = me;
-        SA.chunks1 = seed_chunks;
-        SA.M2 = Bshift;
-        SA.ldm2 = ldb;
-        SA.Ic2 = p.nblk;
-        SA.a2 = amax.get();
-        SA.b2 = bmax.get();
-        SA.S2 = ub_send.get() + (int64_t)k * Umax * ldb;
-        SA.ldS2 = ldb;
-        SA.no_mask2 = 1;
-        if (tune.score_walk) k_score<4, true, 8, 1><<<(seed_chunks + bchunks) * ns, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-        else k_score<4, true, 8, 0><<<(seed_chunks + bchunks) * ns, 256, 0, ls>>>(SA.M, SA.a_rank, SA.rb_off, SA.csr_idx, SA.csr_e, SA.csr_q, SA.pvpi, SA.n_out, SA.S, SA);
-        FY_KERNEL_CHECK();
+        score_args_bounds(SA, seed_chunks, Bloc.get(), ldb, p.nblk, amax.get(), bmax.get(), ub_send.get() + (int64_t)k * Umax * ldb);
+        launch_score(score_kernel(true, tune.score_walk), (seed_chunks + bchunks) * ns, ls, SA);
         R->st.score_launches += 2;
     }
     X.t_score->end(ss, ls);
@@ -179,15 +173,13 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
     coll_reduce_scatter(J, ub_send.get(), UBsum.get(), (int64_t)Umax * ldb, ls);
     ss = X.t_score->begin(ls);
     if (n_mine > 0) {
-        TopNArgs T1{seed.get(), SC, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(),
-                    X.lo, my_a, p.c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
-                    1, (int32_t)SC, surv.get(), n_quads.get(), ldb, tau.get(), nullptr, nullptr};
-        k_topn_fast<<<n_mine, 256, 0, ls>>>(T1, overflow.get(), any_overflow.get(), 0);
-        FY_KERNEL_CHECK();
+        TopNArgs T1 = topn_args(X, p, seed.get(), SC, my_a);
+        topn_pruned(T1, 1, (int32_t)SC, surv.get(), n_quads.get(), ldb, tau.get());
+        launch_topn_pass(ls, T1, n_mine, overflow.get(), any_overflow.get(), 0, false, 0);
     }
     FY_HIP(hipMemsetAsync(n_quads.get(), 0, ((size_t)Umax + 1) * sizeof(int32_t), ls));
     if (n_mine > 0) {
-        k_bound_select<<<grid_for((int64_t)n_mine * 64, 256), 256, 0, ls>>>(UBsum.get(), ldb, p.nblk, seed_blocks, tau.get(), X.pvpi + (my_a - X.lo), n_mine,
+        k_bound_select<<<grid_for((int64_t)n_mine * 64, 256), 256, 0, ls>>>(UBsum.get(), ldb, p.nblk, seed_chunks, tau.get(), X.pvpi + (my_a - X.lo), n_mine,
                                                                             surv.get(), n_quads.get());
         FY_KERNEL_CHECK();
     }
@@ -217,7 +209,7 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
         coll_all_gather(J, entries.get(), entries_all.get(), (int64_t)t_max * (int64_t)sizeof(long long), ls);
         ss = X.t_score->begin(ls);
         // ---- (7) partial exact scores of all survivors over my rows, reduce-scatter to the owners
-        k_score_entries<8><<<ctx->num_cus * 8, 256, 0, ls>>>(Mshift, X.a_rank + pbase, X.b_rank + pbase, my_rowptr.get(), my_idx.get(), my_e.get(), my_q.get(), pv_all.get(),
+        k_score_entries<8><<<ctx->num_cus * 8, 256, 0, ls>>>(Mloc.get(), X.a_rank + pbase, X.b_rank + pbase, my_rowptr.get(), my_idx.get(), my_e.get(), my_q.get(), pv_all.get(),
                                                              entries_all.get(), counts.get(), W, t_max, sbase, Ic, ldm, W, me, Spart.get(),
                                                              X.prune_counters);
         FY_KERNEL_CHECK();
@@ -231,18 +223,13 @@ static void score_cluster_coop(const ScoreShared& X, const Plan& p, hipStream_t 
     // ---- (8) the owner merges seed + survivors for the users that have any
     if (n_mine > 0 && hcounts[me] > 0) {
         const size_t tt = X.t_topn->begin(ls);
-        TopNArgs TA{seed.get(), SC, Ic, X.n_out, X.out_off, P.rank_item_raw.get() + pbase, P.slot2du.get(), P.uid.get(),
-                    X.lo, my_a, p.c, R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get(),
-                    2, (int32_t)SC, surv.get(), n_quads.get(), ldb, tau.get(), Ssurv.get(), quad_prefix.get()};
-        FY_HIP(hipMemsetAsync(any_overflow.get(), 0, sizeof(int32_t), ls));
-        k_topn_fast<<<n_mine, 256, 0, ls>>>(TA, overflow.get(), any_overflow.get(), tune.force_select);
-        FY_KERNEL_CHECK();
-        k_topn_select<<<fy_topn_select_grid(n_mine, ctx->num_cus), 256, 0, ls>>>(TA, overflow.get(), any_overflow.get(), n_mine, X.prune_counters + 2);
-        FY_KERNEL_CHECK();
+        TopNArgs TA = topn_args(X, p, seed.get(), SC, my_a);
+        topn_pruned(TA, 2, (int32_t)SC, surv.get(), n_quads.get(), ldb, tau.get(), Ssurv.get(), quad_prefix.get());
+        launch_topn(ctx, ls, TA, n_mine, overflow.get(), any_overflow.get(), tune.force_select, false, 0, X.prune_counters + 2);
         X.t_topn->end(tt, ls);
     }
     // statistics: blocks checked / kept for my users; log terms of my seed and bound passes = (ratings in my rows) x (columns walked)
-    *X.blocks_total += (int64_t)n_mine * std::max(0, p.nblk - seed_blocks);
+    *X.blocks_total += (int64_t)n_mine * std::max(0, p.nblk - seed_chunks);
     *X.coop_survived += (int64_t)hcounts[me];
     *X.seed_terms_cols += my_ratings * (SC + ldb);
     FY_HIP(hipStreamSynchronize(ls));   // every buffer of this function goes back to the allocator after the stream drained

@@ -85,7 +85,7 @@ def test_rm2_panel_mode_50_clusters_equals_full_pass_all_rows(data, panel50):
 def test_rm2_cooperative_8_ranks_all_rows_against_the_fp64_definition(data, pruned):
     """The cooperative path -- ONE neighbourhood scored by all ranks, every rank building an eighth of the matrix rows, default tuning -- at
     full size: 8 thread ranks on one card, the union of their rows (all 8.1 M) against the fp64 DEFINITION, pure relative 1e-5, and against
-    the single-GPU job's lists.  This path has no fp64 refinement pass (fy_rm2.hip: refine = ... && !p.coop) and sums its partial scores
+    the single-GPU job's lists.  This path has no fp64 refinement pass (fy_rm2.hip, cluster_pass: refine = ... && !p.coop) and sums its partial scores
     over ranks in fp32: the least precise path of the library.  Measured: 4.39e-6 against the definition (99.99th percentile 5.4e-7; the worst
     row is again the user with 11 ratings whose score is -0.83, which the single-GPU job re-scores in fp64 and this path does not), the same
     4.39e-6 against the single-GPU rows, no list differs."""
