@@ -47,6 +47,7 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_COOC_PK")) t.cooc_pk = atoi(e) != 0;
     if (const char* e = getenv("FY_COOC_F32")) t.cooc_f32 = atoi(e) != 0;
     if (const char* e = getenv("FY_COOC_HALF")) t.cooc_half = atoi(e) != 0;
+    if (const char* e = getenv("FY_COOC_RECT")) t.cooc_rect = atoi(e) != 0;
     if (const char* e = getenv("FY_COOC_FX")) t.cooc_fx = atoi(e) != 0;
     if (const char* e = getenv("FY_PANEL_MIN_CLUSTERS")) { int v = atoi(e); if (v >= 1) t.panel_min_clusters = v; }
     if (const char* e = getenv("FY_PANEL_COLS")) { int v = atoi(e); if (v >= 256) { t.panel_cols = v; t.panel_wide_below_users = 0; } }

@@ -56,9 +56,16 @@ struct CoocArgs {
     const int2* __restrict__ item_seg;
     uint32_t pk_bytes;   // size of csr_pk in bytes (< 4 GiB): record count of the buffer descriptor the packed walk loads through
     // RM2 row kernel: explicit item list, item t = (row of the launch << 8) | chunk, with item_seg[t] its segment range.  In
-    // the symmetric (half) walk a row has items only for its own chunk and the chunks behind it.
+    // the symmetric (half) walk a row has items only for its own chunk and the chunks behind it (half == 1) or in front of it (half == 2).
     const int32_t* __restrict__ item_id;
-    int32_t half;        // 1: symmetric walk -- row i holds only the columns j > i, the mirror pass fills the rest
+    // 1: symmetric walk -- row i holds only the columns j > i, the mirror pass fills the rest.
+    // 2: symmetric walk from the unpopular side (CH a multiple of 256, nch > 1, no panel, all rows cut) -- row i of chunk c holds its OWN
+    //    chunk as under 1 (columns j > i, stored from the row's 256-column diagonal block on) and the WHOLE chunks 0 .. c - 1, nothing
+    //    behind its own chunk: the rectangle (rows of chunk a) x (columns of chunk b), a < b, is accumulated as its transpose by the rows
+    //    of chunk b.  Columns are in popularity order, so those rows have few raters, each with a LONG slice in chunk a: the same pair
+    //    visits in fewer, fuller segments.  With cb(X) = 256 X / CH the chunk of block X, the off-diagonal 256 x 256 tile (row block B,
+    //    column block T) is stored iff (cb(T) == cb(B) && T > B) || cb(T) < cb(B) (cooc_tile_stored); the mirror pass owes its transpose.
+    int32_t half;
     // fixed-point accumulation (ACC = unsigned long long, packed walk only): a contribution is added as the integer
     // round(weight * rating * fx_scale), fx_scale = 2^k chosen per cluster so that no single contribution reaches 2^52 and no sum
     // 2^63 (fy_rm2.hip: fx_exponent).  ds_add_u64 is twice as fast as ds_add_f64 on gfx950 (10.8 against 20.9 cycles per wave
@@ -352,8 +359,22 @@ __host__ __device__ inline int64_t cooc_half_item_index(int32_t row, int32_t ch,
     // sum_{c' < c} CH * (nch - c') = CH * (c * nch - c (c - 1) / 2)
     return (int64_t)CH * (c * nch - c * (c - 1) / 2) + (int64_t)(row - c * CH) * (nch - c) + (ch - c);
 }
-inline int64_t cooc_item_count(int32_t nrows, int32_t CH, int32_t nch, bool half) {
+// half == 2 (the walk from the unpopular side): the rows of chunk c have c + 1 items (chunks 0 .. c), so
+// t = sum_{c' < c} CH * (c' + 1) + (row - c * CH) * (c + 1) + ch = CH * c (c + 1) / 2 + (row - c * CH) * (c + 1) + ch
+__host__ __device__ inline int64_t cooc_rect_item_index(int32_t row, int32_t ch, int32_t CH) {
+    const int64_t c = row / CH;
+    return (int64_t)CH * (c * (c + 1) / 2) + (int64_t)(row - c * CH) * (c + 1) + ch;
+}
+// is the off-diagonal 256 x 256 tile (row block B, column block T) stored by the symmetric walk (bpc = blocks per chunk under
+// half == 2, 0 = half == 1: the tiles behind the diagonal)?  Exactly one of (B, T) and (T, B) is.
+__host__ __device__ inline bool cooc_tile_stored(int B, int T, int bpc) {
+    if (bpc <= 0) return T > B;
+    const int cB = B / bpc, cT = T / bpc;
+    return cT == cB ? T > B : cT < cB;
+}
+inline int64_t cooc_item_count(int32_t nrows, int32_t CH, int32_t nch, int half) {
     if (!half) return (int64_t)nrows * nch;
+    if (half == 2) return nrows > 0 ? cooc_rect_item_index(nrows - 1, (nrows - 1) / CH, CH) + 1 : 0;
     return nrows > 0 ? cooc_half_item_index(nrows - 1, nch - 1, CH, nch) + 1 : 0;
 }
 __device__ __forceinline__ void item_list_body(const CoocArgs& A, int2* __restrict__ seg_out, int32_t* __restrict__ id_out) {
@@ -371,6 +392,9 @@ __device__ __forceinline__ void item_list_body(const CoocArgs& A, int2* __restri
                 if (ch >= A.tail_chunks) continue;
                 at = cooc_half_item_index(A.half_rows - 1, A.head_chunks - 1, A.CH, A.head_chunks) + 1 + (int64_t)(row - A.half_rows) * A.tail_chunks + ch;
             }
+        } else if (A.half == 2) {
+            if (ch > row / A.CH) continue;
+            at = cooc_rect_item_index(row, ch, A.CH);
         } else if (A.half) {
             if (ch < row / A.CH) continue;
             at = cooc_half_item_index(row, ch, A.CH, A.nch);
@@ -424,13 +448,14 @@ inline CoocArgs cooc_args(const Prepared& P, const SegTable& T, const CoocGeomet
 }
 // half_row_of_entry != nullptr: symmetric walk (only the columns behind the entry's own row; fy_rm2.hip, struct Half)
 // only_rows_of_entry != nullptr: CSC entries of the rows in front of only_rows_from get no segments (tail-row launches)
+// rect: with half_row_of_entry, the walk from the unpopular side (CoocArgs::half == 2; fy_rm2.hip, Half::rect)
 // max_segments > 0: an upper bound of the number of segments -- the table is allocated for it and the call does not wait for
 // the device (otherwise it reads the exact count back: two host round trips)
 void build_segments(Context* ctx, const int32_t* csc_slot, const float* csc_w, const int32_t* chunk_off, int32_t slot_base,
                     int32_t q0, int32_t nq, int32_t nch, SegTable& out, hipStream_t st = nullptr,
                     const int32_t* half_row_of_entry = nullptr, const int32_t* csr_idx = nullptr, int32_t CH = 0,
                     const int32_t* only_rows_of_entry = nullptr, int32_t only_rows_from = 0, int64_t max_segments = 0,
-                    const int32_t* samples = nullptr);
+                    const int32_t* samples = nullptr, bool rect = false);
 // every 64th entry of csr_idx: what the symmetric cut of the segment tables searches instead of the rows themselves
 void build_csr_samples(Context* ctx, int64_t nnz, const int32_t* csr_idx, DevBuf<int32_t>& samp, hipStream_t st = nullptr);
 

@@ -563,6 +563,9 @@ struct Half {
     // for the chunk limit alone), and the rows from lim_from on have segments only in their first lim_chunks chunks (0 = off) --
     // rows and chunks the item list never names (tail rows behind the panel's chunks; symmetric panel mode: every row)
     int32_t sym_rows, lim_from, lim_chunks;
+    // the walk from the unpopular side (CoocArgs::half == 2): a cut entry has its segments in the chunks IN FRONT of its own chunk
+    // (whole slices) and none behind it; the own chunk is cut as ever
+    int32_t rect;
 };
 __device__ __forceinline__ void seg_counts_body(const int32_t* __restrict__ csc_slot, const int32_t* __restrict__ chunk_off, int32_t slot_base,
                                                 int32_t q0, int32_t nq, int32_t nch, int32_t* __restrict__ cnt, const Half& H) {
@@ -605,7 +608,7 @@ __device__ __forceinline__ void seg_counts_body(const int32_t* __restrict__ csc_
             if (live) {
                 const int32_t next = CO(ch + 1);
                 const int32_t first = ch == own ? behind : prev;
-                n = (ch < own || ch >= climit) ? 0 : (next - first + 63) >> 6;
+                n = ((H.rect ? (own >= 0 && ch > own) : ch < own) || ch >= climit) ? 0 : (next - first + 63) >> 6;
                 prev = next;
             }
             cnt[(int64_t)ch * (nq + 1) + q] = n;
@@ -625,13 +628,14 @@ struct SegDesc {
     int64_t co_off, cnt_off;      // first entry of the table's chunk offsets / of its counts and prefixes
     int32_t use_only_rows, sym_rows;      // sym_rows, lim_from, lim_chunks: Half
     int32_t lim_from, lim_chunks;
+    int32_t rect, pad;            // Half::rect
 };
 __global__ void k_seg_counts_multi(const SegDesc* __restrict__ D, const int32_t* __restrict__ csc_slot, const int32_t* __restrict__ co_all,
                                    int32_t* __restrict__ cnt_all, const int32_t* __restrict__ row_of_entry, const int32_t* __restrict__ csr_idx,
                                    int32_t* __restrict__ start_all, const int32_t* __restrict__ samples) {
     const SegDesc d = D[blockIdx.y];
     const Half H{(d.half || d.lim_chunks > 0) ? row_of_entry : nullptr, csr_idx, d.CH, start_all + d.q0, samples, d.use_only_rows ? row_of_entry : nullptr, d.only_from,
-                 d.half ? d.sym_rows : -1, d.lim_from, d.lim_chunks};
+                 d.half ? d.sym_rows : -1, d.lim_from, d.lim_chunks, d.half ? d.rect : 0};
     seg_counts_body(csc_slot, co_all + d.co_off, d.slot_base, d.q0, d.nq, d.nch, cnt_all + d.cnt_off, H);
 }
 
@@ -702,7 +706,7 @@ __device__ __forceinline__ void seg_fill_body(const int32_t* __restrict__ csc_sl
             int32_t f0 = cov[c], len = cov[c + 1] - cov[c], start = startv[c];
             if (live) {
                 if (own >= 0) {
-                    if (ch < own) len = 0;
+                    if (H.rect ? ch > own : ch < own) len = 0;
                     else if (ch == own) { f0 = own_start; len = cov[c + 1] - f0; }
                 }
                 if (limited && ch >= H.lim_chunks) len = 0;
@@ -744,7 +748,7 @@ __global__ void k_seg_fill_multi(const SegDesc* __restrict__ D, const int32_t* _
                                  const int32_t* __restrict__ row_of_entry, const int32_t* __restrict__ csr_idx, int32_t* __restrict__ start_all) {
     const SegDesc d = D[blockIdx.y];
     const Half H{(d.half || d.lim_chunks > 0) ? row_of_entry : nullptr, csr_idx, d.CH, start_all + d.q0, nullptr, d.use_only_rows ? row_of_entry : nullptr, d.only_from,
-                 d.half ? d.sym_rows : -1, d.lim_from, d.lim_chunks};
+                 d.half ? d.sym_rows : -1, d.lim_from, d.lim_chunks, d.half ? d.rect : 0};
     seg_fill_body(csc_slot, csc_w, co_all + d.co_off, d.slot_base, d.q0, d.nq, d.nch, ptr_all + d.cnt_off, seg, seg_w, H);
 }
 // chunk offsets / packed CSR / block-compressed tail CSR of all planned clusters: blockIdx.y = cluster of the plan
@@ -780,14 +784,14 @@ void build_csr_samples(Context* ctx, int64_t nnz, const int32_t* csr_idx, DevBuf
 void build_segments(Context* ctx, const int32_t* csc_slot, const float* csc_w, const int32_t* chunk_off, int32_t slot_base,
                     int32_t q0, int32_t nq, int32_t nch, SegTable& out, hipStream_t st, const int32_t* half_row_of_entry,
                     const int32_t* csr_idx, int32_t CH, const int32_t* only_rows_of_entry, int32_t only_rows_from, int64_t max_segments,
-                    const int32_t* samples) {
+                    const int32_t* samples, bool rect) {
     if (half_row_of_entry && !samples) FY_FAIL(FY_ERR_STATE, "internal: the symmetric segment table needs the CSR samples");
     if (!st) st = ctx->stream;
     const size_t np = (size_t)nch * ((size_t)nq + 1);
     out.ptr.alloc(ctx, np);
     out.cnt.alloc(ctx, np);
     out.scratch.alloc(ctx, half_row_of_entry ? (size_t)nq + 1 : 1);
-    const Half H{half_row_of_entry, csr_idx, CH, out.scratch.get(), samples, only_rows_of_entry, only_rows_from};
+    const Half H{half_row_of_entry, csr_idx, CH, out.scratch.get(), samples, only_rows_of_entry, only_rows_from, 0, 0, 0, (half_row_of_entry && rect) ? 1 : 0};
     k_seg_counts<<<grid_for((int64_t)nq + 1), 256, 0, st>>>(csc_slot, chunk_off, slot_base, q0, nq, nch, out.cnt.get(), H);
     FY_KERNEL_CHECK();
     exclusive_scan_i32(ctx, out.cnt.get(), out.ptr.get(), np, st);
@@ -845,6 +849,8 @@ struct MEpilogue {
     // the matrix elements to 2^-53): the first head_rows rows of the matrix, whole, at
     // pitch ld_head (symmetric walks: only the columns behind the row are meaningful), and -- symmetric panel mode, whose head rows
     // are not walked over the tail rows' columns -- the first 256 columns of every row from tail_from on.  nullptr = off.
+    // The walk from the unpopular side (CoocArgs::half == 2) keeps tail32 the same way for the rows behind the first chunk (tail_from = CH),
+    // from their items in front of their own chunk; head32 is then CH columns wide where the head rows all lie in the first chunk.
     double* __restrict__ head32;      // (fp64 since the first measurement: fp32 values left 4e-5 on a forced-small row with |score| = 0.15)
     int64_t ld_head;
     int32_t head_rows;
@@ -880,6 +886,32 @@ __device__ __forceinline__ uint32_t fy_max_wave(uint32_t m) {
 // EPI (FY_COOC_EPI): 1 = the plain 24-bit items (no panel, no sub-block maxima, no refinement copy: every item of a one-cluster job but the
 // head rows') take eight columns per lane, and the block maxima of both loops are taken without LDS; 0 = the loop of rounds 3-4 alone,
 // with its __shfl_xor maximum.  Same bytes either way: every element goes through the same roundings, and a maximum has no order.
+// does a plain item (no refinement copy through the four-column loop) take the eight-column loop?
+template <class ACC, int EPI>
+__device__ __forceinline__ bool cooc_epilogue_takes_eight(const CoocArgs& A, const MEpilogue& E) {
+    return EPI && sizeof(ACC) == 8 && A.acc_quarter && !(A.acc_quarter & 1) && !E.Bmax64 && !E.panel_cols && !E.pitch;
+}
+// The head columns of an item that takes the eight-column loop, unrounded, to tail32 (the refinement pass; the walk from the unpopular side:
+// the items in front of the row's own chunk, c0 = the item's first stored column) -- IN FRONT of that loop and with its assignment of columns
+// to threads (lane L of wave w: c0 + 512 w + 8 L ... + 7, then every blockDim * 8 columns), so that a thread reads here exactly what it
+// reads and zeroes there: no barrier between the two, and the loop of every other item stays as it is.  The same expressions as the
+// copying four-column loop's.
+template <class ACC>
+__device__ __forceinline__ void cooc_rm2_tail_copy(const CoocArgs& A, const MEpilogue& E, const ACC* __restrict__ acc, int row, int c0, int c_end) {
+    double* __restrict__ tp = E.tail32 + (int64_t)(row - E.tail_from) * E.head_rows;
+    for (int col = c0 + (int)(threadIdx.x >> 6) * 512 + (int)(threadIdx.x & 63) * 8; col < c_end; col += (int)blockDim.x * 8) {
+        double t[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const ACC a = acc[cooc_acc_index(col - c0 + k, A.acc_quarter)];
+            if constexpr (std::is_integral<ACC>::value) t[k] = (double)a * E.fx_inv;
+            else t[k] = (double)E.w2 * (double)a;
+        }
+        double2* __restrict__ o = reinterpret_cast<double2*>(tp + col);
+#pragma unroll
+        for (int k = 0; k < 4; k++) o[k] = make_double2(t[2 * k], t[2 * k + 1]);
+    }
+}
 template <class ACC, bool COPY, int EPI>
 __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const MEpilogue& E, ACC* __restrict__ acc, int row, int mrow, int c0, int c1, int cb,
                                                        int first_bmax_block) {
@@ -1056,13 +1088,22 @@ __device__ __forceinline__ void cooc_rm2_epilogue(const CoocArgs& A, const MEpil
     const int c1 = (ch == A.nch - 1) ? (int)E.ldm : min(c0 + A.CH, (int)E.ldm);
     // symmetric walk: in the row's own chunk nothing in front of its 256-column diagonal block was accumulated (and the
     // mirror pass writes that part of the row); the block maxima of the diagonal block are the mirror pass's too
-    const int cb = (cooc_row_is_cut(A, row) && c0 <= row) ? (row & ~255) : c0;
-    const int first_bmax_block = A.half ? (row >> 8) + 1 : 0;
+    // (the walk from the unpopular side, half == 2: an item in front of the row's own chunk is a whole chunk, block maxima and all)
+    const bool front = A.half == 2 && c0 + A.CH <= row;
+    const int cb = (cooc_row_is_cut(A, row) && c0 <= row && !front) ? (row & ~255) : c0;
+    const int first_bmax_block = (A.half && !front) ? (row >> 8) + 1 : 0;
     if (E.pack24) {
-        // (block-uniform) does this item hold values the refinement pass wants?
-        const bool copy = E.head32 && (mrow < E.head_rows || (E.tail32 && row >= E.tail_from && c0 < E.head_rows));
+        // (block-uniform) does this item hold values the refinement pass wants?  Under half == 2 the rows behind the first chunk keep
+        // their head columns (tail32), and only in their items in front of their own chunk: ~ (Ic - CH) items of a job, which stay in
+        // the eight-column loop where that loop is taken at all (cooc_rm2_tail_copy in front of it) and take the copying loop otherwise
+        const bool tail_item = E.tail32 && row >= E.tail_from && c0 < E.head_rows && (A.half != 2 || front);
+        const bool tail8 = tail_item && A.half == 2 && cooc_epilogue_takes_eight<ACC, EPI>(A, E);
+        const bool copy = E.head32 && (mrow < E.head_rows || (tail_item && !tail8));
         if (copy) cooc_rm2_epilogue_pack<ACC, true, EPI>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
-        else cooc_rm2_epilogue_pack<ACC, false, EPI>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
+        else {
+            if (tail8) cooc_rm2_tail_copy<ACC>(A, E, acc, row, c0, min(c1, (int)E.head_rows));
+            cooc_rm2_epilogue_pack<ACC, false, EPI>(A, E, acc, row, mrow, c0, c1, cb, first_bmax_block);
+        }
     } else {
         float* __restrict__ out = E.M + (int64_t)mrow * E.ldm;
         for (int col = cb + threadIdx.x; col < c1; col += blockDim.x) {
@@ -1193,6 +1234,11 @@ __global__ void k_item_list_multi(const CoocLaunch* __restrict__ D) {
 // a transposition: 24-bit elements, 256 x 128 source tiles through LDS (k_mirror_tiles: reads 256 row segments of 384 B,
 // writes 128 row segments of 768 B -- one whole 256-column block of the destination rows, whose maximum is the missing
 // Bmax entry), and the 256 x 256 diagonal blocks thread by thread (k_mirror_diag: 1 / 231 of the matrix).
+// After the walk from the unpopular side (CoocArgs::half == 2, `bpc` = 256-column blocks per chunk) the stored off-diagonal tiles are
+// those of cooc_tile_stored(B, T, bpc): behind the diagonal block inside the row's own chunk, and every tile of the chunks in front of
+// it -- Bmax holds exactly those.  Every kernel below asks that one predicate which tiles are sources; the row blocks of the last
+// chunk, the last block too, have sources, and the column blocks of the first chunk (the seed columns) need no tile for the rows of the
+// other chunks.  The diagonal blocks are the same either way.
 __device__ __forceinline__ void fy_unpack24_raw(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t* v) {
     v[0] = d0 & 0xFFFFFFu;
     v[1] = (d0 >> 24) | ((d1 & 0xFFFFu) << 8);
@@ -1213,10 +1259,11 @@ extern __shared__ __attribute__((aligned(16))) unsigned char fy_mirror_lds[];   
 // k_flag_surviving_blocks) -- while the block maxima (Bmax_ != nullptr) are taken from every tile.  The full mirror is write_below =
 // INT_MAX.  Measured: the survivors of the headline job (22 600 (user, block) pairs) lie in 8 of its 231 column blocks.
 __device__ __forceinline__ void mirror_tiles_body(float* __restrict__ M_, int64_t ldm, int32_t Ic, float* __restrict__ Bmax_, int64_t ldb,
-                                                  const int32_t* __restrict__ need = nullptr, int32_t write_below = 0x7FFFFFFF) {
+                                                  const int32_t* __restrict__ need = nullptr, int32_t write_below = 0x7FFFFFFF,
+                                                  int32_t bpc = 0 /* blocks per chunk of the walk from the unpopular side, 0 = the plain half walk */) {
     __shared__ uint32_t rowmax[128];
     const int tj = blockIdx.x, B = blockIdx.y;
-    if (tj < 2 * (B + 1)) return;                         // only tiles strictly behind the diagonal block are sources
+    if ((tj >> 1) == B || !cooc_tile_stored(B, tj >> 1, bpc)) return;      // only tiles the walk stored are sources (plain: strictly behind the diagonal block)
     const int dst_row0 = 128 * tj;
     if (dst_row0 >= Ic) return;                           // destination rows are real rows (the padding columns have none)
     const bool write = B < write_below || (need && need[B] != 0);      // block-uniform
@@ -1271,17 +1318,18 @@ __device__ __forceinline__ void mirror_tiles_body(float* __restrict__ M_, int64_
 }
 
 __global__ __launch_bounds__(1024) void k_mirror_tiles(float* __restrict__ M_, int64_t ldm, int32_t Ic, float* __restrict__ Bmax_, int64_t ldb,
-                                                       const int32_t* __restrict__ need, int32_t write_below) {
-    mirror_tiles_body(M_, ldm, Ic, Bmax_, ldb, need, write_below);
+                                                       const int32_t* __restrict__ need, int32_t write_below, int32_t bpc) {
+    mirror_tiles_body(M_, ldm, Ic, Bmax_, ldb, need, write_below, bpc);
 }
 // Block maxima alone (lazy mirror, first pass, the column blocks nobody reads below the diagonal): Bmax[j][B] = max over the rows i of block B
 // of G[i][j] for the 256 columns j of a tile strictly behind block B.  A wave reads WHOLE 768-byte row segments (one 12-byte load per
 // lane, 16 rows in flight per workgroup step) -- the transposing tile kernel reads 384-byte half segments and stages them through LDS,
 // which this pass has no use for; the 16 waves' maxima meet in LDS and each thread stores one 3-byte entry.
-__global__ __launch_bounds__(1024) void k_colmax_upper(const float* __restrict__ M_, int64_t ldm, int32_t Ic, float* __restrict__ Bmax_, int64_t ldb, int32_t first_block) {
+__global__ __launch_bounds__(1024) void k_colmax_upper(const float* __restrict__ M_, int64_t ldm, int32_t Ic, float* __restrict__ Bmax_, int64_t ldb, int32_t first_block,
+                                                       int32_t bpc) {
     __shared__ uint32_t colmax[256];
     const int tj = blockIdx.x, B = first_block + blockIdx.y;      // tile = columns [256 tj, 256 tj + 256) x rows of block B
-    if (tj <= B) return;                                           // strictly behind the diagonal block
+    if (tj == B || !cooc_tile_stored(B, tj, bpc) || 256 * B >= Ic) return;      // a stored tile (plain: strictly behind the diagonal block)
     const int col0 = 256 * tj;
     if (col0 >= Ic) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1462,21 +1510,23 @@ __global__ __launch_bounds__(256) void k_panel_colmax(const PanelDesc* __restric
 // full mirror: write_below = INT_MAX.  Lazy mirror, first pass (block maxima from every tile, lower triangle only for the column blocks
 // in front of write_below + the diagonal blocks): need = nullptr, write_below = seed blocks.  Second pass (after the survivors are
 // known): Bmax = nullptr, need = the flags, write_below = 0, diag = false -- a tile of an unflagged block leaves at once.
-static void launch_mirror(Context* ctx, float* M, int64_t ldm, int32_t Ic, float* Bmax, int64_t ldb, hipStream_t st, const int32_t* need = nullptr,
+// bpc: blocks per chunk of the walk from the unpopular side (0 = the plain half walk): the rows of the LAST block are sources too
+static void launch_mirror(Context* ctx, float* M, int64_t ldm, int32_t Ic, float* Bmax, int64_t ldb, hipStream_t st, int bpc, const int32_t* need = nullptr,
                           int32_t write_below = 0x7FFFFFFF, bool diag = true) {
     const int nblk = (int)(ldm / 256), ntile = (int)(ldm / 128);
+    const int nsrc = bpc > 0 ? nblk : nblk - 1;      // row blocks with stored tiles
     if (nblk > 1) {
         FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mirror_tiles), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * MIRROR_PITCH));
         // first pass of the lazy mirror: the transposing kernel only over the column blocks it writes (those in front of write_below),
         // the block maxima of all other blocks from the streaming kernel
-        const bool split = !need && Bmax && write_below < nblk - 1;
-        const int ny = split ? write_below : nblk - 1;
+        const bool split = !need && Bmax && write_below < nsrc;
+        const int ny = split ? write_below : nsrc;
         if (ny > 0) {
-            k_mirror_tiles<<<dim3(ntile, ny), 1024, 128 * MIRROR_PITCH, st>>>(M, ldm, Ic, Bmax, ldb, need, write_below);
+            k_mirror_tiles<<<dim3(ntile, ny), 1024, 128 * MIRROR_PITCH, st>>>(M, ldm, Ic, Bmax, ldb, need, write_below, bpc);
             FY_KERNEL_CHECK();
         }
         if (split) {
-            k_colmax_upper<<<dim3(nblk, nblk - 1 - write_below), 1024, 0, st>>>(M, ldm, Ic, Bmax, ldb, write_below);
+            k_colmax_upper<<<dim3(nblk, nsrc - write_below), 1024, 0, st>>>(M, ldm, Ic, Bmax, ldb, write_below, bpc);
             FY_KERNEL_CHECK();
         }
     }
@@ -1886,7 +1936,7 @@ static void build_tables_all(Context* ctx, const Prepared& P, const std::vector<
         // panel mode: the tail rows are walked over their first tail_chunks chunks only; symmetric panel mode: so are the head rows,
         // and those are cut (Half::sym_rows / lim_from / lim_chunks) -- rows and chunks the item list never names get no segments
         SegDesc m{p.sbase, p.q0, p.nq, p.nch, p.CH, (p.half || p.psym) ? 1 : 0, 0, p.nch + 1, co_total, cnt_total, 0, p.psym ? p.p_eff : 0,
-                  p.psym ? 0 : p.p_eff, (p.panel && p.tail_chunks > 0 && p.p_eff < p.Ic) ? p.tail_chunks : 0};
+                  p.psym ? 0 : p.p_eff, (p.panel && p.tail_chunks > 0 && p.p_eff < p.Ic) ? p.tail_chunks : 0, p.rect ? 1 : 0, 0};
         main_of[pi] = (int64_t)hsd.size();
         hsd.push_back(m);
         cnt_total += (int64_t)p.nch * ((int64_t)p.nq + 1);
@@ -2371,7 +2421,7 @@ static std::vector<int32_t> table_signature(const JobPlan& jp) {
     sig.push_back(jp.use_pk ? 1 : 0);
     sig.push_back(plans.size() > 1 && !jp.any_coop ? 1 : 0);
     for (auto& p : plans) {
-        const int32_t v[8] = {p.c, p.CH, p.nch, p.half ? 1 : 0, p.panel ? 1 : 0, p.p_eff, p.tail_chunks, (p.coop ? 1 : 0) | (p.flat ? 2 : 0) | (p.psym ? 4 : 0)};
+        const int32_t v[8] = {p.c, p.CH, p.nch, p.half ? 1 : 0, p.panel ? 1 : 0, p.p_eff, p.tail_chunks, (p.coop ? 1 : 0) | (p.flat ? 2 : 0) | (p.psym ? 4 : 0) | (p.rect ? 8 : 0)};
         sig.insert(sig.end(), v, v + 8);
     }
     return sig;
@@ -2394,7 +2444,7 @@ static void build_tables(fy_rm2_job* J, const JobPlan& jp, size_t pi, const std:
     build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), p.sbase, p.Uc, p.CH, p.nch, co, ts);
     // (exact table sizes: round 2 sized the tables by upper bounds inside the lanes; the lanes build no tables any more)
     build_segments(ctx, P.csc_slot.get(), use_pk ? tc.csc_x_over_s.get() : tc.csc_x.get(), co, p.sbase, p.q0, p.nq, p.nch, tc.segs[pi], ts,
-                   p.half ? tc.csc_rank.get() : nullptr, P.csr_idx.get(), p.CH, nullptr, 0, 0, p.half ? tc.samples.get() : nullptr);
+                   p.half ? tc.csc_rank.get() : nullptr, P.csr_idx.get(), p.CH, nullptr, 0, 0, p.half ? tc.samples.get() : nullptr, p.rect);
     if (p.p_eff < p.Ic) {
         k_tail_blocks<<<std::min<int>(p.Uc, ctx->num_cus * 16), 256, 0, ts>>>(p.sbase, p.Uc, p.p_eff, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(),
                                                                   tc.y_pk.get(), co);
@@ -2679,6 +2729,7 @@ struct ClusterPass {
     bool refine;             // k_refine_rows: the cluster keeps the unrounded values of its head rows (symmetric panel mode: and of the tail rows' head columns)
     int32_t head_rows;       // ... as many as the seed is wide, 256 .. 1024: N = 50 -> 256, N = 100 -> 512; a multiple of 4
     int64_t ld_head;
+    int32_t tail_from;       // first row with a tail32 image (Ic: none)
     int n_chunks;            // 256-column chunks of a score row
     int seed_chunks;         // ... of them scored exactly in front of the bound pass (= the seed blocks)
     bool use_sup;            // bounds over super-blocks, evaluated by the seed chunk's own waves
@@ -2694,7 +2745,10 @@ static ClusterPass cluster_pass(const ScoreShared& X, const ClusterVisit& V) {
     C.w2s = J->S->smooth.w2_of(J->prm.lambda) * (double)X.gscale[(size_t)p.c];
     C.refine = tune.refine && p.pack24 && !p.coop && C.fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
     C.head_rows = (int32_t)std::min<int64_t>(p.Ic & ~3, std::max<int64_t>(256, std::min<int64_t>(1024, (int64_t)tune.seed_chunks * 256)));
-    C.ld_head = p.psym ? (int64_t)p.p_eff : p.ldm;
+    // the rows that keep their head columns in tail32: symmetric panel mode, the tail rows; the walk from the unpopular side, the rows
+    // behind the first chunk (the head rows do not walk them; head rows that all lie in the first chunk store nothing behind it)
+    C.tail_from = p.psym ? p.p_eff : p.rect ? p.CH : p.Ic;
+    C.ld_head = p.psym ? (int64_t)p.p_eff : (p.rect && C.head_rows <= p.CH) ? (int64_t)p.CH : p.ldm;
     C.n_chunks = (int)ceil_div(p.Ic, 256);
     C.seed_chunks = std::min(C.n_chunks, tune.seed_chunks);
     C.use_sup = tune.sup_bounds && !p.panel && !X.jp->long_seed;
@@ -2754,9 +2808,9 @@ static void build_cluster_matrix(const ClusterPass& C) {
     if (p.panel) ME.M = PP.Gp;
     if (C.refine) {
         V.H32->alloc(ctx, (size_t)C.head_rows * C.ld_head + 4);
-        if (p.psym) V.T32->alloc(ctx, (size_t)std::max(1, Ic - p.p_eff) * C.head_rows + 4);
+        if (C.tail_from < Ic) V.T32->alloc(ctx, (size_t)std::max(1, Ic - C.tail_from) * C.head_rows + 4);
         ME.head32 = V.H32->get(); ME.ld_head = C.ld_head; ME.head_rows = C.head_rows;
-        ME.tail32 = p.psym ? V.T32->get() : nullptr; ME.tail_from = p.p_eff;
+        ME.tail32 = C.tail_from < Ic ? V.T32->get() : nullptr; ME.tail_from = C.tail_from;
     }
     if (p.panel) X.R->st.panel_clusters++;
     if (p.panel || p.prune) {     // the bound matrix starts at zero; the maxima of a and b over its blocks (panel mode: 64-column sub-blocks)
@@ -2779,11 +2833,11 @@ static void build_cluster_matrix(const ClusterPass& C) {
         CA.tail_row0 = p.p_eff;
         CA.tail_chunks = p.tail_chunks;
     }
-    CA.half = (p.half || p.psym) ? 1 : 0;
+    CA.half = p.rect ? 2 : (p.half || p.psym) ? 1 : 0;
     if (p.psym) { CA.half_rows = p.p_eff; CA.head_chunks = p.tail_chunks; }
     const int n_items = p.psym ? (int)(cooc_half_item_index(p.p_eff - 1, p.tail_chunks - 1, p.CH, p.tail_chunks) + 1 + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
                         : CA.tail_chunks > 0 ? (int)((int64_t)p.p_eff * p.nch + (int64_t)(Ic - p.p_eff) * p.tail_chunks)
-                                             : (int)cooc_item_count(Ic, p.CH, p.nch, p.half);
+                                             : (int)cooc_item_count(Ic, p.CH, p.nch, CA.half);
     const int64_t visits = (size_t)p.c < P.cluster_deg2.size() ? P.cluster_deg2[p.c] : P.sum_deg2;
     queue_row_kernel(X, V, batched, false, CA, ME, (int64_t)Ic * p.nch, n_items, cooc_item_grab(visits / (p.half ? 2 : 1), n_items));
     X.t_cooc->end(sp, ls);
@@ -2795,7 +2849,7 @@ static void build_cluster_matrix(const ClusterPass& C) {
         // survivor pass the surviving column blocks (mirrored below, once they are known); nothing else of the lower triangle
         // is ever read, so it is not written (round 3 moved 10.7 GB here to fill a triangle of which a few per cent were read)
         const bool lazy = p.prune && tune.lazy_mirror;
-        launch_mirror(ctx, L.M.get(), p.ldm, Ic, p.prune ? L.Bmax.get() : nullptr, p.ldb, ls, nullptr, lazy ? std::min(tune.seed_chunks, p.nblk) : 0x7FFFFFFF);
+        launch_mirror(ctx, L.M.get(), p.ldm, Ic, p.prune ? L.Bmax.get() : nullptr, p.ldb, ls, p.rect ? p.CH / 256 : 0, nullptr, lazy ? std::min(tune.seed_chunks, p.nblk) : 0x7FFFFFFF);
         X.t_mirror->end(sm, ls);
     }
     // (not for long lists: their survivors -- 14 % of the blocks at N = 1000 -- spread over the whole popularity order, the 16 wide
@@ -2862,8 +2916,9 @@ static void refine_rows(const ClusterPass& C, int32_t s0, int32_t nb) {
     RA.rowptr = P.rowptr.get(); RA.csr_idx = P.csr_idx.get(); RA.csr_r = P.csr_r.get(); RA.usum_slot = J->usum_slot.get();
     RA.p_rank = X.p_rank + p.pbase; RA.b_rank = X.b_rank64 + p.pbase;
     RA.colmap = L.colmap.get(); RA.max_item = J->S->max_item; RA.head_rows = head_rows;
-    RA.head32 = C.V.H32->get(); RA.ld_head = C.ld_head; RA.tail32 = p.psym ? C.V.T32->get() : nullptr; RA.tail_from = p.p_eff;
-    if (!RA.head32 || (p.psym && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", p.c);
+    RA.head32 = C.V.H32->get(); RA.ld_head = C.ld_head; RA.tail32 = C.tail_from < p.Ic ? C.V.T32->get() : nullptr; RA.tail_from = C.tail_from;
+    RA.rect_ch = p.rect ? p.CH : 0;
+    if (!RA.head32 || (C.tail_from < p.Ic && !RA.tail32)) FY_FAIL(FY_ERR_STATE, "internal: cluster %d has no fp32 rows for the refinement pass", p.c);
     RA.unscale = 1.0 / (double)X.gscale[(size_t)p.c];
     RA.general = J->S->smooth.general() ? 1 : 0; RA.G = J->smooth_args(); RA.cluster = p.c;
     RA.lambda = prm.lambda; RA.ln_items = std::log((double)prm.number_of_items); RA.ln_users = std::log((double)p.Uc);
@@ -2978,7 +3033,7 @@ static void pruned_front(const ClusterPass& C, const UserBatch& B) {
         FY_HIP(hipMemsetAsync(L.need.get(), 0, ((size_t)p.nblk + 1) * sizeof(int32_t), ls));
         k_flag_surviving_blocks<<<std::min<int>(nb, 4096), 64, 0, ls>>>(nb, L.n_quads.get(), L.surv.get(), p.ldb, L.need.get());
         FY_KERNEL_CHECK();
-        launch_mirror(ctx, L.M.get(), p.ldm, p.Ic, nullptr, p.ldb, ls, L.need.get(), 0, false);
+        launch_mirror(ctx, L.M.get(), p.ldm, p.Ic, nullptr, p.ldb, ls, p.rect ? p.CH / 256 : 0, L.need.get(), 0, false);
         X.t_mirror->end(sm, ls);
     }
     exclusive_scan_i32(ctx, L.n_quads.get(), L.quad_prefix.get(), (size_t)nb + 1, ls, &L.scan_tmp);
@@ -2991,7 +3046,7 @@ static void fallback_full_pass(const ClusterPass& C, const UserBatch& B) {
     const ScoreShared& X = C.X; const Plan& p = C.p; hipStream_t ls = C.ls;
     if (p.half && C.tune.lazy_mirror) {      // the plain full pass reads every row whole: the rest of the lower triangle now
         const size_t sm = X.t_mirror->begin(ls);
-        launch_mirror(C.ctx, C.L.M.get(), p.ldm, p.Ic, nullptr, p.ldb, ls, nullptr, 0x7FFFFFFF, false);
+        launch_mirror(C.ctx, C.L.M.get(), p.ldm, p.Ic, nullptr, p.ldb, ls, p.rect ? p.CH / 256 : 0, nullptr, 0x7FFFFFFF, false);
         X.t_mirror->end(sm, ls);
     }
     const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((X.jp->ws / X.jp->NS) / (p.ldm * 4), B.nb));

@@ -1891,6 +1891,8 @@ __global__ __launch_bounds__(256) void k_bound_select(const float* __restrict__ 
 // exactly those columns (MEpilogue::head32 / tail32: fp64 images of the exact fixed-point sums) and the fp64 statistics (p, b, s_u):
 //     G(j, c) = head32[min(j, c)][max(j, c)]        (row min(j, c) < 256 walked column max(j, c): G is symmetric)
 //             = tail32[j - tail_from][c]            symmetric panel mode, j a tail row (its walk covered the head columns)
+// Under the walk from the unpopular side (rect_ch = CH) the element is kept by the row of the LATER chunk: j and c in one chunk as above;
+// j in a later chunk than c: tail32[j - CH][c]; c in a later one (a seed wider than a chunk): head32[c][j], row c's item in front of its own.
 // and the user's list is put back in order (a re-scored row moves by ~1e-6 of its value).  n gathers and n fp64 logs per row.
 __global__ void k_refine_colmap(int32_t n_cols, const int32_t* __restrict__ rank_item_raw /* offset by pbase */, int32_t* __restrict__ colmap) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1915,6 +1917,7 @@ struct RefineArgs {
     int64_t ld_head;
     const double* __restrict__ tail32;
     int32_t tail_from, head_rows;            // head_rows: rows of head32 = columns of tail32 = columns the pass covers
+    int32_t rect_ch;                         // the walk from the unpopular side (CoocArgs::half == 2): columns per chunk, tail_from = rect_ch; 0 = off
     double unscale;                          // 1 / (the 2^-c the stored matrix is scaled by)
     double lambda, ln_items, ln_users;       // ln(numberOfItems), ln(U_c)
     double users_minus_1;
@@ -1960,7 +1963,12 @@ __global__ __launch_bounds__(256) void k_refine_rows(RefineArgs A) {
                 const int j = A.csr_idx[beg + k];
                 const double x = (double)A.csr_r[beg + k] / su;
                 double g32;
-                if (A.tail32 && j >= A.tail_from) g32 = A.tail32[(int64_t)(j - A.tail_from) * A.head_rows + c];
+                if (A.rect_ch) {
+                    const int cj = j / A.rect_ch, cc = c / A.rect_ch;
+                    if (cj == cc) g32 = A.head32[(int64_t)min(j, c) * A.ld_head + max(j, c)];
+                    else if (cj > cc) g32 = A.tail32[(int64_t)(j - A.tail_from) * A.head_rows + c];
+                    else g32 = A.head32[(int64_t)c * A.ld_head + j];
+                } else if (A.tail32 && j >= A.tail_from) g32 = A.tail32[(int64_t)(j - A.tail_from) * A.head_rows + c];
                 else g32 = A.head32[(int64_t)min(j, c) * A.ld_head + max(j, c)];
                 const double pj = A.p_rank[j];
                 if (A.general) {

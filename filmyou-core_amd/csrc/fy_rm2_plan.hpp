@@ -107,6 +107,10 @@ struct Plan {
     int32_t tail_chunks, p_eff, tail_width;
     int32_t nblk;
     int64_t ldb;
+    // symmetric walk from the unpopular side (CoocArgs::half == 2): a row stores its own chunk from its diagonal block on and the WHOLE
+    // chunks in front of it, nothing behind its own chunk -- the off-diagonal chunk rectangles are walked by the rows with few raters,
+    // whose raters' slices in the popular chunks are long (full segments).  Chunks of whole 256-column blocks only.
+    bool rect;
 };
 
 // everything the planning reads: plain numbers and host vectors
@@ -499,6 +503,7 @@ inline JobPlan plan_job(const PlanInput& in) {
         jp.any_tail = jp.any_tail || p.p_eff < p.Ic;
         jp.co_all = std::max(jp.co_all, (size_t)p.Uc * (p.nch + 1));
         jp.any_half = jp.any_half || p.half || p.p_eff < p.Ic;
+        p.rect = tune.cooc_rect && p.half && !p.panel && !p.psym && !p.coop && !p.flat && p.nch > 1 && p.CH % 256 == 0;
     }
     return jp;
 }

@@ -41,6 +41,8 @@ struct Tuning {
     int cooc_pk = 1;                   // packed 4-byte CSR entries for the row kernel when the ratings are fp16-exact
     int cooc_f32 = 0;                  // row kernel accumulators in fp32 (ds_add_f32): MEASUREMENT ONLY -- 4x slower, see fy_cooc.hpp
     int cooc_half = 1;                 // symmetric walk (upper triangle + mirror pass) for clusters with packed rows
+    int cooc_rect = 1;                 // FY_COOC_RECT=0: the symmetric walk of a row covers its own chunk and the chunks BEHIND it (before DESIGN.md section 7g)
+                                       // instead of its own chunk and the whole chunks IN FRONT of it; last-bit differences in the off-diagonal chunk rectangles
     int cooc_fx = 1;                   // fixed-point (ds_add_u64) accumulation in the packed walk
     int panel_min_clusters = 4;        // column-panel mode when at least this many clusters of the rank are pruned ones
     int prune_min_users = 600;         // clusters with fewer users take the plain full pass
