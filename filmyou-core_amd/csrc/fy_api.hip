@@ -53,7 +53,6 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_PANEL_COLS")) { int v = atoi(e); if (v >= 256) { t.panel_cols = v; t.panel_wide_below_users = 0; } }
     if (const char* e = getenv("FY_PANEL_WIDE_BELOW_USERS")) { int v = atoi(e); if (v >= 0) t.panel_wide_below_users = v; }
     if (const char* e = getenv("FY_PANEL_MAX_CH")) { int v = atoi(e); if (v >= 256) t.panel_max_ch = v; }
-    if (const char* e = getenv("FY_BOUNDED_TABLES")) t.bounded_tables = atoi(e) != 0;
     if (const char* e = getenv("FY_COOC_PLANES")) t.cooc_planes = atoi(e) != 0;
     if (const char* e = getenv("FY_SCORE_HEAVY")) { int v = atoi(e); if (v >= 0) t.score_heavy = v; }
     if (const char* e = getenv("FY_SCORE_WALK")) t.score_walk = atoi(e) != 0;

@@ -19,6 +19,7 @@
 #include "fy_common.hpp"
 #include "fy_prep.hpp"
 #include "fy_rm2_plan.hpp"   // pick_chunks
+#include "fy_rm2_tables.hpp"
 
 namespace fy {
 
@@ -414,20 +415,11 @@ __attribute__((unused)) static __global__ void k_item_list(CoocArgs A, int2* __r
     item_list_body(A, seg_out, id_out);
 }
 
-// segment table of one cluster from its chunk_off table; returns the number of segments (synchronises once)
+// a segment table as the row kernels read it: a view into a SegStore
 struct SegTable {
-    int64_t n_seg = 0;     // segments in the table (an upper bound when the table was sized without a round trip)
-    DevBuf<int32_t> cnt, scratch;   // build_segments' temporaries: they live as long as the table (a lane may still be reading them)
-    DevBuf<int32_t> ptr;   // nch * (nq + 1)
-    DevBuf<int2> seg;
-    DevBuf<float> w;
-    // a table that is a RANGE of the job's one table over all clusters (fy_rm2.hip: build_tables_all) owns nothing: views
-    const int32_t* v_ptr = nullptr;
-    const int2* v_seg = nullptr;
-    const float* v_w = nullptr;
-    const int32_t* ptr_() const { return v_ptr ? v_ptr : ptr.get(); }
-    const int2* seg_() const { return v_seg ? v_seg : seg.get(); }
-    const float* w_() const { return v_w ? v_w : w.get(); }
+    const int32_t* ptr = nullptr;   // nch * (nq + 1) prefixes
+    const int2* seg = nullptr;
+    const float* w = nullptr;
 };
 // What every launch of a row kernel says the same way: the CSC of the structure, a segment table, where the cluster lies and how its
 // rows are cut into chunks, all Ic rows in one launch, the CSR operands (csr_w: the weights of the unpacked walk; csr_pk: the packed
@@ -441,27 +433,52 @@ struct CoocGeometry {
 inline CoocGeometry cooc_geometry(const Plan& p) { return CoocGeometry{p.pbase, p.sbase, p.Ic, p.CH, p.nch, p.q0, p.nq}; }
 inline CoocArgs cooc_args(const Prepared& P, const SegTable& T, const CoocGeometry& g, const float* csr_w, const uint32_t* csr_pk) {
     CoocArgs A{};
-    A.rank_pair = P.rank_pair.get(); A.pair_start = P.pair_start.get(); A.seg_ptr = T.ptr_(); A.seg = T.seg_(); A.seg_w = T.w_();
+    A.rank_pair = P.rank_pair.get(); A.pair_start = P.pair_start.get(); A.seg_ptr = T.ptr; A.seg = T.seg; A.seg_w = T.w;
     A.csr_idx = P.csr_idx.get(); A.csr_w = csr_w; A.csr_pk = csr_pk; A.pk_bytes = (uint32_t)std::min<int64_t>((int64_t)P.nnz * 4, 0xFFFFFFFFll);
     A.pbase = g.pbase; A.slot_base = g.slot_base; A.Ic = g.Ic; A.CH = g.CH; A.nch = g.nch; A.nrows = g.Ic; A.q0 = g.q0; A.nq = g.nq;
     return A;
 }
-// half_row_of_entry != nullptr: symmetric walk (only the columns behind the entry's own row; fy_rm2.hip, struct Half)
-// only_rows_of_entry != nullptr: CSC entries of the rows in front of only_rows_from get no segments (tail-row launches)
-// rect: with half_row_of_entry, the walk from the unpopular side (CoocArgs::half == 2; fy_rm2.hip, Half::rect)
-// max_segments > 0: an upper bound of the number of segments -- the table is allocated for it and the call does not wait for
-// the device (otherwise it reads the exact count back: two host round trips)
-void build_segments(Context* ctx, const int32_t* csc_slot, const float* csc_w, const int32_t* chunk_off, int32_t slot_base,
-                    int32_t q0, int32_t nq, int32_t nch, SegTable& out, hipStream_t st = nullptr,
-                    const int32_t* half_row_of_entry = nullptr, const int32_t* csr_idx = nullptr, int32_t CH = 0,
-                    const int32_t* only_rows_of_entry = nullptr, int32_t only_rows_from = 0, int64_t max_segments = 0,
-                    const int32_t* samples = nullptr, bool rect = false);
+// ---- the walk tables (descriptors: fy_rm2_tables.hpp; kernels and host sequence: fy_cooc_tables.hpp, part of fy_rm2.hip)
+// the arrays the segment tables of one group read
+struct SegArrays {
+    const int32_t* __restrict__ csc_slot;       // rater slot of every CSC entry
+    const float* __restrict__ csc_w;            // its weight
+    const int32_t* __restrict__ chunk_off;      // chunk offsets (SegDesc::co_off is relative to this)
+    const int32_t* __restrict__ row_of_entry;   // row of every CSC entry: tables with half, lim_chunks or only_from
+    const int32_t* __restrict__ samples;        // [k] = csr_idx[64 k] (build_csr_samples): tables with half
+};
+struct SegGroup {
+    SegArrays in;
+    const SegDesc* desc;      // (host)
+    size_t n;
+};
+// the segment tables of one build: all prefixes in one array, all segments in one numbering
+struct SegStore {
+    int64_t n_seg = 0;
+    DevBuf<int32_t> ptr;
+    DevBuf<int2> seg;
+    DevBuf<float> w;
+    SegTable view(const SegDesc& d) const { return SegTable{ptr.get() + d.cnt_off, seg.get(), w.get()}; }
+};
+// counts, one scan, one read-back of the total, fill, closing synchronisation (two host round trips whatever the number of tables)
+void build_segment_tables(Context* ctx, const SegGroup* groups, size_t n_groups, SegStore& out, hipStream_t st = nullptr);
+inline void build_segment_table(Context* ctx, const SegArrays& in, const SegDesc& d, SegStore& out, hipStream_t st = nullptr) {
+    const SegGroup g{in, &d, 1};
+    build_segment_tables(ctx, &g, 1, out, st);
+}
 // every 64th entry of csr_idx: what the symmetric cut of the segment tables searches instead of the rows themselves
 void build_csr_samples(Context* ctx, int64_t nnz, const int32_t* csr_idx, DevBuf<int32_t>& samp, hipStream_t st = nullptr);
 
-// chunk_off table for one cluster: one thread per (slot, boundary)
-void build_chunk_offsets(Context* ctx, const int32_t* rowptr, const int32_t* csr_idx, int32_t slot_base, int32_t n_slots,
-                         int32_t CH, int32_t nch, int32_t* chunk_off, hipStream_t st = nullptr);
+// The descriptors of the CSR-side table kernels on the device (alive until the stream has run the kernels), with their host copy.
+struct CsrDescs {
+    std::vector<CsrDesc> h;
+    DevBuf<CsrDesc> d;
+};
+CsrDescs upload_csr_descs(Context* ctx, std::vector<CsrDesc> h, hipStream_t st = nullptr);
+// chunk offsets of every described cluster: one thread per (slot, boundary)
+void build_chunk_offsets(Context* ctx, const CsrDescs& C, const int32_t* rowptr, const int32_t* csr_idx, int32_t* co_all, hipStream_t st = nullptr);
+// packed CSR (column index relative to its chunk | fp16 of csr_r) of every described range [f0, f1)
+void pack_csr(Context* ctx, const CsrDescs& C, const int32_t* csr_idx, const float* csr_r, uint32_t* pk, hipStream_t st = nullptr);
 
 // columns of LDS accumulators a workgroup of the RM2 row kernel allocates for chunks of CH columns: its epilogue reads whole
 // 256-column blocks up to the padded row length, which overshoots a chunk whose width is not a multiple of 256 by < 256

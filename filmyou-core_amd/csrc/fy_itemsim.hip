@@ -1082,15 +1082,17 @@ fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ra
     int32_t CH, nch;
     pick_chunks(Ic, max_ch, CH, nch);
     DevBuf<int32_t> chunk_off(ctx, (size_t)P.nU * (nch + 1));
-    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), 0, P.nU, CH, nch, chunk_off.get());
+    const CsrDescs cd = upload_csr_descs(ctx, {csr_desc(0, P.nU, CH, nch)});
+    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), chunk_off.get());
     if (rows_mine > 0 && !symmetric) {
-        SegTable segs;
-        build_segments(ctx, P.csc_slot.get(), csc_w.get(), chunk_off.get(), 0, 0, (int32_t)P.nnz, nch, segs);
+        SegStore segs;
+        const SegDesc sd = seg_desc(0, 0, (int32_t)P.nnz, nch);
+        build_segment_table(ctx, SegArrays{P.csc_slot.get(), csc_w.get(), chunk_off.get(), nullptr, nullptr}, sd, segs);
         if (use_pk) {
             k_isim_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), measure, csr_pk.get());
             FY_KERNEL_CHECK();
         }
-        CoocArgs CA = cooc_args(P, segs, CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, csr_w.get(), use_pk ? csr_pk.get() : nullptr);
+        CoocArgs CA = cooc_args(P, segs.view(sd), CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, csr_w.get(), use_pk ? csr_pk.get() : nullptr);
         CA.row0 = prm->rank; CA.nrows = rows_mine; CA.row_stride = prm->world;      // this rank's rows: rank, rank + world, ...
         DevBuf<int2> item_seg(ctx, (size_t)rows_mine * nch);
         DevBuf<int32_t> part_cnt(ctx, (size_t)rows_mine * nch);
@@ -1248,7 +1250,8 @@ fy_itemsim_job* itemsim_prepare(Context* ctx, const fy_itemsim_params* prm, cons
     J->nch = (int32_t)ceil_div(Ic, std::min<int64_t>(ctx->tune.isim_req_chunk, round_up(Ic, 64)));
     J->CH = (int32_t)round_up(ceil_div(Ic, J->nch), 64);
     J->choff.alloc(ctx, (size_t)P.nU * (size_t)(J->nch + 1));
-    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), 0, P.nU, J->CH, J->nch, J->choff.get());
+    const CsrDescs cd = upload_csr_descs(ctx, {csr_desc(0, P.nU, J->CH, J->nch)});
+    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), J->choff.get());
     DevBuf<long long> d_walk(ctx, Ic);
     k_isim_req_walk<<<grid_for((int64_t)Ic * 64, 256), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.rowptr.get(), d_walk.get());
     FY_KERNEL_CHECK();

@@ -374,68 +374,7 @@ __global__ void k_csc_rank(int64_t nnz, const int32_t* __restrict__ csc_pair, co
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x) out[q] = pair_rank[csc_pair[q]];
 }
 
-// packed CSR of one cluster for the row kernel (fy_cooc.hpp): column index relative to its chunk | fp16 raw rating
-__device__ __forceinline__ void pack_csr_body(int32_t f0, int32_t f1, int32_t CH, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r,
-                                              uint32_t* __restrict__ pk) {
-    for (int64_t f = f0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < f1; f += (int64_t)gridDim.x * blockDim.x)
-        pk[f] = (uint32_t)(csr_idx[f] % CH) | ((uint32_t)__half_as_ushort(__float2half(csr_r[f])) << 16);
-}
-__global__ void k_pack_csr(int32_t f0, int32_t f1, int32_t CH, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r,
-                           uint32_t* __restrict__ pk) {
-    pack_csr_body(f0, f1, CH, csr_idx, csr_r, pk);
-}
-
-// Column-panel mode, tail rows (rows >= p_eff, few raters each): their co-ratings with the columns behind p_eff are needed only
-// as upper bounds of the 64-column block maxima.  For a row i and a block B
-//     max_{j in B} sum_v x_vi x_vj  <=  sum_v x_vi max_{j in B} x_vj ,
-// and the right-hand side is the row kernel's own sum over a CSR compressed to ONE entry per (rater, block): the block index
-// relative to p_eff | the largest raw rating of the rater in the block, in the packed format of k_pack_csr.  With 2-17 raters
-// per tail row the sum of maxima is within ~14 % of the exact maximum (measured at ML-25M shape in 50 clusters: 1088
-// surviving blocks instead of 1080), a row needs ONE item with (I_c - p_eff) / 64 accumulators instead of one item per
-// 8192-column chunk, and no matrix element behind the panel is ever formed.
-// The user's compressed entries are written in place of the first entries of its CSR range (y_pk is as long as the CSR),
-// co2[2 k] / co2[2 k + 1] = their range: the "chunk offsets" of a one-chunk segment table.
-__device__ __forceinline__ void tail_blocks_body(int32_t slot_base, int32_t n_slots, int32_t p_eff, const int32_t* __restrict__ rowptr,
-                                                const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r, uint32_t* __restrict__ y_pk,
-                                                int32_t* __restrict__ co2) {
-    // One workgroup per user: the entries behind p_eff are a suffix of the row (found by a binary search), its 64-entry pieces
-    // are dealt to the four waves; a piece looks one entry back for the block of its predecessor and takes its output slots
-    // from an LDS counter (the order of a user's compressed entries does not matter: the sums they enter are integer sums).
-    __shared__ int sh_count;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int32_t k = blockIdx.x; k < n_slots; k += gridDim.x) {      // block-uniform
-        const int32_t base = rowptr[slot_base + k], end = rowptr[slot_base + k + 1];
-        int32_t lo = base, hi = end;                                  // first entry with column >= p_eff
-        while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (csr_idx[mid] < p_eff) lo = mid + 1; else hi = mid; }
-        const int32_t first = lo;
-        if (threadIdx.x == 0) sh_count = 0;
-        __syncthreads();
-        for (int32_t f0 = first + wave * 64; f0 < end; f0 += 4 * 64) {   // wave-uniform
-            const int32_t f = f0 + lane;
-            const int blk = f < end ? (csr_idx[f] - p_eff) >> 6 : -1;
-            int prev = __shfl_up(blk, 1, 64);
-            if (lane == 0) prev = f0 > first ? (csr_idx[f0 - 1] - p_eff) >> 6 : -1;
-            const bool start = blk >= 0 && blk != prev;
-            const unsigned long long bal = __ballot(start);
-            int at = 0;
-            if (lane == 0 && bal) at = atomicAdd(&sh_count, (int)__popcll(bal));
-            at = __shfl(at, 0, 64);
-            if (start) {
-                float m = csr_r[f];
-                for (int32_t g = f + 1; g < end && ((csr_idx[g] - p_eff) >> 6) == blk; g++) m = fmaxf(m, csr_r[g]);
-                y_pk[base + at + __popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)blk | ((uint32_t)__half_as_ushort(__float2half(m)) << 16);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) { co2[2 * k] = base; co2[2 * k + 1] = base + sh_count; }
-        __syncthreads();     // sh_count is read before the next user resets it
-    }
-}
-__global__ __launch_bounds__(256) void k_tail_blocks(int32_t slot_base, int32_t n_slots, int32_t p_eff, const int32_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r, uint32_t* __restrict__ y_pk,
-                                                     int32_t* __restrict__ co2) {
-    tail_blocks_body(slot_base, n_slots, p_eff, rowptr, csr_idx, csr_r, y_pk, co2);
-}
+#include "fy_cooc_tables.hpp"   // the walk tables of the row kernel: their kernels and the one host sequence that builds them (part of this translation unit)
 
 // one wave per user row: x = r / s_u and e = (1-l)(b_j - x) + l (U_c - 1) p_j  (all fp64, rounded once)
 // GEN (general smoothing): x = r' / d_u, e = e~_uj (fy_e_general), q = p_j; csr_r holds r', pb_rank (p, b~), usum_slot d by slot
@@ -510,307 +449,6 @@ __global__ void k_user_meta(int32_t lo, int32_t hi, const int32_t* __restrict__ 
         if (terms) atomicAdd(&counters[0], terms);
         if (scored) atomicAdd(&counters[1], scored);
     }
-}
-
-// ================================================================ chunk offsets for the row kernel
-__device__ __forceinline__ void chunk_offsets_body(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_idx, int32_t slot_base,
-                                                   int32_t n_slots, int32_t CH, int32_t nch, int32_t* __restrict__ chunk_off) {
-    const int64_t total = (int64_t)n_slots * (nch + 1);
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t v = (int32_t)(t / (nch + 1)), ch = (int32_t)(t % (nch + 1));
-        const int32_t a = rowptr[slot_base + v], b = rowptr[slot_base + v + 1];
-        int32_t lo = a, hi = b;
-        const int32_t key = ch * CH;   // first entry with idx >= key
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (csr_idx[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        chunk_off[t] = (ch == nch) ? b : lo;
-    }
-}
-__global__ void k_chunk_offsets(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_idx, int32_t slot_base,
-                                int32_t n_slots, int32_t CH, int32_t nch, int32_t* __restrict__ chunk_off) {
-    chunk_offsets_body(rowptr, csr_idx, slot_base, n_slots, CH, nch, chunk_off);
-}
-
-void build_chunk_offsets(Context* ctx, const int32_t* rowptr, const int32_t* csr_idx, int32_t slot_base, int32_t n_slots,
-                         int32_t CH, int32_t nch, int32_t* chunk_off, hipStream_t st) {
-    const int64_t total = (int64_t)n_slots * (nch + 1);
-    if (total == 0) return;
-    k_chunk_offsets<<<grid_for(total), 256, 0, st ? st : ctx->stream>>>(rowptr, csr_idx, slot_base, n_slots, CH, nch, chunk_off);
-    FY_KERNEL_CHECK();
-}
-
-// ---- segment table (fy_cooc.hpp): counts, exclusive prefix, fill
-// HALF mode (symmetric walk): the co-rating Gram is symmetric, so row i accumulates only the columns j > i and a mirror pass
-// fills the lower triangle (k_mirror_*).  For the CSC entry (rater v, row i) the chunks in front of i's own chunk have no
-// segments, and in i's chunk the rater's slice starts behind the position of i in the rater's CSR row (`Half::start`,
-// found once by a binary search in k_seg_counts and re-used by k_seg_fill).
-#ifndef FY_SAMPLE_SHIFT
-#define FY_SAMPLE_SHIFT 6     // the symmetric cut searches every 64th CSR entry (measured, ML-25M job, tables / row kernel ms: exact cut 4.57 / 7.84; stride 64: 2.96 / 8.48 = 25.6 ms per job; stride 16: 3.23 / 8.21 = 25.7; Netflix shape 77.1 / 79.1 ms per job)
-#endif
-struct Half {
-    const int32_t* __restrict__ row_of_entry;   // [q0 + q]: the row (rank inside the cluster) of CSC entry q; nullptr = full walk
-    const int32_t* __restrict__ csr_idx;
-    int32_t CH;
-    int32_t* __restrict__ start;                // [q]: where the slice of CSC entry q starts in the row's own chunk: the 64-entry-aligned CSR
-                                                // position in front of (v, i) -- the row kernel masks the entries at or before column i
-    const int32_t* __restrict__ samp;           // [k] = csr_idx[64 k]: every 64th CSR entry (k_csr_samples)
-    // tail-row launches (column-panel mode): entries of the rows in front of only_from get no segments
-    const int32_t* __restrict__ only_rows;      // [q0 + q]: row of the entry; nullptr = all rows
-    int32_t only_from;
-    // column-panel mode: only the rows in front of sym_rows are cut (0 = all rows, plain half walk; < 0 = none: row_of_entry is set
-    // for the chunk limit alone), and the rows from lim_from on have segments only in their first lim_chunks chunks (0 = off) --
-    // rows and chunks the item list never names (tail rows behind the panel's chunks; symmetric panel mode: every row)
-    int32_t sym_rows, lim_from, lim_chunks;
-    // the walk from the unpopular side (CoocArgs::half == 2): a cut entry has its segments in the chunks IN FRONT of its own chunk
-    // (whole slices) and none behind it; the own chunk is cut as ever
-    int32_t rect;
-};
-__device__ __forceinline__ void seg_counts_body(const int32_t* __restrict__ csc_slot, const int32_t* __restrict__ chunk_off, int32_t slot_base,
-                                                int32_t q0, int32_t nq, int32_t nch, int32_t* __restrict__ cnt, const Half& H) {
-    // one thread per CSC entry: the rater's nch + 1 chunk offsets are one contiguous gather -- ONE 16-byte load where a row of the
-    // table is four offsets (three chunks: ML-25M shape).  Round 4: the kernel ran at 72 % of the L2's request rate (6.5 requests per
-    // entry, TCP_TCC_READ_REQ), most of them the same 16 bytes fetched offset by offset from 64 different rows per wave instruction.
-    const bool row4 = nch == 3 && (reinterpret_cast<uintptr_t>(chunk_off) & 15) == 0;      // (kernel-uniform)
-    const bool row2 = nch == 1 && (reinterpret_cast<uintptr_t>(chunk_off) & 7) == 0;       // one chunk (Netflix shape): two offsets, 8 bytes
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q <= nq; q += (int64_t)gridDim.x * blockDim.x) {
-        const bool live = q < nq && !(H.only_rows && H.only_rows[q0 + q] < H.only_from);
-        const int32_t* co = live ? chunk_off + (int64_t)(csc_slot[q0 + q] - slot_base) * (nch + 1) : nullptr;
-        int4 c4 = make_int4(0, 0, 0, 0);
-        if (live && row4) c4 = *reinterpret_cast<const int4*>(co);
-        if (live && row2) { const int2 v = *reinterpret_cast<const int2*>(co); c4.x = v.x; c4.y = v.y; }
-        auto CO = [&](int k) -> int32_t { return (row4 || row2) ? (k == 0 ? c4.x : k == 1 ? c4.y : k == 2 ? c4.z : c4.w) : co[k]; };
-        int32_t prev = live ? CO(0) : 0;
-        int32_t own = -1, behind = 0, climit = nch;
-        const int32_t r_e = (live && H.row_of_entry) ? H.row_of_entry[q0 + q] : 0;
-        if (live && H.row_of_entry && H.lim_chunks > 0 && r_e >= H.lim_from) climit = H.lim_chunks;
-        if (live && H.row_of_entry && (H.sym_rows == 0 || r_e < H.sym_rows)) {
-            const int32_t r = r_e;
-            own = r / H.CH;
-            // Where does the slice behind (v, i) start?  Exactly: behind the position of i in the rater's row -- a binary search over the
-            // row slice in the 100-400 MB csr_idx per CSC entry (1.6 ms of the ML-25M job, 10.6 ms at Netflix shape, round 2).  Now: the
-            // last aligned CSR position inside the slice whose entry is <= r, found in the SAMPLES (every 2^FY_SAMPLE_SHIFT-th entry: a few MB,
-            // cache-resident, a handful of probes); the few entries between it and i are masked by the row kernel (column <= row).
-            constexpr int SS = FY_SAMPLE_SHIFT;
-            const int32_t co_own = CO(own), co_next = CO(own + 1);
-            int32_t klo = (co_own + (1 << SS) - 1) >> SS, khi = (co_next + (1 << SS) - 1) >> SS;      // samples inside the slice: [klo, khi)
-            while (klo < khi) {                                                    // first k with samp[k] > r
-                const int32_t mid = (klo + khi) >> 1;
-                if (H.samp[mid] <= r) klo = mid + 1; else khi = mid;
-            }
-            const int32_t lo = max(co_own, (klo - 1) << SS);                      // (no sample <= r inside the slice: its beginning)
-            behind = lo;
-            H.start[q] = lo;
-        }
-        for (int32_t ch = 0; ch < nch; ch++) {
-            int32_t n = 0;
-            if (live) {
-                const int32_t next = CO(ch + 1);
-                const int32_t first = ch == own ? behind : prev;
-                n = ((H.rect ? (own >= 0 && ch > own) : ch < own) || ch >= climit) ? 0 : (next - first + 63) >> 6;
-                prev = next;
-            }
-            cnt[(int64_t)ch * (nq + 1) + q] = n;
-        }
-    }
-}
-__global__ void k_seg_counts(const int32_t* __restrict__ csc_slot, const int32_t* __restrict__ chunk_off, int32_t slot_base,
-                             int32_t q0, int32_t nq, int32_t nch, int32_t* __restrict__ cnt, Half H) {
-    seg_counts_body(csc_slot, chunk_off, slot_base, q0, nq, nch, cnt, H);
-}
-// The tables of ALL clusters of a job in one pass (many clusters, the reference's regime): blockIdx.y = table.  A table's counts /
-// prefixes are a range of one array (cnt_off), so ONE scan numbers the segments of all tables and one fill writes them -- built
-// cluster by cluster the same 25 M CSC entries cost ~15 small launches and a host round trip per cluster: 20 ms at 50 clusters
-// against 4.6 ms for the one-cluster job.
-struct SegDesc {
-    int32_t slot_base, q0, nq, nch, CH, half, only_from, co_stride;
-    int64_t co_off, cnt_off;      // first entry of the table's chunk offsets / of its counts and prefixes
-    int32_t use_only_rows, sym_rows;      // sym_rows, lim_from, lim_chunks: Half
-    int32_t lim_from, lim_chunks;
-    int32_t rect, pad;            // Half::rect
-};
-__global__ void k_seg_counts_multi(const SegDesc* __restrict__ D, const int32_t* __restrict__ csc_slot, const int32_t* __restrict__ co_all,
-                                   int32_t* __restrict__ cnt_all, const int32_t* __restrict__ row_of_entry, const int32_t* __restrict__ csr_idx,
-                                   int32_t* __restrict__ start_all, const int32_t* __restrict__ samples) {
-    const SegDesc d = D[blockIdx.y];
-    const Half H{(d.half || d.lim_chunks > 0) ? row_of_entry : nullptr, csr_idx, d.CH, start_all + d.q0, samples, d.use_only_rows ? row_of_entry : nullptr, d.only_from,
-                 d.half ? d.sym_rows : -1, d.lim_from, d.lim_chunks, d.half ? d.rect : 0};
-    seg_counts_body(csc_slot, co_all + d.co_off, d.slot_base, d.q0, d.nq, d.nch, cnt_all + d.cnt_off, H);
-}
-
-// One wave fills the segments of 64 consecutive CSC entries of one chunk cooperatively: the group's segments are
-// contiguous in the table (exclusive prefix `ptr`), lane l writes segment base + l, base + l + 64, ... after finding its
-// owner among the 64 entries with a binary search over shuffled prefix values -- every store of the 3 GB table is
-// coalesced (one thread per entry writing its own run of segments reached 1.1 TB/s).
-__device__ __forceinline__ void seg_fill_body(const int32_t* __restrict__ csc_slot, const float* __restrict__ csc_w, const int32_t* __restrict__ chunk_off,
-                                              int32_t slot_base, int32_t q0, int32_t nq, int32_t nch, const int32_t* __restrict__ ptr,
-                                              int2* __restrict__ seg, float* __restrict__ seg_w, const Half& H) {
-    // A wave takes the group's entries through up to CB chunks at once: what is per ENTRY (rater slot, row, weight) is loaded once, and the
-    // loads that are per (entry, chunk) -- chunk offsets, segment prefixes -- are all in flight before the first segment is written.
-    // (Round 4: one (group, chunk) per wave iteration meant one dependent chain slot -> chunk offsets -> prefix per ~100 segments: the fill
-    // ran at 1.4 TB/s of stores, bound by that latency.)
-    constexpr int CB = 4;
-    const bool row4 = nch == 3 && (reinterpret_cast<uintptr_t>(chunk_off) & 15) == 0;      // a table row = four offsets = one 16-byte load
-    const bool row2 = nch == 1 && (reinterpret_cast<uintptr_t>(chunk_off) & 7) == 0;       // two offsets = one 8-byte load
-    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    const int64_t n_groups = ((int64_t)nq + 63) >> 6;
-    const int32_t n_cb = (nch + CB - 1) / CB;
-    const int64_t total_work = n_groups * n_cb;
-    for (int64_t gw = blockIdx.x * (int64_t)wpb + (threadIdx.x >> 6); gw < total_work; gw += (int64_t)gridDim.x * wpb) {
-        const int32_t ch0 = (int32_t)(gw / n_groups) * CB;
-        const int64_t g = gw - (int64_t)(ch0 / CB) * n_groups;
-        const int64_t q = g * 64 + lane;
-        const int64_t q_end = min((int64_t)nq, g * 64 + 64);
-        const bool live = q < nq;
-        int32_t cov[CB + 1], startv[CB], endv[CB];
-        int32_t r = 0, own = -1, own_start = 0;
-        bool dead = false, limited = false;
-        float w = 0.0f;
-#pragma unroll
-        for (int c = 0; c < CB; c++) {      // (wave-uniform tests)
-            startv[c] = 0;
-            endv[c] = ch0 + c < nch ? ptr[(int64_t)(ch0 + c) * (nq + 1) + q_end] : 0;
-            if (live && ch0 + c < nch) startv[c] = ptr[(int64_t)(ch0 + c) * (nq + 1) + q];
-        }
-#pragma unroll
-        for (int c = 0; c <= CB; c++) cov[c] = 0;
-        if (live) {
-            const int32_t* co = chunk_off + (int64_t)(csc_slot[q0 + q] - slot_base) * (nch + 1) + ch0;
-            if (row4) {
-                const int4 v = *reinterpret_cast<const int4*>(co);      // (ch0 = 0: the whole row)
-                cov[0] = v.x; cov[1] = v.y; cov[2] = v.z; cov[3] = v.w;
-            } else if (row2) {
-                const int2 v = *reinterpret_cast<const int2*>(co);
-                cov[0] = v.x; cov[1] = v.y;
-            } else {
-#pragma unroll
-                for (int c = 0; c <= CB; c++)
-                    if (ch0 + c <= nch) cov[c] = co[c];
-            }
-            if (H.row_of_entry) {
-                r = H.row_of_entry[q0 + q];
-                if (H.sym_rows == 0 || r < H.sym_rows) {
-                    own = r / H.CH;
-                    if (own >= ch0 && own < ch0 + CB) own_start = H.start[q];
-                }
-                limited = H.lim_chunks > 0 && r >= H.lim_from;
-            }
-            if (H.only_rows && H.only_rows[q0 + q] < H.only_from) dead = true;
-            w = csc_w[q0 + q];
-        }
-#pragma unroll
-        for (int c = 0; c < CB; c++) {
-            const int32_t ch = ch0 + c;
-            if (ch >= nch) break;                             // wave-uniform
-            int32_t f0 = cov[c], len = cov[c + 1] - cov[c], start = startv[c];
-            if (live) {
-                if (own >= 0) {
-                    if (H.rect ? ch > own : ch < own) len = 0;
-                    else if (ch == own) { f0 = own_start; len = cov[c + 1] - f0; }
-                }
-                if (limited && ch >= H.lim_chunks) len = 0;
-                if (dead) len = 0;
-            } else len = 0;
-            const int32_t base = __shfl(start, 0, 64);
-            const int32_t total = endv[c] - base;                 // segments of the whole group
-            if (!live) start = base + total;                      // inactive lanes sit behind the last segment
-            const int32_t rel = start - base;
-            for (int32_t kk = 0; kk < total; kk += 64) {         // wave-uniform trip count: the shuffles need every lane alive
-                const int32_t k = kk + lane;
-                int lo = 0, hi = 63;                              // largest lane j with rel_j <= k (rel is non-decreasing)
-#pragma unroll
-                for (int it = 0; it < 6; it++) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    const int32_t rm = __shfl(rel, mid, 64);
-                    if (rm <= k) lo = mid; else hi = mid - 1;
-                }
-                // entries with zero segments share their rel with the next entry: the owner is the LAST lane with rel <= k
-                const int32_t off = k - __shfl(rel, lo, 64);
-                const int32_t of0 = __shfl(f0, lo, 64), olen = __shfl(len, lo, 64);
-                const float ow = __shfl(w, lo, 64);
-                if (k < total) {
-                    seg[base + k] = make_int2(of0 + 64 * off, min(64, olen - 64 * off));
-                    seg_w[base + k] = ow;
-                }
-            }
-        }
-    }
-}
-
-__global__ void k_seg_fill(const int32_t* __restrict__ csc_slot, const float* __restrict__ csc_w, const int32_t* __restrict__ chunk_off,
-                           int32_t slot_base, int32_t q0, int32_t nq, int32_t nch, const int32_t* __restrict__ ptr,
-                           int2* __restrict__ seg, float* __restrict__ seg_w, Half H) {
-    seg_fill_body(csc_slot, csc_w, chunk_off, slot_base, q0, nq, nch, ptr, seg, seg_w, H);
-}
-__global__ void k_seg_fill_multi(const SegDesc* __restrict__ D, const int32_t* __restrict__ csc_slot, const float* __restrict__ csc_w,
-                                 const int32_t* __restrict__ co_all, const int32_t* __restrict__ ptr_all, int2* __restrict__ seg, float* __restrict__ seg_w,
-                                 const int32_t* __restrict__ row_of_entry, const int32_t* __restrict__ csr_idx, int32_t* __restrict__ start_all) {
-    const SegDesc d = D[blockIdx.y];
-    const Half H{(d.half || d.lim_chunks > 0) ? row_of_entry : nullptr, csr_idx, d.CH, start_all + d.q0, nullptr, d.use_only_rows ? row_of_entry : nullptr, d.only_from,
-                 d.half ? d.sym_rows : -1, d.lim_from, d.lim_chunks, d.half ? d.rect : 0};
-    seg_fill_body(csc_slot, csc_w, co_all + d.co_off, d.slot_base, d.q0, d.nq, d.nch, ptr_all + d.cnt_off, seg, seg_w, H);
-}
-// chunk offsets / packed CSR / block-compressed tail CSR of all planned clusters: blockIdx.y = cluster of the plan
-struct CoDesc {
-    int32_t slot_base, n_slots, CH, nch, f0, f1, p_eff, has_tail;
-    int64_t co_off, co_tail_off;
-};
-__global__ void k_chunk_offsets_multi(const CoDesc* __restrict__ D, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_idx,
-                                      int32_t* __restrict__ co_all) {
-    const CoDesc d = D[blockIdx.y];
-    chunk_offsets_body(rowptr, csr_idx, d.slot_base, d.n_slots, d.CH, d.nch, co_all + d.co_off);
-}
-__global__ void k_pack_csr_multi(const CoDesc* __restrict__ D, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r, uint32_t* __restrict__ pk) {
-    const CoDesc d = D[blockIdx.y];
-    pack_csr_body(d.f0, d.f1, d.CH, csr_idx, csr_r, pk);
-}
-__global__ __launch_bounds__(256) void k_tail_blocks_multi(const CoDesc* __restrict__ D, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_idx,
-                                                           const float* __restrict__ csr_r, uint32_t* __restrict__ y_pk, int32_t* __restrict__ co_tail_all) {
-    const CoDesc d = D[blockIdx.y];
-    if (!d.has_tail) return;       // block-uniform
-    tail_blocks_body(d.slot_base, d.n_slots, d.p_eff, rowptr, csr_idx, csr_r, y_pk, co_tail_all + d.co_tail_off);
-}
-__global__ void k_csr_samples(int64_t n_samples, const int32_t* __restrict__ csr_idx, int32_t* __restrict__ samp) {
-    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n_samples; k += (int64_t)gridDim.x * blockDim.x) samp[k] = csr_idx[k << FY_SAMPLE_SHIFT];
-}
-// every 64th entry of csr_idx (what the symmetric cut of the segment tables searches, Half::samp)
-void build_csr_samples(Context* ctx, int64_t nnz, const int32_t* csr_idx, DevBuf<int32_t>& samp, hipStream_t st) {
-    const int64_t n = (nnz + (1 << FY_SAMPLE_SHIFT) - 1) >> FY_SAMPLE_SHIFT;
-    samp.alloc(ctx, (size_t)n + 1);
-    if (n) k_csr_samples<<<grid_for(n), 256, 0, st ? st : ctx->stream>>>(n, csr_idx, samp.get());
-    FY_KERNEL_CHECK();
-}
-void build_segments(Context* ctx, const int32_t* csc_slot, const float* csc_w, const int32_t* chunk_off, int32_t slot_base,
-                    int32_t q0, int32_t nq, int32_t nch, SegTable& out, hipStream_t st, const int32_t* half_row_of_entry,
-                    const int32_t* csr_idx, int32_t CH, const int32_t* only_rows_of_entry, int32_t only_rows_from, int64_t max_segments,
-                    const int32_t* samples, bool rect) {
-    if (half_row_of_entry && !samples) FY_FAIL(FY_ERR_STATE, "internal: the symmetric segment table needs the CSR samples");
-    if (!st) st = ctx->stream;
-    const size_t np = (size_t)nch * ((size_t)nq + 1);
-    out.ptr.alloc(ctx, np);
-    out.cnt.alloc(ctx, np);
-    out.scratch.alloc(ctx, half_row_of_entry ? (size_t)nq + 1 : 1);
-    const Half H{half_row_of_entry, csr_idx, CH, out.scratch.get(), samples, only_rows_of_entry, only_rows_from, 0, 0, 0, (half_row_of_entry && rect) ? 1 : 0};
-    k_seg_counts<<<grid_for((int64_t)nq + 1), 256, 0, st>>>(csc_slot, chunk_off, slot_base, q0, nq, nch, out.cnt.get(), H);
-    FY_KERNEL_CHECK();
-    exclusive_scan_i32(ctx, out.cnt.get(), out.ptr.get(), np, st);
-    int64_t total = max_segments;
-    if (max_segments <= 0) {
-        int32_t t32 = 0;   // the last count is 0 by construction: the last prefix is the total
-        FY_HIP(hipMemcpyAsync(&t32, out.ptr.get() + (np - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        FY_HIP(hipStreamSynchronize(st));
-        total = t32;
-    }
-    out.n_seg = total;
-    out.seg.alloc(ctx, (size_t)total);
-    out.w.alloc(ctx, (size_t)total);
-    if ((int64_t)nch * nq > 0) {
-        k_seg_fill<<<grid_for((((int64_t)nq + 63) >> 6) * nch * 64, 256, 256 * 64), 256, 0, st>>>(csc_slot, csc_w, chunk_off, slot_base, q0, nq, nch, out.ptr.get(),
-                                                                 out.seg.get(), out.w.get(), H);
-        FY_KERNEL_CHECK();
-    }
-    if (max_segments <= 0) FY_HIP(hipStreamSynchronize(st));     // (the callers of the exact mode release their inputs right after the call)
 }
 
 // ================================================================ G build: co-rating row kernel + RM2 epilogue
@@ -1182,7 +820,7 @@ __device__ __forceinline__ void cooc_rm2_body(const CoocArgs& A, const MEpilogue
         }
         const int c0 = (id & 255) * A.CH;
         // symmetric walk: in the row's OWN chunk the slices start at a 64-aligned position in front of the row's column (segment
-        // table: Half::start); the entries at or before it are masked here -- row i accumulates only the columns j > i
+        // table: k_seg_counts' cut start); the entries at or before it are masked here -- row i accumulates only the columns j > i
         const int row_of_item = A.row0 + (id >> 8) * (A.row_stride ? A.row_stride : 1);
         const int rmask = (cooc_row_is_cut(A, row_of_item) && row_of_item >= c0 && row_of_item < c0 + A.CH) ? row_of_item - c0 : -1;
         if constexpr (PK) cooc_accumulate_pk<ACC>(A, acc, s0, s1, batch, rmask);
@@ -1572,17 +1210,14 @@ using namespace fy;
 // & FY_RM2_NO_CACHE builds it afresh and does not keep it: the "cold" job, which bench.py times as its headline value.
 struct TableCache {
     bool valid = false;
-    int64_t total_segments = 0;         // segments in all tables of the job (fy_stats::cooc_segments)
     std::vector<int32_t> sig;           // what the tables were built for: per planned cluster (c, CH, nch, half, panel, p_eff, tail_chunks), + flags
     bool have_x = false;
     DevBuf<float> csc_x, csc_x_over_s;  // x = r / s_v (and x / s_v for the packed walk) per CSC entry: ratings only
     DevBuf<uint32_t> csr_pk, y_pk;      // packed CSR (chunk-relative columns), block-compressed CSR of the tail rows
     DevBuf<int32_t> csc_rank, samples;      // row of every CSC entry; every 64th CSR entry (symmetric cut)
-    std::vector<SegTable> segs, segs_tail;
-    // many clusters: ONE table over all of them (build_tables_all); segs / segs_tail are then views into these
-    DevBuf<int32_t> g_co, g_co_tail, g_cnt, g_ptr, g_start;
-    DevBuf<int2> g_seg;
-    DevBuf<float> g_w;
+    CsrDescs csr_descs;
+    SegStore store;                     // the segment tables of all planned clusters; store.n_seg = fy_stats::cooc_segments
+    std::vector<SegTable> segs, segs_tail;      // [plan]: views into it (main walk; tail-row bounds of panel mode)
 };
 struct RM2Static {
     // key
@@ -1702,17 +1337,17 @@ bool fy::gram_half_build(Context* ctx, const Prepared& P, const float* csc_w, co
     EventTimer t_tab(ctx), t_walk(ctx);
     const size_t s0 = t_tab.begin();
     DevBuf<uint32_t> csr_pk(ctx, (size_t)P.nnz);
-    k_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(0, (int32_t)P.nnz, CH, P.csr_idx.get(), csr_ones ? csr_ones : P.csr_r.get(), csr_pk.get());
-    FY_KERNEL_CHECK();
-    DevBuf<int32_t> co(ctx, (size_t)P.nU * (nch + 1)), csc_rank(ctx, (size_t)P.nnz);
-    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), 0, P.nU, CH, nch, co.get(), st);
+    DevBuf<int32_t> co(ctx, (size_t)P.nU * (nch + 1)), csc_rank(ctx, (size_t)P.nnz), samples;
     k_csc_rank<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.pair_rank.get(), csc_rank.get());
     FY_KERNEL_CHECK();
-    SegTable segs;
-    DevBuf<int32_t> samples;
     build_csr_samples(ctx, P.nnz, P.csr_idx.get(), samples, st);
-    build_segments(ctx, P.csc_slot.get(), csc_w, co.get(), 0, 0, (int32_t)P.nnz, nch, segs, st, csc_rank.get(), P.csr_idx.get(), CH, nullptr, 0, 0, samples.get());
-    CoocArgs CA = cooc_args(P, segs, CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, nullptr, csr_pk.get());
+    const CsrDescs cd = upload_csr_descs(ctx, {csr_desc(0, P.nU, CH, nch, 0, (int32_t)P.nnz)}, st);      // (queued behind the two kernels above)
+    pack_csr(ctx, cd, P.csr_idx.get(), csr_ones ? csr_ones : P.csr_r.get(), csr_pk.get(), st);
+    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), co.get(), st);
+    SegStore segs;
+    const SegDesc sd = seg_desc(0, 0, (int32_t)P.nnz, nch, CH, true);
+    build_segment_table(ctx, SegArrays{P.csc_slot.get(), csc_w, co.get(), csc_rank.get(), samples.get()}, sd, segs, st);
+    CoocArgs CA = cooc_args(P, segs.view(sd), CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, nullptr, csr_pk.get());
     CA.half = 1;
     CA.fx_scale = std::ldexp(1.0, fxk);
     CA.acc32 = acc32 ? 1 : 0;
@@ -1916,116 +1551,6 @@ static void validate_params(const fy_rm2_params* p) {
     } else if (!(p->lambda >= 0.0 && p->lambda <= 1.0)) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "lambda must be in [0, 1]");
     if (p->world <= 0 || p->rank < 0 || p->rank >= p->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", p->rank, p->world);
     if (p->number_of_recommendations < 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "numberOfRecommendations must be >= 0");
-}
-
-// The row kernel's tables of ALL planned clusters in one pass over the CSR / CSC (no cooperative cluster among them): packed CSR,
-// chunk offsets, the tail rows' block-compressed CSR, and both segment tables (main walk; tail-row bounds) of every cluster as
-// ranges of ONE table -- one count launch, ONE scan, one host round trip for the size, one fill.  tc.segs / tc.segs_tail become views.
-static void build_tables_all(Context* ctx, const Prepared& P, const std::vector<Plan>& plans, const std::vector<int32_t>& csr_range, bool use_pk,
-                             TableCache& tc, hipStream_t st) {
-    const size_t np = plans.size();
-    std::vector<CoDesc> hco(np);
-    std::vector<SegDesc> hsd;
-    std::vector<int64_t> main_of(np, -1), tail_of(np, -1);
-    int64_t co_total = 0, co_tail_total = 0, cnt_total = 0;
-    int32_t max_slots = 1, max_f = 1, max_nq = 1;
-    for (size_t pi = 0; pi < np; pi++) {
-        const Plan& p = plans[pi];
-        const bool tail = p.p_eff < p.Ic;
-        hco[pi] = CoDesc{p.sbase, p.Uc, p.CH, p.nch, csr_range[2 * pi], csr_range[2 * pi + 1], p.p_eff, tail ? 1 : 0, co_total, co_tail_total};
-        // panel mode: the tail rows are walked over their first tail_chunks chunks only; symmetric panel mode: so are the head rows,
-        // and those are cut (Half::sym_rows / lim_from / lim_chunks) -- rows and chunks the item list never names get no segments
-        SegDesc m{p.sbase, p.q0, p.nq, p.nch, p.CH, (p.half || p.psym) ? 1 : 0, 0, p.nch + 1, co_total, cnt_total, 0, p.psym ? p.p_eff : 0,
-                  p.psym ? 0 : p.p_eff, (p.panel && p.tail_chunks > 0 && p.p_eff < p.Ic) ? p.tail_chunks : 0, p.rect ? 1 : 0, 0};
-        main_of[pi] = (int64_t)hsd.size();
-        hsd.push_back(m);
-        cnt_total += (int64_t)p.nch * ((int64_t)p.nq + 1);
-        co_total += (int64_t)p.Uc * (p.nch + 1);
-        max_slots = std::max(max_slots, p.Uc);
-        max_f = std::max(max_f, csr_range[2 * pi + 1] - csr_range[2 * pi]);
-        max_nq = std::max(max_nq, p.nq);
-    }
-    for (size_t pi = 0; pi < np; pi++) {      // the tail tables behind the main ones (their chunk offsets are the k_tail_blocks ranges)
-        const Plan& p = plans[pi];
-        if (p.p_eff >= p.Ic) continue;
-        SegDesc t{p.sbase, p.q0, p.nq, 1, 0, 0, p.p_eff, 2, hco[pi].co_tail_off, cnt_total, 1, 0, 0, 0};
-        tail_of[pi] = (int64_t)hsd.size();
-        hsd.push_back(t);
-        cnt_total += (int64_t)p.nq + 1;
-    }
-    // (co_tail_off: two entries per slot of every plan with tail rows, in plan order)
-    {
-        int64_t off = 0;
-        for (size_t pi = 0; pi < np; pi++) {
-            hco[pi].co_tail_off = off;
-            if (plans[pi].p_eff < plans[pi].Ic) off += 2 * (int64_t)plans[pi].Uc;
-        }
-        co_tail_total = off;
-        for (size_t pi = 0; pi < np; pi++)
-            if (tail_of[pi] >= 0) hsd[(size_t)tail_of[pi]].co_off = hco[pi].co_tail_off;
-    }
-    if (cnt_total + 1 >= (int64_t)0x7FFFFFF0) FY_FAIL(FY_ERR_UNSUPPORTED, "segment tables of %zu clusters need %lld prefix entries (limit 2^31)", np, (long long)cnt_total);
-    DevBuf<CoDesc> d_co(ctx, np);
-    DevBuf<SegDesc> d_sd(ctx, hsd.size());
-    FY_HIP(hipMemcpyAsync(d_co.get(), hco.data(), np * sizeof(CoDesc), hipMemcpyHostToDevice, st));
-    FY_HIP(hipMemcpyAsync(d_sd.get(), hsd.data(), hsd.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
-    tc.g_co.alloc(ctx, (size_t)std::max<int64_t>(1, co_total));
-    tc.g_co_tail.alloc(ctx, (size_t)std::max<int64_t>(1, co_tail_total));
-    tc.g_cnt.alloc(ctx, (size_t)cnt_total + 1);
-    tc.g_ptr.alloc(ctx, (size_t)cnt_total + 1);
-    tc.g_start.alloc(ctx, (size_t)P.nnz + 1);
-    const dim3 g_slots((unsigned)grid_for((int64_t)max_slots * 8, 256, 1024), (unsigned)np);
-    if (use_pk) {
-        k_pack_csr_multi<<<dim3((unsigned)grid_for(max_f, 256, 1024), (unsigned)np), 256, 0, st>>>(d_co.get(), P.csr_idx.get(), P.csr_r.get(), tc.csr_pk.get());
-        FY_KERNEL_CHECK();
-    }
-    k_chunk_offsets_multi<<<g_slots, 256, 0, st>>>(d_co.get(), P.rowptr.get(), P.csr_idx.get(), tc.g_co.get());
-    FY_KERNEL_CHECK();
-    if (co_tail_total > 0) {
-        k_tail_blocks_multi<<<dim3((unsigned)std::min<int>(max_slots, ctx->num_cus * 4), (unsigned)np), 256, 0, st>>>(d_co.get(), P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(),
-                                                                                                                  tc.y_pk.get(), tc.g_co_tail.get());
-        FY_KERNEL_CHECK();
-    }
-    // main tables read g_co, tail tables g_co_tail: two launches of the count / fill kernels (the offsets are relative to either array)
-    const unsigned n_main = (unsigned)np, n_tail = (unsigned)(hsd.size() - np);
-    const dim3 g_q((unsigned)grid_for((int64_t)max_nq + 1, 256, 2048), n_main), g_qt((unsigned)grid_for((int64_t)max_nq + 1, 256, 2048), std::max(1u, n_tail));
-    k_seg_counts_multi<<<g_q, 256, 0, st>>>(d_sd.get(), P.csc_slot.get(), tc.g_co.get(), tc.g_cnt.get(), tc.csc_rank.get(), P.csr_idx.get(), tc.g_start.get(), tc.samples.get());
-    FY_KERNEL_CHECK();
-    if (n_tail) {
-        k_seg_counts_multi<<<g_qt, 256, 0, st>>>(d_sd.get() + np, P.csc_slot.get(), tc.g_co_tail.get(), tc.g_cnt.get(), tc.csc_rank.get(), P.csr_idx.get(), tc.g_start.get(), tc.samples.get());
-        FY_KERNEL_CHECK();
-    }
-    FY_HIP(hipMemsetAsync(tc.g_cnt.get() + cnt_total, 0, sizeof(int32_t), st));
-    exclusive_scan_i32(ctx, tc.g_cnt.get(), tc.g_ptr.get(), (size_t)cnt_total + 1, st);
-    int32_t total = 0;
-    FY_HIP(hipMemcpyAsync(&total, tc.g_ptr.get() + cnt_total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FY_HIP(hipStreamSynchronize(st));       // the ONE host round trip of the job's tables (d_co / d_sd's host copies are done too)
-    tc.g_seg.alloc(ctx, (size_t)std::max(1, total));
-    tc.g_w.alloc(ctx, (size_t)std::max(1, total));
-    tc.total_segments = total;
-    const float* csc_w = use_pk ? tc.csc_x_over_s.get() : tc.csc_x.get();
-    const dim3 g_f((unsigned)grid_for((((int64_t)max_nq + 63) >> 6) * 64 * 4, 256, 4096), n_main), g_ft((unsigned)grid_for((((int64_t)max_nq + 63) >> 6) * 64, 256, 4096), std::max(1u, n_tail));
-    k_seg_fill_multi<<<g_f, 256, 0, st>>>(d_sd.get(), P.csc_slot.get(), csc_w, tc.g_co.get(), tc.g_ptr.get(), tc.g_seg.get(), tc.g_w.get(), tc.csc_rank.get(),
-                                          P.csr_idx.get(), tc.g_start.get());
-    FY_KERNEL_CHECK();
-    if (n_tail) {
-        k_seg_fill_multi<<<g_ft, 256, 0, st>>>(d_sd.get() + np, P.csc_slot.get(), tc.csc_x_over_s.get(), tc.g_co_tail.get(), tc.g_ptr.get(), tc.g_seg.get(), tc.g_w.get(),
-                                               tc.csc_rank.get(), P.csr_idx.get(), tc.g_start.get());
-        FY_KERNEL_CHECK();
-    }
-    FY_HIP(hipStreamSynchronize(st));       // d_co / d_sd go back to the allocator
-    for (size_t pi = 0; pi < np; pi++) {
-        SegTable& m = tc.segs[pi];
-        m.v_ptr = tc.g_ptr.get() + hsd[(size_t)main_of[pi]].cnt_off;
-        m.v_seg = tc.g_seg.get();
-        m.v_w = tc.g_w.get();
-        if (tail_of[pi] >= 0) {
-            SegTable& t = tc.segs_tail[pi];
-            t.v_ptr = tc.g_ptr.get() + hsd[(size_t)tail_of[pi]].cnt_off;
-            t.v_seg = tc.g_seg.get();
-            t.v_w = tc.g_w.get();
-        }
-    }
 }
 
 fy_rm2_job* fy::rm2_prepare(Context* ctx, const fy_rm2_params* prm, const fy_ratings* R, int64_t n_map, const int32_t* map_user,
@@ -2419,7 +1944,7 @@ static std::vector<int32_t> table_signature(const JobPlan& jp) {
     const std::vector<Plan>& plans = jp.plans;
     std::vector<int32_t> sig;
     sig.push_back(jp.use_pk ? 1 : 0);
-    sig.push_back(plans.size() > 1 && !jp.any_coop ? 1 : 0);
+    sig.push_back(1);      // (one layout over all planned clusters, whatever their number)
     for (auto& p : plans) {
         const int32_t v[8] = {p.c, p.CH, p.nch, p.half ? 1 : 0, p.panel ? 1 : 0, p.p_eff, p.tail_chunks, (p.coop ? 1 : 0) | (p.flat ? 2 : 0) | (p.psym ? 4 : 0) | (p.rect ? 8 : 0)};
         sig.insert(sig.end(), v, v + 8);
@@ -2427,56 +1952,18 @@ static std::vector<int32_t> table_signature(const JobPlan& jp) {
     return sig;
 }
 
-// One cluster's tables: packed CSR with chunk-relative indices for its CH, chunk offsets, segment table (+ the tail rows'
-// one-chunk table over the block-compressed CSR in panel mode).  `co` = scratch for p.Uc * (p.nch + 1) offsets.
-static void build_tables(fy_rm2_job* J, const JobPlan& jp, size_t pi, const std::vector<int32_t>& csr_range, hipStream_t ts, int32_t* co) {
-    Context* ctx = J->ctx;
-    const Prepared& P = J->P;
-    TableCache& tc = J->S->tables;
-    const bool use_pk = jp.use_pk;
-    const Plan& p = jp.plans[pi];
-    const int32_t f0 = csr_range[2 * pi], f1 = csr_range[2 * pi + 1];
-    if (use_pk && f1 > f0) {
-        k_pack_csr<<<grid_for(f1 - f0), 256, 0, ts>>>(f0, f1, p.CH, P.csr_idx.get(), P.csr_r.get(), tc.csr_pk.get());
-        FY_KERNEL_CHECK();
-    }
-    if (p.coop) return;
-    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), p.sbase, p.Uc, p.CH, p.nch, co, ts);
-    // (exact table sizes: round 2 sized the tables by upper bounds inside the lanes; the lanes build no tables any more)
-    build_segments(ctx, P.csc_slot.get(), use_pk ? tc.csc_x_over_s.get() : tc.csc_x.get(), co, p.sbase, p.q0, p.nq, p.nch, tc.segs[pi], ts,
-                   p.half ? tc.csc_rank.get() : nullptr, P.csr_idx.get(), p.CH, nullptr, 0, 0, p.half ? tc.samples.get() : nullptr, p.rect);
-    if (p.p_eff < p.Ic) {
-        k_tail_blocks<<<std::min<int>(p.Uc, ctx->num_cus * 16), 256, 0, ts>>>(p.sbase, p.Uc, p.p_eff, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(),
-                                                                  tc.y_pk.get(), co);
-        FY_KERNEL_CHECK();
-        build_segments(ctx, P.csc_slot.get(), tc.csc_x_over_s.get(), co, p.sbase, p.q0, p.nq, 1, tc.segs_tail[pi], ts, nullptr, nullptr, 0,
-                       tc.csc_rank.get(), p.p_eff, 0);
-    }
-}
-
 // Everything the row kernels of the plan need, on the main stream before the lanes fork; nothing when a job with the same signature
-// has left them (`tables_cached`).  Fills csr_range; `co_lane` keeps the chunk-offset scratch of build_tables alive.
-static void build_job_tables(fy_rm2_job* J, const JobPlan& jp, bool tables_cached, std::vector<int32_t>& csr_range, std::vector<DevBuf<int32_t>>& co_lane) {
+// has left them (`tables_cached`).  Fills csr_range.  The tables of ALL planned clusters are built in one pass over the CSR / CSC
+// (layout_tables, fy_rm2_tables.hpp): packed CSR and chunk offsets of every cluster, the tail rows' block-compressed CSR, and both
+// segment tables (main walk; tail-row bounds) of every cluster as ranges of ONE store -- one count launch per group, ONE scan, one
+// host round trip for the size, one fill.  A cooperative cluster gets its packed CSR here; its ranks build the tables of their own
+// rows (coop_build_rows).  (Building cluster by cluster cost a host round trip per table: 20 ms at 50 clusters.)
+static void build_job_tables(fy_rm2_job* J, const JobPlan& jp, bool tables_cached, std::vector<int32_t>& csr_range) {
     Context* ctx = J->ctx;
     const Prepared& P = J->P;
     hipStream_t st = ctx->stream;
     TableCache& tc = J->S->tables;
     const std::vector<Plan>& plans = jp.plans;
-    if (!tables_cached) {
-        tc.valid = false;
-        tc.segs.clear();
-        tc.segs_tail.clear();
-        tc.segs.resize(plans.size());
-        tc.segs_tail.resize(plans.size());
-        tc.csr_pk.alloc(ctx, jp.use_pk ? (size_t)P.nnz : 1);
-        tc.y_pk.alloc(ctx, jp.any_tail ? (size_t)P.nnz : 1);     // k_tail_blocks
-        tc.csc_rank.alloc(ctx, jp.any_half ? (size_t)P.nnz : 1);     // row (rank inside its cluster) of every CSC entry
-        if (jp.any_half) {
-            k_csc_rank<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.pair_rank.get(), tc.csc_rank.get());
-            FY_KERNEL_CHECK();
-            build_csr_samples(ctx, P.nnz, P.csr_idx.get(), tc.samples, st);
-        }
-    }
     // first / last CSR entry of every planned cluster (slots are cluster-major): one round trip for all of them
     csr_range.assign(2 * plans.size() + 2, 0);
     {
@@ -2487,20 +1974,46 @@ static void build_job_tables(fy_rm2_job* J, const JobPlan& jp, bool tables_cache
         }
         gather_to_host_i32(ctx, P.rowptr.get(), where, csr_range.data());
     }
-    // With several lanes and no cooperative cluster the tables are built by the lane that uses them, right before the row
-    // kernel: table building is mostly host round trips (sizes of the segment tables), 23 ms for 50 clusters during which the
-    // chip idled; in a lane they hide behind the other lanes' kernels.  (A cooperative job packs every cluster's CSR up front.)
-    // Several clusters and none of them cooperative: ONE table over all of them, built here on the main stream (build_tables_all).
-    // (Round 2 let every lane build its cluster's tables right before the row kernel, to hide their host round trips behind the
-    // other lanes: 20 ms of tables at 50 clusters.)
-    const bool all_at_once = plans.size() > 1 && !jp.any_coop;
-    co_lane.resize((size_t)jp.NS);
-    if (!all_at_once)
-        for (auto& b : co_lane) b.alloc(ctx, jp.co_all);
     if (tables_cached) return;
-    if (all_at_once) build_tables_all(ctx, P, plans, csr_range, jp.use_pk, tc, st);
-    else
-        for (size_t pi = 0; pi < plans.size(); pi++) build_tables(J, jp, pi, csr_range, st, co_lane[0].get());
+    tc.valid = false;
+    tc.csr_pk.alloc(ctx, jp.use_pk ? (size_t)P.nnz : 1);
+    tc.y_pk.alloc(ctx, jp.any_tail ? (size_t)P.nnz : 1);     // k_tail_blocks
+    tc.csc_rank.alloc(ctx, jp.any_half ? (size_t)P.nnz : 1);     // row (rank inside its cluster) of every CSC entry
+    if (jp.any_half) {      // (queued behind the round trip above and in front of the descriptors' upload, which hides behind them on the idle stream)
+        k_csc_rank<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.pair_rank.get(), tc.csc_rank.get());
+        FY_KERNEL_CHECK();
+        build_csr_samples(ctx, P.nnz, P.csr_idx.get(), tc.samples, st);
+    }
+    TableLayout L;
+    try {
+        L = layout_tables(plans, csr_range);
+    } catch (const PlanError& e) {
+        FY_FAIL(e.code, "%s", e.msg.c_str());
+    }
+    const size_t np = plans.size();
+    DevBuf<int32_t> co(ctx, (size_t)std::max<int64_t>(1, L.co_total)), co_tail(ctx, (size_t)std::max<int64_t>(1, L.co_tail_total));
+    tc.csr_descs = upload_csr_descs(ctx, L.csr, st);      // (kept with the tables: a job without a table of its own has no closing synchronisation)
+    const CsrDescs& cd = tc.csr_descs;
+    if (jp.use_pk) pack_csr(ctx, cd, P.csr_idx.get(), P.csr_r.get(), tc.csr_pk.get(), st);
+    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), co.get(), st);
+    if (L.co_tail_total > 0) {
+        int32_t max_slots = 1;
+        for (auto& d : L.csr) max_slots = std::max(max_slots, d.n_slots);
+        k_tail_blocks<<<dim3((unsigned)std::min<int>(max_slots, ctx->num_cus * (np == 1 ? 16 : 4)), (unsigned)np), 256, 0, st>>>(cd.d.get(), P.rowptr.get(), P.csr_idx.get(),
+                                                                                                                     P.csr_r.get(), tc.y_pk.get(), co_tail.get());
+        FY_KERNEL_CHECK();
+    }
+    // main tables read co, tail tables co_tail (their "chunk offsets" are the k_tail_blocks ranges): two groups of one build
+    const SegGroup groups[2] = {
+        {SegArrays{P.csc_slot.get(), jp.use_pk ? tc.csc_x_over_s.get() : tc.csc_x.get(), co.get(), tc.csc_rank.get(), tc.samples.get()}, L.seg.data(), L.n_main},
+        {SegArrays{P.csc_slot.get(), tc.csc_x_over_s.get(), co_tail.get(), tc.csc_rank.get(), tc.samples.get()}, L.seg.data() + L.n_main, L.seg.size() - L.n_main}};
+    build_segment_tables(ctx, groups, 2, tc.store, st);
+    tc.segs.assign(np, SegTable{});
+    tc.segs_tail.assign(np, SegTable{});
+    for (size_t pi = 0; pi < np; pi++) {
+        if (L.main_of[pi] >= 0) tc.segs[pi] = tc.store.view(L.seg[(size_t)L.main_of[pi]]);
+        if (L.tail_of[pi] >= 0) tc.segs_tail[pi] = tc.store.view(L.seg[(size_t)L.tail_of[pi]]);
+    }
 }
 
 // ---- 5. flat batch (Plan::flat): matrix build, scores and lists of all those clusters, one launch per kernel, on the main stream
@@ -3297,24 +2810,18 @@ static void score_clusters(const ScoreShared& X, std::vector<Lane>& lanes, Panel
 }
 
 // ---- 8. what the job says about itself: counters of the pruned passes, the tables, the bytes the row kernels stored
-static void fill_score_stats(const ScoreShared& X, bool tables_cached, const std::vector<int32_t>& sig) {
+static void fill_score_stats(const ScoreShared& X, const std::vector<int32_t>& sig) {
     fy_rm2_job* J = X.J;
     Context* ctx = X.J->ctx;
     fy_result* R = X.R;
     const JobPlan& jp = *X.jp;
     TableCache& tc = J->S->tables;
-    const bool all_at_once = jp.plans.size() > 1 && !jp.any_coop;
     unsigned long long hc[6];
     d2h(ctx, hc, X.prune_counters, 6);
     sync(ctx);
-    if (!tables_cached && !all_at_once) {        // (build_tables_all counts its one table itself)
-        tc.total_segments = 0;
-        for (auto& t : tc.segs) tc.total_segments += t.n_seg;
-        for (auto& t : tc.segs_tail) tc.total_segments += t.n_seg;
-    }
     tc.sig = sig;          // every table of the plan has been built and used: a later job with the same plan re-uses them
     tc.valid = true;
-    R->st.cooc_segments = tc.total_segments;
+    R->st.cooc_segments = tc.store.n_seg;
     for (auto& p : jp.plans) {       // what the row kernels store (the mirror pass and the column maxima are priced separately)
         const int64_t eb = p.pack24 ? 3 : 4;
         if (p.coop) continue;
@@ -3467,8 +2974,7 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
         R->st.tables_from_cache = tables_cached ? 1 : 0;
         span_tables = t_tables.begin();
         std::vector<int32_t> csr_range;
-        std::vector<DevBuf<int32_t>> co_lane;
-        build_job_tables(J, jp, tables_cached, csr_range, co_lane);
+        build_job_tables(J, jp, tables_cached, csr_range);
         t_tables.end(span_tables);
 
         const ScoreShared X{J, R.get(), &tune, &jp, A.b_rank32.get(), J->b_rank.get(), A.p_rank.get(), A.a_rank.get(),
@@ -3491,7 +2997,7 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
         // (the guard's destructor drains the lanes and the main stream before any buffer of this scope is released)
 
         // ---- 8. stats
-        fill_score_stats(X, tables_cached, sig);
+        fill_score_stats(X, sig);
     }
     // rm2/userSum and rm2/itemColl stay in HBM until somebody asks for them
     if (J->S->sharded) {

@@ -40,10 +40,11 @@ static void coop_build_rows(const ScoreShared& X, const Plan& p, hipStream_t ls,
     const int32_t Uc = p.Uc, sbase = p.sbase, pbase = p.pbase, Ic = p.Ic, CH = p.CH, nch = p.nch, nrows = Ic > r0 ? (Ic - r0 + W - 1) / W : 0;
     const int64_t ldm = p.ldm, ldb = p.ldb;
     DevBuf<int32_t> co_tmp(ctx, (size_t)Uc * (nch + 1));
-    SegTable seg;
+    SegStore seg;
     DevBuf<int2> item_seg(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * nch));
     DevBuf<int32_t> item_id(ctx, (size_t)std::max<int64_t>(1, (int64_t)nrows * nch)), item_counter(ctx, 1);
-    build_chunk_offsets(ctx, P.rowptr.get(), P.csr_idx.get(), sbase, Uc, CH, nch, co_tmp.get(), ls);
+    const CsrDescs cd = upload_csr_descs(ctx, {csr_desc(sbase, Uc, CH, nch)}, ls);
+    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), co_tmp.get(), ls);
     std::vector<int32_t> hls((size_t)nrows + 1, 0);
     for (int32_t i = 0; i < nrows; i++) hls[i + 1] = hls[i] + hcnt[r0 + (int64_t)i * W];
     DevBuf<int32_t> local_start(ctx, (size_t)nrows + 1), my_slot(ctx, (size_t)std::max<int64_t>(1, my_ratings));
@@ -54,13 +55,14 @@ static void coop_build_rows(const ScoreShared& X, const Plan& p, hipStream_t ls,
                                                                           local_start.get(), P.csc_slot.get(), X.csc_x, my_slot.get(), my_w.get());
         FY_KERNEL_CHECK();
     }
-    build_segments(ctx, my_slot.get(), my_w.get(), co_tmp.get(), sbase, 0, (int32_t)my_ratings, nch, seg, ls);
+    // (the segment table covers my rows' CSC entries alone, renumbered row by row: q0 = 0, nq = local entries)
+    const SegDesc sd = seg_desc(sbase, 0, (int32_t)my_ratings, nch);
+    build_segment_table(ctx, SegArrays{my_slot.get(), my_w.get(), co_tmp.get(), nullptr, nullptr}, sd, seg, ls);
     FY_HIP(hipMemsetAsync(Bloc, 0, (size_t)std::max<int64_t>(1, (int64_t)nrows * ldb) * 3, ls));
     k_block_amax<<<grid_for(ldb), 256, 0, ls>>>(Ic, (int32_t)ldb, X.a_rank + pbase, X.b_rank + pbase, amax, bmax);
     FY_KERNEL_CHECK();
     if (nrows > 0) {
-        // (the segment table covers my rows' CSC entries alone, renumbered row by row: q0 = 0, nq = local entries)
-        CoocArgs CA = cooc_args(P, seg, CoocGeometry{pbase, sbase, Ic, CH, nch, 0, (int32_t)my_ratings}, X.csr_x, X.csr_pk);
+        CoocArgs CA = cooc_args(P, seg.view(sd), CoocGeometry{pbase, sbase, Ic, CH, nch, 0, (int32_t)my_ratings}, X.csr_x, X.csr_pk);
         CA.row0 = r0; CA.nrows = nrows; CA.row_stride = W; CA.local_start = local_start.get();
         const int fxk = (X.csr_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) : -1;
         CA.fx_scale = fxk >= 0 ? std::ldexp(1.0, fxk) : 0.0;

@@ -233,7 +233,7 @@ struct JobPlan {
     int n_groups = 1;
     int NS = 0;                          // lanes
     bool any_coop = false, any_tail = false, any_half = false;
-    size_t co_all = 1;
+    size_t co_all = 1;                   // chunk offsets of the largest cluster (no reader in the library any more: the tables' layout is layout_tables'; pinned by the golden plans)
     // elements of the per-lane buffers
     size_t m_el = 1, s_el = 1, ov_el = 1, bm_el = 1, ub_el = 1, am_el = 1, gp_el = 1, b64_el = 1, a64_el = 1, is_el = 1;
 };
@@ -498,7 +498,7 @@ inline JobPlan plan_job(const PlanInput& in) {
         }
     }
     for (auto& p : plans) jp.any_coop = jp.any_coop || p.coop;
-    // (segment tables of the row kernel: which optional parts any cluster needs, and the chunk-offset scratch of the largest)
+    // (segment tables of the row kernel: which optional parts any cluster needs; their layout: fy_rm2_tables.hpp)
     for (auto& p : plans) {
         jp.any_tail = jp.any_tail || p.p_eff < p.Ic;
         jp.co_all = std::max(jp.co_all, (size_t)p.Uc * (p.nch + 1));

@@ -48,7 +48,6 @@ struct Tuning {
     int prune_min_users = 600;         // clusters with fewer users take the plain full pass
     int panel_wide_below_users = 2500; // panel mode: clusters with fewer users keep twice the panel columns
     int panel_cols = 4096;             // columns of a row kept in panel mode (the seed columns and the popular blocks)
-    bool bounded_tables = true;        // FY_BOUNDED_TABLES=0: exact table sizes (two host round trips per table)
     bool cooc_planes = true;           // FY_COOC_PLANES=0: linear accumulator layout (measurement only)
     int score_heavy = 512;             // users with more ratings are walked by a whole workgroup of the scoring kernel (0 = off)
     int score_walk = 1;                // FY_SCORE_WALK=0: the 24-bit scoring kernels walk every batch the first way (v_readlane triplets, a mask test per row); same bits, measurement and parity tests only

@@ -149,6 +149,50 @@ def test_collectives_installed_but_clusters_stay_local(forced):
     assert_topn_matches(rows, ref, 20)
 
 
+def test_cooperative_boundary_cluster_beside_panel_clusters(forced, monkeypatch):
+    """One job with BOTH kinds of cluster on a rank.  With at least as many non-empty clusters as ranks every rank owns whole clusters
+    (rank_slot_range) and nothing is cooperative, so the mix needs FEWER clusters than ranks: MovieLens-100K shape on 4 ranks in 3
+    clusters, 80 % of the users in the last one.  The ranks then own equal shares of the work: rank 0 holds the two small clusters
+    whole plus the head of the big one, which spans all four ranks and is scored cooperatively.  The small clusters are pruned
+    (FY_PRUNE_MIN_USERS below their ~95 users) and, two being FY_PANEL_MIN_CLUSTERS here, take two-phase panel mode; chunks and panel
+    forced to 256 columns make the rows behind the panel tail rows, and clusters that are whole on their rank take the symmetric
+    panel.  The tables of rank 0 hold a cooperative cluster's packed-CSR range beside cut and chunk-limited panel tables; the rows
+    are the oracle's and those of the same job with the branch and bound off."""
+    from util import skewed_clustering
+    monkeypatch.setenv("FY_PRUNE_MIN_USERS", "50")
+    monkeypatch.setenv("FY_PANEL_MIN_CLUSTERS", "2")
+    monkeypatch.setenv("FY_PANEL_COLS", "256")
+    monkeypatch.setenv("FY_COOC_MAX_CH", "256")
+    P, S = pkg(), synth()
+    u, i, s, facts = S.generate("ml100k")
+    data = (u.numpy(), i.numpy(), s.numpy())
+    uu = np.unique(data[0])
+    world, K, top_n = 4, 3, 20
+    clustering = (uu, skewed_clustering(uu, K, big_at=K - 1, big_share=0.8))
+    ref = oracle.rm2(*data, lam=0.1, number_of_items=facts["n_items"], number_of_recommendations=1 << 30, number_of_clusters=K,
+                     map_user=clustering[0], map_cluster=clustering[1], n_threads=8)
+    conf = P.Configuration()
+    conf.set("lambda", "0.1")
+    conf.setInt("numberOfItems", facts["n_items"])
+    conf.setInt("numberOfClusters", K)
+    conf.setInt("numberOfRecommendations", top_n)
+    out, comms = run_threads(world, data, clustering, conf)
+    rows = {k: np.concatenate([o[0][k] for o in out]) for k in ("user", "item", "score", "cluster")}
+    print("   per rank: panel_clusters %s, blocks_total %s, cooc_segments %s, collectives %s"
+          % ([o[1]["panel_clusters"] for o in out], [o[1]["blocks_total"] for o in out], [o[1]["cooc_segments"] for o in out], [dict(c.calls) for c in comms]))
+    assert any(o[1]["panel_clusters"] > 0 for o in out), "no rank took panel mode"
+    assert all(c.calls["reduce_scatter_f32"] >= 2 for c in comms), "no cluster was scored cooperatively"
+    assert_topn_matches(rows, ref, top_n)
+    monkeypatch.setenv("FY_PRUNE", "0")
+    full_out, _ = run_threads(world, data, clustering, conf)
+    assert all(o[1]["panel_clusters"] == 0 and o[1]["blocks_total"] == 0 for o in full_out)
+    full = {k: np.concatenate([o[0][k] for o in full_out]) for k in ("user", "item", "score", "cluster")}
+    from fullsize_checks import assert_same_lists
+    from util import ATOL
+    n_diff, worst = assert_same_lists(rows, full, score_rtol=1e-5, score_atol=ATOL)
+    assert n_diff <= 4, n_diff
+
+
 def test_failing_collective_fails_the_job(forced):
     P = pkg()
     data, clustering, conf, _ = make("tiny", 1)
