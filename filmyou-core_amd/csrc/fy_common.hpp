@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -205,6 +206,40 @@ struct SyncOnUnwind {
         if (std::uncaught_exceptions() > n0) (void)hipStreamSynchronize(st);
     }
 };
+
+// ---------------------------------------------------------------- launch grids and the device helpers every translation unit uses
+// workgroups of a grid-stride launch over n elements
+inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
+    int64_t g = ceil_div(n, block);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
+}
+
+// 32-bit key that orders like the float (any sign, -0 < +0), and its inverse
+__device__ __forceinline__ uint32_t fy_order_key(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float fy_order_unkey(uint32_t k) {
+    const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+    return __uint_as_float(b);
+}
+
+// descending bitonic sort of P2 (power of two) 64-bit keys in LDS; every thread of the block calls it
+__device__ __forceinline__ void fy_bitonic_desc(uint64_t* v, int P2) {
+    for (int k = 2; k <= P2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < P2; i += blockDim.x) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const uint64_t x = v[i], y = v[l];
+                    const bool desc = (i & k) == 0;
+                    if (desc ? (x < y) : (x > y)) { v[i] = y; v[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
 
 }  // namespace fy
 

@@ -29,11 +29,6 @@
 
 namespace fy {
 
-static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 // similarity rows (grouped by item) -> per-column row start / length, entries re-expressed as columns
 __global__ void k_icf_index_sims(int64_t n, const int32_t* __restrict__ s_item, const int32_t* __restrict__ s_other,
                                  const int32_t* __restrict__ iid, int32_t nI, const int32_t* __restrict__ pair_rank,

@@ -23,10 +23,6 @@
 namespace fy {
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, block), cap));
-}
-
 // requested raw user id -> (slot << 32 | dense index), or all ones for an id nobody has
 __global__ void k_icfr_find_users(int64_t n, const int32_t* __restrict__ ids, const int32_t* __restrict__ uid, int32_t nU,
                                   const int32_t* __restrict__ du2slot, uint64_t* __restrict__ found) {

@@ -7,11 +7,12 @@
 //   cosine        sim(i, j) = sum_u (r_ui / |r_.i|) (r_uj / |r_.j|)      (rows L2-normalised, then dot products)
 //   co-occurrence sim(i, j) = #users who rated both
 // and the five other measures of Mahout 0.8's RowSimilarityJob (include/filmyou.h has the table): each is a dot product d of
-// per-item transformed columns, then a scalar function of (d, a_i, a_j, number of users) -- the isim_finish_* functions below,
-// fp64, shared by every kernel that turns an accumulator into a similarity.
+// per-item transformed columns, then a scalar function of (d, a_i, a_j, number of users) -- the isim_finish_* functions of
+// fy_itemsim_kernels.hpp, fp64, shared by every kernel that turns an accumulator into a similarity.  What a measure is (weight, norm,
+// finish, kernel template) is the table isim_measure of fy_itemsim_plan.hpp; nothing here compares a measure id with a constant.
 // Over co-rated pairs only, j != i when excludeSelfSimilarity, sim >= threshold (no threshold: sim > 0), the
 // maxSimilaritiesPerRow best per item (ties, unspecified in Mahout, by ascending item id).
-// Two builds:
+// Two builds; isim_route (fy_itemsim_plan.hpp, a pure host function with a CPU test) says which one a job takes:
 //  * symmetric (round 3; cosine on positive fp16-exact ratings, one rank, the benchmark sizes): the product is symmetric, so
 //    only its upper triangle is accumulated -- by the RM2 row kernel itself (fy_rm2.hip: gram_half_build: symmetric walk,
 //    fixed-point ds_add_u64, half the pair visits) into an fp32 matrix in HBM -- and k_isim_sweep streams every element ONCE
@@ -19,6 +20,9 @@
 //    it is read down the column, 64 rows (= 256-byte row segments) at a time.  No mirror pass.
 //  * row at a time (every other configuration): a workgroup owns item row i, accumulates it chunk by chunk in LDS (fp64) and
 //    keeps a running top-K in LDS; no I x I matrix is written, only I x K rows leave the chip.
+// Host flow of itemsim_build: isim_front (checks, input preparation, structure, norms -- shared with itemsim_prepare), the route,
+// itemsim_symmetric or itemsim_row_at_a_time, k_isim_compact, statistics.  The prepared job of the request pass
+// (fy_itemsim_request.hip) is built at the end of this file from the same front.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -31,11 +35,6 @@
 #include "fy_rm2.hpp"
 
 namespace fy {
-
-static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
 
 // one WORKGROUP per item (pair): L2 norm of the item's rating column in a fixed summation order (thread-strided partial sums, wave
 // shuffles, the four waves' partials in order), and -- round 4 -- the column's rating sum and largest rating in the same pass (the
@@ -99,34 +98,31 @@ __global__ __launch_bounds__(256) void k_item_norms(int32_t nP, const int32_t* _
     }
 }
 
-// ---- the measures (include/filmyou.h): weight of a preference, and similarity from the dot product d of two weighted columns
-// cosine and Euclidean distance multiply the ratings themselves, the count measures ones
-__host__ __device__ inline bool isim_weight_is_rating(int measure) { return measure == FY_SIMILARITY_COSINE || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE; }
-// weight where nothing is applied in the epilogue.  norm: cosine ||r_.i||, Pearson ||c_.i||; centre: Pearson (sum |r|) / n (else unused)
-__device__ __forceinline__ float isim_weight(int measure, float r, double norm, double centre) {
-    switch (measure) {
-        case FY_SIMILARITY_COSINE: return (float)((double)r / norm);
-        case FY_SIMILARITY_EUCLIDEAN_DISTANCE: return r;
-        case FY_SIMILARITY_PEARSON_CORRELATION: return (float)(((double)r - centre) / norm);       // 0 / 0 = NaN for a constant item: its pairs drop out
+// ---- the weight of a preference (fy_itemsim_plan.hpp: IsimMeasure) where nothing is applied in the epilogue: the 8-byte walk.
+// norm: cosine ||r_.i||, Pearson ||c_.i||; centre: Pearson (sum |r|) / n (else unused)
+__device__ __forceinline__ float isim_weight(const IsimMeasure& m, float r, double norm, double centre) {
+    switch (m.weight) {
+        case ISIM_W_RATING: return m.inv_norm ? (float)((double)r / norm) : r;
+        case ISIM_W_PEARSON: return (float)(((double)r - centre) / norm);       // 0 / 0 = NaN for a constant item: its pairs drop out
         default: return 1.0f;
     }
 }
 __global__ void k_csc_weights(int64_t nnz, const int32_t* __restrict__ csc_pair, const float* __restrict__ csc_r,
                               const double* __restrict__ norm, const double* __restrict__ centre, int measure, float* __restrict__ csc_w) {
-    const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    const IsimMeasure m = isim_measure(measure);
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x) {
         const int32_t p = csc_pair[q];
-        csc_w[q] = isim_weight(measure, csc_r[q], norm[p], pearson ? centre[p] : 0.0);
+        csc_w[q] = isim_weight(m, csc_r[q], norm[p], m.weight == ISIM_W_PEARSON ? centre[p] : 0.0);
     }
 }
 
 __global__ void k_csr_weights(int64_t nnz, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r,
                               const int32_t* __restrict__ rank_pair, const double* __restrict__ norm, const double* __restrict__ centre, int measure,
                               float* __restrict__ csr_w) {
-    const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
+    const IsimMeasure m = isim_measure(measure);
     for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < nnz; f += (int64_t)gridDim.x * blockDim.x) {
         const int32_t p = rank_pair[csr_idx[f]];
-        csr_w[f] = isim_weight(measure, csr_r[f], norm[p], pearson ? centre[p] : 0.0);
+        csr_w[f] = isim_weight(m, csr_r[f], norm[p], m.weight == ISIM_W_PEARSON ? centre[p] : 0.0);
     }
 }
 
@@ -158,7 +154,7 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
         const int ch_begin = split ? item - mine * A.nch : 0, ch_end = split ? ch_begin + 1 : A.nch;
         const int slot = mine * A.nch + ch_begin;     // where this item's list goes
         const int row = A.row0 + mine * stride;
-        const double scale_row = M != FY_SIMILARITY_COSINE ? E.aux[row] : E.inv_norm ? E.inv_norm[row] : 1.0;
+        const double scale_row = isim_row_scale<M>(E, row);
         for (int ch = ch_begin; ch < ch_end; ch++) {
             cooc_accumulate_row<PK>(A, row, ch, mine);
             __syncthreads();
@@ -181,12 +177,9 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
 #pragma unroll
                     for (int x = 0; x < ISIM_SAMPLE / 64; x++) {
                         const int t = (int)(((int64_t)(tid * (ISIM_SAMPLE / 64) + x) * ncol) / ISIM_SAMPLE);
-                        const int col = c0 + t;
-                        const double a = acc[t];
-                        const float sv = isim_row_value<M>(E, a, scale_row, col);
-                        bool ok = E.has_threshold ? (sv >= E.threshold) : (sv > 0.0f);
-                        if (E.exclude_self && col == row) ok = false;
-                        k4[x] = ok ? isim_order_key(sv) : 0u;
+                        uint32_t key;
+                        const bool ok = isim_candidate<M>(E, acc[t], scale_row, row, c0 + t, key);
+                        k4[x] = ok ? key : 0u;
                     }
                     uint32_t best = 0;
                     for (int r = 0; r < ISIM_SAMPLE_RANK; r++) {
@@ -212,12 +205,9 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
                 if (guess != 0) {   // block-uniform
                     int mine_cnt = 0;
                     for (int t = tid; t < ncol; t += blockDim.x) {
-                        const int col = c0 + t;
-                        const double a = acc[t];
-                        const float sv = isim_row_value<M>(E, a, scale_row, col);
-                        bool ok = E.has_threshold ? (sv >= E.threshold) : (sv > 0.0f);
-                        if (E.exclude_self && col == row) ok = false;
-                        mine_cnt += ok && isim_order_key(sv) >= guess;
+                        uint32_t key;
+                        const bool ok = isim_candidate<M>(E, acc[t], scale_row, row, c0 + t, key);
+                        mine_cnt += ok && key >= guess;
                     }
                     for (int o = 32; o > 0; o >>= 1) mine_cnt += __shfl_down(mine_cnt, o, 64);
                     if ((tid & 63) == 0 && mine_cnt) atomicAdd(&sh_aux[1], (uint32_t)mine_cnt);
@@ -233,28 +223,14 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
                     bool want = false;
                     uint64_t c = 0;
                     if (t < ncol) {
-                        const double a = acc[t];
                         const int col = c0 + t;
-                        const float s = isim_row_value<M>(E, a, scale_row, col);
-                        bool ok = E.has_threshold ? (s >= E.threshold) : (s > 0.0f);
-                        if (E.exclude_self && col == row) ok = false;
-                        const uint32_t key = isim_order_key(s);
+                        uint32_t key;
+                        const bool ok = isim_candidate<M>(E, acc[t], scale_row, row, col, key);
                         want = ok && key >= (stepwise ? sh_tau : tau);
-                        if (want) c = ((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - E.rank_item_raw[col]);
+                        if (want) c = isim_composite(key, E.rank_item_raw[col]);
                         else acc[t] = 0.0;
                     }
-                    // one LDS atomic per wave
-                    const unsigned long long bal = __ballot(want);
-                    if (bal) {
-                        const int lane = tid & 63;
-                        uint32_t at = 0;
-                        if (lane == __ffsll((long long)bal) - 1) at = atomicAdd(&sh_cnt, (uint32_t)__popcll(bal));
-                        at = __shfl(at, __ffsll((long long)bal) - 1, 64);
-                        if (want) {
-                            const uint32_t pos = at + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                            if (pos < (uint32_t)E.cap) { cand[pos] = c; acc[t] = 0.0; }
-                        }
-                    }
+                    if (isim_append<true>(cand, &sh_cnt, (uint32_t)E.cap, want, c)) acc[t] = 0.0;
                     if (stepwise) {
                         __syncthreads();
                         if (sh_cnt + blockDim.x > (uint32_t)E.cap) isim_cut(cand, E.K, E.cap, hist, &sh_cnt, &sh_tau, sh_aux);
@@ -271,14 +247,7 @@ __global__ void k_cooc_itemsim(CoocArgs A, ISimEpilogue E, int* __restrict__ nex
                 }
             }
         }
-        isim_select(cand, (int)sh_cnt, E.K, hist, &sh_cnt, &sh_tau, sh_aux);   // then only ~K entries are left to sort
-        const int n = (int)sh_cnt;
-        int P2 = 1;
-        while (P2 < n) P2 <<= 1;
-        for (int i = n + tid; i < P2; i += blockDim.x) cand[i] = 0ull;
-        __syncthreads();
-        isim_sort_desc(cand, P2);
-        const int keep = min(n, E.K);
+        const int keep = isim_finish_list(cand, E.K, hist, &sh_cnt, &sh_tau, sh_aux);
         if (tid == 0) E.part_cnt[slot] = keep;
         for (int i = tid; i < keep; i += blockDim.x) E.part[(int64_t)slot * E.K + i] = cand[i];
         __syncthreads();   // everybody is done with sh_cnt / cand before the next item resets them
@@ -313,7 +282,7 @@ struct SweepArgs {
     const int32_t* __restrict__ rank_item_raw;
     uint32_t* __restrict__ tau_g;              // [Ic]: key a candidate of the row must reach
     int32_t* __restrict__ gcnt;                // [Ic]: candidates appended
-    uint64_t* __restrict__ glist;              // [Ic][capg]: key << 32 | (0x7FFFFFFF - raw item id)
+    uint64_t* __restrict__ glist;              // [Ic][capg]: isim_composite of the positive key
     int32_t capg;
     int32_t* __restrict__ overflow;            // [Ic]
     uint32_t* __restrict__ hist_g;             // [Ic][64]: the row's candidates by key bucket (all pieces of the band add to it)
@@ -352,13 +321,13 @@ __device__ __forceinline__ void sweep_take(const SweepArgs& A, uint32_t* tau_l, 
     bool trig = false;
     if (pass) {
         const float sf = sweep_value<M>(A, v, i, col);
-        const uint32_t key = __float_as_uint(sf);
+        const uint32_t key = isim_positive_key(sf);
         if (sf > 0.0f && key >= tau_l[rl]) {
             int bk = (int)(key >> SWEEP_KEY_SHIFT) - SWEEP_KEY_BASE;
             bk = bk < 0 ? 0 : (bk > 63 ? 63 : bk);
             atomicAdd(&A.hist_g[(int64_t)i * 64 + bk], 1u);
             const int pos = atomicAdd(&A.gcnt[i], 1);
-            if (pos < A.capg) A.glist[(int64_t)i * A.capg + pos] = ((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - A.rank_item_raw[col]);
+            if (pos < A.capg) A.glist[(int64_t)i * A.capg + pos] = isim_composite(key, A.rank_item_raw[col]);
             else A.overflow[i] = 1;
             trig = pos + 1 >= A.K && ((pos + 1) & 7) == 0;
         }
@@ -520,8 +489,8 @@ __device__ __forceinline__ uint64_t isim_self_candidate(const SweepArgs& A, int 
         const double a = A.invn[i];      // the item's dot product with itself is its own norm (number of raters; sum r^2)
         sf = (float)isim_finish<M>(a, a, a, A.n_cols);
     }
-    const uint32_t key = __float_as_uint(sf);
-    return (sf > 0.0f && key >= A.tau0) ? (((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - A.rank_item_raw[i])) : 0ull;
+    const uint32_t key = isim_positive_key(sf);
+    return (sf > 0.0f && key >= A.tau0) ? isim_composite(key, A.rank_item_raw[i]) : 0ull;
 }
 
 // One WAVE per row: the K best of the row's candidate list (a few hundred entries of 8 bytes, L2-resident), sorted by
@@ -531,6 +500,7 @@ __device__ __forceinline__ uint64_t isim_self_candidate(const SweepArgs& A, int 
 // input).  No workgroup barrier anywhere: 59 047 workgroups with ~40 barriers each were 2.0 ms, this is one pass of waves.
 // Rows whose list overflowed in the sweep are handed to k_isim_redo.
 constexpr int FIN_SURV = 512, FIN_SMALL = 128;
+static_assert(FIN_SURV == ISIM_PLAN_FIN_SURV, "fy_itemsim_plan.hpp routes by the list length k_isim_finish can sort");
 template <int M>
 __global__ __launch_bounds__(256) void k_isim_finish(SweepArgs A, int32_t* __restrict__ redo_list, int32_t* __restrict__ n_redo) {
     __shared__ uint64_t surv_all[4][FIN_SURV];
@@ -627,8 +597,8 @@ __global__ __launch_bounds__(256) void k_isim_finish(SweepArgs A, int32_t* __res
     if (lane == 0) A.out_cnt[i] = keep;
     for (int t = lane; t < keep; t += 64) {
         const uint64_t c = surv[t];
-        A.out_other[(int64_t)i * A.K + t] = 0x7FFFFFFF - (int32_t)(uint32_t)c;
-        A.out_sim[(int64_t)i * A.K + t] = __uint_as_float((uint32_t)(c >> 32));
+        A.out_other[(int64_t)i * A.K + t] = isim_composite_item(c);
+        A.out_sim[(int64_t)i * A.K + t] = isim_composite_sim_positive(c);
     }
 }
 
@@ -651,37 +621,23 @@ __global__ __launch_bounds__(256) void k_isim_redo(SweepArgs A, const int32_t* _
             if (col < A.Ic && col != i) {
                 const float v = col > i ? A.G[(int64_t)i * A.ldm + col] : A.G[(int64_t)col * A.ldm + i];
                 const float sf = sweep_value<M>(A, v, i, col);
-                const uint32_t key = __float_as_uint(sf);
+                const uint32_t key = isim_positive_key(sf);
                 want = sf > 0.0f && key >= sh_tau;
-                c = ((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - A.rank_item_raw[col]);
+                c = isim_composite(key, A.rank_item_raw[col]);
             }
-            const unsigned long long bal = __ballot(want);
-            if (bal) {
-                const int lane = tid & 63;
-                uint32_t at = 0;
-                if (lane == __ffsll((long long)bal) - 1) at = atomicAdd(&sh_cnt, (uint32_t)__popcll(bal));
-                at = __shfl(at, __ffsll((long long)bal) - 1, 64);
-                if (want) cand[at + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = c;
-            }
+            isim_append<false>(cand, &sh_cnt, 0, want, c);
             __syncthreads();
             if (sh_cnt + 256 + 1 > (uint32_t)ISIM_CAP) isim_cut(cand, A.K, ISIM_CAP, hist, &sh_cnt, &sh_tau, sh_aux);   // block-uniform (+ 1: the diagonal)
         }
         const uint64_t c_self = isim_self_candidate<M>(A, i);
         if (c_self && tid == 0) cand[sh_cnt++] = c_self;
         __syncthreads();
-        isim_select(cand, (int)sh_cnt, A.K, hist, &sh_cnt, &sh_tau, sh_aux);
-        const int n = (int)sh_cnt;
-        int P2 = 1;
-        while (P2 < n) P2 <<= 1;
-        for (int t = n + tid; t < P2; t += 256) cand[t] = 0ull;
-        __syncthreads();
-        isim_sort_desc(cand, P2);
-        const int keep = min(n, A.K);
+        const int keep = isim_finish_list(cand, A.K, hist, &sh_cnt, &sh_tau, sh_aux);
         if (tid == 0) A.out_cnt[i] = keep;
         for (int t = tid; t < keep; t += 256) {
             const uint64_t c = cand[t];
-            A.out_other[(int64_t)i * A.K + t] = 0x7FFFFFFF - (int32_t)(uint32_t)c;
-            A.out_sim[(int64_t)i * A.K + t] = __uint_as_float((uint32_t)(c >> 32));
+            A.out_other[(int64_t)i * A.K + t] = isim_composite_item(c);
+            A.out_sim[(int64_t)i * A.K + t] = isim_composite_sim_positive(c);
         }
         __syncthreads();     // everybody is done with cand / sh_cnt before the next row resets them
     }
@@ -739,44 +695,34 @@ __global__ void k_fill_u32(int64_t n, uint32_t v, uint32_t* __restrict__ out) {
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) out[t] = v;
 }
 
-// the symmetric build; false = not applicable here (the caller runs the row-at-a-time build).  cnt / other / sim as the other build leaves them.
-template <int M>
-static void launch_isim_sweep(Context* ctx, const SweepArgs& SA, int npieces, int32_t* redo_list, int32_t* n_redo) {
-    hipStream_t st = ctx->stream;
-    k_isim_sweep<M><<<SA.nbands * npieces, 256, (size_t)(SA.piece + 256 + 64) * sizeof(float), st>>>(SA);
-    FY_KERNEL_CHECK();
-    k_isim_finish<M><<<(int)ceil_div(SA.Ic, 4), 256, 0, st>>>(SA, redo_list, n_redo);
-    FY_KERNEL_CHECK();
-    k_isim_redo<M><<<ctx->num_cus * 2, 256, 0, st>>>(SA, redo_list, n_redo);
-    FY_KERNEL_CHECK();
-}
-// aux: a_i of the finishing measures in rank order (nullptr for cosine)
-static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const Prepared& P, const double* norm, const float* colsum, const float* colmax,
-                              const double* aux, int32_t* cnt, int32_t* other, float* sim, double* ms_cooc, fy_stats* st_out) {
+// the per-item arrays of a job (isim_front fills them): pair order, aux / inv_norm rank order
+struct IsimItems {
+    DevBuf<double> norm;                 // ||r_.i||
+    DevBuf<double> sumsq;                // sum r^2 (Euclidean distance)
+    DevBuf<double> centre, cnorm;        // Pearson: (sum |r|) / n and ||r - centre||
+    DevBuf<float> colsum, colmax;        // full build: the bounds of the symmetric build's fixed-point scale
+    DevBuf<double> aux;                  // a_i of the finishing measures
+    DevBuf<double> inv_norm;             // 1 / ||r_.i|| (request: filled by the front; full build: by its packed walk)
+};
+
+// The symmetric build of a job that isim_route (fy_itemsim_plan.hpp) sent here.  false = gram_half_build declined (fixed-point
+// scale, chunk count): the caller runs the row-at-a-time build.  cnt / other / sim as the other build leaves them.
+static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const Prepared& P, const IsimItems& N, int32_t* cnt, int32_t* other, float* sim,
+                              double* ms_cooc, fy_stats* st_out) {
     const Tuning& tune = ctx->tune;
     const int32_t Ic = P.nP, K = prm->max_similarities_per_item;
-    const int measure = prm->similarity;
-    const bool cosine = measure == FY_SIMILARITY_COSINE;
-    // the count measures multiply ones: the fixed-point sums are exact integers whatever the ratings are
-    const bool counts = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD || measure == FY_SIMILARITY_CITY_BLOCK;
-    if (!cosine && !counts && measure != FY_SIMILARITY_EUCLIDEAN_DISTANCE) return false;      // co-occurrence, Pearson: row at a time
-    if (tune.isim_gram == 0 || prm->world != 1 || !tune.cooc_pk || (!counts && (!P.ratings_fp16_exact || !P.ratings_positive)) ||
-        K > FIN_SURV / 2 || (prm->has_threshold && !(prm->threshold > 0.0)))
-        return false;
-    // cosine takes this build from isim_gram_min_items items on.  The other measures take it only when it is forced
-    // (FY_ISIM_GRAM=1): their sweep has not been shown faster than their row-at-a-time build.
-    if (tune.isim_gram < 0 && (!cosine || Ic < tune.isim_gram_min_items)) return false;
+    const bool cosine = prm->similarity == FY_SIMILARITY_COSINE, counts = isim_measure(prm->similarity).counts;
+    const double* aux = N.aux.get();
     const int64_t ldm = round_up(Ic, 256), slack = 1024;
-    if ((uint64_t)Ic * (uint64_t)ldm * 4 > ctx->total_mem / 3) return false;     // the fp32 matrix must fit comfortably
     hipStream_t st = ctx->stream;
     DevBuf<double> invn(ctx, (size_t)Ic);
     DevBuf<float> invn32(ctx, (size_t)(ldm + slack));
     DevBuf<uint32_t> d_bounds(ctx, 2);
     d_bounds.zero();
     if (cosine)
-        k_isim_gram_prep<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), colsum, colmax, norm, invn.get(), invn32.get(), d_bounds.get());
+        k_isim_gram_prep<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), N.colsum.get(), N.colmax.get(), N.norm.get(), invn.get(), invn32.get(), d_bounds.get());
     else
-        k_isim_gram_prep_aux<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), colsum, colmax, aux, counts ? 1 : 0, invn32.get(), d_bounds.get());
+        k_isim_gram_prep_aux<<<grid_for(ldm + slack, 256, 256), 256, 0, st>>>(Ic, ldm + slack, P.rank_pair.get(), N.colsum.get(), N.colmax.get(), aux, counts ? 1 : 0, invn32.get(), d_bounds.get());
     FY_KERNEL_CHECK();
     uint32_t hb[2];
     d2h(ctx, hb, d_bounds.get(), 2);
@@ -816,13 +762,14 @@ static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const 
     const int npieces = (int)ceil_div(Ic, SA.piece);
     DevBuf<int32_t> redo_list(ctx, (size_t)Ic), n_redo(ctx, 1);
     n_redo.zero();
-    switch (measure) {
-        case FY_SIMILARITY_TANIMOTO_COEFFICIENT: launch_isim_sweep<FY_SIMILARITY_TANIMOTO_COEFFICIENT>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
-        case FY_SIMILARITY_LOGLIKELIHOOD: launch_isim_sweep<FY_SIMILARITY_LOGLIKELIHOOD>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
-        case FY_SIMILARITY_CITY_BLOCK: launch_isim_sweep<FY_SIMILARITY_CITY_BLOCK>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
-        case FY_SIMILARITY_EUCLIDEAN_DISTANCE: launch_isim_sweep<FY_SIMILARITY_EUCLIDEAN_DISTANCE>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
-        default: launch_isim_sweep<FY_SIMILARITY_COSINE>(ctx, SA, npieces, redo_list.get(), n_redo.get()); break;
-    }
+    isim_dispatch(prm->similarity, [&](auto M) {
+        k_isim_sweep<decltype(M)::value><<<SA.nbands * npieces, 256, (size_t)(SA.piece + 256 + 64) * sizeof(float), st>>>(SA);
+        FY_KERNEL_CHECK();
+        k_isim_finish<decltype(M)::value><<<(int)ceil_div(SA.Ic, 4), 256, 0, st>>>(SA, redo_list.get(), n_redo.get());
+        FY_KERNEL_CHECK();
+        k_isim_redo<decltype(M)::value><<<ctx->num_cus * 2, 256, 0, st>>>(SA, redo_list.get(), n_redo.get());
+        FY_KERNEL_CHECK();
+    });
     t_all.end(sp);
     DevBuf<unsigned long long> d_cands(ctx, 1);
     d_cands.zero();
@@ -843,12 +790,12 @@ static bool itemsim_symmetric(Context* ctx, const fy_itemsim_params* prm, const 
 // packed CSR (fy_cooc.hpp): column index relative to its chunk | the raw rating (or 1 for the co-occurrence count) as fp16
 __global__ void k_isim_pack_csr(int64_t nnz, int32_t CH, const int32_t* __restrict__ csr_idx, const float* __restrict__ csr_r, int measure,
                                 uint32_t* __restrict__ pk) {
-    const bool rating = isim_weight_is_rating(measure);
+    const bool rating = isim_measure(measure).weight == ISIM_W_RATING;
     for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < nnz; f += (int64_t)gridDim.x * blockDim.x)
         pk[f] = (uint32_t)(csr_idx[f] % CH) | ((uint32_t)__half_as_ushort(__float2half(rating ? csr_r[f] : 1.0f)) << 16);
 }
 __global__ void k_isim_raw_weights(int64_t nnz, const float* __restrict__ csc_r, int measure, float* __restrict__ csc_w) {
-    const bool rating = isim_weight_is_rating(measure);
+    const bool rating = isim_measure(measure).weight == ISIM_W_RATING;
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x)
         csc_w[q] = rating ? csc_r[q] : 1.0f;
 }
@@ -864,40 +811,11 @@ __global__ void k_isim_rank_norms(int32_t Ic, const int32_t* __restrict__ rank_p
         aux[r] = sumsq ? sumsq[pr] : (double)(pair_start[pr + 1] - pair_start[pr]);
     }
 }
-template <int M>
-static void launch_cooc_itemsim(bool pk, int grid, int block, size_t lds, hipStream_t st, const CoocArgs& CA, const ISimEpilogue& IE, int* next_row) {
-    if (pk) {
-        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_itemsim<true, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_cooc_itemsim<true, M><<<grid, block, lds, st>>>(CA, IE, next_row);
-    } else {
-        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cooc_itemsim<false, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_cooc_itemsim<false, M><<<grid, block, lds, st>>>(CA, IE, next_row);
-    }
-    FY_KERNEL_CHECK();
-}
-
 __global__ void k_isim_count_heavy(int32_t rows_mine, int32_t rank, int32_t world, const int32_t* __restrict__ rank_pair,
                                    const int32_t* __restrict__ pair_start, int32_t heavy, int32_t* __restrict__ n_heavy) {
     for (int32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < rows_mine; m += gridDim.x * blockDim.x) {
         const int32_t pr = rank_pair[rank + m * world];
         if (pair_start[pr + 1] - pair_start[pr] > heavy) atomicAdd(n_heavy, 1);
-    }
-}
-
-__global__ void k_isim_compact(int32_t rows_mine, int32_t K, int32_t rank, int32_t world, const int32_t* __restrict__ cnt,
-                               const int32_t* __restrict__ off, const int32_t* __restrict__ other, const float* __restrict__ sim,
-                               const int32_t* __restrict__ rank_item_raw, int32_t* __restrict__ o_item,
-                               int32_t* __restrict__ o_other, float* __restrict__ o_sim, int32_t* __restrict__ o_aux) {
-    const int wpb = blockDim.x >> 6, lane = threadIdx.x & 63;
-    for (int32_t m = blockIdx.x * wpb + (threadIdx.x >> 6); m < rows_mine; m += gridDim.x * wpb) {
-        const int32_t item = rank_item_raw[rank + m * world];
-        for (int i = lane; i < cnt[m]; i += 64) {
-            const int64_t o = (int64_t)off[m] + i;
-            o_item[o] = item;
-            o_other[o] = other[(int64_t)m * K + i];
-            o_sim[o] = sim[(int64_t)m * K + i];
-            o_aux[o] = 0;
-        }
     }
 }
 
@@ -975,181 +893,198 @@ static std::unique_ptr<fy_ratings> filter_user_prefs(Context* ctx, const fy_rati
     return F;
 }
 
-// what both entry points (the full build, the prepared job) refuse, in the order the full build has always checked it: the input
-// preparation's options before the preparation runs, the rest behind it
-static void isim_check_prefs(const fy_itemsim_params* prm) {
+// The front of both entry points: the checks in the order the full build has always made them (the input preparation's options
+// before the preparation runs, the rest behind it), the filtered ratings, the structure, and the per-item arrays of the measure.
+// false = no rating is left (P says so; nothing else is filled).  for_request: the prepared job -- no column bounds, 1 / norm for
+// every epilogue.  t_total / t_prep: the full build's clocks (the whole job from here on; build_structure alone).
+static bool isim_front(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in, bool for_request, Prepared& P, IsimItems& N,
+                       EventTimer* t_total = nullptr, EventTimer* t_prep = nullptr) {
     if (prm->min_prefs_per_user < 0 || prm->max_prefs_per_user < 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "minPrefsPerUser / maxPrefsPerUser must be >= 0");
-}
-static void isim_check_params(const fy_itemsim_params* prm) {
+    const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
     if (prm->similarity < FY_SIMILARITY_COSINE || prm->similarity > FY_SIMILARITY_PEARSON_CORRELATION)
         FY_FAIL(FY_ERR_INVALID_ARGUMENT, "similarity must be one of the FY_SIMILARITY_* constants (0 .. %d)", (int)FY_SIMILARITY_PEARSON_CORRELATION);
-    const int measure = prm->similarity;
-    if (measure == FY_SIMILARITY_PEARSON_CORRELATION && prm->has_threshold && !(prm->threshold > 0.0))
+    if (prm->similarity == FY_SIMILARITY_PEARSON_CORRELATION && prm->has_threshold && !(prm->threshold > 0.0))
         FY_FAIL(FY_ERR_UNSUPPORTED, "SIMILARITY_PEARSON_CORRELATION with a threshold <= 0: a co-rated pair whose centred products cancel to 0 "
                                     "cannot be told from a pair nobody co-rated");
     if (prm->max_similarities_per_item <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "maxSimilaritiesPerRow must be > 0");
     if (prm->max_similarities_per_item > ISIM_MAX_K)
         FY_FAIL(FY_ERR_UNSUPPORTED, "maxSimilaritiesPerRow %d exceeds the kernel limit %d", prm->max_similarities_per_item, ISIM_MAX_K);
     if (prm->world <= 0 || prm->rank < 0 || prm->rank >= prm->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", prm->rank, prm->world);
-}
-static void isim_check_euclidean(int measure, const Prepared& P) {
-    if (measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE && !P.ratings_positive)
+    if (t_total) t_total->begin();
+    const size_t sp = t_prep ? t_prep->begin() : 0;
+    build_structure(ctx, filtered ? filtered.get() : R_in, 1, 0, nullptr, nullptr, nullptr, true, P);
+    if (t_prep) t_prep->end(sp);
+    if (P.nnz == 0) return false;
+    if (prm->similarity == FY_SIMILARITY_EUCLIDEAN_DISTANCE && !P.ratings_positive)
         FY_FAIL(FY_ERR_UNSUPPORTED, "SIMILARITY_EUCLIDEAN_DISTANCE on data with a non-positive preference: a co-rated pair whose products sum to 0 "
                                     "cannot be told from a pair nobody co-rated");
-}
-
-fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in) {
-    isim_check_prefs(prm);
-    const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
-    const fy_ratings* R = filtered ? filtered.get() : R_in;
-    isim_check_params(prm);
-    const int measure = prm->similarity;
-    hipStream_t st = ctx->stream;
-    std::unique_ptr<fy_result> Rs(new fy_result);
-    Rs->ctx = ctx;
-    Rs->kind = 1;
-    EventTimer t_prep(ctx), t_cooc(ctx), t_total(ctx);
-    const size_t sp0 = t_total.begin();
-    const size_t sp1 = t_prep.begin();
-    Prepared P;
-    build_structure(ctx, R, 1, 0, nullptr, nullptr, nullptr, true, P);
-    t_prep.end(sp1);
-    Rs->st.nnz = P.nnz;
-    Rs->st.n_users = P.nU;
-    Rs->st.n_items = P.nI;
-    if (P.nnz == 0) {
-        t_total.end(sp0);
-        sync(ctx);
-        return Rs.release();
-    }
-    isim_check_euclidean(measure, P);
+    const IsimMeasure m = isim_measure(prm->similarity);
+    const bool pearson = m.weight == ISIM_W_PEARSON, sumsq = m.a == ISIM_A_SUMSQ;
     const int32_t Ic = P.nP;   // single "cluster": every item is a pair
-    const int cosine = measure == FY_SIMILARITY_COSINE;
-    const bool pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
-    // the measures that finish (dot, a_i, a_j, N) in the epilogue; for the others the dot product is the similarity
-    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
-                          measure == FY_SIMILARITY_CITY_BLOCK || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
-    // packed row kernel (4-byte CSR entries, norms applied in the epilogue) when every rating is fp16-exact; Pearson's centred
-    // weights are not: it always takes the 8-byte-entry walk
-    const Tuning& tune = ctx->tune;
-    const bool use_pk = P.ratings_fp16_exact && tune.cooc_pk && !pearson;
-    DevBuf<double> norm(ctx, Ic), inv_norm(ctx, Ic);
-    DevBuf<float> colsum(ctx, Ic), colmax(ctx, Ic);
-    DevBuf<double> sumsq(ctx, measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE ? Ic : 1), centre(ctx, pearson ? Ic : 1), cnorm(ctx, pearson ? Ic : 1);
-    DevBuf<double> aux(ctx, finishes ? Ic : 1);
+    hipStream_t st = ctx->stream;
+    N.norm.alloc(ctx, Ic);
+    N.inv_norm.alloc(ctx, Ic);
+    if (!for_request) { N.colsum.alloc(ctx, Ic); N.colmax.alloc(ctx, Ic); }
+    N.sumsq.alloc(ctx, sumsq ? Ic : 1);
+    N.centre.alloc(ctx, pearson ? Ic : 1);
+    N.cnorm.alloc(ctx, pearson ? Ic : 1);
+    N.aux.alloc(ctx, m.finishes ? Ic : 1);
+    // the norms, by one kernel in a fixed summation order: the full build and a request see the same bits
     const int norm_grid = std::min<int>(Ic, ctx->num_cus * 32);
     if (pearson)
-        k_item_norms<true><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), colsum.get(), colmax.get(), nullptr, centre.get(), cnorm.get());
+        k_item_norms<true><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), N.norm.get(), N.colsum.get(), N.colmax.get(), nullptr, N.centre.get(), N.cnorm.get());
     else
-        k_item_norms<false><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), colsum.get(), colmax.get(),
-                                                       measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE ? sumsq.get() : nullptr, nullptr, nullptr);
+        k_item_norms<false><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), N.norm.get(), N.colsum.get(), N.colmax.get(), sumsq ? N.sumsq.get() : nullptr,
+                                                       nullptr, nullptr);
     FY_KERNEL_CHECK();
-    if (finishes) {
-        k_isim_rank_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE ? sumsq.get() : nullptr, aux.get());
+    if (m.finishes) {
+        k_isim_rank_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), sumsq ? N.sumsq.get() : nullptr, N.aux.get());
         FY_KERNEL_CHECK();
     }
-    const double* wnorm = pearson ? cnorm.get() : norm.get();      // the norm the pre-divided weights use
-    const int K = prm->max_similarities_per_item;
+    if (for_request && m.inv_norm) {
+        k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), N.norm.get(), N.inv_norm.get());
+        FY_KERNEL_CHECK();
+    }
+    return true;
+}
+
+// column chunks of the row-at-a-time kernel and every user's row offsets at their boundaries
+struct IsimChunks {
+    int32_t CH, nch, cap;
+    DevBuf<int32_t> chunk_off;
+};
+
+// The row-at-a-time build of this rank's rows (rank, rank + world, ...): the weights of the walk the route names, the segment table,
+// k_cooc_itemsim over (row, chunk) items, k_isim_merge.  Returns whether the row kernel ran (a rank without rows has nothing to build).
+static bool itemsim_row_at_a_time(Context* ctx, const fy_itemsim_params* prm, const Prepared& P, IsimItems& N, bool use_pk, const IsimChunks& C, int32_t rows_mine,
+                                  int32_t* cnt, int32_t* other, float* sim, EventTimer& t_cooc) {
+    const Tuning& tune = ctx->tune;
+    hipStream_t st = ctx->stream;
+    const int measure = prm->similarity;
+    const IsimMeasure m = isim_measure(measure);
+    const int32_t Ic = P.nP, K = prm->max_similarities_per_item, CH = C.CH, nch = C.nch;
+    DevBuf<float> csc_w(ctx, (size_t)P.nnz), csr_w(ctx, use_pk ? 1 : (size_t)P.nnz);
+    DevBuf<uint32_t> csr_pk(ctx, use_pk ? (size_t)P.nnz : 1);
+    if (use_pk) {
+        k_isim_raw_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_r.get(), measure, csc_w.get());
+        FY_KERNEL_CHECK();
+        if (m.inv_norm) {
+            k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), N.norm.get(), N.inv_norm.get());
+            FY_KERNEL_CHECK();
+        }
+    } else {
+        const double* wnorm = m.weight == ISIM_W_PEARSON ? N.cnorm.get() : N.norm.get();      // the norm the pre-divided weights use
+        k_csc_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.csc_r.get(), wnorm, N.centre.get(), measure, csc_w.get());
+        FY_KERNEL_CHECK();
+        k_csr_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csr_idx.get(), P.csr_r.get(), P.rank_pair.get(), wnorm, N.centre.get(), measure, csr_w.get());
+        FY_KERNEL_CHECK();
+    }
+    if (rows_mine <= 0) return false;
+    SegStore segs;
+    const SegDesc sd = seg_desc(0, 0, (int32_t)P.nnz, nch);
+    build_segment_table(ctx, SegArrays{P.csc_slot.get(), csc_w.get(), C.chunk_off.get(), nullptr, nullptr}, sd, segs);
+    if (use_pk) {
+        k_isim_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), measure, csr_pk.get());
+        FY_KERNEL_CHECK();
+    }
+    CoocArgs CA = cooc_args(P, segs.view(sd), CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, csr_w.get(), use_pk ? csr_pk.get() : nullptr);
+    CA.row0 = prm->rank; CA.nrows = rows_mine; CA.row_stride = prm->world;      // this rank's rows: rank, rank + world, ...
+    DevBuf<int2> item_seg(ctx, (size_t)rows_mine * nch);
+    DevBuf<int32_t> part_cnt(ctx, (size_t)rows_mine * nch);
+    part_cnt.zero();
+    // rows are in popularity order: the rows with more than ISIM_HEAVY raters are a prefix
+    DevBuf<int32_t> d_heavy(ctx, 1);
+    d_heavy.zero();
+    k_isim_count_heavy<<<grid_for(rows_mine), 256, 0, st>>>(rows_mine, prm->rank, prm->world, P.rank_pair.get(), P.pair_start.get(), tune.isim_heavy, d_heavy.get());
+    FY_KERNEL_CHECK();
+    const int32_t heavy_rows = nch > 1 ? fetch(ctx, d_heavy.get()) : 0;
+    const int64_t n_items = (int64_t)heavy_rows * nch + (rows_mine - heavy_rows);
+    DevBuf<uint64_t> part(ctx, (size_t)rows_mine * nch * K);
+    k_item_segments<<<grid_for((int64_t)rows_mine * nch), 256, 0, st>>>(CA, item_seg.get());
+    FY_KERNEL_CHECK();
+    CA.item_seg = item_seg.get();
+    ISimEpilogue IE{P.rank_item_raw.get(), K, prm->exclude_self, prm->has_threshold, (float)prm->threshold, prm->rank,
+                    prm->world, cnt, other, sim, (use_pk && m.inv_norm) ? N.inv_norm.get() : nullptr,
+                    m.finishes ? N.aux.get() : nullptr, (double)P.nU, part_cnt.get(), part.get(), heavy_rows, (int32_t)n_items, C.cap};
+    const size_t lds = (size_t)CH * 8 + (size_t)C.cap * 8;
+    const int block = lds > 48 * 1024 ? 1024 : 256;
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / block, (160 * 1024) / (lds + 1024)));
+    const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->num_cus * per_cu);
+    DevBuf<int32_t> next_row(ctx, 1);
+    next_row.zero();
+    const size_t sp = t_cooc.begin();
+    isim_dispatch(measure, [&](auto M) {
+        const auto kernel = use_pk ? k_cooc_itemsim<true, decltype(M)::value> : k_cooc_itemsim<false, decltype(M)::value>;
+        FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        kernel<<<grid, block, lds, st>>>(CA, IE, next_row.get());
+        FY_KERNEL_CHECK();
+    });
+    k_isim_merge<<<std::min(rows_mine, ctx->num_cus * 8), 256, 0, st>>>(rows_mine, nch, K, part_cnt.get(), part.get(), cnt, other, sim);
+    FY_KERNEL_CHECK();
+    t_cooc.end(sp);
+    sync(ctx);   // part / item_seg go back to the allocator at the end of this scope
+    return true;
+}
+
+// n rows for a result of kind 1: (item, other item, similarity, 0)
+void isim_result_rows(fy_result* R, int64_t n) {
+    R->n = n;
+    for (DevBuf<int32_t>* b : {&R->d_key0, &R->d_key1, &R->d_aux}) b->alloc(R->ctx, (size_t)n);
+    R->d_value.alloc(R->ctx, (size_t)n);
+}
+// the empty result of kind 1 (item similarities) over the job's structure: what both entry points and the request pass start from
+std::unique_ptr<fy_result> isim_empty_result(Context* ctx, const Prepared& P) {
+    std::unique_ptr<fy_result> R(new fy_result);
+    R->ctx = ctx;
+    R->kind = 1;
+    R->st.nnz = P.nnz;
+    R->st.n_users = P.nU;
+    R->st.n_items = P.nI;
+    isim_result_rows(R.get(), 0);
+    R->d_user_id.alloc(ctx, 0);
+    R->d_item_id.alloc(ctx, 0);
+    return R;
+}
+
+// front, route, one of the two builds, compact, statistics
+fy_result* itemsim_build(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in) {
+    EventTimer t_prep(ctx), t_cooc(ctx), t_total(ctx);
+    Prepared P;
+    IsimItems N;
+    const bool any = isim_front(ctx, prm, R_in, false, P, N, &t_total, &t_prep);
+    std::unique_ptr<fy_result> Rs = isim_empty_result(ctx, P);
+    hipStream_t st = ctx->stream;
+    if (!any) { t_total.end(0); sync(ctx); return Rs.release(); }
+    const Tuning& tune = ctx->tune;
+    const int32_t Ic = P.nP, K = prm->max_similarities_per_item;
+    const IsimRoute route = isim_route({prm->similarity, K, prm->world, prm->has_threshold != 0, prm->threshold, Ic, P.ratings_fp16_exact, P.ratings_positive,
+                                        (uint64_t)ctx->total_mem, tune.isim_gram, tune.isim_gram_min_items, tune.cooc_pk});
     const int32_t rows_mine = (Ic - prm->rank + prm->world - 1) / prm->world;
     DevBuf<int32_t> cnt(ctx, (size_t)rows_mine + 1), off(ctx, (size_t)rows_mine + 1), other(ctx, (size_t)rows_mine * K);
     DevBuf<float> sim(ctx, (size_t)rows_mine * K);
     cnt.zero();
     double ms_sym = 0.0;
-    const bool symmetric = itemsim_symmetric(ctx, prm, P, norm.get(), colsum.get(), colmax.get(), finishes ? aux.get() : nullptr, cnt.get(), other.get(), sim.get(), &ms_sym, &Rs->st);
-    if (symmetric) Rs->st.cooc_launches = 1;
-    DevBuf<float> csc_w(ctx, symmetric ? 1 : (size_t)P.nnz), csr_w(ctx, (use_pk || symmetric) ? 1 : (size_t)P.nnz);
-    DevBuf<uint32_t> csr_pk(ctx, (use_pk && !symmetric) ? (size_t)P.nnz : 1);
-    if (symmetric) {
-    } else if (use_pk) {
-        k_isim_raw_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_r.get(), measure, csc_w.get());
-        FY_KERNEL_CHECK();
-        if (cosine) {
-            k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), norm.get(), inv_norm.get());
-            FY_KERNEL_CHECK();
-        }
-    } else {
-        k_csc_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csc_pair.get(), P.csc_r.get(), wnorm, centre.get(), measure, csc_w.get());
-        FY_KERNEL_CHECK();
-        k_csr_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csr_idx.get(), P.csr_r.get(), P.rank_pair.get(), wnorm, centre.get(), measure, csr_w.get());
-        FY_KERNEL_CHECK();
-    }
-
+    const bool symmetric = route.symmetric && itemsim_symmetric(ctx, prm, P, N, cnt.get(), other.get(), sim.get(), &ms_sym, &Rs->st);
     // LDS = fp64 accumulators + candidate buffer <= 160 KiB.  (A 512-entry buffer would allow three column chunks instead of
     // four at ML-25M shape, but the extra cuts cost more than the shorter walk gains: 28.5 against 27.2 ms.)
-    const int cap = ISIM_CAP;
-    int max_ch = ((160 * 1024 - cap * 8 - 2048) / 8) / 256 * 256;
+    IsimChunks C;
+    C.cap = ISIM_CAP;
+    int max_ch = ((160 * 1024 - C.cap * 8 - 2048) / 8) / 256 * 256;
     if (tune.cooc_max_ch_forced && tune.cooc_max_ch <= max_ch) max_ch = tune.cooc_max_ch;   // test hook: force column chunks
-    int32_t CH, nch;
-    pick_chunks(Ic, max_ch, CH, nch);
-    DevBuf<int32_t> chunk_off(ctx, (size_t)P.nU * (nch + 1));
-    const CsrDescs cd = upload_csr_descs(ctx, {csr_desc(0, P.nU, CH, nch)});
-    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), chunk_off.get());
-    if (rows_mine > 0 && !symmetric) {
-        SegStore segs;
-        const SegDesc sd = seg_desc(0, 0, (int32_t)P.nnz, nch);
-        build_segment_table(ctx, SegArrays{P.csc_slot.get(), csc_w.get(), chunk_off.get(), nullptr, nullptr}, sd, segs);
-        if (use_pk) {
-            k_isim_pack_csr<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, CH, P.csr_idx.get(), P.csr_r.get(), measure, csr_pk.get());
-            FY_KERNEL_CHECK();
-        }
-        CoocArgs CA = cooc_args(P, segs.view(sd), CoocGeometry{0, 0, Ic, CH, nch, 0, (int32_t)P.nnz}, csr_w.get(), use_pk ? csr_pk.get() : nullptr);
-        CA.row0 = prm->rank; CA.nrows = rows_mine; CA.row_stride = prm->world;      // this rank's rows: rank, rank + world, ...
-        DevBuf<int2> item_seg(ctx, (size_t)rows_mine * nch);
-        DevBuf<int32_t> part_cnt(ctx, (size_t)rows_mine * nch);
-        part_cnt.zero();
-        // rows are in popularity order: the rows with more than ISIM_HEAVY raters are a prefix
-        const int32_t heavy_raters = tune.isim_heavy;
-        DevBuf<int32_t> d_heavy(ctx, 1);
-        d_heavy.zero();
-        k_isim_count_heavy<<<grid_for(rows_mine), 256, 0, st>>>(rows_mine, prm->rank, prm->world, P.rank_pair.get(), P.pair_start.get(), heavy_raters, d_heavy.get());
-        FY_KERNEL_CHECK();
-        const int32_t heavy_rows = nch > 1 ? fetch(ctx, d_heavy.get()) : 0;
-        const int64_t n_items = (int64_t)heavy_rows * nch + (rows_mine - heavy_rows);
-        DevBuf<uint64_t> part(ctx, (size_t)rows_mine * nch * K);
-        k_item_segments<<<grid_for((int64_t)rows_mine * nch), 256, 0, st>>>(CA, item_seg.get());
-        FY_KERNEL_CHECK();
-        CA.item_seg = item_seg.get();
-        ISimEpilogue IE{P.rank_item_raw.get(), K, prm->exclude_self, prm->has_threshold, (float)prm->threshold, prm->rank,
-                        prm->world, cnt.get(), other.get(), sim.get(), (use_pk && cosine) ? inv_norm.get() : nullptr,
-                        finishes ? aux.get() : nullptr, (double)P.nU, part_cnt.get(), part.get(), heavy_rows, (int32_t)n_items, cap};
-        const size_t lds = (size_t)CH * 8 + (size_t)cap * 8;
-        const int block = lds > 48 * 1024 ? 1024 : 256;
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / block, (160 * 1024) / (lds + 1024)));
-        const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->num_cus * per_cu);
-        DevBuf<int32_t> next_row(ctx, 1);
-        next_row.zero();
-        const size_t sp = t_cooc.begin();
-        switch (measure) {
-            case FY_SIMILARITY_TANIMOTO_COEFFICIENT: launch_cooc_itemsim<FY_SIMILARITY_TANIMOTO_COEFFICIENT>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
-            case FY_SIMILARITY_LOGLIKELIHOOD: launch_cooc_itemsim<FY_SIMILARITY_LOGLIKELIHOOD>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
-            case FY_SIMILARITY_CITY_BLOCK: launch_cooc_itemsim<FY_SIMILARITY_CITY_BLOCK>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
-            case FY_SIMILARITY_EUCLIDEAN_DISTANCE: launch_cooc_itemsim<FY_SIMILARITY_EUCLIDEAN_DISTANCE>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;
-            default: launch_cooc_itemsim<FY_SIMILARITY_COSINE>(use_pk, grid, block, lds, st, CA, IE, next_row.get()); break;   // cosine, co-occurrence, Pearson
-        }
-        k_isim_merge<<<std::min(rows_mine, ctx->num_cus * 8), 256, 0, st>>>(rows_mine, nch, K, part_cnt.get(), part.get(), cnt.get(), other.get(),
-                                                                            sim.get());
-        FY_KERNEL_CHECK();
-        t_cooc.end(sp);
-        sync(ctx);   // part / item_seg go back to the allocator at the end of this scope
-        Rs->st.cooc_launches = 1;
-    }
+    pick_chunks(Ic, max_ch, C.CH, C.nch);
+    C.chunk_off.alloc(ctx, (size_t)P.nU * (C.nch + 1));
+    const CsrDescs cd = upload_csr_descs(ctx, {csr_desc(0, P.nU, C.CH, C.nch)});
+    build_chunk_offsets(ctx, cd, P.rowptr.get(), P.csr_idx.get(), C.chunk_off.get());
+    if (symmetric || itemsim_row_at_a_time(ctx, prm, P, N, route.packed, C, rows_mine, cnt.get(), other.get(), sim.get(), t_cooc)) Rs->st.cooc_launches = 1;
     exclusive_scan_i32(ctx, cnt.get(), off.get(), (size_t)rows_mine + 1);
     const int64_t n = fetch(ctx, off.get() + rows_mine);
-    Rs->n = n;
-    Rs->d_key0.alloc(ctx, (size_t)n);
-    Rs->d_key1.alloc(ctx, (size_t)n);
-    Rs->d_value.alloc(ctx, (size_t)n);
-    Rs->d_aux.alloc(ctx, (size_t)n);
+    isim_result_rows(Rs.get(), n);
     if (rows_mine > 0 && n > 0) {
-        k_isim_compact<<<grid_for((int64_t)rows_mine * 64, 256), 256, 0, st>>>(rows_mine, K, prm->rank, prm->world, cnt.get(), off.get(),
-                                                                               other.get(), sim.get(), P.rank_item_raw.get(),
-                                                                               Rs->d_key0.get(), Rs->d_key1.get(), Rs->d_value.get(),
-                                                                               Rs->d_aux.get());
+        k_isim_compact<<<grid_for((int64_t)rows_mine * 64, 256), 256, 0, st>>>(rows_mine, K, nullptr, prm->rank, prm->world, cnt.get(), off.get(), other.get(), sim.get(),
+                                                                               P.rank_item_raw.get(), Rs->d_key0.get(), Rs->d_key1.get(), Rs->d_value.get(), Rs->d_aux.get());
         FY_KERNEL_CHECK();
     }
-    Rs->d_user_id.alloc(ctx, 0);
-    Rs->d_item_id.alloc(ctx, 0);
-    t_total.end(sp0);
+    t_total.end(0);
     sync(ctx);
     Rs->st.recs = n;
     Rs->st.pair_contribs = P.sum_deg2;
@@ -1194,49 +1129,22 @@ __global__ void k_isim_req_pearson_unit(int32_t Ic, const int32_t* __restrict__ 
 }
 
 fy_itemsim_job* itemsim_prepare(Context* ctx, const fy_itemsim_params* prm, const fy_ratings* R_in) {
-    isim_check_prefs(prm);
-    const std::unique_ptr<fy_ratings> filtered = filter_user_prefs(ctx, R_in, prm->min_prefs_per_user, prm->max_prefs_per_user);
-    const fy_ratings* R = filtered ? filtered.get() : R_in;
-    isim_check_params(prm);
-    const int measure = prm->similarity;
-    hipStream_t st = ctx->stream;
     std::unique_ptr<fy_itemsim_job> J(new fy_itemsim_job);
     J->ctx = ctx;
     J->prm = *prm;
     Prepared& P = J->P;
-    build_structure(ctx, R, 1, 0, nullptr, nullptr, nullptr, true, P);
-    if (P.nnz == 0) {
-        sync(ctx);
-        return J.release();
-    }
-    isim_check_euclidean(measure, P);
+    IsimItems N;
+    if (!isim_front(ctx, prm, R_in, true, P, N)) { sync(ctx); return J.release(); }
+    hipStream_t st = ctx->stream;
     const int32_t Ic = P.nP;
-    const bool cosine = measure == FY_SIMILARITY_COSINE, pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
-    const bool euclidean = measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
-    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
-                          measure == FY_SIMILARITY_CITY_BLOCK || euclidean;
-    // the norms of the full build, by its kernels (fixed summation order)
-    DevBuf<double> norm(ctx, Ic), sumsq(ctx, euclidean ? Ic : 1);
-    J->centre.alloc(ctx, pearson ? Ic : 1);
-    J->cnorm.alloc(ctx, pearson ? Ic : 1);
-    J->inv_norm.alloc(ctx, (cosine || pearson) ? Ic : 1);
-    J->aux.alloc(ctx, finishes ? Ic : 1);
+    const IsimMeasure m = isim_measure(prm->similarity);
+    const bool pearson = m.weight == ISIM_W_PEARSON;
+    // the job owns what its requests read; the norms themselves are only needed for the bounds below
+    J->centre = std::move(N.centre);
+    J->cnorm = std::move(N.cnorm);
+    J->inv_norm = std::move(N.inv_norm);
+    J->aux = std::move(N.aux);
     J->csr_w.alloc(ctx, pearson ? (size_t)P.nnz : 1);
-    const int norm_grid = std::min<int>(Ic, ctx->num_cus * 32);
-    if (pearson)
-        k_item_norms<true><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), nullptr, nullptr, nullptr, J->centre.get(), J->cnorm.get());
-    else
-        k_item_norms<false><<<norm_grid, 256, 0, st>>>(Ic, P.pair_start.get(), P.csc_r.get(), norm.get(), nullptr, nullptr, euclidean ? sumsq.get() : nullptr, nullptr,
-                                                       nullptr);
-    FY_KERNEL_CHECK();
-    if (finishes) {
-        k_isim_rank_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), P.pair_start.get(), euclidean ? sumsq.get() : nullptr, J->aux.get());
-        FY_KERNEL_CHECK();
-    }
-    if (cosine) {
-        k_isim_inv_norms<<<grid_for(Ic), 256, 0, st>>>(Ic, P.rank_pair.get(), norm.get(), J->inv_norm.get());
-        FY_KERNEL_CHECK();
-    }
     if (pearson) {
         k_isim_req_pearson_weights<<<grid_for(P.nnz), 256, 0, st>>>(P.nnz, P.csr_idx.get(), P.csr_r.get(), P.rank_pair.get(), J->centre.get(), J->cnorm.get(),
                                                                    J->csr_w.get());
@@ -1264,7 +1172,7 @@ fy_itemsim_job* itemsim_prepare(Context* ctx, const fy_itemsim_params* prm, cons
     d2h(ctx, raw.data(), P.rank_item_raw.get(), (size_t)Ic);
     d2h(ctx, rank_pair.data(), P.rank_pair.get(), (size_t)Ic);
     d2h(ctx, pair_start.data(), P.pair_start.get(), (size_t)Ic + 1);
-    d2h(ctx, h_norm.data(), norm.get(), (size_t)Ic);
+    d2h(ctx, h_norm.data(), N.norm.get(), (size_t)Ic);
     d2h(ctx, J->walk.data(), d_walk.get(), (size_t)Ic);
     sync(ctx);
     std::vector<std::pair<int32_t, int32_t>> by_raw((size_t)Ic);
@@ -1273,12 +1181,11 @@ fy_itemsim_job* itemsim_prepare(Context* ctx, const fy_itemsim_params* prm, cons
     J->raw_sorted.resize((size_t)Ic);
     J->rank_of_sorted.resize((size_t)Ic);
     for (int32_t k = 0; k < Ic; k++) { J->raw_sorted[(size_t)k] = by_raw[(size_t)k].first; J->rank_of_sorted[(size_t)k] = by_raw[(size_t)k].second; }
-    const bool weight_is_rating = isim_weight_is_rating(measure);
     double max_norm = 0.0;
     for (double x : h_norm) max_norm = std::max(max_norm, x);
     for (int32_t r = 0; r < Ic; r++) {
         const int32_t pr = rank_pair[(size_t)r];
-        h_bound[(size_t)r] = pearson ? 1.0 : weight_is_rating ? h_norm[(size_t)pr] * max_norm : (double)(pair_start[(size_t)pr + 1] - pair_start[(size_t)pr]);
+        h_bound[(size_t)r] = pearson ? 1.0 : m.weight == ISIM_W_RATING ? h_norm[(size_t)pr] * max_norm : (double)(pair_start[(size_t)pr + 1] - pair_start[(size_t)pr]);
     }
     J->bound.alloc(ctx, Ic);
     h2d(ctx, J->bound.get(), h_bound.data(), (size_t)Ic);

@@ -1,8 +1,10 @@
 // fy_itemsim_kernels.hpp -- device code the two item-similarity translation units share (fy_itemsim.hip: the full build,
-// fy_itemsim_request.hip: rows on request): the measures' finishing functions, the order key, the running top-K in LDS
-// (select / cut / sort), the similarity of an accumulator, and the merge of a row's per-chunk lists.
+// fy_itemsim_request.hip: rows on request): the measures' finishing functions, the composite key of a candidate in its two
+// encodings, the running top-K in LDS (append / select / cut / finish), the candidate test of a row kernel's accumulator, the one
+// compact kernel and the merge of a row's per-chunk lists.  What a measure is and which template it instantiates: fy_itemsim_plan.hpp.
 #pragma once
 #include "fy_common.hpp"
+#include "fy_itemsim_plan.hpp"
 
 namespace fy {
 
@@ -33,14 +35,15 @@ __device__ __forceinline__ double isim_finish(double d, double ai, double aj, do
     }
 }
 
-__device__ __forceinline__ uint32_t isim_order_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float isim_order_unkey(uint32_t k) {
-    const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    return __uint_as_float(b);
-}
+// A candidate is one 64-bit composite: similarity key << 32 | (0x7FFFFFFF - raw item id), so that descending composites are
+// descending similarities with ties by ascending item id, all distinct.  The key has two encodings; a list holds ONE of them:
+//   * ordered: fy_order_key, any sign -- the row kernels (full build, request), their per-chunk lists and k_isim_merge;
+//   * positive: the float's own bits, which order like the floats only for similarities > 0 -- the symmetric build (sweep, finish, redo).
+__device__ __forceinline__ uint64_t isim_composite(uint32_t key, int32_t raw_id) { return ((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - raw_id); }
+__device__ __forceinline__ int32_t isim_composite_item(uint64_t c) { return 0x7FFFFFFF - (int32_t)(uint32_t)c; }
+__device__ __forceinline__ float isim_composite_sim_ordered(uint64_t c) { return fy_order_unkey((uint32_t)(c >> 32)); }
+__device__ __forceinline__ uint32_t isim_positive_key(float s) { return __float_as_uint(s); }
+__device__ __forceinline__ float isim_composite_sim_positive(uint64_t c) { return __uint_as_float((uint32_t)(c >> 32)); }
 
 constexpr int ISIM_CAP = 2048;      // candidate buffer (LDS)
 constexpr int ISIM_MAX_K = 1024;
@@ -70,21 +73,6 @@ struct ISimEpilogue {
     int32_t n_items;                   // heavy_rows * nch + (rows - heavy_rows)
     int32_t cap;                       // candidate buffer entries in LDS (power of two, >= 2 K, <= ISIM_CAP)
 };
-
-__device__ __forceinline__ void isim_sort_desc(uint64_t* v, int P2) {
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P2; i += blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const uint64_t x = v[i], y = v[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (x < y) : (x > y)) { v[i] = y; v[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // Cuts the n candidates in LDS down to (at least) the K best without sorting them: two 256-bin histogram levels over the
 // order keys (bits 31..24, then 23..16) locate a 16-bit key prefix T with  #(key >= T) >= K  and  #(key >= T + 1 prefix) < K;
@@ -147,7 +135,7 @@ __device__ __forceinline__ void isim_cut(uint64_t* cand, int K, int cap, uint32_
         __syncthreads();
         for (int i = n + tid; i < cap; i += blockDim.x) cand[i] = 0ull;
         __syncthreads();
-        isim_sort_desc(cand, cap);
+        fy_bitonic_desc(cand, cap);
         if (tid == 0) {
             *sh_cnt = (uint32_t)min(n, K);
             if (n >= K) *sh_tau = (uint32_t)(cand[K - 1] >> 32);   // inclusive: a later tie with a smaller item id still wins
@@ -164,6 +152,57 @@ template <int M>
 __device__ __forceinline__ float isim_row_value(const ISimEpilogue& E, double a, double row_term, int col) {
     if constexpr (M == FY_SIMILARITY_COSINE) return E.inv_norm ? (float)isim_finish_product(a, row_term, E.inv_norm[col]) : (float)a;
     else return a != 0.0 ? (float)isim_finish<M>(a, row_term, E.aux[col], E.n_cols) : __builtin_nanf("");
+}
+
+// the row's own term of isim_row_value: a_i of a finishing measure, 1 / ||r_.i|| of the packed cosine, else nothing
+template <int M>
+__device__ __forceinline__ double isim_row_scale(const ISimEpilogue& E, int row) {
+    return M != FY_SIMILARITY_COSINE ? E.aux[row] : E.inv_norm ? E.inv_norm[row] : 1.0;
+}
+
+// The candidate test of a row kernel: the similarity of (row, col) from the accumulator a, the job's threshold (none: > 0), the
+// diagonal.  Returns whether the job accepts the pair, and its ordered key (meaningful either way: the running threshold compares it).
+template <int M>
+__device__ __forceinline__ bool isim_candidate(const ISimEpilogue& E, double a, double row_term, int row, int col, uint32_t& key) {
+    const float s = isim_row_value<M>(E, a, row_term, col);
+    bool ok = E.has_threshold ? (s >= E.threshold) : (s > 0.0f);
+    if (E.exclude_self && col == row) ok = false;
+    key = fy_order_key(s);
+    return ok;
+}
+
+// Appends the composites of the lanes that `want` to the candidate buffer in LDS with one atomic per wave; every lane of the wave
+// calls it.  Returns whether this lane's composite was stored.  BOUNDED (k_cooc_itemsim): the count moves past `cap` when the buffer
+// is full and the entry is not written -- the caller leaves its accumulator in place and comes back.  Not BOUNDED (request, redo):
+// the caller cuts the buffer before a step could overflow it, and the kernel carries no compare (`cap` is not read).
+template <bool BOUNDED>
+__device__ __forceinline__ bool isim_append(uint64_t* cand, uint32_t* sh_cnt, uint32_t cap, bool want, uint64_t c) {
+    const unsigned long long bal = __ballot(want);
+    bool stored = false;
+    if (bal) {
+        const int lane = threadIdx.x & 63;
+        uint32_t at = 0;
+        if (lane == __ffsll((long long)bal) - 1) at = atomicAdd(sh_cnt, (uint32_t)__popcll(bal));
+        at = __shfl(at, __ffsll((long long)bal) - 1, 64);
+        if (want) {
+            const uint32_t pos = at + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            if (!BOUNDED || pos < cap) { cand[pos] = c; stored = true; }
+        }
+    }
+    return stored;
+}
+
+// The tail of a list: cut the *sh_cnt candidates to ~K (isim_select), pad to a power of two, sort.  Returns how many to keep; they
+// are the front of cand, best first.  Every thread of the block calls it; the caller stores them its own way.
+__device__ __forceinline__ int isim_finish_list(uint64_t* cand, int K, uint32_t* hist, uint32_t* sh_cnt, uint32_t* sh_tau, uint32_t* sh_aux) {
+    isim_select(cand, (int)*sh_cnt, K, hist, sh_cnt, sh_tau, sh_aux);   // then only ~K entries are left to sort
+    const int n = (int)*sh_cnt;
+    int P2 = 1;
+    while (P2 < n) P2 <<= 1;
+    for (int i = n + threadIdx.x; i < P2; i += blockDim.x) cand[i] = 0ull;
+    __syncthreads();
+    fy_bitonic_desc(cand, P2);
+    return min(n, K);
 }
 
 // one workgroup per row: fold the chunks' top-K lists (each sorted, disjoint columns) into the row's top K
@@ -184,17 +223,36 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void k_isim_mer
             while (P2 < tot) P2 <<= 1;
             for (int i = tot + tid; i < P2; i += blockDim.x) buf[i] = 0ull;
             __syncthreads();
-            isim_sort_desc(buf, P2);
+            fy_bitonic_desc(buf, P2);
             have = min(tot, K);
         }
         __syncthreads();
         if (tid == 0) out_cnt[m] = have;
         for (int i = tid; i < have; i += blockDim.x) {
             const uint64_t c = buf[i];
-            out_other[(int64_t)m * K + i] = 0x7FFFFFFF - (int32_t)(uint32_t)c;
-            out_sim[(int64_t)m * K + i] = isim_order_unkey((uint32_t)(c >> 32));
+            out_other[(int64_t)m * K + i] = isim_composite_item(c);
+            out_sim[(int64_t)m * K + i] = isim_composite_sim_ordered(c);
         }
         __syncthreads();
+    }
+}
+
+// the lists of rows -> the result, one wave per row.  rows: the popularity ranks of the rows (a request's, ascending); nullptr: the
+// strided rows of a rank of the full build, rank + m * world
+__attribute__((unused)) static __global__ void k_isim_compact(int32_t n, int32_t K, const int32_t* __restrict__ rows, int32_t rank, int32_t world,
+                                                              const int32_t* __restrict__ cnt, const int32_t* __restrict__ off, const int32_t* __restrict__ other,
+                                                              const float* __restrict__ sim, const int32_t* __restrict__ rank_item_raw, int32_t* __restrict__ o_item,
+                                                              int32_t* __restrict__ o_other, float* __restrict__ o_sim, int32_t* __restrict__ o_aux) {
+    const int wpb = blockDim.x >> 6, lane = threadIdx.x & 63;
+    for (int32_t m = blockIdx.x * wpb + (threadIdx.x >> 6); m < n; m += gridDim.x * wpb) {
+        const int32_t item = rank_item_raw[rows ? rows[m] : rank + m * world];
+        for (int i = lane; i < cnt[m]; i += 64) {
+            const int64_t o = (int64_t)off[m] + i;
+            o_item[o] = item;
+            o_other[o] = other[(int64_t)m * K + i];
+            o_sim[o] = sim[(int64_t)m * K + i];
+            o_aux[o] = 0;
+        }
     }
 }
 

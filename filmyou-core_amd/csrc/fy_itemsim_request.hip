@@ -7,9 +7,10 @@
 //                    do not depend on the order of the atomics, requests are bit-reproducible) + the candidate buffer.  Groups of
 //                    16 lanes take one rater at a time; the slice of the rater's row inside the chunk comes from the offsets kept
 //                    at prepare.  Then the accumulators are read back as fp64 and streamed through the running top-K of the full
-//                    build (isim_row_value, isim_cut, isim_select, isim_sort_desc: fy_itemsim_kernels.hpp), 1024 columns a step;
-//                    the chunk's K best are left as composite keys.
-//   k_isim_merge     (the full build's) folds a row's chunks; k_isim_req_compact writes the result in popularity order.
+//                    build (isim_candidate, isim_append, isim_cut, isim_finish_list: fy_itemsim_kernels.hpp), 1024 columns a step;
+//                    the chunk's K best are left as composites with the ordered key.
+//   k_isim_merge     (the full build's) folds a row's chunks; k_isim_compact (shared too) writes the result in popularity order.
+// Which instantiation a measure takes -- its weight, its finish -- comes from fy_itemsim_plan.hpp (isim_measure, isim_dispatch).
 // Nothing here launches or loops over the ratings or over all users: ids are mapped by a binary search per requested id in the
 // job's sorted raw ids (host), marking / deduplication / ordering sort the <= n row indices.
 #include <algorithm>
@@ -24,7 +25,6 @@ namespace {
 
 constexpr int ROWS_THREADS = 1024;   // 64 groups of 16 lanes, a group walks one rater's row at a time
 constexpr int ROWS_GROUP = 16;
-enum { W_RATING = 0, W_ONE = 1, W_PEARSON = 2 };      // what a preference weighs (include/filmyou.h: the column transform)
 
 struct ReqRowsArgs {
     const int32_t* __restrict__ rows;       // [n] popularity ranks of the batch's rows, ascending
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_isim_req_rows(ReqRowsArgs A, I
     const double scale = ldexp(1.0, 61 - ex), unscale = ldexp(1.0, ex - 61);
     double centre = 0.0, inv_cnorm = 0.0;
     bool walk = true;
-    if constexpr (W == W_PEARSON) {
+    if constexpr (W == ISIM_W_PEARSON) {
         centre = A.centre[pr];
         const double cn = A.cnorm[pr];
         walk = cn != 0.0;                       // a constant item has no row (block-uniform)
@@ -77,14 +77,14 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_isim_req_rows(ReqRowsArgs A, I
         for (int32_t q = q0 + g; q < q1; q += ROWS_THREADS / ROWS_GROUP) {
             const int32_t v = A.csc_slot[q];
             double wj = scale;
-            if constexpr (W == W_RATING) wj = (double)A.csc_r[q] * scale;
-            if constexpr (W == W_PEARSON) wj = (((double)A.csc_r[q] - centre) * inv_cnorm) * scale;
+            if constexpr (W == ISIM_W_RATING) wj = (double)A.csc_r[q] * scale;
+            if constexpr (W == ISIM_W_PEARSON) wj = (((double)A.csc_r[q] - centre) * inv_cnorm) * scale;
             const int32_t f0 = A.choff[(int64_t)v * stride + ch], f1 = A.choff[(int64_t)v * stride + ch + 1];
             for (int32_t f = f0 + gl; f < f1; f += ROWS_GROUP) {
                 const int32_t i = A.csr_idx[f] - c0;
                 double wi = 1.0;
-                if constexpr (W == W_RATING) wi = (double)A.csr_r[f];
-                if constexpr (W == W_PEARSON) wi = A.csr_w[f];
+                if constexpr (W == ISIM_W_RATING) wi = (double)A.csr_r[f];
+                if constexpr (W == ISIM_W_PEARSON) wi = A.csr_w[f];
                 if (i >= 0 && i < ncol) atomicAdd(&acc[i], (unsigned long long)__double2ll_rn(wj * wi));
             }
         }
@@ -95,76 +95,40 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_isim_req_rows(ReqRowsArgs A, I
     __syncthreads();
     // The full build's running top-K, one step of ROWS_THREADS columns at a time: a candidate must reach the key sh_tau, the buffer
     // is cut back to the K best (isim_cut raises sh_tau) whenever the next step might not fit.  Exact for any input.
-    const double scale_row = M != FY_SIMILARITY_COSINE ? E.aux[row] : E.inv_norm ? E.inv_norm[row] : 1.0;
+    const double scale_row = isim_row_scale<M>(E, row);
     for (int32_t base = 0; base < ncol; base += ROWS_THREADS) {
         const int32_t t = base + tid;
         bool want = false;
         uint64_t c = 0;
         if (t < ncol) {
             const int32_t col = c0 + t;
-            const float s = isim_row_value<M>(E, __longlong_as_double((long long)acc[t]), scale_row, col);
-            bool ok = E.has_threshold ? (s >= E.threshold) : (s > 0.0f);
-            if (E.exclude_self && col == row) ok = false;
-            const uint32_t key = isim_order_key(s);
+            uint32_t key;
+            const bool ok = isim_candidate<M>(E, __longlong_as_double((long long)acc[t]), scale_row, row, col, key);
             want = ok && key >= sh_tau;
-            if (want) c = ((uint64_t)key << 32) | (uint32_t)(0x7FFFFFFF - E.rank_item_raw[col]);
+            if (want) c = isim_composite(key, E.rank_item_raw[col]);
         }
-        const unsigned long long bal = __ballot(want);
-        if (bal) {      // one LDS atomic per wave
-            const int lane = tid & 63;
-            uint32_t at = 0;
-            if (lane == __ffsll((long long)bal) - 1) at = atomicAdd(&sh_cnt, (uint32_t)__popcll(bal));
-            at = __shfl(at, __ffsll((long long)bal) - 1, 64);
-            if (want) cand[at + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = c;      // (fits: sh_cnt + ROWS_THREADS <= cap before the step)
-        }
+        isim_append<false>(cand, &sh_cnt, 0, want, c);      // (fits: sh_cnt + ROWS_THREADS <= cap before the step)
         __syncthreads();
         const uint32_t have = sh_cnt;
         __syncthreads();      // everybody has read the count before the next step's atomics move it
         if (have + ROWS_THREADS > (uint32_t)E.cap) isim_cut(cand, E.K, E.cap, hist, &sh_cnt, &sh_tau, sh_aux);      // block-uniform
     }
-    isim_select(cand, (int)sh_cnt, E.K, hist, &sh_cnt, &sh_tau, sh_aux);      // then only ~K entries are left to sort
-    const int n = (int)sh_cnt;
-    int P2 = 1;
-    while (P2 < n) P2 <<= 1;
-    for (int i = n + tid; i < P2; i += ROWS_THREADS) cand[i] = 0ull;
-    __syncthreads();
-    isim_sort_desc(cand, P2);
-    const int keep = min(n, E.K);
+    const int keep = isim_finish_list(cand, E.K, hist, &sh_cnt, &sh_tau, sh_aux);
     const int64_t slot = (int64_t)mine * A.nch + ch;
     if (tid == 0) E.part_cnt[slot] = keep;
     for (int i = tid; i < keep; i += ROWS_THREADS) E.part[slot * E.K + i] = cand[i];
 }
 
-// the lists of the request's rows -> the result, one wave per row (rows are in popularity order already)
-__global__ void k_isim_req_compact(int32_t n, int32_t K, const int32_t* __restrict__ rows, const int32_t* __restrict__ cnt,
-                                   const int32_t* __restrict__ off, const int32_t* __restrict__ other, const float* __restrict__ sim,
-                                   const int32_t* __restrict__ rank_item_raw, int32_t* __restrict__ o_item, int32_t* __restrict__ o_other,
-                                   float* __restrict__ o_sim, int32_t* __restrict__ o_aux) {
-    const int wpb = blockDim.x >> 6, lane = threadIdx.x & 63;
-    for (int32_t m = blockIdx.x * wpb + (threadIdx.x >> 6); m < n; m += gridDim.x * wpb) {
-        const int32_t item = rank_item_raw[rows[m]];
-        for (int i = lane; i < cnt[m]; i += 64) {
-            const int64_t o = (int64_t)off[m] + i;
-            o_item[o] = item;
-            o_other[o] = other[(int64_t)m * K + i];
-            o_sim[o] = sim[(int64_t)m * K + i];
-            o_aux[o] = 0;
-        }
-    }
-}
-
 using RowsKernel = void (*)(ReqRowsArgs, ISimEpilogue);
-// the instantiation of a measure: its weight and its finish
-RowsKernel rows_kernel(int measure) {
-    switch (measure) {
-        case FY_SIMILARITY_COSINE: return k_isim_req_rows<FY_SIMILARITY_COSINE, W_RATING>;
-        case FY_SIMILARITY_COOCCURRENCE: return k_isim_req_rows<FY_SIMILARITY_COSINE, W_ONE>;
-        case FY_SIMILARITY_TANIMOTO_COEFFICIENT: return k_isim_req_rows<FY_SIMILARITY_TANIMOTO_COEFFICIENT, W_ONE>;
-        case FY_SIMILARITY_LOGLIKELIHOOD: return k_isim_req_rows<FY_SIMILARITY_LOGLIKELIHOOD, W_ONE>;
-        case FY_SIMILARITY_CITY_BLOCK: return k_isim_req_rows<FY_SIMILARITY_CITY_BLOCK, W_ONE>;
-        case FY_SIMILARITY_EUCLIDEAN_DISTANCE: return k_isim_req_rows<FY_SIMILARITY_EUCLIDEAN_DISTANCE, W_RATING>;
-        default: return k_isim_req_rows<FY_SIMILARITY_COSINE, W_PEARSON>;      // Pearson: the dot product of the normalised columns
-    }
+// the instantiation of a measure: its finish (the template measure), and its weight -- fixed by a finishing measure, one of the three
+// where the dot product is the similarity
+RowsKernel rows_kernel(int similarity) {
+    const int weight = isim_measure(similarity).weight;
+    return isim_dispatch(similarity, [&](auto M) -> RowsKernel {
+        constexpr int m = decltype(M)::value;
+        if constexpr (m != FY_SIMILARITY_COSINE) return k_isim_req_rows<m, isim_measure(m).weight>;
+        else return weight == ISIM_W_RATING ? k_isim_req_rows<m, ISIM_W_RATING> : weight == ISIM_W_ONE ? k_isim_req_rows<m, ISIM_W_ONE> : k_isim_req_rows<m, ISIM_W_PEARSON>;
+    });
 }
 
 }  // namespace
@@ -190,20 +154,17 @@ int64_t itemsim_build_rank_rows(fy_itemsim_job* J, const int32_t* rows, int64_t 
     SyncOnUnwind drain(st);      // a failure in the loop drains the stream before the partial lists go
     int64_t batches = 0;
 
-    const int measure = prm.similarity;
-    const bool cosine = measure == FY_SIMILARITY_COSINE, pearson = measure == FY_SIMILARITY_PEARSON_CORRELATION;
-    const bool finishes = measure == FY_SIMILARITY_TANIMOTO_COEFFICIENT || measure == FY_SIMILARITY_LOGLIKELIHOOD ||
-                          measure == FY_SIMILARITY_CITY_BLOCK || measure == FY_SIMILARITY_EUCLIDEAN_DISTANCE;
+    const IsimMeasure m = isim_measure(prm.similarity);
     const int cap = ISIM_CAP;
     const size_t lds = (size_t)CH * 8 + (size_t)cap * 8;
-    const RowsKernel kernel = rows_kernel(measure);
+    const RowsKernel kernel = rows_kernel(prm.similarity);
     FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (int64_t b0 = 0; b0 < n; b0 += per_batch) {
         const int32_t nb = (int32_t)std::min<int64_t>(per_batch, n - b0);
         ReqRowsArgs A{rows + b0, Ic, CH, nch, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.csc_r.get(), J->choff.get(),
                       P.csr_idx.get(), P.csr_r.get(), J->csr_w.get(), J->centre.get(), J->cnorm.get(), J->bound.get()};
         ISimEpilogue E{P.rank_item_raw.get(), K, prm.exclude_self, prm.has_threshold, (float)prm.threshold, prm.rank, prm.world, nullptr, nullptr,
-                       nullptr, (cosine || pearson) ? J->inv_norm.get() : nullptr, finishes ? J->aux.get() : nullptr, (double)P.nU, part_cnt.get(),
+                       nullptr, (m.inv_norm || m.weight == ISIM_W_PEARSON) ? J->inv_norm.get() : nullptr, m.finishes ? J->aux.get() : nullptr, (double)P.nU, part_cnt.get(),
                        part.get(), 0, 0, cap};
         const unsigned grid = (unsigned)((int64_t)nb * nch);
         const size_t sp_c = t_cooc.begin();
@@ -224,21 +185,10 @@ fy_result* itemsim_rows(fy_itemsim_job* J, const fy_itemsim_request* rq) {
     const Prepared& P = J->P;
     const fy_itemsim_params& prm = J->prm;
     hipStream_t st = ctx->stream;
-    std::unique_ptr<fy_result> R(new fy_result);
-    R->ctx = ctx;
-    R->kind = 1;
+    std::unique_ptr<fy_result> R = isim_empty_result(ctx, P);
     R->has_itemsim_request_stats = true;
     R->irq.items_asked = rq->n_items;
     R->irq.chunks = J->nch;
-    R->st.nnz = P.nnz;
-    R->st.n_users = P.nU;
-    R->st.n_items = P.nI;
-    R->d_key0.alloc(ctx, 0);
-    R->d_key1.alloc(ctx, 0);
-    R->d_value.alloc(ctx, 0);
-    R->d_aux.alloc(ctx, 0);
-    R->d_user_id.alloc(ctx, 0);
-    R->d_item_id.alloc(ctx, 0);
     if (P.nnz == 0 || rq->n_items == 0) return R.release();
 
     // ---- the request: known items of this rank's shard, once each, in the order of the full build (popularity rank)
@@ -279,15 +229,11 @@ fy_result* itemsim_rows(fy_itemsim_job* J, const fy_itemsim_request* rq) {
     d2h(ctx, h_cnt.data(), cnt.get(), (size_t)n);
     const int64_t n_out = fetch(ctx, off.get() + n);
     for (int32_t c : h_cnt) R->irq.rows_emitted += c > 0;
-    R->n = n_out;
-    R->d_key0.alloc(ctx, (size_t)n_out);
-    R->d_key1.alloc(ctx, (size_t)n_out);
-    R->d_value.alloc(ctx, (size_t)n_out);
-    R->d_aux.alloc(ctx, (size_t)n_out);
+    isim_result_rows(R.get(), n_out);
     if (n_out > 0) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n * 64, 256), 256 * 16));
-        k_isim_req_compact<<<grid, 256, 0, st>>>((int32_t)n, K, d_rows.get(), cnt.get(), off.get(), other.get(), sim.get(), P.rank_item_raw.get(),
-                                                 R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get());
+        k_isim_compact<<<grid, 256, 0, st>>>((int32_t)n, K, d_rows.get(), 0, 0, cnt.get(), off.get(), other.get(), sim.get(), P.rank_item_raw.get(),
+                                             R->d_key0.get(), R->d_key1.get(), R->d_value.get(), R->d_aux.get());
         FY_KERNEL_CHECK();
     }
     t_topn.end(sp_t);

@@ -1,6 +1,7 @@
 // fy_itemsim_request.hpp -- the prepared item-similarity job (fy_itemsim_prepare: fy_itemsim.hip) and its request pass
 // (fy_itemsim_rows: fy_itemsim_request.hip).
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "fy_prep.hpp"
@@ -38,6 +39,9 @@ struct fy_itemsim_job {
 };
 
 namespace fy {
+// the empty result of kind 1 over a job's structure, and its arrays sized for n rows (fy_itemsim.hip)
+std::unique_ptr<fy_result> isim_empty_result(Context*, const Prepared&);
+void isim_result_rows(fy_result*, int64_t n);
 fy_itemsim_job* itemsim_prepare(Context*, const fy_itemsim_params*, const fy_ratings*);
 fy_result* itemsim_rows(fy_itemsim_job*, const fy_itemsim_request*);
 // rows of the given popularity ranks (device, ascending) -> cnt[n], other[n * K] (raw ids), sim[n * K]; returns the batches launched

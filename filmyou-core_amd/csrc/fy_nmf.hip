@@ -19,11 +19,6 @@
 
 namespace fy {
 
-static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 constexpr int NMF_MAX_K = 256;
 constexpr int NMF_GRAM_BLOCKS = 256;
 

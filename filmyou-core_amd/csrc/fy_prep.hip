@@ -86,11 +86,6 @@ void inclusive_scan_i64(Context* c, const int64_t* in, int64_t* out, size_t n) {
 // ---------------------------------------------------------------- kernels
 enum { ERR_NEG_ID = 1, ERR_DUP = 2, ERR_CLUSTER_RANGE = 4, NOTE_NOT_FP16 = 8, NOTE_NONPOSITIVE = 16 };
 
-static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 // largest user / item id among the kept ratings: the sort keys are packed into as few bits as the ids need (every 8 bits
 // less is one radix pass over 25 M pairs less)
 __global__ void k_max_ids(int64_t n, const int32_t* __restrict__ user, const int32_t* __restrict__ item,

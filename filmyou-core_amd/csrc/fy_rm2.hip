@@ -26,11 +26,6 @@
 
 namespace fy {
 
-static inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
-    int64_t g = ceil_div(n, block);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 // ================================================================ statistics (jobs RM2-1 / RM2-2)
 // One walk over the CSC gives everything that is summed per (cluster, item) column: this rank's PARTIAL rating sum (users
 // in slots [lo, hi), the exchange buffer), b = sum_v r_vi / s_v, and the row kernel's work model sum_v n_v.

@@ -511,15 +511,6 @@ struct TopNArgs {
     const int32_t* __restrict__ quad_prefix;
 };
 
-__device__ __forceinline__ uint32_t fy_order_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fy_order_unkey(uint32_t k) {
-    const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    return __uint_as_float(b);
-}
-
 constexpr int TOPN_MAX = 2048;       // longest list (min(numberOfRecommendations, items of the cluster))
 constexpr int TOPN_CAP = 4096;       // candidate buffer of k_topn_fast (LDS)
 constexpr int TOPN_BINS = 4096;
@@ -527,23 +518,6 @@ constexpr int TOPN_SAMPLE = 1024;    // leading columns that give the lower boun
 constexpr int TOPN_LONG = 256;       // lists longer than this take k_topn_long
 constexpr int PRUNE_BLOCK_COLS = 256;   // candidate block of the branch and bound = one column chunk
 constexpr int SEED_CHUNKS_MAX = 40;     // widest seed of the branch and bound: 5 N columns for the longest list (TOPN_MAX), in 256-column chunks
-
-// descending bitonic sort of P2 (power of two) 64-bit keys in LDS; every thread of the block calls it
-__device__ __forceinline__ void fy_bitonic_desc(uint64_t* v, int P2) {
-    for (int k = 2; k <= P2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P2; i += blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const uint64_t x = v[i], y = v[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (x < y) : (x > y)) { v[i] = y; v[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 // Fast path, one pass over the score row.  The columns are in popularity order and RM2 scores grow with the
 // popularity of the candidate, so the K-th best of the first TOPN_SAMPLE columns is a tight LOWER bound tau of the

@@ -39,7 +39,7 @@ def limits():
         assert m, name
         return int(m.group(1)), _product(m.group(2))
     L = {"NMF_CHUNK": const(nmf, "NMF_CHUNK"), "NMF_MAX_K": const(nmf, "NMF_MAX_K"), "RF_CHUNK": const(refine, "RF_CHUNK"),
-         "RF_MAX_K": const(refine, "RF_MAX_K"), "NMF_GRAM_BLOCKS": const(nmf, "NMF_GRAM_BLOCKS"), "grid_for": grid(nmf, "grid_for"), "rf_grid": grid(refine, "rf_grid")}
+         "RF_MAX_K": const(refine, "RF_MAX_K"), "NMF_GRAM_BLOCKS": const(nmf, "NMF_GRAM_BLOCKS"), "grid_for": grid(source("fy_common.hpp"), "grid_for"), "rf_grid": grid(refine, "rf_grid")}
     m = re.search(r"grid_thread = .*?min<int64_t>\((\d+), \(\(int64_t\)n_rows \+ 255\) / 256\)", cluster)
     w = re.search(r"grid_wave = .*?min<int64_t>\((\d+), \(\(int64_t\)n_rows \+ 3\) / 4\)", cluster)
     assert m and w

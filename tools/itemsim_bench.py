@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the item-item similarity build for every measure: `python tools/itemsim_bench.py [--shape ml25m] [--k 100] [--reps 5]
-[--out profiles/itemsim/measures_ml25m.json]`.
+[--out profiles/itemsim/measures_ml25m.json] [--job KEY=VALUE ...] [--dump DIR]`.
 
 For each of the seven measures of include/filmyou.h at a `synth` shape: the build on the default route, with the symmetric
 build forced where the measure admits it (FY_ISIM_GRAM=1) and on the forced row-at-a-time route (FY_ISIM_GRAM=0), one warm-up run
@@ -8,7 +8,13 @@ each, then `reps` timed runs, ALTERNATING the routes.  Reported per
 (measure, route): every run's whole-build time (fy_stats ms_total: device time from the prepared structure to the compacted
 rows) and its kernels' time (ms_cooc), the median and spread (max - min) of the whole build, unordered_pairs / s from the median,
 and which route ran (symmetric = the upper triangle + band sweep, fy_stats isim_candidates > 0; otherwise row at a time).  The
-ratings are resident (one Ratings object); nothing is compared here -- tests/test_itemsim_measures_gpu.py does that."""
+ratings are resident (one Ratings object); nothing is compared here -- tests/test_itemsim_measures_gpu.py does that.
+
+`--job KEY=VALUE` (repeatable; the value is JSON) passes a further argument to RowSimilarityJob.run: excludeSelfSimilarity=false,
+threshold=0.25, world=2, rank=1, minPrefsPerUser=20, maxPrefsPerUser=100.  `--dump DIR` writes the rows of the first run of each
+(measure, route) as DIR/<measure>.<route>.{item,other,sim}.npy, in the order the job returned them, and DIR/stats.json with that
+run's recs, isim_candidates, isim_redone_rows and cooc_launches: two builds of the library are compared byte for byte that way
+(`--reps 0` runs nothing else)."""
 import argparse
 import importlib
 import json
@@ -28,7 +34,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--measures", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--job", action="append", default=[], metavar="KEY=VALUE")
+    ap.add_argument("--dump", default="")
     a = ap.parse_args()
+    job_kw = {k: json.loads(v) for k, v in (kv.split("=", 1) for kv in a.job)}
+    dumped = {}
     import torch
     if not torch.cuda.is_available():
         sys.exit("itemsim_bench: no GPU (there is no CPU fallback and no CPU timing)")
@@ -53,8 +63,15 @@ def main():
             os.environ.pop("FY_ISIM_GRAM", None)
         else:
             os.environ["FY_ISIM_GRAM"] = forced
-        res = job.run(R, similarityClassname=measure, maxSimilaritiesPerRow=a.k)
+        res = job.run(R, similarityClassname=measure, maxSimilaritiesPerRow=a.k, **job_kw)
         st = dict(res.stats)
+        if a.dump and (measure, route) not in dumped:
+            os.makedirs(a.dump, exist_ok=True)
+            for name, arr in res.rows().items():
+                np.save(os.path.join(a.dump, "%s.%s.%s.npy" % (measure, route, name)), arr)
+            dumped[(measure, route)] = {k: st[k] for k in ("recs", "isim_candidates", "isim_redone_rows", "cooc_launches")}
+            with open(os.path.join(a.dump, "stats.json"), "w") as f:
+                json.dump({"%s.%s" % k: v for k, v in dumped.items()}, f, indent=1, sort_keys=True)
         res.close()
         return st
 
@@ -73,6 +90,8 @@ def main():
                 r["route_ran"] = "symmetric" if st["isim_candidates"] > 0 else "row_at_a_time"
                 r["unordered_pairs"] = st["unordered_pairs"]
                 r["rows"] = st["recs"]
+        if a.reps == 0:
+            continue
         for r in rec.values():
             t = r["ms_total_runs"]
             r["ms_total_median"] = float(np.median(t))

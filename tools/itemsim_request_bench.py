@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times requests for the similarity rows of named items (RowSimilarityJob.prepare + PreparedItemSimilarity.rows) beside the full build:
 `python tools/itemsim_request_bench.py [--shape ml25m] [--measure SIMILARITY_COSINE,SIMILARITY_LOGLIKELIHOOD] [--sizes 1,100,10000]
- [--reps 5] [--k 100] [--out profiles/itemsim_request/ml25m.json]`.
+ [--reps 5] [--k 100] [--out profiles/itemsim_request/ml25m.json] [--dump DIR]`.
 
 The ratings are put into HBM once.  Per measure a job is prepared once and kept; after one warm-up of every configuration, `reps`
 rounds ALTERNATE them in one run:
@@ -17,7 +17,11 @@ THE SAME RUN, are evaluated and printed, never enforced:
   prepare takes no longer than the full build plus the spread observed across the rounds (the larger of the two spreads).
 `break_even_share`: the share of the items at which a request costs a full build, interpolated linearly between the two measured
 request sizes that bracket the full build's median (None: every request, the all-items one included, is cheaper).  Nothing is
-compared for correctness here: tests/test_itemsim_request_gpu.py does that."""
+compared for correctness here: tests/test_itemsim_request_gpu.py does that.
+
+`--dump DIR` writes the rows of the first request of each size (the items are fixed by --seed) as
+DIR/<measure>.<rows:N>.{item,other,sim}.npy, in the order the request returned them, and DIR/stats.json with that request's recs and
+request statistics: two builds of the library are compared byte for byte that way (`--reps 0` runs nothing else)."""
 import argparse
 import importlib
 import json
@@ -53,7 +57,9 @@ def main():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--seed", type=int, default=20261018)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dump", default="")
     a = ap.parse_args()
+    dumped = {}
     import torch
     if not torch.cuda.is_available():
         sys.exit("itemsim_request_bench: no GPU (there is no CPU fallback and no CPU timing)")
@@ -92,6 +98,13 @@ def main():
                 res = prepared.rows(asked[name])
                 info[name] = dict(res.request_stats, recs=res.stats["recs"], lib_ms_total=res.stats["ms_total"], lib_ms_cooc=res.stats["ms_cooc"],
                                   lib_ms_topn=res.stats["ms_topn"])
+                if a.dump and (measure, name) not in dumped:
+                    os.makedirs(a.dump, exist_ok=True)
+                    for col, arr in res.rows().items():
+                        np.save(os.path.join(a.dump, "%s.%s.%s.npy" % (measure, name.replace(":", "_"), col)), arr)
+                    dumped[(measure, name)] = dict(res.request_stats, recs=res.stats["recs"], cooc_launches=res.stats["cooc_launches"])
+                    with open(os.path.join(a.dump, "stats.json"), "w") as f:
+                        json.dump({"%s.%s" % k: v for k, v in dumped.items()}, f, indent=1, sort_keys=True)
             e1.record(stream)
             e1.synchronize()
             wall = (time.perf_counter() - t0) * 1e3
@@ -107,6 +120,8 @@ def main():
                 times[c][0].append(ms)
                 times[c][1].append(wall)
         prepared.close()
+        if a.reps == 0:
+            continue
         rec = {c: dict(summary(*times[c]), **info.get(c, {})) for c in configs}
         full = rec["full"]
         print("== %s, %s, K = %d, %d rounds" % (a.shape, measure, a.k, a.reps), flush=True)
