@@ -40,6 +40,19 @@ void sort_pairs_u64_f32(Context* c, uint64_t* kin, uint64_t* kout, float* vin, f
 void sort_keys_u64(Context* c, uint64_t* kin, uint64_t* kout, size_t n, int end_bit, int begin_bit) {
     if (n == 0) return;
     size_t bytes = 0;
+    if (begin_bit > 0 && end_bit >= 64) {
+        // rocPRIM sorts up to 2^20 keys by merging, with a comparison that masks the keys by (T(1) << end_bit) - 1 ^ (T(1) << begin_bit) - 1
+        // (device/detail/device_radix_sort.hpp, radix_merge_compare): for end_bit == 64 the first shift has no value, the mask comes out
+        // as the bits BELOW begin_bit and the keys are ordered by those.  The packed user sort reaches bit 64 when ib + ub + 16 == 64
+        // (1 400 ratings with 24-bit ids on both axes came back ordered by item, and the job reported a duplicate rating).  Such a sort
+        // takes the radix passes, which count the bits, whatever its size: the same stable order.  (The pair sorts never get here:
+        // their keys end at ib + ub <= 63.)
+        using radix_only = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
+        FY_HIP(rocprim::radix_sort_keys<radix_only>(nullptr, bytes, kin, kout, n, (unsigned)begin_bit, 64u, c->stream));
+        DevBuf<char> tmp(c, bytes);
+        FY_HIP(rocprim::radix_sort_keys<radix_only>(tmp.get(), bytes, kin, kout, n, (unsigned)begin_bit, 64u, c->stream));
+        return;
+    }
     FY_HIP(rocprim::radix_sort_keys(nullptr, bytes, kin, kout, n, (unsigned)begin_bit, (unsigned)end_bit, c->stream));
     DevBuf<char> tmp(c, bytes);
     FY_HIP(rocprim::radix_sort_keys(tmp.get(), bytes, kin, kout, n, (unsigned)begin_bit, (unsigned)end_bit, c->stream));
@@ -755,7 +768,8 @@ void build_structure(Context* ctx, const fy_ratings* R, int32_t K, int64_t n_map
     // nnz-sized sorts move KEYS ALONE -- 16 bytes per rating and pass instead of 24 / 32 / 24.
     int pb = 0;
     if (n_in) {
-        const int ib0 = std::max(1, bits_for((uint64_t)std::max(0, R->max_item))), ub0 = std::max(1, bits_for((uint64_t)(R->max_user + 1)));
+        // (max_user + 1 in 64 bits: user id 2^31 - 1 is legal input and the int32 sum has no value)
+        const int ib0 = std::max(1, bits_for((uint64_t)std::max(0, R->max_item))), ub0 = std::max(1, bits_for((uint64_t)((int64_t)R->max_user + 1)));
         const int kb0 = bits_for((uint64_t)std::max(0, K - 1));
         // (slots and item indices never need more bits than the user / item ids they number)
         if (ctx->tune.prep_packed && R->scores_fp16_exact && ib0 + ub0 + 16 <= 64 && kb0 + ib0 + ub0 + 16 <= 64) pb = 16;
@@ -764,7 +778,7 @@ void build_structure(Context* ctx, const fy_ratings* R, int32_t K, int64_t n_map
     if (n_in) {
         // (the id bounds were found when the ratings entered HBM, fy_ratings_create: a property of the container like nnz)
         const int32_t hmax[2] = {R->max_user, R->max_item};
-        const uint32_t drop_user = (uint32_t)(hmax[0] + 1);
+        const uint32_t drop_user = (uint32_t)hmax[0] + 1u;       // at most 2^31: fits, and no signed sum
         ib = std::max(1, bits_for((uint64_t)std::max(0, hmax[1])));
         const int ub = std::max(1, bits_for(drop_user));
         k_user_item_keys<<<grid_for(n_in), 256, 0, st>>>(n_in, R->user.get(), R->item.get(), R->score.get(),

@@ -418,8 +418,10 @@ void build_submap(Context* ctx, const fy_ratings* R, int32_t K, int64_t n_map, c
         max_map = std::max(max_map, map_user[t]);
     }
     if (std::max(max_map, R->max_user) == INT32_MAX) FY_FAIL(FY_ERR_UNSUPPORTED, "user id 2^31 - 1");
-    const int32_t nT = std::max(max_map, R->max_user) + 1, I = R->max_item + 1;
-    if ((int64_t)K * std::max(I, 1) + 1 > (int64_t)INT32_MAX) FY_FAIL(FY_ERR_UNSUPPORTED, "numberOfClusters x (largest item id + 1) exceeds 2^31");
+    const int32_t nT = std::max(max_map, R->max_user) + 1;
+    const int64_t I64 = (int64_t)R->max_item + 1;       // (item id 2^31 - 1: the sum has no int32 value; refused by the bound below)
+    if ((int64_t)K * std::max<int64_t>(I64, 1) + 1 > (int64_t)INT32_MAX) FY_FAIL(FY_ERR_UNSUPPORTED, "numberOfClusters x (largest item id + 1) exceeds 2^31");
+    const int32_t I = (int32_t)I64;
     P.ctx = ctx; P.K = K; P.n_tab = nT; P.I = I;
     P.launches = 0;
     const int64_t n_in = R->nnz;

@@ -76,7 +76,15 @@ void* fy_context_stream(fy_context*);
  * mappers receive them: table ratings(user int, item int, score float) (test/.../util/CassandraUtils.java:93-94) or
  * SequenceFile<IntPairWritable(user,item), FloatWritable> (M/util/DataInitialization.java:164-172).
  * `location`: FY_HOST pointers are copied over PCIe; FY_DEVICE pointers (HBM of the context's GPU) are copied
- * device-to-device, so the caller keeps ownership either way. */
+ * device-to-device, so the caller keeps ownership either way.
+ * Id range: every user and item id in [0, 2^31 - 1] is accepted (a negative id is FY_ERR_NEGATIVE_ID), sparse or dense; the
+ * jobs depend on the ids through their order alone.  RM2, item similarity and item-based CF (full jobs and requests) size
+ * nothing by the largest id, with two exceptions that only switch an optimisation off: RM2's refinement pass keeps a table of
+ * (largest item id + 1) entries and runs only while that id is below 2^28, and the sharded multi-rank prep lays its exchange
+ * buffer out by raw id and is used only while (largest user id + 1) + (largest item id + 1) <= 2^25.  fy_submap_create and
+ * fy_cluster_refine DO size their tables by raw id (largest user id of ratings and map + 1 entries; numberOfClusters x (largest
+ * item id + 1) entries): user id 2^31 - 1, or that product reaching 2^31, is FY_ERR_UNSUPPORTED.  fy_nmf_* takes ids in
+ * [1, numberOfUsers] / [1, numberOfItems] by contract. */
 enum { FY_HOST = 0, FY_DEVICE = 1 };
 int fy_ratings_create(fy_context*, int64_t nnz, const int32_t* user, const int32_t* item, const float* score,
                       int location, fy_ratings** out);
