@@ -489,6 +489,9 @@ struct MEpilogue {
     int32_t head_rows;
     double* __restrict__ tail32;
     int32_t tail_from;
+    // fp64 accumulators (the unpacked walk, FY_COOC_FX=0): the scale of those copies in fp64 -- w2 is its fp32 rounding, which would leave
+    // 6e-8 relative on every copied element; the sums themselves are ds_add_f64 sums, good to a few 2^-53 in whatever order they came
+    double w2d;
 };
 
 // Cross-lane maxima of the epilogue without an LDS instruction (as ds_bpermute shuffles the six steps of a 64-lane maximum were six
@@ -538,7 +541,7 @@ __device__ __forceinline__ void cooc_rm2_tail_copy(const CoocArgs& A, const MEpi
         for (int k = 0; k < 8; k++) {
             const ACC a = acc[cooc_acc_index(col - c0 + k, A.acc_quarter)];
             if constexpr (std::is_integral<ACC>::value) t[k] = (double)a * E.fx_inv;
-            else t[k] = (double)E.w2 * (double)a;
+            else t[k] = E.w2d * (double)a;
         }
         double2* __restrict__ o = reinterpret_cast<double2*>(tp + col);
 #pragma unroll
@@ -639,7 +642,7 @@ __device__ __forceinline__ void cooc_rm2_epilogue_pack(const CoocArgs& A, const 
             for (int q = 0; q < 4; q++) {
                 float f;                                      // columns >= Ic were never touched: 0
                 if constexpr (std::is_integral<ACC>::value) { const double d = (double)ap[q * qs] * E.fx_inv; f = (float)d; if constexpr (COPY) f4[q] = d; }
-                else { f = E.w2 * (float)ap[q * qs]; if constexpr (COPY) f4[q] = (double)E.w2 * (double)ap[q * qs]; }
+                else { f = E.w2 * (float)ap[q * qs]; if constexpr (COPY) f4[q] = E.w2d * (double)ap[q * qs]; }
                 ap[q * qs] = (ACC)0;
                 v[q] = (__float_as_uint(f) + radd) >> FY_P24_SHIFT;    // 0 <= f < 2: 7 exponent + 17 mantissa bits, round to nearest (or up)
             }
@@ -2251,7 +2254,9 @@ static ClusterPass cluster_pass(const ScoreShared& X, const ClusterVisit& V) {
     ClusterPass C{X, V, p, *V.L, V.ls, J->ctx, J->P, tune};
     C.fxk = (X.jp->use_pk && tune.cooc_fx && !J->fx_bounds.empty()) ? fx_exponent(&J->fx_bounds[3 * (size_t)p.c]) : -1;
     C.w2s = J->S->smooth.w2_of(J->prm.lambda) * (double)X.gscale[(size_t)p.c];
-    C.refine = tune.refine && p.pack24 && !p.coop && C.fxk >= 0 && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
+    // (either accumulator the job computes with: the fixed-point sums, or the fp64 sums of the unpacked walk -- a rating of 3.3 must not cost a
+    // job its refinement pass; not the fp32 accumulators of the measurement build alone)
+    C.refine = tune.refine && p.pack24 && !p.coop && (C.fxk >= 0 || !tune.cooc_f32) && J->S->max_item >= 0 && J->S->max_item < (1 << 28) && p.Ic >= 8;
     C.head_rows = (int32_t)std::min<int64_t>(p.Ic & ~3, std::max<int64_t>(256, std::min<int64_t>(1024, (int64_t)tune.seed_chunks * 256)));
     // the rows that keep their head columns in tail32: symmetric panel mode, the tail rows; the walk from the unpopular side, the rows
     // behind the first chunk (the head rows do not walk them; head rows that all lie in the first chunk store nothing behind it)
@@ -2319,6 +2324,7 @@ static void build_cluster_matrix(const ClusterPass& C) {
         if (C.tail_from < Ic) V.T32->alloc(ctx, (size_t)std::max(1, Ic - C.tail_from) * C.head_rows + 4);
         ME.head32 = V.H32->get(); ME.ld_head = C.ld_head; ME.head_rows = C.head_rows;
         ME.tail32 = C.tail_from < Ic ? V.T32->get() : nullptr; ME.tail_from = C.tail_from;
+        ME.w2d = w2s;
     }
     if (p.panel) X.R->st.panel_clusters++;
     if (p.panel || p.prune) {     // the bound matrix starts at zero; the maxima of a and b over its blocks (panel mode: 64-column sub-blocks)
