@@ -15,10 +15,10 @@ from ._native import build, LIB_PATH
 from .host import (BaselineRecommenderJob, ClusterAssignmentJob, Configuration, Context, FilmYouError, ItemRecommendations, ItemSimilarities, NMFDriver, PreparedItemSimilarity, PreparedRM2, Ratings, Recommendations, RM2Job,
                    RowSimilarityJob, SIMILARITY_COSINE, SIMILARITY_COOCCURRENCE, SIMILARITY_TANIMOTO_COEFFICIENT, SIMILARITY_LOGLIKELIHOOD,
                    SIMILARITY_CITY_BLOCK, SIMILARITY_EUCLIDEAN_DISTANCE, SIMILARITY_PEARSON_CORRELATION, ClusterRefinementJob, RMRecommenderDriver,
-                   SubClusterMappingJob, SubClusterMappings, read_id_file, write_similarity_pairs)
+                   SubClusterMappingJob, SubClusterMappings, read_id_file, write_similarity_pairs, Evaluation, Evaluator)
 
 __all__ = ["build", "BaselineRecommenderJob", "ClusterAssignmentJob", "ItemRecommendations", "NMFDriver", "LIB_PATH", "Configuration", "Context", "FilmYouError", "ItemSimilarities", "PreparedItemSimilarity", "PreparedRM2", "Ratings",
            "Recommendations", "RM2Job", "RowSimilarityJob", "SIMILARITY_COSINE", "SIMILARITY_COOCCURRENCE", "SIMILARITY_TANIMOTO_COEFFICIENT",
            "SIMILARITY_LOGLIKELIHOOD", "SIMILARITY_CITY_BLOCK", "SIMILARITY_EUCLIDEAN_DISTANCE", "SIMILARITY_PEARSON_CORRELATION", "_native",
            "ClusterRefinementJob", "RMRecommenderDriver", "SubClusterMappingJob", "SubClusterMappings", "read_id_file",
-           "write_similarity_pairs"]
+           "write_similarity_pairs", "Evaluation", "Evaluator"]

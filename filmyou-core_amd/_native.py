@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp"]
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_eval.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -32,6 +32,7 @@ SYMBOLS = [
     "fy_submap_items", "fy_submap_matrix", "fy_submap_destroy", "fy_cluster_refine", "fy_refined_n_users", "fy_refined_n_counts",
     "fy_refined_clustering", "fy_refined_layout", "fy_refined_h_size", "fy_refined_w_size", "fy_refined_factors",
     "fy_refined_stats", "fy_refined_free",
+    "fy_ratings_holdout", "fy_result_create_lists", "fy_eval_prepare", "fy_eval_lists", "fy_eval_destroy",
 ]
 
 
@@ -199,6 +200,19 @@ class RatingsUpdateStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class EvalParams(C.Structure):
+    _fields_ = [("n_cutoffs", C.c_int32), ("cutoffs", C.c_int32 * 8), ("gain", C.c_int32), ("flags", C.c_uint32),
+                ("relevance_threshold", C.c_double)]
+
+
+class EvalSums(C.Structure):
+    _fields_ = [("lists", C.c_int64), ("users_evaluated", C.c_int64), ("lists_without_relevant", C.c_int64),
+                ("relevant_users", C.c_int64), ("relevant_entries", C.c_int64), ("distinct_items", C.c_int64),
+                ("n_cutoffs", C.c_int32), ("reserved", C.c_int32), ("cutoffs", C.c_int32 * 8), ("hits", C.c_int64 * 8),
+                ("users_hit", C.c_int64 * 8), ("recall", C.c_double * 8), ("ap", C.c_double * 8), ("rr", C.c_double * 8),
+                ("ndcg", C.c_double * 8), ("ms", C.c_double)]
+
+
 class Stats(C.Structure):
     _fields_ = [("nnz", C.c_int64), ("n_users", C.c_int64), ("n_items", C.c_int64),
                 ("n_clusters_nonempty", C.c_int64), ("users_scored", C.c_int64), ("recs", C.c_int64),
@@ -332,5 +346,11 @@ def load():
     L.fy_refined_stats.argtypes = [vp, C.POINTER(RefineStats)]
     L.fy_refined_free.argtypes = [vp]
     L.fy_refined_free.restype = None
+    L.fy_ratings_holdout.argtypes = [vp, vp, C.c_double, C.c_uint64, pvp, pvp]
+    L.fy_result_create_lists.argtypes = [vp, i64, vp, vp, vp, C.c_int, pvp]
+    L.fy_eval_prepare.argtypes = [vp, C.POINTER(EvalParams), vp, pvp]
+    L.fy_eval_lists.argtypes = [vp, vp, C.POINTER(EvalSums), vp, vp]
+    L.fy_eval_destroy.argtypes = [vp]
+    L.fy_eval_destroy.restype = None
     _lib = L
     return L

@@ -12,6 +12,7 @@
 #include "fy_rm2_request.hpp"
 #include "fy_itemsim_request.hpp"
 #include "fy_itemcf_request.hpp"
+#include "fy_eval.hpp"
 
 namespace fy {
 static thread_local char g_err[512] = "";
@@ -511,6 +512,60 @@ int fy_itemsim_pairs(fy_context* c, fy_result* sims, fy_result** out) {
     FY_HIP(hipSetDevice(c->c.device));
     *out = fy::itemsim_pairs(&c->c, sims);
     FY_CATCH
+}
+
+// ---------------------------------------------------------------- offline evaluation
+int fy_ratings_holdout(fy_context* c, const fy_ratings* r, double fraction, uint64_t seed, fy_ratings** train, fy_ratings** test) {
+    if (train) *train = nullptr;
+    if (test) *test = nullptr;
+    if (!train || !test) { set_error("train or test is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!c || !r) { set_error("context or ratings is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->ctx != &c->c) { set_error("ratings belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    fy::ratings_holdout(&c->c, r, fraction, seed, train, test);
+    FY_CATCH
+}
+
+int fy_result_create_lists(fy_context* c, int64_t n, const int32_t* user, const int32_t* item, const float* value, int location, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!c) { set_error("context is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (n < 0 || (n > 0 && (!user || !item || !value))) { set_error("row arrays are NULL or n < 0"); return FY_ERR_INVALID_ARGUMENT; }
+    if (location != FY_HOST && location != FY_DEVICE) { set_error("location must be FY_HOST or FY_DEVICE"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::result_create_lists(&c->c, n, user, item, value, location);
+    FY_CATCH
+}
+
+int fy_eval_prepare(fy_context* c, const fy_eval_params* p, const fy_ratings* test, fy_eval** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!c || !p || !test) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (test->ctx != &c->c) { set_error("ratings belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::eval_prepare(&c->c, p, test);
+    FY_CATCH
+}
+
+int fy_eval_lists(fy_eval* e, fy_result* lists, fy_eval_sums* out, int32_t* per_user_id_or_null, double* per_user_or_null) {
+    if (!e || !lists || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (lists->ctx != e->ctx) { set_error("the lists belong to another context (or live on the host only)"); return FY_ERR_INVALID_ARGUMENT; }
+    if (lists->kind != 0 && lists->kind != 2) { set_error("not a list result: item similarities and item pairs cannot be evaluated"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(e->ctx);
+    fy::eval_lists(e, lists, out, per_user_id_or_null, per_user_or_null);
+    FY_CATCH
+}
+
+void fy_eval_destroy(fy_eval* e) {
+    if (!e) return;
+    fy::Context* ctx = e->ctx;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    delete e;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
 }
 
 // ---------------------------------------------------------------- results

@@ -230,6 +230,14 @@ class Ratings:
         r.update_stats = st.as_dict()
         return r
 
+    def holdout(self, fraction, seed=0):
+        """fy_ratings_holdout: ``(train, test)``, two new Ratings.  A rating goes to ``test`` by a hash of its (user, item) and
+        ``seed`` alone (include/filmyou.h states it), so its side does not change when other ratings are written; both sides
+        keep this object's order and the scores' bits.  This object is only read."""
+        tr, te = C.c_void_p(), C.c_void_p()
+        _check(self._lib.fy_ratings_holdout(self.ctx._h, self._h, float(fraction), int(seed) & (2 ** 64 - 1), C.byref(tr), C.byref(te)))
+        return (Ratings._adopt(self.ctx, tr, int(self._lib.fy_ratings_nnz(tr))), Ratings._adopt(self.ctx, te, int(self._lib.fy_ratings_nnz(te))))
+
     def to_host(self):
         """fy_ratings_copy_out: (user, item, score) numpy arrays of the COO as it lives in HBM, in its order."""
         n = int(self._lib.fy_ratings_nnz(self._h))
@@ -674,6 +682,138 @@ class ItemRecommendations(_Result):
             self._rows = {"user": _np(L.fy_result_key0(h), n, np.int32), "item": _np(L.fy_result_key1(h), n, np.int32),
                           "score": _np(L.fy_result_value(h), n, np.float32)}
         return self._rows
+
+    @classmethod
+    def from_rows(cls, ctx, user, item, score):
+        """fy_result_create_lists: a list result from rows made elsewhere (the reference's own output read by
+        seqfile.read_intpair_float, say), so that ``Evaluator.evaluate`` can take them.  Rows as given: grouped by user, best
+        first; a user with two separate runs of rows is refused.  Numpy arrays or torch tensors on the context's GPU."""
+        lib = _native.load()
+        if _is_torch_tensor(user):
+            import torch
+            assert user.is_cuda and item.is_cuda and score.is_cuda, "device tensors expected"
+            assert user.dtype == torch.int32 and item.dtype == torch.int32 and score.dtype == torch.float32
+            user, item, score = user.contiguous(), item.contiguous(), score.contiguous()
+            torch.cuda.current_stream(user.device).synchronize()   # producer stream != the context's stream
+            n, ptrs, loc = user.numel(), (user.data_ptr(), item.data_ptr(), score.data_ptr()), 1
+        else:
+            user, item = _i32(user), _i32(item)
+            score = np.ascontiguousarray(score, dtype=np.float32)
+            n, ptrs, loc = len(user), (user.ctypes.data, item.ctypes.data, score.ctypes.data), 0
+        assert n == len(item) == len(score)
+        res = C.c_void_p()
+        _check(lib.fy_result_create_lists(ctx._h, n, ptrs[0], ptrs[1], ptrs[2], loc, C.byref(res)))
+        return cls(res, ctx)
+
+
+class Evaluation:
+    """What ``Evaluator.evaluate`` returns: the counters and, per cutoff, the SUMS over the evaluated lists (fy_eval_sums), as
+    attributes and numpy arrays in cutoff order.  ``per_user`` (None unless asked for): {"user": ids in list order, "hits",
+    "recall", "ap", "rr", "ndcg": lists x cutoffs float64, NaN for a list that was not evaluated}."""
+
+    COUNTERS = ("lists", "users_evaluated", "lists_without_relevant", "relevant_users", "relevant_entries")
+    SUMS = ("recall", "ap", "rr", "ndcg")
+
+    def __init__(self, cutoffs, counters, hits, users_hit, sums, distinct_items=None, ms=0.0, per_user=None):
+        self.cutoffs = tuple(int(c) for c in cutoffs)
+        for k in self.COUNTERS:
+            setattr(self, k, int(counters[k]))
+        self.hits = np.asarray(hits, dtype=np.int64)
+        self.users_hit = np.asarray(users_hit, dtype=np.int64)
+        for k in self.SUMS:
+            setattr(self, k, np.asarray(sums[k], dtype=np.float64))
+        self.distinct_items = distinct_items
+        self.ms = float(ms)
+        self.per_user = per_user
+
+    def means(self, count_missing=False):
+        """{"precision", "recall", "map", "mrr", "ndcg", "hit_rate": arrays in cutoff order}: the sums over ``users_evaluated``;
+        count_missing=True divides by ``relevant_users`` instead, so users with relevant test items and no list count as zeros.
+        NaN where that count is 0."""
+        d = float(self.relevant_users if count_missing else self.users_evaluated)
+        d = d if d > 0 else float("nan")
+        n = np.asarray(self.cutoffs, dtype=np.float64)
+        return {"precision": self.hits / (n * d), "recall": self.recall / d, "map": self.ap / d, "mrr": self.rr / d,
+                "ndcg": self.ndcg / d, "hit_rate": self.users_hit / d}
+
+    @classmethod
+    def merge(cls, parts):
+        """The evaluation of a multi-rank job from its ranks' evaluations (each rank evaluates its own lists with an evaluator
+        prepared from the same test ratings): counters and sums are added in the order given (rank order).  ``distinct_items`` is
+        None (the union of the ranks' item sets is not formed) and ``per_user`` is dropped."""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("nothing to merge")
+        first = parts[0]
+        for p in parts[1:]:
+            if p.cutoffs != first.cutoffs or p.relevant_users != first.relevant_users or p.relevant_entries != first.relevant_entries:
+                raise ValueError("the evaluations come from different evaluators")
+        counters = {k: sum(getattr(p, k) for p in parts) for k in ("lists", "users_evaluated", "lists_without_relevant")}
+        counters["relevant_users"], counters["relevant_entries"] = first.relevant_users, first.relevant_entries
+        sums = {}
+        for k in cls.SUMS:
+            acc = np.zeros(len(first.cutoffs), dtype=np.float64)
+            for p in parts:
+                acc = acc + getattr(p, k)
+            sums[k] = acc
+        return cls(first.cutoffs, counters, sum(p.hits for p in parts), sum(p.users_hit for p in parts), sums, None,
+                   sum(p.ms for p in parts))
+
+
+class Evaluator:
+    """Ranking metrics of list results where they lie in HBM (fy_eval_*; include/filmyou.h states the definitions).
+
+    Prepared once from the ``test`` Ratings (a hold-out, ``Ratings.holdout``): a test entry is relevant iff its score is
+    >= ``relevance_threshold``; ``gain`` = ``binary`` (1), ``linear`` (the score) or ``exp2`` (2^score - 1) for nDCG; ``cutoffs``
+    strictly ascending, each at most 4096; ``coverage`` also counts the distinct items recommended.  ``test`` may be closed
+    afterwards."""
+
+    GAIN = {"binary": 0, "linear": 1, "exp2": 2}
+
+    def __init__(self, ctx, test, cutoffs=(10,), relevance_threshold=4.0, gain="binary", coverage=False):
+        self._lib = _native.load()
+        self._ctx = ctx
+        self._h = None
+        if gain not in self.GAIN:
+            raise ValueError("gain must be binary, linear or exp2 (got %r)" % (gain,))
+        cutoffs = tuple(int(c) for c in cutoffs)
+        if not 1 <= len(cutoffs) <= 8:
+            raise ValueError("1 to 8 cutoffs")
+        p = _native.EvalParams(len(cutoffs), (C.c_int32 * 8)(*cutoffs), self.GAIN[gain], 1 if coverage else 0, float(relevance_threshold))
+        h = C.c_void_p()
+        _check(self._lib.fy_eval_prepare(ctx._h, C.byref(p), test._h, C.byref(h)))
+        self._h = h
+        self.cutoffs = cutoffs
+
+    def evaluate(self, result, per_user=False):
+        """fy_eval_lists on a ``Recommendations`` or ``ItemRecommendations`` of this evaluator's context.  Returns an ``Evaluation``."""
+        s = _native.EvalSums()
+        ids = vals = None
+        if per_user:
+            # `lists` is at most the result's row count; a first call without the arrays says how many there are
+            _check(self._lib.fy_eval_lists(self._h, result._h, C.byref(s), None, None))
+            ids = np.empty(s.lists, dtype=np.int32)
+            vals = np.empty((s.lists, len(self.cutoffs), 5), dtype=np.float64)
+        _check(self._lib.fy_eval_lists(self._h, result._h, C.byref(s), ids.ctypes.data if per_user else None,
+                                       vals.ctypes.data if per_user else None))
+        n = s.n_cutoffs
+        pu = None
+        if per_user:
+            pu = {"user": ids, "hits": vals[:, :, 0], "recall": vals[:, :, 1], "ap": vals[:, :, 2], "rr": vals[:, :, 3], "ndcg": vals[:, :, 4]}
+        return Evaluation(list(s.cutoffs)[:n], {k: getattr(s, k) for k in Evaluation.COUNTERS}, list(s.hits)[:n], list(s.users_hit)[:n],
+                          {k: list(getattr(s, k))[:n] for k in Evaluation.SUMS}, s.distinct_items if s.distinct_items >= 0 else None, s.ms, pu)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._ctx._h:
+                self._lib.fy_eval_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BaselineRecommenderJob:

@@ -20,6 +20,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/filmyou.h"
@@ -104,6 +105,86 @@ inline Ratings applyWrites(const Ratings& source, const Writes& w, fy_ratings_up
     fy_context_destroy(ctx);
     return out;
 }
+
+// The hold-out split of host records (fy_ratings_holdout): {train, test}, both in source order; a rating's side is a hash of its
+// (user, item) and the seed alone.  Like applyWrites this mirror moves records; a host that keeps its fy_ratings resident calls
+// fy_ratings_holdout itself.  Throws std::runtime_error("holdout failed!: ...").
+inline std::pair<Ratings, Ratings> holdout(const Ratings& source, double fraction, uint64_t seed = 0, int device = 0) {
+    fy_context* ctx = nullptr;
+    fy_ratings *src = nullptr, *part[2] = {nullptr, nullptr};
+    auto release = [&]() {
+        for (fy_ratings* p : part) fy_ratings_destroy(p);
+        fy_ratings_destroy(src);
+        if (ctx) fy_context_destroy(ctx);
+    };
+    auto fail = [&](const char* what) {
+        const std::string msg = std::string("holdout failed!: ") + what + ": " + fy_last_error();
+        release();
+        throw std::runtime_error(msg);
+    };
+    if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+    if (fy_ratings_create(ctx, (int64_t)source.user.size(), source.user.data(), source.item.data(), source.score.data(), FY_HOST, &src) != FY_OK) fail("ratings");
+    if (fy_ratings_holdout(ctx, src, fraction, seed, &part[0], &part[1]) != FY_OK) fail("split");
+    std::pair<Ratings, Ratings> out;
+    Ratings* side[2] = {&out.first, &out.second};
+    for (int k = 0; k < 2; k++) {
+        const size_t n = (size_t)fy_ratings_nnz(part[k]);
+        side[k]->user.resize(n); side[k]->item.resize(n); side[k]->score.resize(n);
+        if (fy_ratings_copy_out(part[k], side[k]->user.data(), side[k]->item.data(), side[k]->score.data()) != FY_OK) fail("copy_out");
+    }
+    release();
+    return out;
+}
+
+// Ranking metrics of list results where they lie in HBM (fy_eval_*; include/filmyou.h states the definitions): prepared once from
+// the test records on the caller's context, evaluate() takes any list result of that context.  The sums of fy_eval_sums are SUMS
+// over the evaluated lists; the mean* accessors divide by users_evaluated, or by relevant_users with countMissing (users with
+// relevant test items and no list then count as zeros).
+class Evaluator {
+   public:
+    Evaluator(fy_context* ctx, const Ratings& test, const std::vector<int32_t>& cutoffs = {10}, double relevanceThreshold = 4.0,
+              int gain = FY_EVAL_GAIN_BINARY, bool coverage = false) {
+        if (cutoffs.empty() || cutoffs.size() > FY_EVAL_MAX_CUTOFFS) throw std::invalid_argument("Evaluator: 1 to 8 cutoffs");
+        fy_eval_params p{};
+        p.n_cutoffs = (int32_t)cutoffs.size();
+        for (size_t k = 0; k < cutoffs.size(); k++) p.cutoffs[k] = cutoffs[k];
+        p.gain = gain;
+        p.flags = coverage ? FY_EVAL_COVERAGE : 0u;
+        p.relevance_threshold = relevanceThreshold;
+        fy_ratings* t = nullptr;
+        if (fy_ratings_create(ctx, (int64_t)test.user.size(), test.user.data(), test.item.data(), test.score.data(), FY_HOST, &t) != FY_OK)
+            throw std::runtime_error(std::string("Evaluator failed!: test ratings: ") + fy_last_error());
+        const int rc = fy_eval_prepare(ctx, &p, t, &eval_);
+        fy_ratings_destroy(t);      // the evaluator owns its tables
+        if (rc != FY_OK) throw std::runtime_error(std::string("Evaluator failed!: ") + fy_last_error());
+    }
+    Evaluator(const Evaluator&) = delete;
+    Evaluator& operator=(const Evaluator&) = delete;
+    ~Evaluator() { fy_eval_destroy(eval_); }      // before its context
+
+    fy_eval_sums evaluate(fy_result* lists, std::vector<int32_t>* perUserId = nullptr, std::vector<double>* perUser = nullptr) const {
+        fy_eval_sums s{};
+        if (perUserId || perUser) {     // `lists` is at most the row count
+            const size_t rows = (size_t)fy_result_size(lists);
+            if (perUserId) perUserId->assign(rows, 0);
+            if (perUser) perUser->assign(rows * 5 * FY_EVAL_MAX_CUTOFFS, 0.0);
+        }
+        if (fy_eval_lists(eval_, lists, &s, perUserId ? perUserId->data() : nullptr, perUser ? perUser->data() : nullptr) != FY_OK)
+            throw std::runtime_error(std::string("Evaluator failed!: ") + fy_last_error());
+        if (perUserId) perUserId->resize((size_t)s.lists);
+        if (perUser) perUser->resize((size_t)s.lists * 5 * (size_t)s.n_cutoffs);
+        return s;
+    }
+    static double users(const fy_eval_sums& s, bool countMissing) { return (double)(countMissing ? s.relevant_users : s.users_evaluated); }
+    static double meanPrecision(const fy_eval_sums& s, int c, bool countMissing = false) { return (double)s.hits[c] / ((double)s.cutoffs[c] * users(s, countMissing)); }
+    static double meanRecall(const fy_eval_sums& s, int c, bool countMissing = false) { return s.recall[c] / users(s, countMissing); }
+    static double meanAP(const fy_eval_sums& s, int c, bool countMissing = false) { return s.ap[c] / users(s, countMissing); }
+    static double meanRR(const fy_eval_sums& s, int c, bool countMissing = false) { return s.rr[c] / users(s, countMissing); }
+    static double meanNDCG(const fy_eval_sums& s, int c, bool countMissing = false) { return s.ndcg[c] / users(s, countMissing); }
+
+   private:
+    fy_eval* eval_ = nullptr;
+};
 
 // The smoothing of the user language model (include/filmyou.h, FY_RM2_SMOOTHING_*) from the Configuration keys `smoothing` (jm --
 // the default, parameter `lambda` --, dirichlet with `mu`, absoluteDiscounting with `delta`; case does not matter) into
@@ -205,6 +286,44 @@ class RM2Job {
         return 0;
     }
     int64_t allGathers = 0, reduceScatters = 0, collectiveBytes = 0;   // of the last runRank
+
+    // run() with the lists evaluated where they lie, before they are downloaded for the sink: one context, the staged entry points,
+    // an Evaluator prepared from `test` (cutoffs, relevanceThreshold, gain as in fy::host::Evaluator).  evaluation holds the sums.
+    fy_eval_sums evaluation{};
+    int runEvaluated(const Ratings& r, const Clustering& c, const Ratings& test, const std::vector<int32_t>& cutoffs, double relevanceThreshold,
+                     const PreferenceSink& sink, int gain = FY_EVAL_GAIN_BINARY, int device = 0) {
+        fy_rm2_params p = params();
+        fy_context* ctx = nullptr;
+        fy_ratings* rt = nullptr;
+        fy_rm2_job* job = nullptr;
+        fy_result* res = nullptr;
+        auto release = [&]() {
+            if (res) fy_result_free(res);
+            if (job) fy_rm2_job_destroy(job);
+            if (rt) fy_ratings_destroy(rt);
+            if (ctx) fy_context_destroy(ctx);
+        };
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("RM2 failed!: ") + what + ": " + fy_last_error();
+            release();
+            throw std::runtime_error(msg);
+        };
+        std::vector<int32_t> cc = counts(c, p.number_of_clusters);
+        if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+        if (fy_ratings_create(ctx, (int64_t)r.user.size(), r.user.data(), r.item.data(), r.score.data(), FY_HOST, &rt) != FY_OK) fail("ratings");
+        if (fy_rm2_prepare(ctx, &p, rt, (int64_t)c.user.size(), c.user.data(), c.cluster.data(), cc.empty() ? nullptr : cc.data(), &job) != FY_OK) fail("prepare");
+        if (fy_rm2_score(job, &res) != FY_OK) fail("score");
+        try {
+            Evaluator ev(ctx, test, cutoffs, relevanceThreshold, gain);
+            evaluation = ev.evaluate(res);
+        } catch (...) {
+            release();
+            throw;
+        }
+        collect(res, sink);
+        release();
+        return 0;
+    }
 
     // RM2 on request (fy_rm2_score_users): the lists of the listed raw user ids alone, with the work sized by the request --
     // "usersFile" of the Python host.  `users` empty = read the configuration key usersFile (one id per line, fy_idfile_read).

@@ -107,6 +107,12 @@ int main(int argc, char** argv) {
     // rm2_main --writes <writes.txt> <ratings.txt> ... : fy::host::applyWrites first ("user item score remove" per line, in order), the job on the result
     const char* writes_file = nullptr;
     if (argc == 9 && !users_file && strcmp(argv[1], "--writes") == 0) { writes_file = argv[2]; argv += 2; argc -= 2; }
+    // rm2_main --evaluate <test.txt> <cutoff> <ratings.txt> ... : RM2Job::runEvaluated, the job's lists evaluated on the GPU against the test
+    // ratings ("user item score" per line) at that cutoff; relevanceThreshold=<x> (default 4) may trail.  One `eval ...` line on stderr.
+    // <test.txt> = holdout:<fraction>:<seed> splits <ratings.txt> instead (fy::host::holdout): the job runs on the train side.
+    const char* eval_file = nullptr;
+    int eval_cutoff = 0;
+    if (argc == 10 && !users_file && !writes_file && strcmp(argv[1], "--evaluate") == 0) { eval_file = argv[2]; eval_cutoff = atoi(argv[3]); argv += 3; argc -= 3; }
     if (argc != 7) { fprintf(stderr, "usage: %s ratings clustering lambda numberOfItems numberOfClusters numberOfRecommendations\n", argv[0]); return 2; }
     fy::host::Ratings r;
     fy::host::Clustering c;
@@ -149,6 +155,28 @@ int main(int argc, char** argv) {
             job.runUsers(r, c, {}, sink);
             fprintf(stderr, "request users_known %lld clusters_touched %lld slab_rows %lld full_pass_clusters %lld\n", (long long)job.requestStats.users_known,
                     (long long)job.requestStats.clusters_touched, (long long)job.requestStats.slab_rows, (long long)job.requestStats.full_pass_clusters);
+        } else if (eval_file) {
+            fy::host::Ratings test;
+            double fraction = 0.0;
+            unsigned long long seed = 0;
+            if (sscanf(eval_file, "holdout:%lf:%llu", &fraction, &seed) == 2) {      // no file: the job runs on the train side of the split
+                auto parts = fy::host::holdout(r, fraction, seed);
+                r = std::move(parts.first);
+                test = std::move(parts.second);
+                fprintf(stderr, "holdout train %zu test %zu\n", r.user.size(), test.user.size());
+            } else {
+                f = fopen(eval_file, "r");
+                if (!f) { perror(eval_file); return 2; }
+                while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) test.add(u, i, s);
+                fclose(f);
+            }
+            job.runEvaluated(r, c, test, {eval_cutoff}, conf.getDouble("relevanceThreshold", 4.0), sink);
+            const fy_eval_sums& e = job.evaluation;
+            using E = fy::host::Evaluator;
+            fprintf(stderr, "eval lists %lld users_evaluated %lld lists_without_relevant %lld relevant_users %lld relevant_entries %lld cutoff %d hits %lld users_hit %lld "
+                    "precision %.17g recall %.17g map %.17g mrr %.17g ndcg %.17g\n", (long long)e.lists, (long long)e.users_evaluated,
+                    (long long)e.lists_without_relevant, (long long)e.relevant_users, (long long)e.relevant_entries, (int)e.cutoffs[0], (long long)e.hits[0],
+                    (long long)e.users_hit[0], E::meanPrecision(e, 0), E::meanRecall(e, 0), E::meanAP(e, 0), E::meanRR(e, 0), E::meanNDCG(e, 0));
         } else if (rccl) {
             char id[128];
             if (fy_rccl_unique_id(id) != FY_OK) { fprintf(stderr, "RM2 failed!: %s\n", fy_last_error()); return 1; }

@@ -669,6 +669,88 @@ int fy_mapfile_write_int_double(const char* dir, int64_t n, const int32_t* key, 
 int fy_idfile_read(const char* path, int64_t* n, int32_t** ids);
 void fy_buffer_free(void*);
 
+/* ------------------------------------------------------------------ offline evaluation: hold-out split and ranking metrics
+ * (csrc/fy_eval.hip).  The reference ships its item-based recommender as a baseline to compare RM2 against
+ * and has no evaluator of its own; these calls say which lists recommend better without moving a list off the GPU.
+ *
+ * Hold-out split.  Two NEW, independent ratings objects from a resident one; the source is only read and what the jobs kept on it
+ * stays valid.  Entry (user, item) goes to *test iff (z >> 40) < floor(fraction * 2^24), all arithmetic modulo 2^64:
+ *     k = ((uint64)(uint32) user << 32) | (uint32) item
+ *     z = k + seed * 0x9E3779B97F4A7C15
+ *     z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31
+ * The decision depends on the key alone: a duplicate key lands on one side, and the side of a rating does not change when other
+ * ratings are written (fy_ratings_apply).  Both outputs keep the source order, scores are stored bit for bit, and the id bounds
+ * kept with each output are those of its own contents (fy_ratings_apply, rule 5).  fraction outside [0, 1] or NaN is
+ * FY_ERR_INVALID_ARGUMENT; 0 gives (a copy, an empty object), 1 the reverse.  On any failure both outputs are NULL. */
+int fy_ratings_holdout(fy_context*, const fy_ratings* source, double fraction, uint64_t seed, fy_ratings** train, fy_ratings** test);
+
+/* A list result from rows made elsewhere (for example the reference's own output file read by fy_seqfile_read_intpair_float), so
+ * that those lists can be evaluated too: a result of the item-CF list kind (aux = 0, no side outputs, fy_result_stats: recs = n,
+ * users_scored = lists).  `location` (FY_HOST / FY_DEVICE) as in fy_ratings_create; the arrays may be freed when the call returns.
+ * Rows are taken as given: grouped by user, best first.  A user whose rows form two separate runs is FY_ERR_INVALID_ARGUMENT
+ * (checked on the device).  An item named twice in one list is NOT checked and counts twice in every metric.  n > 2^31 - 1 is
+ * FY_ERR_UNSUPPORTED. */
+int fy_result_create_lists(fy_context*, int64_t n, const int32_t* user, const int32_t* item, const float* value, int location,
+                           fy_result** out);
+
+/* The evaluator: prepared once from the test ratings, it computes the ranking metrics of any list result (fy_rm2_score,
+ * fy_rm2_score_users, fy_itemcf_recommend*, fy_result_create_lists) where the result lies in HBM.
+ * Parameters: cutoffs strictly ascending, each in [1, FY_EVAL_MAX_CUTOFF], 1 <= n_cutoffs <= FY_EVAL_MAX_CUTOFFS.  A test entry is
+ * RELEVANT iff (double) score >= relevance_threshold (NaN: never).  Its gain is 1 (FY_EVAL_GAIN_BINARY), score
+ * (FY_EVAL_GAIN_LINEAR) or 2^score - 1 (FY_EVAL_GAIN_EXP2), in fp64; every other item has gain 0.  The two graded gains require
+ * relevance_threshold > 0.  Anything else is FY_ERR_INVALID_ARGUMENT; a (user, item) that `test` holds twice is
+ * FY_ERR_DUPLICATE_RATING; more than 2^31 - 1 test entries or list rows is FY_ERR_UNSUPPORTED.  The evaluator owns its tables: the
+ * test ratings may be destroyed after fy_eval_prepare; the evaluator itself is destroyed before its context.  fy_eval_lists refuses
+ * with FY_ERR_INVALID_ARGUMENT a result of the item-similarity or item-pairs kind, a result of another context, and a result whose
+ * rows live on the host only (fy_rm2_run, fy_itemsim_run: their context is gone).
+ * Definitions (fp64; positions p from 1; the list cut at cutoff N; R_u = the relevant items of the list's user):
+ *     a list is EVALUATED iff |R_u| > 0
+ *     hits_N = |top_N of the list, in R_u|        precision = hits_N / N  (N, not the list's length)        recall = hits_N / |R_u|
+ *     AP_N   = (sum over the hit positions p <= N of hits_p / p) / min(|R_u|, N)
+ *     RR_N   = 1 / (first hit position <= N), else 0
+ *     DCG_N  = sum over p <= N of gain_p / log2(p + 1)
+ *     nDCG_N = DCG_N / IDCG_N,  IDCG_N = the same sum over the user's min(N, |R_u|) largest gains in descending order
+ * The value column of the lists is never read: -inf and NaN scores are fine, only the row order counts.
+ * fy_eval_sums holds SUMS over the evaluated lists, not means: the ranks of a multi-rank job evaluate their own lists and the host
+ * adds the sums in rank order (precision = hits / (N * users_evaluated), the other means = sum / users_evaluated, or / relevant_users
+ * to count the users that have relevant test items and no list as zeros).  The sums are bit-identical from run to run: per-list
+ * values are reduced in a fixed order.  With FY_EVAL_COVERAGE, distinct_items = the number of different items among the first
+ * cutoffs[n_cutoffs - 1] rows of all lists OF THIS RESULT (-1 without the flag); the union over the ranks of a multi-rank job is
+ * not formed.  ms = HIP-event time of the call.
+ * Per-list outputs, both optional HOST arrays in list order: per_user_id_or_null (`lists` ids) and per_user_or_null
+ * (lists x n_cutoffs x 5 doubles: hits, recall, AP, RR, nDCG per cutoff; NaN for a list that is not evaluated).  Size them from
+ * fy_result_size (an upper bound of `lists`) or call once with NULLs and read `lists`. */
+#define FY_EVAL_MAX_CUTOFFS 8
+#define FY_EVAL_MAX_CUTOFF 4096
+enum { FY_EVAL_GAIN_BINARY = 0, FY_EVAL_GAIN_LINEAR = 1, FY_EVAL_GAIN_EXP2 = 2 };
+#define FY_EVAL_COVERAGE 1u
+typedef struct {
+    int32_t n_cutoffs;
+    int32_t cutoffs[FY_EVAL_MAX_CUTOFFS];
+    int32_t gain;                 /* FY_EVAL_GAIN_* */
+    uint32_t flags;               /* FY_EVAL_COVERAGE */
+    double relevance_threshold;
+} fy_eval_params;
+typedef struct {
+    int64_t lists;                    /* lists of the result */
+    int64_t users_evaluated;          /* lists whose user has a relevant test entry */
+    int64_t lists_without_relevant;   /* lists - users_evaluated */
+    int64_t relevant_users;           /* users of `test` with a relevant entry */
+    int64_t relevant_entries;
+    int64_t distinct_items;           /* FY_EVAL_COVERAGE; -1 otherwise */
+    int32_t n_cutoffs;
+    int32_t reserved;
+    int32_t cutoffs[FY_EVAL_MAX_CUTOFFS];
+    int64_t hits[FY_EVAL_MAX_CUTOFFS];        /* per cutoff: sum of hits_N */
+    int64_t users_hit[FY_EVAL_MAX_CUTOFFS];   /* evaluated lists with hits_N > 0 */
+    double recall[FY_EVAL_MAX_CUTOFFS], ap[FY_EVAL_MAX_CUTOFFS], rr[FY_EVAL_MAX_CUTOFFS], ndcg[FY_EVAL_MAX_CUTOFFS];
+    double ms;
+} fy_eval_sums;
+typedef struct fy_eval fy_eval;
+int fy_eval_prepare(fy_context*, const fy_eval_params*, const fy_ratings* test, fy_eval** out);
+int fy_eval_lists(fy_eval*, fy_result* lists, fy_eval_sums* out, int32_t* per_user_id_or_null, double* per_user_or_null);
+void fy_eval_destroy(fy_eval*);
+
 #ifdef __cplusplus
 }
 #endif
