@@ -88,6 +88,7 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_ISIM_PIECE")) { int v = atoi(e); if (v >= 64 && v <= 8192 && v % 64 == 0) t.isim_piece = v; }
     if (const char* e = getenv("FY_ISIM_REQ_CHUNK")) { int v = atoi(e); if (v >= 64 && v <= 16384 && v % 64 == 0) t.isim_req_chunk = v; }
     if (const char* e = getenv("FY_ISIM_REQ_ROWS")) t.isim_req_rows = std::max(0, atoi(e));
+    if (const char* e = getenv("FY_ICF_EST_CHUNK")) { int v = atoi(e); if (v >= 1 && v <= fy::ICF_EST_CHUNK_MAX) t.icf_est_chunk = v; }
 }
 
 // Every entry point that reaches the GPU selects its context's device first: allocations, new streams and kernel attributes
@@ -485,6 +486,27 @@ int fy_itemcf_recommend_prepared(fy_itemsim_job* j, const fy_itemcf_params* p, c
     FY_CATCH
 }
 
+int fy_itemcf_estimate_prepared(fy_itemsim_job* j, const fy_itemcf_params* p, const fy_itemcf_pairs* pairs, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !p || !pairs) { set_error("job, parameters or pairs are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(j->ctx);
+    *out = fy::itemcf_estimate_prepared(j, p, pairs->n_pairs, pairs->users, pairs->items, pairs->location);
+    FY_CATCH
+}
+
+int fy_itemcf_estimate_ratings(fy_itemsim_job* j, const fy_itemcf_params* p, const fy_ratings* asked, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !p || !asked) { set_error("job, parameters or ratings are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (asked->ctx != j->ctx) { set_error("the asked ratings belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(j->ctx);
+    *out = fy::itemcf_estimate_prepared(j, p, asked->nnz, asked->user.get(), asked->item.get(), FY_DEVICE);
+    FY_CATCH
+}
+
 void fy_itemsim_job_drop_rows(fy_itemsim_job* j) {
     if (!j) return;
     if (j->ctx) (void)hipSetDevice(j->ctx->device);
@@ -557,6 +579,16 @@ int fy_eval_lists(fy_eval* e, fy_result* lists, fy_eval_sums* out, int32_t* per_
     FY_TRY
     select_device(e->ctx);
     fy::eval_lists(e, lists, out, per_user_id_or_null, per_user_or_null);
+    FY_CATCH
+}
+
+int fy_eval_estimates(fy_context* c, fy_result* estimates, const fy_ratings* truth, const fy_eval_error_params* params_or_null, fy_eval_errors* out) {
+    if (!c || !estimates || !truth || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (estimates->ctx != &c->c || truth->ctx != &c->c) { set_error("estimates / truth belong to another context"); return FY_ERR_INVALID_ARGUMENT; }
+    if (estimates->kind != 4) { set_error("not a result of fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    fy::eval_estimates(&c->c, estimates, truth, params_or_null, out);
     FY_CATCH
 }
 
@@ -635,6 +667,12 @@ int fy_result_itemcf_request_stats(fy_result* r, fy_itemcf_request_stats* out) {
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     if (!r->has_itemcf_request_stats) { set_error("not a result of fy_itemcf_recommend_prepared"); return FY_ERR_STATE; }
     *out = r->crq;
+    return FY_OK;
+}
+int fy_result_itemcf_estimate_stats(fy_result* r, fy_itemcf_estimate_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_itemcf_estimate_stats) { set_error("not a result of fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings"); return FY_ERR_STATE; }
+    *out = r->est;
     return FY_OK;
 }
 void fy_result_free(fy_result* r) {

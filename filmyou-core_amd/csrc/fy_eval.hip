@@ -353,7 +353,85 @@ __global__ void k_ev_sum_slices(const double* __restrict__ part_f, const long lo
     }
 }
 
-__global__ void k_ev_list_users(int32_t n_lists, const int32_t* __restrict__ lstart, const int32_t* __restrict__ key0, int32_t* __restrict__ out) {
+// ---------------------------------------------------------------- rating errors of an estimates result (fy_eval_estimates)
+// The siblings of k_ev_sum_lists / k_ev_sum_slices for one row per PAIR: the per-pair terms are formed where they are summed (no
+// per-pair values in HBM), the order is the same fixed one: slice b of EV_SLICES takes rows [b * per, (b + 1) * per), thread t of its
+// block the rows t, t + 256, ... of the slice, the threads meet in the xor butterfly, the four waves in wave order, the slices in slice
+// order.  Integer sums: rows per status [0 .. 7], rows in the sums [8], OK rows with a truth score that is not finite [9], rows whose
+// (user, item) is not the truth entry's [10].
+constexpr int EV_ERR_NF = 3;         // sum |e|, sum e^2, sum e
+constexpr int EV_ERR_NI = 11;
+struct EvalErrors {
+    int32_t n, per;
+    const int32_t* key0;             // the estimates' rows
+    const int32_t* key1;
+    const float* value;
+    const int32_t* aux;
+    const int32_t* t_user;           // the truth entries of the same rows (already offset)
+    const int32_t* t_item;
+    const float* t_score;
+    int32_t has_clamp;
+    double lo, hi;
+};
+__global__ void __launch_bounds__(256) k_ev_sum_errors(EvalErrors E, double* __restrict__ part_f, long long* __restrict__ part_i) {
+    const int32_t lo = min(E.n, (int32_t)blockIdx.x * E.per), hi = min(E.n, lo + E.per);
+    double f[EV_ERR_NF] = {0.0, 0.0, 0.0};
+    long long n[EV_ERR_NI];
+#pragma unroll
+    for (int k = 0; k < EV_ERR_NI; k++) n[k] = 0;
+    for (int32_t r = lo + (int32_t)threadIdx.x; r < hi; r += 256) {
+        const int32_t status = E.aux[r] & 7;
+#pragma unroll
+        for (int q = 0; q < 8; q++) n[q] += status == q;
+        n[10] += E.key0[r] != E.t_user[r] || E.key1[r] != E.t_item[r];
+        if (status != FY_ESTIMATE_OK) continue;
+        const double truth = (double)E.t_score[r];
+        if (!(fabs(truth) <= 1.7976931348623157e308)) {          // NaN or infinite
+            n[9]++;
+            continue;
+        }
+        double est = (double)E.value[r];
+        if (E.has_clamp) est = est < E.lo ? E.lo : est > E.hi ? E.hi : est;
+        const double e = est - truth;
+        n[8]++;
+        f[0] += fabs(e);
+        f[1] += __dmul_rn(e, e);
+        f[2] += e;
+    }
+    __shared__ double sh_f[4][EV_ERR_NF];
+    __shared__ long long sh_i[4][EV_ERR_NI];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < EV_ERR_NF; k++) {
+        const double s = ev_wave_sum(f[k]);
+        if (lane == 0) sh_f[wv][k] = s;
+    }
+#pragma unroll
+    for (int k = 0; k < EV_ERR_NI; k++) {
+        long long s = n[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) sh_i[wv][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < EV_ERR_NF) part_f[blockIdx.x * EV_ERR_NF + threadIdx.x] = ((sh_f[0][threadIdx.x] + sh_f[1][threadIdx.x]) + sh_f[2][threadIdx.x]) + sh_f[3][threadIdx.x];
+    if (threadIdx.x < EV_ERR_NI) part_i[blockIdx.x * EV_ERR_NI + threadIdx.x] = sh_i[0][threadIdx.x] + sh_i[1][threadIdx.x] + sh_i[2][threadIdx.x] + sh_i[3][threadIdx.x];
+}
+__global__ void k_ev_sum_error_slices(const double* __restrict__ part_f, const long long* __restrict__ part_i, double* __restrict__ sum_f, long long* __restrict__ sum_i) {
+    const int k = threadIdx.x;
+    if (k < EV_ERR_NF) {
+        double s = 0.0;
+        for (int b = 0; b < EV_SLICES; b++) s += part_f[b * EV_ERR_NF + k];
+        sum_f[k] = s;
+    }
+    if (k < EV_ERR_NI) {
+        long long s = 0;
+        for (int b = 0; b < EV_SLICES; b++) s += part_i[b * EV_ERR_NI + k];
+        sum_i[k] = s;
+    }
+}
+
+__global__ void k_ev_list_users(int32_t n_lists,const int32_t* __restrict__ lstart, const int32_t* __restrict__ key0, int32_t* __restrict__ out) {
     for (int32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n_lists; l += gridDim.x * blockDim.x) out[l] = key0[lstart[l]];
 }
 
@@ -657,6 +735,55 @@ void eval_lists(fy_eval* E, fy_result* R, fy_eval_sums* out, int32_t* per_user_i
         sync(ctx);
     }
     S.lists_without_relevant = S.lists - S.users_evaluated;
+    S.ms = timer.total_ms();
+    *out = S;
+}
+
+// ================================================================ fy_eval_estimates
+void eval_estimates(Context* ctx, fy_result* R, const fy_ratings* T, const fy_eval_error_params* p, fy_eval_errors* out) {
+    if (p && p->has_clamp && !(p->clamp_lo <= p->clamp_hi)) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "clamp [%g, %g]: the bounds must be numbers with lo <= hi", p->clamp_lo, p->clamp_hi);
+    if (R->n > INT32_MAX) FY_FAIL(FY_ERR_UNSUPPORTED, "%lld estimate rows: at most 2^31 - 1", (long long)R->n);
+    const int32_t n = (int32_t)R->n;
+    const int64_t off = R->est.pair_offset;
+    if (off < 0 || off + n > T->nnz)
+        FY_FAIL(FY_ERR_INVALID_ARGUMENT, "the estimates are the pairs %lld .. %lld of their list, `truth` holds %lld entries", (long long)off, (long long)(off + n), (long long)T->nnz);
+    hipStream_t sm = ctx->stream;
+    fy_eval_errors S{};
+    S.pairs = n;
+    EventTimer timer(ctx);
+    const size_t span = timer.begin();
+    if (n) {
+        DevBuf<double> part_f(ctx, (size_t)EV_SLICES * EV_ERR_NF), sum_f(ctx, EV_ERR_NF);
+        DevBuf<long long> part_i(ctx, (size_t)EV_SLICES * EV_ERR_NI), sum_i(ctx, EV_ERR_NI);
+        EvalErrors E{};
+        E.n = n;
+        E.per = (int32_t)ceil_div((int64_t)n, (int64_t)EV_SLICES);
+        E.key0 = R->d_key0.get(); E.key1 = R->d_key1.get(); E.value = R->d_value.get(); E.aux = R->d_aux.get();
+        E.t_user = T->user.get() + off; E.t_item = T->item.get() + off; E.t_score = T->score.get() + off;
+        E.has_clamp = p && p->has_clamp;
+        E.lo = E.has_clamp ? p->clamp_lo : 0.0;
+        E.hi = E.has_clamp ? p->clamp_hi : 0.0;
+        k_ev_sum_errors<<<EV_SLICES, 256, 0, sm>>>(E, part_f.get(), part_i.get());
+        FY_KERNEL_CHECK();
+        k_ev_sum_error_slices<<<1, 64, 0, sm>>>(part_f.get(), part_i.get(), sum_f.get(), sum_i.get());
+        FY_KERNEL_CHECK();
+        timer.end(span);
+        double h_f[EV_ERR_NF];
+        long long h_i[EV_ERR_NI];
+        d2h(ctx, h_f, sum_f.get(), EV_ERR_NF);
+        d2h(ctx, h_i, sum_i.get(), EV_ERR_NI);
+        sync(ctx);
+        if (h_i[10]) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "%lld rows of the estimates name another (user, item) than the entry of `truth` at their position", h_i[10]);
+        for (int q = 0; q < 8; q++) S.by_status[q] = h_i[q];
+        S.estimated = h_i[8];
+        S.truth_not_finite = h_i[9];
+        S.sum_abs = h_f[0];
+        S.sum_sq = h_f[1];
+        S.sum_err = h_f[2];
+    } else {
+        timer.end(span);
+        sync(ctx);
+    }
     S.ms = timer.total_ms();
     *out = S;
 }

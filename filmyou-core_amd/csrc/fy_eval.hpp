@@ -24,5 +24,7 @@ void ratings_holdout(Context* ctx, const fy_ratings* R, double fraction, uint64_
 fy_result* result_create_lists(Context* ctx, int64_t n, const int32_t* user, const int32_t* item, const float* value, int location);
 fy_eval* eval_prepare(Context* ctx, const fy_eval_params* p, const fy_ratings* test);
 void eval_lists(fy_eval* E, fy_result* lists, fy_eval_sums* out, int32_t* per_user_id, double* per_user);
+// the error sums of an estimates result (kind 4) against the truth entries at the same positions; p may be NULL (no clamp)
+void eval_estimates(Context* ctx, fy_result* estimates, const fy_ratings* truth, const fy_eval_error_params* p, fy_eval_errors* out);
 
 }  // namespace fy

@@ -1,0 +1,445 @@
+// fy_itemcf_estimate.hip -- item-based CF: the estimated preference of named (user, item) pairs on a prepared similarity job
+// (fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings; include/filmyou.h).
+//
+// estimate(u, i) is the cell (u, i) of the list pass (k_icf_accumulate + k_icf_finalize, fy_itemcf.hip) before the top-N.  The list
+// pass pays a dense accumulator row over the catalogue per user; here the work is sized by the pairs asked for:
+//   k_est_find_users     per pair: the user's slot (binary search), a flag per slot; scan + k_est_list_users: the known users once
+//                        each in slot order -- the slot list icfr_rows_for_users (fy_itemcf_request.hip) takes, as the list pass does
+//   icfr_rows_for_users  thresholds, the set J, the rows the job's store lacks: built and kept (shared with the list pass)
+//   k_est_keys           per pair: (position of the user in the slot list << 32 | column of the item) and its place in the input;
+//                        an unknown user / item gets its row here and an all-ones key
+//   sort                 rocPRIM radix sort of (key, place): equal keys are one TARGET, a user's targets are adjacent, columns ascending
+//   heads, chunks        a user's targets are cut into chunks of at most CH (FY_ICF_EST_CHUNK)
+//   k_icf_estimate       ONE WAVE per (user, chunk).  LDS per wave: the chunk's columns (ascending), fp64 num / den, int cnt, own flag.
+//                        The wave walks the user's kept preferences in CSR order; the 64 lanes stride over row j's entries, each lane
+//                        binary-searches its entry's column among the chunk's columns and, on a hit, adds to that target's cells
+//                        with plain LDS read-modify-writes.  Then the finish of k_icf_finalize and the scatter to every place of the key.
+// Why the bits are the list pass's: a cell receives pd * s (rounded product, then rounded sum: the atomicAdd of a product there, the
+// explicit __dmul_rn / __dadd_rn here), |s| and 1 once per contributing preference, in the order of the user's preferences.  The
+// rows walked per (user, chunk) are the user's kept rows: the work model is fy_itemcf_estimate_stats.row_entries_walked.
+#include <limits>
+#include <memory>
+
+#include "fy_itemcf_request.hpp"
+
+namespace fy {
+namespace {
+
+constexpr uint64_t EST_NO_KEY = ~0ull;
+constexpr int EST_AGG = 10;      // status counts [0 .. 7], users with an OK pair [8], row entries walked [9]
+
+// pair t: the slot of its user (-1: nobody has the id) and that slot's flag
+__global__ void k_est_find_users(int64_t n, const int32_t* __restrict__ users, const int32_t* __restrict__ uid, int32_t nU,
+                                 const int32_t* __restrict__ du2slot, int32_t* __restrict__ pslot, int32_t* __restrict__ flag) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t raw = users[t];
+        int32_t lo = 0, hi = nU;
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (uid[mid] < raw) lo = mid + 1; else hi = mid;
+        }
+        int32_t s = -1;
+        if (lo < nU && uid[lo] == raw) {
+            s = du2slot[lo];
+            flag[s] = 1;                                         // (every writer stores the same word)
+        }
+        pslot[t] = s;
+    }
+}
+
+__global__ void k_est_list_users(int32_t nU, const int32_t* __restrict__ flag, const int32_t* __restrict__ pos, int32_t* __restrict__ list) {
+    for (int32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < nU; s += gridDim.x * blockDim.x)
+        if (flag[s]) list[pos[s]] = s;
+}
+
+// The row of every pair as far as it is known here, its sort key and its place.  pslot == nullptr: a job over no preferences.
+__global__ void k_est_keys(int64_t n, const int32_t* __restrict__ users, const int32_t* __restrict__ items, const int32_t* __restrict__ pslot,
+                           const int32_t* __restrict__ pos, const int32_t* __restrict__ iid, int32_t nI, const int32_t* __restrict__ pair_rank,
+                           uint64_t* __restrict__ keys, uint32_t* __restrict__ place, int32_t* __restrict__ o_user, int32_t* __restrict__ o_item,
+                           float* __restrict__ o_value, int32_t* __restrict__ o_aux) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t it = items[t];
+        const int32_t slot = pslot ? pslot[t] : -1;
+        const int32_t col = slot >= 0 ? icf_column(iid, nI, pair_rank, it) : -1;
+        o_user[t] = users[t];
+        o_item[t] = it;
+        o_value[t] = __builtin_nanf("");
+        o_aux[t] = slot < 0 ? FY_ESTIMATE_UNKNOWN_USER : col < 0 ? FY_ESTIMATE_UNKNOWN_ITEM : FY_ESTIMATE_OK;      // (OK: the estimate kernel writes the row)
+        if (keys) {
+            keys[t] = col >= 0 ? (((uint64_t)(uint32_t)pos[slot] << 32) | (uint32_t)col) : EST_NO_KEY;
+            place[t] = (uint32_t)t;
+        }
+    }
+}
+
+// sorted keys: head[t] = first entry of a target; n_valid[0] = entries in front of the all-ones keys
+__global__ void k_est_heads(int32_t n, const uint64_t* __restrict__ skeys, uint32_t* __restrict__ head, int32_t* __restrict__ n_valid) {
+    for (int32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+        const bool valid = skeys[t] != EST_NO_KEY;
+        head[t] = valid && (t == 0 || skeys[t] != skeys[t - 1]);
+        if (valid && (t == n - 1 || skeys[t + 1] == EST_NO_KEY)) n_valid[0] = t + 1;
+    }
+}
+// tkey[m], tfirst[m] = key and first sorted entry of target m; tfirst[targets] = n_valid
+__global__ void k_est_targets(int32_t n_valid, const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ head,
+                              const uint32_t* __restrict__ head_incl, uint64_t* __restrict__ tkey, int32_t* __restrict__ tfirst) {
+    for (int32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_valid; t += gridDim.x * blockDim.x) {
+        if (head[t]) {
+            tkey[head_incl[t] - 1] = skeys[t];
+            tfirst[head_incl[t] - 1] = t;
+        }
+        if (t == n_valid - 1) tfirst[head_incl[t]] = n_valid;
+    }
+}
+// target m opens a chunk iff its distance from the first target of its user is a multiple of CH
+__global__ void k_est_chunk_heads(int32_t nT, const uint64_t* __restrict__ tkey, int32_t CH, uint32_t* __restrict__ chead) {
+    for (int32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < nT; m += gridDim.x * blockDim.x) {
+        const uint64_t first_key = tkey[m] & 0xFFFFFFFF00000000ull;
+        int32_t lo = 0, hi = m;
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (tkey[mid] < first_key) lo = mid + 1; else hi = mid;
+        }
+        chead[m] = (m - lo) % CH == 0;
+    }
+}
+__global__ void k_est_chunks(int32_t nT, const uint32_t* __restrict__ chead, const uint32_t* __restrict__ cincl, int32_t* __restrict__ cstart) {
+    for (int32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < nT; m += gridDim.x * blockDim.x) {
+        if (chead[m]) cstart[cincl[m] - 1] = m;
+        if (m == nT - 1) cstart[cincl[m]] = nT;
+    }
+}
+
+struct EstArgs {
+    const int32_t* __restrict__ rowptr;
+    const int32_t* __restrict__ csr_idx;
+    const float* __restrict__ csr_r;
+    const float* __restrict__ thr;          // by position in the slot list
+    const int32_t* __restrict__ list;       // slot of the user at a position
+    const int32_t* __restrict__ row_cnt;    // the job's row store: row j = entries j * K .. + row_cnt[j]
+    const int32_t* __restrict__ col_other;
+    const float* __restrict__ sim;
+    int32_t K, boolean_data, n_chunks, ld;  // ld: targets a wave has room for (the chunk size rounded up to even)
+    const int32_t* __restrict__ cstart;     // n_chunks + 1
+    const uint64_t* __restrict__ tkey;
+    const int32_t* __restrict__ tfirst;     // targets + 1
+    const uint32_t* __restrict__ splace;    // place in the input of every sorted entry
+    float* __restrict__ o_value;
+    int32_t* __restrict__ o_aux;
+    long long* __restrict__ walked;         // per chunk
+    int32_t* __restrict__ chunk_ok;         // per chunk: one of its targets is FY_ESTIMATE_OK
+};
+
+// the LDS writes of the wave's lanes so far are visible to every lane's reads behind this point (one wave: its DS operations are
+// executed in the order issued; this keeps the compiler from moving them across)
+__device__ __forceinline__ void est_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// position of column c among the chunk's ascending columns, -1 when it is none of them
+__device__ __forceinline__ int32_t est_find(const int32_t* col, int32_t nt, int32_t c) {
+    int32_t lo = 0, hi = nt;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (col[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    return (lo < nt && col[lo] == c) ? lo : -1;
+}
+
+__global__ void __launch_bounds__(256) k_icf_estimate(EstArgs A) {
+    extern __shared__ double est_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int32_t c = blockIdx.x * 4 + w;
+    if (c >= A.n_chunks) return;                                 // (no workgroup barrier below: the waves are independent)
+    // this wave's 28 B per target: num, den (fp64), col, cnt, own (int32)
+    double* num = est_lds + (size_t)w * A.ld * 7 / 2;
+    double* den = num + A.ld;
+    int32_t* col = (int32_t*)(den + A.ld);
+    int32_t* cnt = col + A.ld;
+    int32_t* own = cnt + A.ld;
+    const int32_t m0 = A.cstart[c], nt = A.cstart[c + 1] - m0;
+    const int32_t k = (int32_t)(A.tkey[m0] >> 32);
+    const int32_t slot = A.list[k];
+    const float thr = A.thr[k];
+    for (int32_t i = lane; i < nt; i += 64) {
+        col[i] = (int32_t)(uint32_t)A.tkey[m0 + i];
+        num[i] = 0.0;
+        den[i] = 0.0;
+        cnt[i] = 0;
+        own[i] = 0;
+    }
+    est_wave_sync();
+    long long walked = 0;
+    const int32_t f1 = A.rowptr[slot + 1];
+    for (int32_t f = A.rowptr[slot]; f < f1; f++) {              // preferences in CSR order; everything but the inner loop is wave-uniform
+        const float p = A.csr_r[f];
+        if (p < thr) continue;
+        const int32_t j = A.csr_idx[f];
+        const int32_t n = A.row_cnt[j];
+        if (n == 0) continue;                                    // no similarity row: contributes nothing, not even its self entry (k_icf_accumulate)
+        walked += n;
+        const int32_t t0 = j * A.K;
+        const double pd = A.boolean_data ? 1.0 : (double)p;
+        // INVARIANT: a row holds a column at most once and the chunk's targets are distinct columns, so within this loop no two lanes
+        // touch one cell; between two rows est_wave_sync orders the lanes.  Each cell therefore sees its additions in preference order.
+        for (int32_t t = lane; t < n; t += 64) {
+            const int32_t i = A.col_other[t0 + t];
+            if (i < 0) continue;
+            const int32_t h = est_find(col, nt, i);
+            if (h < 0) continue;
+            const double s = (double)A.sim[t0 + t];
+            num[h] = __dadd_rn(num[h], __dmul_rn(pd, s));
+            den[h] = __dadd_rn(den[h], fabs(s));
+            cnt[h] += 1;
+        }
+        if (lane == 0) {                                         // the (j, NaN) self entry: the item itself drops out
+            const int32_t h = est_find(col, nt, j);
+            if (h >= 0) own[h] = 1;
+        }
+        est_wave_sync();
+    }
+    // ---- the finish of k_icf_finalize, the status, and the row of every asked pair of the target
+    bool ok = false;
+    for (int32_t i = lane; i < nt; i += 64) {
+        float v = __builtin_nanf("");
+        int32_t status;
+        const int32_t n = cnt[i];
+        const double nm = num[i];
+        if (own[i]) status = FY_ESTIMATE_OWN_PREFERENCE;
+        else if (A.boolean_data ? n < 1 : n < 2) status = FY_ESTIMATE_TOO_FEW;
+        else if (!(nm != 0.0)) status = FY_ESTIMATE_ZERO_NUMERATOR;
+        else {
+            v = A.boolean_data ? (float)nm : (float)(nm / den[i]);
+            status = v == v ? FY_ESTIMATE_OK : FY_ESTIMATE_NOT_A_NUMBER;
+        }
+        ok |= status == FY_ESTIMATE_OK;
+        for (int32_t q = A.tfirst[m0 + i]; q < A.tfirst[m0 + i + 1]; q++) {
+            const uint32_t at = A.splace[q];
+            A.o_value[at] = v;
+            A.o_aux[at] = status;
+        }
+    }
+    const bool any_ok = __any(ok);
+    if (lane == 0) {
+        A.walked[c] = walked;
+        A.chunk_ok[c] = any_ok;
+    }
+}
+
+// rows per status
+__global__ void k_est_count_status(int64_t n, const int32_t* __restrict__ aux, unsigned long long* __restrict__ agg) {
+    unsigned long long mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t s = aux[t] & 7;
+#pragma unroll
+        for (int q = 0; q < 8; q++) mine[q] += s == q;
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        unsigned long long v = mine[q];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&agg[q], v);
+    }
+}
+// the walk of all chunks; users with an OK pair: the first chunk of a user (its chunks are adjacent) that holds one
+__global__ void k_est_count_chunks(int32_t n_chunks, const int32_t* __restrict__ cstart, const uint64_t* __restrict__ tkey,
+                                   const long long* __restrict__ walked, const int32_t* __restrict__ chunk_ok, unsigned long long* __restrict__ agg) {
+    unsigned long long users = 0, walk = 0;
+    for (int32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += gridDim.x * blockDim.x) {
+        walk += (unsigned long long)walked[c];
+        if (!chunk_ok[c]) continue;
+        const uint64_t user = tkey[cstart[c]] >> 32;
+        bool first = true;
+        for (int32_t b = c - 1; b >= 0 && first && (tkey[cstart[b]] >> 32) == user; b--) first = !chunk_ok[b];
+        users += first;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        users += __shfl_down(users, o, 64);
+        walk += __shfl_down(walk, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (users) atomicAdd(&agg[8], users);
+        if (walk) atomicAdd(&agg[9], walk);
+    }
+}
+
+}  // namespace
+
+fy_result* itemcf_estimate_prepared(fy_itemsim_job* J, const fy_itemcf_params* prm, int64_t n_all_pairs, const int32_t* users, const int32_t* items,
+                                    int location) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    if (prm->max_prefs_per_user <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "maxPrefsPerUser must be > 0");
+    if (prm->world <= 0 || prm->rank < 0 || prm->rank >= prm->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", prm->rank, prm->world);
+    if (n_all_pairs < 0 || (n_all_pairs > 0 && (!users || !items))) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "users / items is NULL or n_pairs < 0");
+    if (location != FY_HOST && location != FY_DEVICE) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "location must be FY_HOST or FY_DEVICE");
+    if (n_all_pairs > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "%lld pairs: at most 2^31 - 1", (long long)n_all_pairs);
+    icfr_check_job(J);
+    const int32_t K = J->prm.max_similarities_per_item, nP = P.nP;
+    if ((int64_t)nP * K > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "the row store would exceed 2^31 entries");
+    // this rank's pairs: a contiguous range of the pair list
+    const int64_t off = n_all_pairs * prm->rank / prm->world;
+    const int32_t n = (int32_t)(n_all_pairs * (prm->rank + 1) / prm->world - off);
+    hipStream_t st = ctx->stream;
+    std::unique_ptr<fy_result> Rs(new fy_result);
+    Rs->ctx = ctx;
+    Rs->kind = 4;
+    Rs->n = n;
+    Rs->has_itemcf_estimate_stats = true;
+    fy_itemcf_estimate_stats& es = Rs->est;
+    es.pairs_asked = n;
+    es.pair_offset = off;
+    es.rows_stored = J->store.rows;
+    Rs->st.nnz = P.nnz;
+    Rs->st.n_users = P.nU;
+    Rs->st.n_items = P.nI;
+    Rs->st.recs = n;
+    Rs->d_user_id.alloc(ctx, 0);
+    Rs->d_item_id.alloc(ctx, 0);
+    Rs->d_key0.alloc(ctx, (size_t)n);
+    Rs->d_key1.alloc(ctx, (size_t)n);
+    Rs->d_value.alloc(ctx, (size_t)n);
+    Rs->d_aux.alloc(ctx, (size_t)n);
+    if (n == 0) return Rs.release();
+
+    EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx);
+    unsigned long long h_agg[EST_AGG] = {};
+    SyncOnUnwind drain(st);      // behind the host ends of the queued copies (and the caller's id arrays); the buffers below are released before it drains
+    const size_t sp_total = t_total.begin();
+    size_t sp_tab = t_tables.begin();
+    DevBuf<int32_t> own_users, own_items;
+    const int32_t *d_users = users + off, *d_items = items + off;
+    if (location == FY_HOST) {
+        own_users.alloc(ctx, (size_t)n);
+        own_items.alloc(ctx, (size_t)n);
+        h2d(ctx, own_users.get(), users + off, (size_t)n);
+        h2d(ctx, own_items.get(), items + off, (size_t)n);
+        d_users = own_users.get();
+        d_items = own_items.get();
+    }
+    DevBuf<unsigned long long> agg(ctx, EST_AGG);
+    agg.zero();
+    int32_t* o_user = Rs->d_key0.get();
+    int32_t* o_item = Rs->d_key1.get();
+    float* o_value = Rs->d_value.get();
+    int32_t* o_aux = Rs->d_aux.get();
+
+    // ---- the known users of the range once each, in slot order
+    int32_t n_known = 0;
+    DevBuf<int32_t> pslot, upos, list;
+    if (P.nnz > 0) {
+        DevBuf<int32_t> flag(ctx, (size_t)P.nU + 1);
+        pslot.alloc(ctx, (size_t)n);
+        upos.alloc(ctx, (size_t)P.nU + 1);
+        flag.zero();
+        k_est_find_users<<<grid_for(n), 256, 0, st>>>(n, d_users, P.uid.get(), P.nU, P.du2slot.get(), pslot.get(), flag.get());
+        FY_KERNEL_CHECK();
+        exclusive_scan_i32(ctx, flag.get(), upos.get(), (size_t)P.nU + 1);
+        n_known = fetch(ctx, upos.get() + P.nU);
+        if (n_known < 0 || n_known > P.nU) FY_FAIL(FY_ERR_HIP, "estimate: %d known users of %d", n_known, P.nU);
+        if (n_known > 0) {
+            list.alloc(ctx, (size_t)n_known);
+            k_est_list_users<<<grid_for(P.nU), 256, 0, st>>>(P.nU, flag.get(), upos.get(), list.get());
+            FY_KERNEL_CHECK();
+        }
+    }
+    es.users_known = n_known;
+    int32_t n_targets = 0, n_chunks = 0;
+    if (n_known == 0) {
+        // nobody is known: every row is written by the key pass
+        k_est_keys<<<grid_for(n), 256, 0, st>>>(n, d_users, d_items, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, o_user, o_item, o_value, o_aux);
+        FY_KERNEL_CHECK();
+        t_tables.end(sp_tab);
+    } else {
+        // ---- thresholds, the set J, the rows the store lacks: built and kept
+        DevBuf<float> thr(ctx, (size_t)n_known + 1);
+        IcfrRows built;
+        icfr_rows_for_users(J, list.get(), 0, n_known, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
+        es.items_needed = built.items_needed;
+        es.rows_built = built.rows_built;
+        es.rows_from_store = built.rows_from_store;
+        es.rows_stored = built.rows_stored;
+        es.pair_contribs = built.pair_contribs;
+        es.batches = built.batches;
+        const fy_itemsim_job::RowStore& store = J->store;
+
+        // ---- pairs -> keys, sorted; targets; chunks
+        sp_tab = t_tables.begin();
+        const int32_t CH = std::max(1, std::min(ctx->tune.icf_est_chunk, ICF_EST_CHUNK_MAX));
+        DevBuf<uint64_t> keys(ctx, (size_t)n), skeys(ctx, (size_t)n);
+        DevBuf<uint32_t> place(ctx, (size_t)n), splace(ctx, (size_t)n), head(ctx, (size_t)n), head_incl(ctx, (size_t)n);
+        DevBuf<int32_t> n_valid(ctx, 1);
+        n_valid.zero();
+        k_est_keys<<<grid_for(n), 256, 0, st>>>(n, d_users, d_items, pslot.get(), upos.get(), P.iid.get(), P.nI, P.pair_rank.get(), keys.get(), place.get(),
+                                               o_user, o_item, o_value, o_aux);
+        FY_KERNEL_CHECK();
+        sort_pairs_u64_u32(ctx, keys.get(), skeys.get(), place.get(), splace.get(), (size_t)n);
+        k_est_heads<<<grid_for(n), 256, 0, st>>>(n, skeys.get(), head.get(), n_valid.get());
+        FY_KERNEL_CHECK();
+        inclusive_scan_u32(ctx, head.get(), head_incl.get(), (size_t)n);
+        int32_t h_valid = 0;
+        uint32_t h_targets = 0;
+        d2h(ctx, &h_valid, n_valid.get(), 1);
+        d2h(ctx, &h_targets, head_incl.get() + (n - 1), 1);
+        sync(ctx);
+        n_targets = (int32_t)h_targets;
+        if (h_valid < 0 || h_valid > n || n_targets < 0 || n_targets > h_valid || (n_targets == 0) != (h_valid == 0))
+            FY_FAIL(FY_ERR_HIP, "estimate: %d targets in %d valid pairs of %d", n_targets, h_valid, n);
+        if (n_targets > 0) {
+            DevBuf<uint64_t> tkey(ctx, (size_t)n_targets);
+            DevBuf<int32_t> tfirst(ctx, (size_t)n_targets + 1);
+            DevBuf<uint32_t> chead(ctx, (size_t)n_targets), cincl(ctx, (size_t)n_targets);
+            k_est_targets<<<grid_for(h_valid), 256, 0, st>>>(h_valid, skeys.get(), head.get(), head_incl.get(), tkey.get(), tfirst.get());
+            FY_KERNEL_CHECK();
+            k_est_chunk_heads<<<grid_for(n_targets), 256, 0, st>>>(n_targets, tkey.get(), CH, chead.get());
+            FY_KERNEL_CHECK();
+            inclusive_scan_u32(ctx, chead.get(), cincl.get(), (size_t)n_targets);
+            n_chunks = (int32_t)fetch(ctx, cincl.get() + (n_targets - 1));
+            if (n_chunks < 1 || n_chunks > n_targets) FY_FAIL(FY_ERR_HIP, "estimate: %d chunks over %d targets", n_chunks, n_targets);
+            DevBuf<int32_t> cstart(ctx, (size_t)n_chunks + 1), chunk_ok(ctx, (size_t)n_chunks);
+            DevBuf<long long> walked(ctx, (size_t)n_chunks);
+            k_est_chunks<<<grid_for(n_targets), 256, 0, st>>>(n_targets, chead.get(), cincl.get(), cstart.get());
+            FY_KERNEL_CHECK();
+            t_tables.end(sp_tab);
+
+            // ---- the estimate kernel: one wave per (user, chunk)
+            const size_t sp_score = t_score.begin();
+            EstArgs A{};
+            A.rowptr = P.rowptr.get(); A.csr_idx = P.csr_idx.get(); A.csr_r = P.csr_r.get();
+            A.thr = thr.get(); A.list = list.get();
+            A.row_cnt = store.cnt.get(); A.col_other = store.other.get(); A.sim = store.sim.get();
+            A.K = K; A.boolean_data = prm->boolean_data; A.n_chunks = n_chunks; A.ld = (int32_t)round_up(CH, 2);
+            A.cstart = cstart.get(); A.tkey = tkey.get(); A.tfirst = tfirst.get(); A.splace = splace.get();
+            A.o_value = o_value; A.o_aux = o_aux; A.walked = walked.get(); A.chunk_ok = chunk_ok.get();
+            k_icf_estimate<<<(int)ceil_div((int64_t)n_chunks, (int64_t)4), 256, (size_t)4 * A.ld * 28, st>>>(A);
+            FY_KERNEL_CHECK();
+            t_score.end(sp_score);
+            k_est_count_chunks<<<grid_for(n_chunks), 256, 0, st>>>(n_chunks, cstart.get(), tkey.get(), walked.get(), chunk_ok.get(), agg.get());
+            FY_KERNEL_CHECK();
+        } else {
+            t_tables.end(sp_tab);
+        }
+    }
+    k_est_count_status<<<grid_for(n), 256, 0, st>>>(n, o_aux, agg.get());
+    FY_KERNEL_CHECK();
+    t_total.end(sp_total);
+    d2h(ctx, h_agg, agg.get(), EST_AGG);
+    sync(ctx);
+    for (int q = 0; q < 8; q++) es.by_status[q] = (int64_t)h_agg[q];
+    es.targets = n_targets;
+    es.chunks = n_chunks;
+    es.row_entries_walked = (int64_t)h_agg[9];
+    Rs->st.users_scored = (int64_t)h_agg[8];
+    Rs->st.pair_contribs = es.pair_contribs;
+    Rs->st.cooc_launches = es.batches;
+    Rs->st.score_launches = (int64_t)t_score.count();
+    Rs->st.ms_tables = t_tables.total_ms();
+    Rs->st.ms_cooc = t_cooc.total_ms();
+    Rs->st.ms_score = t_score.total_ms();
+    Rs->st.ms_total = t_total.total_ms();
+    return Rs.release();
+}
+
+}  // namespace fy

@@ -14,6 +14,8 @@
 //   accumulate .. compact   icf_score_lists of the filtered pass with row_start[j] = j * K and row_cnt read from the store
 // The per-cell order of additions is the order of the user's preferences, as in the filtered pass, so the result is the filtered
 // pass's bit for bit when it is fed the rows fy_itemsim_rows returns; the store changes where a row comes from, never its bits.
+// The steps from the thresholds to k_icfr_fill_store are icfr_rows_for_users, which the estimates for named pairs
+// (fy_itemcf_estimate.hip) call too: a row built for either pass serves the other.
 #include <algorithm>
 #include <limits>
 #include <memory>
@@ -103,15 +105,91 @@ __global__ void k_icfr_fill_store(int32_t n, int32_t K, int32_t n_cols, const in
 
 void itemsim_job_drop_rows(fy_itemsim_job* J) { J->store = fy_itemsim_job::RowStore{}; }
 
+void icfr_check_job(const fy_itemsim_job* J) {
+    if (J->prm.world != 1) FY_FAIL(FY_ERR_UNSUPPORTED, "the similarity job was prepared as rank %d of %d: every rank needs any row (prepare with world = 1)", J->prm.rank, J->prm.world);
+    if (J->prm.min_prefs_per_user > 1 || J->prm.max_prefs_per_user != 0)
+        FY_FAIL(FY_ERR_UNSUPPORTED, "the similarity job was prepared with minPrefsPerUser / maxPrefsPerUser: its rows are no longer the users' preferences");
+}
+
+void icfr_rows_for_users(fy_itemsim_job* J, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
+                         size_t sp_tab, EventTimer& t_cooc, IcfrRows& rq) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    const int32_t K = J->prm.max_similarities_per_item, nP = P.nP, nmine = hi - lo;
+    hipStream_t st = ctx->stream;
+    std::vector<int32_t> h_missing;
+    int32_t h_need = 0, h_build = 0;
+    SyncOnUnwind drain(st);      // behind the host ends of the queued copies; the scratch buffers below go back to the allocator before it drains
+    icf_thresholds(ctx, P, list, lo, hi, max_prefs, thr);
+
+    // ---- the row store of the job, on the first call: every buffer or none
+    fy_itemsim_job::RowStore& store = J->store;
+    if (!store.allocated) {
+        fy_itemsim_job::RowStore fresh;
+        fresh.state.alloc(ctx, (size_t)nP);
+        fresh.cnt.alloc(ctx, (size_t)nP);
+        fresh.start.alloc(ctx, (size_t)nP);
+        fresh.other.alloc(ctx, (size_t)nP * K);
+        fresh.sim.alloc(ctx, (size_t)nP * K);
+        fresh.state.zero();
+        fresh.cnt.zero();
+        k_icfr_row_starts<<<grid_for(nP), 256, 0, st>>>(nP, K, fresh.start.get());
+        FY_KERNEL_CHECK();
+        fresh.allocated = true;
+        store = std::move(fresh);
+    }
+
+    // ---- J: the columns of the kept preferences; those the store lacks, ascending
+    DevBuf<uint32_t> need(ctx, (size_t)ceil_div(nP, 32));
+    DevBuf<int32_t> missing(ctx, (size_t)nP + 1), pos(ctx, (size_t)nP + 1), n_needed(ctx, 1);
+    need.zero();
+    n_needed.zero();
+    k_icfr_mark_items<<<grid_for((int64_t)nmine * 64, 256), 256, 0, st>>>(lo, hi, list, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), thr, nP, need.get());
+    FY_KERNEL_CHECK();
+    k_icfr_split<<<grid_for((int64_t)nP + 1), 256, 0, st>>>(nP, need.get(), store.state.get(), missing.get(), n_needed.get());
+    FY_KERNEL_CHECK();
+    exclusive_scan_i32(ctx, missing.get(), pos.get(), (size_t)nP + 1);
+    d2h(ctx, &h_need, n_needed.get(), 1);
+    d2h(ctx, &h_build, pos.get() + nP, 1);      // the scan's total: the missing columns
+    sync(ctx);
+    const int64_t n_need = h_need, n_build = h_build;
+    rq.items_needed = n_need;
+    rq.rows_built = n_build;
+    rq.rows_from_store = n_need - n_build;
+    DevBuf<int32_t> rows(ctx, (size_t)n_build);
+    if (n_build > 0) {
+        k_icfr_list_missing<<<grid_for(nP), 256, 0, st>>>(nP, missing.get(), pos.get(), rows.get());
+        FY_KERNEL_CHECK();
+        h_missing.resize((size_t)n_build);
+        d2h(ctx, h_missing.data(), rows.get(), (size_t)n_build);
+    }
+    t_tables.end(sp_tab);
+
+    // ---- build the missing rows and keep them
+    if (n_build > 0) {
+        DevBuf<int32_t> cnt(ctx, (size_t)n_build), other(ctx, (size_t)n_build * K);
+        DevBuf<float> sim(ctx, (size_t)n_build * K);
+        rq.batches = itemsim_build_rank_rows(J, rows.get(), n_build, cnt.get(), other.get(), sim.get(), t_cooc, t_cooc);
+        const size_t sp_f = t_cooc.begin();
+        k_icfr_fill_store<<<grid_for(n_build * 64, 256), 256, 0, st>>>((int32_t)n_build, K, nP, rows.get(), cnt.get(), other.get(), sim.get(), P.iid.get(),
+                                                                      P.nI, P.pair_rank.get(), store.state.get(), store.cnt.get(), store.other.get(),
+                                                                      store.sim.get());
+        FY_KERNEL_CHECK();
+        t_cooc.end(sp_f);
+        store.rows += n_build;
+        sync(ctx);      // the list of the built rows is on the host
+        for (int32_t r : h_missing) rq.pair_contribs += J->walk[(size_t)r];
+    }
+    rq.rows_stored = store.rows;
+}
+
 fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* prm, const fy_itemcf_filter* filt) {
     Context* ctx = J->ctx;
     const Prepared& P = J->P;
     if (!filt || !filt->has_users)
         FY_FAIL(FY_ERR_INVALID_ARGUMENT, "fy_itemcf_recommend_prepared needs the users to recommend for (has_users); lists for every user are fy_itemcf_recommend's");
     icf_check_arguments(prm, filt);
-    if (J->prm.world != 1) FY_FAIL(FY_ERR_UNSUPPORTED, "the similarity job was prepared as rank %d of %d: every rank needs any row (prepare with world = 1)", J->prm.rank, J->prm.world);
-    if (J->prm.min_prefs_per_user > 1 || J->prm.max_prefs_per_user != 0)
-        FY_FAIL(FY_ERR_UNSUPPORTED, "the similarity job was prepared with minPrefsPerUser / maxPrefsPerUser: its rows are no longer the users' preferences");
+    icfr_check_job(J);
     const int32_t K = J->prm.max_similarities_per_item, nP = P.nP;
     hipStream_t st = ctx->stream;
     std::unique_ptr<fy_result> Rs(new fy_result);
@@ -140,8 +218,7 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
 
     EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx), t_topn(ctx);
     std::vector<uint64_t> found((size_t)filt->n_users);
-    std::vector<int32_t> slots, dus, h_missing;
-    int32_t h_need = 0, h_build = 0;
+    std::vector<int32_t> slots, dus;
     // behind the host ends of the queued copies (and the caller's id arrays).  The scratch buffers below are declared after it and so
     // go back to the allocator BEFORE a failure drains the stream, as in icf_run: the allocator hands blocks out again on this same
     // stream only, and no later call queues work before this one has unwound.
@@ -190,68 +267,16 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     h2d(ctx, list_du.get(), dus.data(), (size_t)n_all);
     if (filt->has_items) icf_allow_bitmap(ctx, P, filt, allow);
     DevBuf<float> thr(ctx, (size_t)nmine + 1);
-    icf_thresholds(ctx, P, list.get(), lo, hi, prm->max_prefs_per_user, thr.get());
-
-    // ---- the row store of the job, on the first call: every buffer or none
+    // ---- thresholds, the set J, the rows the store lacks: built and kept
+    IcfrRows built;
+    icfr_rows_for_users(J, list.get(), lo, hi, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
+    rq.items_needed = built.items_needed;
+    rq.rows_built = built.rows_built;
+    rq.rows_from_store = built.rows_from_store;
+    rq.rows_stored = built.rows_stored;
+    rq.pair_contribs = built.pair_contribs;
+    rq.batches = built.batches;
     fy_itemsim_job::RowStore& store = J->store;
-    if (!store.allocated) {
-        fy_itemsim_job::RowStore fresh;
-        fresh.state.alloc(ctx, (size_t)nP);
-        fresh.cnt.alloc(ctx, (size_t)nP);
-        fresh.start.alloc(ctx, (size_t)nP);
-        fresh.other.alloc(ctx, (size_t)nP * K);
-        fresh.sim.alloc(ctx, (size_t)nP * K);
-        fresh.state.zero();
-        fresh.cnt.zero();
-        k_icfr_row_starts<<<grid_for(nP), 256, 0, st>>>(nP, K, fresh.start.get());
-        FY_KERNEL_CHECK();
-        fresh.allocated = true;
-        store = std::move(fresh);
-    }
-
-    // ---- J: the columns of the kept preferences; those the store lacks, ascending
-    DevBuf<uint32_t> need(ctx, (size_t)ceil_div(nP, 32));
-    DevBuf<int32_t> missing(ctx, (size_t)nP + 1), pos(ctx, (size_t)nP + 1), n_needed(ctx, 1);
-    need.zero();
-    n_needed.zero();
-    k_icfr_mark_items<<<grid_for((int64_t)nmine * 64, 256), 256, 0, st>>>(lo, hi, list.get(), P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), thr.get(),
-                                                                        nP, need.get());
-    FY_KERNEL_CHECK();
-    k_icfr_split<<<grid_for((int64_t)nP + 1), 256, 0, st>>>(nP, need.get(), store.state.get(), missing.get(), n_needed.get());
-    FY_KERNEL_CHECK();
-    exclusive_scan_i32(ctx, missing.get(), pos.get(), (size_t)nP + 1);
-    d2h(ctx, &h_need, n_needed.get(), 1);
-    d2h(ctx, &h_build, pos.get() + nP, 1);      // the scan's total: the missing columns
-    sync(ctx);
-    const int64_t n_need = h_need, n_build = h_build;
-    rq.items_needed = n_need;
-    rq.rows_built = n_build;
-    rq.rows_from_store = n_need - n_build;
-    DevBuf<int32_t> rows(ctx, (size_t)n_build);
-    if (n_build > 0) {
-        k_icfr_list_missing<<<grid_for(nP), 256, 0, st>>>(nP, missing.get(), pos.get(), rows.get());
-        FY_KERNEL_CHECK();
-        h_missing.resize((size_t)n_build);
-        d2h(ctx, h_missing.data(), rows.get(), (size_t)n_build);
-    }
-    t_tables.end(sp_tab);
-
-    // ---- build the missing rows and keep them
-    if (n_build > 0) {
-        DevBuf<int32_t> cnt(ctx, (size_t)n_build), other(ctx, (size_t)n_build * K);
-        DevBuf<float> sim(ctx, (size_t)n_build * K);
-        rq.batches = itemsim_build_rank_rows(J, rows.get(), n_build, cnt.get(), other.get(), sim.get(), t_cooc, t_cooc);
-        const size_t sp_f = t_cooc.begin();
-        k_icfr_fill_store<<<grid_for(n_build * 64, 256), 256, 0, st>>>((int32_t)n_build, K, nP, rows.get(), cnt.get(), other.get(), sim.get(), P.iid.get(),
-                                                                      P.nI, P.pair_rank.get(), store.state.get(), store.cnt.get(), store.other.get(),
-                                                                      store.sim.get());
-        FY_KERNEL_CHECK();
-        t_cooc.end(sp_f);
-        store.rows += n_build;
-        sync(ctx);      // the list of the built rows is on the host
-        for (int32_t r : h_missing) rq.pair_contribs += J->walk[(size_t)r];
-    }
-    rq.rows_stored = store.rows;
 
     // ---- accumulate, finalize, top-N, compact: the filtered pass, reading the store
     DevBuf<int32_t> n_lists;

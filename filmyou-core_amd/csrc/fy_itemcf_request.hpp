@@ -37,7 +37,23 @@ void icf_score_lists(Context*, const fy_itemcf_params*, const Prepared&, const I
                      const uint32_t* allow, int32_t lo, int32_t hi, const float* thr, fy_result* Rs, EventTimer& t_score, EventTimer& t_topn,
                      DevBuf<int32_t>& n_lists);
 
+// ---- the front half of a pass that reads a prepared job's rows: fy_itemcf_recommend_prepared and the estimates (fy_itemcf_estimate.hip)
+// what the job must be to serve either (world == 1, no minPrefsPerUser / maxPrefsPerUser of its own), and that its store fits
+void icfr_check_job(const fy_itemsim_job*);
+struct IcfrRows {
+    int64_t items_needed = 0, rows_built = 0, rows_from_store = 0, rows_stored = 0, pair_contribs = 0, batches = 0;
+};
+// For the users lo .. hi of the slot list (device, ascending slots): thr[k - lo] (hi - lo + 1 floats of the caller), the set J of
+// their kept preferences, J against the job's row store (allocated here on the first call), the missing rows built and kept.  The
+// caller has begun span sp_tab of t_tables (its own id -> slot work is inside it); it is ended here, in front of the row build,
+// whose spans go to t_cooc.  Synchronises.  When it returns, row j of every kept preference is in J->store.
+void icfr_rows_for_users(fy_itemsim_job* J, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
+                         size_t sp_tab, EventTimer& t_cooc, IcfrRows& out);
+
+constexpr int ICF_EST_CHUNK_MAX = 512;   // FY_ICF_EST_CHUNK: targets a wave of the estimate kernel holds in LDS (4 waves x 28 B x 512 = 56 KiB)
 fy_result* itemcf_recommend_prepared(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_filter*);
+// users / items: the whole pair list, n raw ids each, host or device (location); the rank's range is cut inside
+fy_result* itemcf_estimate_prepared(fy_itemsim_job*, const fy_itemcf_params*, int64_t n, const int32_t* users, const int32_t* items, int location);
 void itemsim_job_drop_rows(fy_itemsim_job*);
 
 }  // namespace fy

@@ -7,7 +7,7 @@
 // result rows live in HBM until an accessor asks for them
 struct fy_result {
     fy::Context* ctx = nullptr;
-    int kind = 0;   // 0 = RM2, 1 = item-sim, 2 = item-CF lists, 3 = item pairs
+    int kind = 0;   // 0 = RM2, 1 = item-sim, 2 = item-CF lists, 3 = item pairs, 4 = item-CF estimates (one row per asked pair)
     int64_t n = 0;
     fy::DevBuf<int32_t> d_key0, d_key1, d_aux;
     fy::DevBuf<float> d_value;
@@ -21,6 +21,8 @@ struct fy_result {
     fy_itemsim_request_stats irq{};
     bool has_itemcf_request_stats = false;    // a result of fy_itemcf_recommend_prepared
     fy_itemcf_request_stats crq{};
+    bool has_itemcf_estimate_stats = false;   // a result of fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings (kind 4)
+    fy_itemcf_estimate_stats est{};
     // host mirrors, filled on first access
     bool rows_on_host = false, sums_on_host = false;
     std::vector<int32_t> h_key0, h_key1, h_aux, h_user_id, h_item_id;

@@ -83,6 +83,9 @@ struct Tuning {
     int isim_req_chunk = 8192;         // FY_ISIM_REQ_CHUNK: most columns (64-bit LDS accumulators) a workgroup of the row kernel owns (a row's chunks are balanced); read at fy_itemsim_prepare,
                                        // which keeps the row offsets for this width
     int isim_req_rows = 0;             // FY_ISIM_REQ_ROWS: rows per batch of a request (0 = as many as the partial lists of workspace_default hold)
+    // item-CF estimates for named pairs (fy_itemcf_estimate.hip); changes no result
+    int icf_est_chunk = 256;           // FY_ICF_EST_CHUNK: most distinct targets of one user a wave of the estimate kernel holds in LDS (28 B each; four
+                                       // waves a workgroup: 28 KiB at 256); at most 512
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -397,6 +397,16 @@ def _i32(a):
     return np.ascontiguousarray(a if a is not None else [], dtype=np.int32)
 
 
+def _pair_ids(a):
+    """ids of asked pairs: every pair is answered, so an id outside int32 cannot be passed over -- it is refused"""
+    a = np.asarray(a).reshape(-1)
+    if a.dtype != np.int32:
+        a = np.asarray(a, dtype=np.int64) if len(a) else np.zeros(0, dtype=np.int64)
+        if ((a < -2 ** 31) | (a >= 2 ** 31)).any():
+            raise ValueError("an id of a pair is outside int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 class RM2Job:
     """Relevance Model 2 job (M/rm/RM2Job.java:54-272) on one MI355X (or one rank of several).
 
@@ -760,6 +770,82 @@ class Evaluation:
                    sum(p.ms for p in parts))
 
 
+FY_ESTIMATE_OK, FY_ESTIMATE_UNKNOWN_USER, FY_ESTIMATE_UNKNOWN_ITEM, FY_ESTIMATE_OWN_PREFERENCE = 0, 1, 2, 3
+FY_ESTIMATE_TOO_FEW, FY_ESTIMATE_ZERO_NUMERATOR, FY_ESTIMATE_NOT_A_NUMBER = 4, 5, 6
+
+
+class EstimateErrors:
+    """Rating-error SUMS of estimates against true scores (fy_eval_errors): ``pairs``, ``estimated`` (the OK rows with a finite
+    truth score: what the sums run over), ``truth_not_finite``, ``by_status`` (rows per FY_ESTIMATE_* code), ``sum_abs``,
+    ``sum_sq``, ``sum_err`` and ``ms``; the means are properties (NaN when nothing was estimated)."""
+
+    def __init__(self, pairs, estimated, truth_not_finite, by_status, sum_abs, sum_sq, sum_err, ms=0.0):
+        self.pairs, self.estimated, self.truth_not_finite = int(pairs), int(estimated), int(truth_not_finite)
+        self.by_status = [int(x) for x in by_status]
+        self.sum_abs, self.sum_sq, self.sum_err, self.ms = float(sum_abs), float(sum_sq), float(sum_err), float(ms)
+
+    def _mean(self, x):
+        return x / self.estimated if self.estimated > 0 else float("nan")
+
+    @property
+    def mae(self):
+        return self._mean(self.sum_abs)
+
+    @property
+    def rmse(self):
+        return float(np.sqrt(self._mean(self.sum_sq)))
+
+    @property
+    def bias(self):
+        return self._mean(self.sum_err)
+
+    @property
+    def coverage(self):
+        return self.estimated / self.pairs if self.pairs > 0 else float("nan")
+
+    @classmethod
+    def merge(cls, parts):
+        """The errors of a multi-rank estimate from its ranks' errors: counters and sums are added in the order given (rank order)."""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("nothing to merge")
+        sums = [0.0, 0.0, 0.0]
+        for p in parts:
+            sums = [sums[0] + p.sum_abs, sums[1] + p.sum_sq, sums[2] + p.sum_err]
+        return cls(sum(p.pairs for p in parts), sum(p.estimated for p in parts), sum(p.truth_not_finite for p in parts),
+                   [sum(p.by_status[q] for p in parts) for q in range(8)], sums[0], sums[1], sums[2], sum(p.ms for p in parts))
+
+
+class PreferenceEstimates(_Result):
+    """What ``PreparedItemSimilarity.estimate`` returns: one row per asked pair, in the order asked -- (user, item, estimate float32,
+    status); the estimate is NaN unless the status is FY_ESTIMATE_OK.  ``estimate_stats`` (fy_itemcf_estimate_stats) beside ``stats``."""
+
+    def __init__(self, handle, ctx=None):
+        super().__init__(handle, ctx)
+        self.stats = self._stats()
+        self.size = self._lib.fy_result_size(handle)
+        self._rows = None
+        es = _native.ItemCFEstimateStats()
+        _check(self._lib.fy_result_itemcf_estimate_stats(handle, C.byref(es)))
+        self.estimate_stats = es.as_dict()
+
+    def rows(self):
+        if self._rows is None:
+            L, h, n = self._lib, self._h, self.size
+            self._rows = {"user": _np(L.fy_result_key0(h), n, np.int32), "item": _np(L.fy_result_key1(h), n, np.int32),
+                          "estimate": _np(L.fy_result_value(h), n, np.float32), "status": _np(L.fy_result_aux(h), n, np.int32)}
+        return self._rows
+
+    def errors(self, truth, clamp=None):
+        """fy_eval_estimates: the error sums against ``truth``, a resident ``Ratings`` whose entries (from this result's pair offset
+        on) are the asked pairs in the same order -- the ``Ratings`` the estimates were asked for, typically.  ``clamp=(lo, hi)``
+        clamps every estimate into the rating scale first.  Returns an ``EstimateErrors``; nothing is downloaded but the sums."""
+        p = _native.EvalErrorParams(0, 0, 0.0, 0.0) if clamp is None else _native.EvalErrorParams(1, 0, float(clamp[0]), float(clamp[1]))
+        e = _native.EvalErrors()
+        _check(self._lib.fy_eval_estimates(self._ctx._h, self._h, truth._h, C.byref(p), C.byref(e)))
+        return EstimateErrors(e.pairs, e.estimated, e.truth_not_finite, list(e.by_status), e.sum_abs, e.sum_sq, e.sum_err, e.ms)
+
+
 class Evaluator:
     """Ranking metrics of list results where they lie in HBM (fy_eval_*; include/filmyou.h states the definitions).
 
@@ -1028,6 +1114,39 @@ class PreparedItemSimilarity:
         except FilmYouError as e:
             raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
         return ItemRecommendations(res, self._ctx, request=True)
+
+    def estimate(self, pairs, maxPrefsPerUser=50, booleanData=False, rank=0, world=1):
+        """fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings: what would this user give this item -- the cell (user, item) of
+        the pass ``recommend`` runs, before the top-N (bit for bit the list's score wherever a list holds the pair), with the work
+        sized by the pairs.  ``pairs``: ``(users, items)`` raw-id arrays (numpy, or int32 torch tensors on the context's GPU), or a
+        resident ``Ratings`` whose (user, item) columns are asked in its order (the ``test`` side of ``Ratings.holdout``: no id
+        leaves the GPU).  (rank, world) cut the pair list.  Rows built stay on the job like ``recommend``'s.  Returns a
+        ``PreferenceEstimates``."""
+        p = _native.ItemCFParams(0, int(maxPrefsPerUser), 1 if booleanData else 0, int(rank), int(world), 0)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            if isinstance(pairs, Ratings):
+                _check(self._lib.fy_itemcf_estimate_ratings(self._h, C.byref(p), pairs._h, C.byref(res)))
+            else:
+                users, items = pairs
+                if _is_torch_tensor(users):
+                    import torch
+                    assert users.is_cuda and items.is_cuda, "device tensors expected"
+                    assert users.dtype == torch.int32 and items.dtype == torch.int32
+                    users, items = users.contiguous(), items.contiguous()
+                    torch.cuda.current_stream(users.device).synchronize()   # producer stream != the context's stream
+                    n, ptrs, loc = users.numel(), (users.data_ptr(), items.data_ptr()), 1
+                    assert n == items.numel()
+                else:
+                    users, items = _pair_ids(users), _pair_ids(items)
+                    n, ptrs, loc = len(users), (users.ctypes.data, items.ctypes.data), 0
+                    assert n == len(items)
+                q = _native.ItemCFPairs(n, ptrs[0] if n else None, ptrs[1] if n else None, loc)
+                _check(self._lib.fy_itemcf_estimate_prepared(self._h, C.byref(p), C.byref(q), C.byref(res)))
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
+        return PreferenceEstimates(res, self._ctx)
 
     def drop_rows(self):
         """fy_itemsim_job_drop_rows: releases the similarity rows kept by ``recommend``; the job stays valid."""

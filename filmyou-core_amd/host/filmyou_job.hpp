@@ -15,6 +15,7 @@
 // (M/rm/AbstractRM2Reducer.java:404-406).
 #pragma once
 #include <cctype>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -185,6 +186,26 @@ class Evaluator {
    private:
     fy_eval* eval_ = nullptr;
 };
+
+// Rating-error sums of an estimates result (BaselineRecommenderJob::estimatePairs) against the true scores (fy_eval_estimates;
+// Mahout's AverageAbsoluteDifferenceRecommenderEvaluator / RMSRecommenderEvaluator): record r of `truth` is the pair of row
+// pair_offset + r of the estimates.  clamp = {lo, hi} clamps every estimate first.  SUMS; mae / rmse / coverage divide them.
+// Throws std::runtime_error("estimateErrors failed!: ...").
+inline fy_eval_errors estimateErrors(fy_context* ctx, fy_result* estimates, const Ratings& truth, const double* clamp = nullptr) {
+    fy_ratings* t = nullptr;
+    if (fy_ratings_create(ctx, (int64_t)truth.user.size(), truth.user.data(), truth.item.data(), truth.score.data(), FY_HOST, &t) != FY_OK)
+        throw std::runtime_error(std::string("estimateErrors failed!: truth ratings: ") + fy_last_error());
+    fy_eval_error_params p{};
+    if (clamp) { p.has_clamp = 1; p.clamp_lo = clamp[0]; p.clamp_hi = clamp[1]; }
+    fy_eval_errors e{};
+    const int rc = fy_eval_estimates(ctx, estimates, t, &p, &e);
+    fy_ratings_destroy(t);
+    if (rc != FY_OK) throw std::runtime_error(std::string("estimateErrors failed!: ") + fy_last_error());
+    return e;
+}
+inline double mae(const fy_eval_errors& e) { return e.sum_abs / (double)e.estimated; }
+inline double rmse(const fy_eval_errors& e) { return std::sqrt(e.sum_sq / (double)e.estimated); }
+inline double coverage(const fy_eval_errors& e) { return (double)e.estimated / (double)e.pairs; }
 
 // The smoothing of the user language model (include/filmyou.h, FY_RM2_SMOOTHING_*) from the Configuration keys `smoothing` (jm --
 // the default, parameter `lambda` --, dirichlet with `mu`, absoluteDiscounting with `delta`; case does not matter) into
@@ -546,6 +567,7 @@ class PreparedItemSimilarity {
     }
     ~PreparedItemSimilarity() { close(); }
     fy_itemsim_job* job() const { return job_; }
+    fy_context* context() const { return ctx_; }
     void dropRows() { fy_itemsim_job_drop_rows(job_); }      // the row store; the job stays valid
     void close() {
         if (job_) fy_itemsim_job_destroy(job_);
@@ -707,6 +729,40 @@ class BaselineRecommenderJob {
         fy_result_free(res);
         fy_buffer_free(items);
         return 0;
+    }
+
+    // "What would this user give this item": the cell (user, item) of the pass recommendUsers runs, before the top-N
+    // (fy_itemcf_estimate_prepared; maxPrefsPerUser and booleanData are read at each call).  One row per pair in the order given:
+    // the sink (may be empty) receives (user, item, estimate, FY_ESTIMATE_* status), the estimate is NaN unless the status is
+    // FY_ESTIMATE_OK.  Returns the result, which lives on prepared.context() -- estimateErrors takes it -- and is the caller's to
+    // release with fy_result_free before the prepared job is closed.
+    using EstimateSink = std::function<void(int32_t user, int32_t item, float estimate, int32_t status)>;
+    fy_itemcf_estimate_stats estimateStats{};
+    fy_result* estimatePairs(PreparedItemSimilarity& prepared, const std::vector<int32_t>& users, const std::vector<int32_t>& items,
+                             const EstimateSink& sink = nullptr) {
+        if (!prepared.job()) throw std::runtime_error("BaselineRecommenderJob failed!: estimatePairs on a closed prepared job");
+        if (users.size() != items.size()) throw std::invalid_argument("estimatePairs: users and items differ in length");
+        fy_itemcf_params cp{};
+        cp.max_prefs_per_user = maxPrefsPerUser;
+        cp.boolean_data = booleanData ? 1 : 0;
+        cp.world = 1;
+        fy_itemcf_pairs q{};
+        q.n_pairs = (int64_t)users.size();
+        q.users = users.empty() ? nullptr : users.data();
+        q.items = items.empty() ? nullptr : items.data();
+        q.location = FY_HOST;
+        fy_result* res = nullptr;
+        if (fy_itemcf_estimate_prepared(prepared.job(), &cp, &q, &res) != FY_OK)
+            throw std::runtime_error(std::string("BaselineRecommenderJob failed!: estimate: ") + fy_last_error());
+        if (sink) {
+            const int64_t n = fy_result_size(res);
+            const int32_t *u = fy_result_key0(res), *i = fy_result_key1(res), *st = fy_result_aux(res);
+            const float* v = fy_result_value(res);
+            for (int64_t k = 0; k < n; k++) sink(u[k], i[k], v[k], st[k]);
+        }
+        fy_result_stats(res, &stats);
+        fy_result_itemcf_estimate_stats(res, &estimateStats);
+        return res;
     }
 };
 

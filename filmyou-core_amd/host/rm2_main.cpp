@@ -89,6 +89,58 @@ static int main_recommend_users(char** a) {
     return 0;
 }
 
+// rm2_main --estimate-pairs <test.txt> <ratings.txt> <similarityClassname> <K> <maxPrefs>
+//   : BaselineRecommenderJob::prepare on the ratings + estimatePairs for the (user, item) of the test ratings ("user item score" per line)
+//   + estimateErrors against their scores.  <test.txt> = holdout:<fraction>:<seed> splits <ratings.txt> instead: prepared on the train side.
+//   Prints "user item estimate status"; one `estimate ...` line on stderr.
+static int main_estimate_pairs(char** a) {
+    fy::host::Ratings r, test;
+    FILE* f = fopen(a[1], "r");
+    if (!f) { perror(a[1]); return 2; }
+    int u, i; float s;
+    while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) r.add(u, i, s);
+    fclose(f);
+    try {
+        double fraction = 0.0;
+        unsigned long long seed = 0;
+        if (sscanf(a[0], "holdout:%lf:%llu", &fraction, &seed) == 2) {
+            auto parts = fy::host::holdout(r, fraction, seed);
+            r = std::move(parts.first);
+            test = std::move(parts.second);
+            fprintf(stderr, "holdout train %zu test %zu\n", r.user.size(), test.user.size());
+        } else {
+            f = fopen(a[0], "r");
+            if (!f) { perror(a[0]); return 2; }
+            while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) test.add(u, i, s);
+            fclose(f);
+        }
+        fy::host::BaselineRecommenderJob job;
+        job.similarityClassname = a[2];
+        job.maxSimilaritiesPerItem = atoi(a[3]);
+        job.maxPrefsPerUser = atoi(a[4]);
+        fy::host::PreparedItemSimilarity prepared = job.prepare(r);
+        fy_result* est = job.estimatePairs(prepared, test.user, test.item,
+                                           [](int32_t user, int32_t item, float v, int32_t status) { printf("%d %d %.9g %d\n", user, item, v, status); });
+        fy_eval_errors e{};
+        try {
+            e = fy::host::estimateErrors(prepared.context(), est, test);
+        } catch (...) {
+            fy_result_free(est);
+            throw;
+        }
+        fy_result_free(est);
+        fprintf(stderr, "estimate pairs %lld estimated %lld truth_not_finite %lld ok %lld unknown_user %lld unknown_item %lld own_preference %lld too_few %lld "
+                "zero_numerator %lld not_a_number %lld row_entries_walked %lld mae %.17g rmse %.17g\n", (long long)e.pairs, (long long)e.estimated,
+                (long long)e.truth_not_finite, (long long)e.by_status[0], (long long)e.by_status[1], (long long)e.by_status[2], (long long)e.by_status[3],
+                (long long)e.by_status[4], (long long)e.by_status[5], (long long)e.by_status[6], (long long)job.estimateStats.row_entries_walked,
+                fy::host::mae(e), fy::host::rmse(e));
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     std::vector<std::pair<std::string, std::string>> extra;      // trailing key=value arguments
     while (argc > 1 && argv[argc - 1][0] != '-' && strchr(argv[argc - 1], '=') && !strchr(argv[argc - 1], '/')) {
@@ -99,6 +151,7 @@ int main(int argc, char** argv) {
     if (argc == 9 && strcmp(argv[1], "--files") == 0) return main_files(argv + 2);
     if (argc == 8 && strcmp(argv[1], "--recommend-users") == 0) return main_recommend_users(argv + 2);
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
+    if (argc == 7 && strcmp(argv[1], "--estimate-pairs") == 0) return main_estimate_pairs(argv + 2);
     bool rccl = false;
     // rm2_main --users <users.txt> <ratings.txt> ... : RM2Job::runUsers, lists for the ids of the usersFile alone
     const char* users_file = nullptr;

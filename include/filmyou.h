@@ -751,6 +751,100 @@ int fy_eval_prepare(fy_context*, const fy_eval_params*, const fy_ratings* test, 
 int fy_eval_lists(fy_eval*, fy_result* lists, fy_eval_sums* out, int32_t* per_user_id_or_null, double* per_user_or_null);
 void fy_eval_destroy(fy_eval*);
 
+/* ------------------------------------------------------------------ item-based CF: estimated preferences for named pairs; MAE / RMSE
+ * (csrc/fy_itemcf_estimate.hip, csrc/fy_eval.hip).  Mahout's ItemBasedRecommender.estimatePreference asked of
+ * the DISTRIBUTED job: estimate(u, i) is the cell (u, i) of the pass fy_itemcf_recommend_prepared runs for the same prepared job, the
+ * same max_prefs_per_user and boolean_data, without an allow-list, before the top-N.  It is NOT Mahout's non-distributed
+ * estimatePreference (every preference, untruncated similarities).  Restated from the published algorithm like every Mahout class of
+ * this package: PARITY UNPINNED.
+ * The contributing preferences are the user's kept ones: p >= the max_prefs_per_user-th largest value, ties at the cut kept.  A
+ * kept preference j contributes to (u, i) iff row j of the job (its max_similarities_per_item best entries) holds i.  The additions
+ * run in the order of the user's preferences, in fp64: num += pref * sim (pref = 1 with boolean_data), den += |sim|, cnt += 1; the
+ * finish is the list pass's: (float)(num / den) where cnt > 1, (float) num where cnt > 0 with boolean_data, nothing where num == 0.
+ * So wherever a list of fy_itemcf_recommend_prepared holds (u, i), the estimate is that float BIT FOR BIT, and a pair the list pass
+ * can never emit has a status that says why.  A kept preference whose row is empty adds nothing, not even its self entry (as in the
+ * list pass): its own cell is an ordinary cell.
+ * Every asked pair gets exactly one row, in the order asked; a pair asked twice is answered twice.  Row: key0 = user, key1 = item
+ * (as asked), value = the estimate (NaN unless the status is FY_ESTIMATE_OK), aux = the status, the FIRST of these that applies: */
+enum {
+    FY_ESTIMATE_OK = 0,               /* value is the prediction */
+    FY_ESTIMATE_UNKNOWN_USER = 1,     /* no kept preference: an id outside the data, or a negative id */
+    FY_ESTIMATE_UNKNOWN_ITEM = 2,     /* nobody rated it: the item has no column */
+    FY_ESTIMATE_OWN_PREFERENCE = 3,   /* the item is one of the user's kept (strongest) preferences: the (j, NaN) self entry of the list
+                                         pass.  An item the user rated below the cut is an ordinary cell, as in the list pass */
+    FY_ESTIMATE_TOO_FEW = 4,          /* fewer than two contributing preferences (fewer than one with boolean_data) */
+    FY_ESTIMATE_ZERO_NUMERATOR = 5,   /* numerator exactly 0: the reducer's nonZeroes() skip */
+    FY_ESTIMATE_NOT_A_NUMBER = 6      /* the arithmetic gave NaN (a NaN preference or similarity): the list pass drops such a cell */
+};
+/* Pairs: two arrays of raw ids, FY_HOST or FY_DEVICE (HBM of the job's context); they may be freed when the call returns.
+ * fy_itemcf_estimate_ratings asks for the (user, item) columns of a resident ratings object of the job's context in its COO order
+ * (typically the test side of fy_ratings_holdout: no id leaves the GPU); its scores are not read.
+ * (rank, world) of fy_itemcf_params cut the PAIR LIST into contiguous ranges [n rank / world, n (rank + 1) / world): a rank's result
+ * holds its own range and remembers the offset of its first pair (fy_itemcf_estimate_stats.pair_offset; fy_eval_estimates reads
+ * it).  num_recommendations is ignored.  The failures are fy_itemcf_recommend_prepared's: a job prepared with world != 1 or with
+ * min_prefs_per_user / max_prefs_per_user is FY_ERR_UNSUPPORTED, NULL arguments and max_prefs_per_user <= 0 are
+ * FY_ERR_INVALID_ARGUMENT, more than 2^31 - 1 pairs are FY_ERR_UNSUPPORTED.  Zero pairs, or a job over an empty preference
+ * matrix (every pair: FY_ESTIMATE_UNKNOWN_USER), build nothing.
+ * The rows the estimates need are the rows of the kept preferences of the asked users; they come from and stay in the job's row
+ * store, shared with fy_itemcf_recommend_prepared in both directions.
+ * Work: equal pairs form one target; a user's distinct targets are cut into chunks of FY_ICF_EST_CHUNK (default 256) and ONE WAVE
+ * per (user, chunk) walks the user's rows once, so row_entries_walked is paid per chunk, not per pair.  Nothing is sized by the
+ * catalogue: no dense accumulator row, no top-N, no global atomics on the cells.
+ * fy_result_stats: nnz, n_users, n_items (the job's), recs = rows, users_scored = distinct users with at least one OK pair,
+ * pair_contribs, cooc_launches (= batches), score_launches, ms_tables (keys, sort, thresholds, the set J), ms_cooc (row kernel,
+ * merge, store fill), ms_score (the estimate kernel), ms_total; ms_prepare = 0 and ms_topn = 0.
+ * The result is a kind of its own: fy_eval_lists, fy_itemsim_pairs and fy_itemcf_recommend* refuse it with
+ * FY_ERR_INVALID_ARGUMENT; fy_result_key0 / key1 / value / aux read it. */
+typedef struct {
+    int64_t n_pairs;
+    const int32_t* users;     /* raw user ids */
+    const int32_t* items;     /* raw item ids */
+    int location;             /* FY_HOST | FY_DEVICE */
+} fy_itemcf_pairs;
+typedef struct {
+    int64_t pairs_asked;         /* rows of this result (this rank's range of the pair list) */
+    int64_t pair_offset;         /* position of the first of them in the whole pair list */
+    int64_t by_status[8];        /* rows per FY_ESTIMATE_* code */
+    int64_t users_known;         /* distinct users of the range with a kept preference */
+    int64_t targets;             /* distinct (known user, known item) pairs: what the estimate kernel computes */
+    int64_t chunks;              /* (user, chunk of targets) = waves of the estimate kernel */
+    int64_t items_needed;        /* these six as in fy_itemcf_request_stats */
+    int64_t rows_built;
+    int64_t rows_from_store;
+    int64_t rows_stored;
+    int64_t pair_contribs;
+    int64_t batches;
+    int64_t row_entries_walked;  /* sum over the chunks of sum over the user's kept preferences j of the entries of row j */
+} fy_itemcf_estimate_stats;
+int fy_itemcf_estimate_prepared(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_pairs*, fy_result** out);
+int fy_itemcf_estimate_ratings(fy_itemsim_job*, const fy_itemcf_params*, const fy_ratings* asked, fy_result** out);
+int fy_result_itemcf_estimate_stats(fy_result*, fy_itemcf_estimate_stats* out);   /* FY_ERR_STATE on any other result */
+
+/* Rating-error sums of an estimates result against the true scores (Mahout's AverageAbsoluteDifferenceRecommenderEvaluator and
+ * RMSRecommenderEvaluator).  Row r of `estimates` is compared with entry pair_offset + r of `truth` (a resident ratings object of the
+ * same context, in its COO order): the (user, item) of the two must agree row for row, which is checked on the device; a
+ * disagreement, or a range that does not fit into `truth`, is FY_ERR_INVALID_ARGUMENT.  Only FY_ESTIMATE_OK rows whose truth score is
+ * finite enter the sums: e = (double) estimate - (double) truth score, the estimate first clamped into [clamp_lo, clamp_hi] when
+ * has_clamp (clamp_lo > clamp_hi or a NaN bound: FY_ERR_INVALID_ARGUMENT; params == NULL: no clamp).
+ * SUMS, not means: MAE = sum_abs / estimated, RMSE = sqrt(sum_sq / estimated), bias = sum_err / estimated, coverage = estimated /
+ * pairs; the ranks of a multi-rank job add their sums in rank order like fy_eval_sums.  The three sums are bit-identical from run to
+ * run: per-thread partial sums over fixed slices in a fixed order, no floating-point atomics. */
+typedef struct {
+    int32_t has_clamp;
+    int32_t reserved;
+    double clamp_lo, clamp_hi;
+} fy_eval_error_params;
+typedef struct {
+    int64_t pairs;                /* rows of `estimates` */
+    int64_t estimated;            /* rows that entered the sums */
+    int64_t truth_not_finite;     /* FY_ESTIMATE_OK rows left out because the truth score is NaN or infinite */
+    int64_t by_status[8];         /* rows per FY_ESTIMATE_* code */
+    double sum_abs, sum_sq, sum_err;
+    double ms;                    /* HIP-event time of the call */
+} fy_eval_errors;
+int fy_eval_estimates(fy_context*, fy_result* estimates, const fy_ratings* truth, const fy_eval_error_params* params_or_null,
+                      fy_eval_errors* out);
+
 #ifdef __cplusplus
 }
 #endif
