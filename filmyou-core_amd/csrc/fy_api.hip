@@ -79,6 +79,8 @@ void fy::load_tuning_from_env(Tuning& t) {
     if (const char* e = getenv("FY_MAX_SURV_FRAC")) { double v = atof(e); if (v >= 0.0) t.max_surv_frac = v; }
     if (const char* e = getenv("FY_REQ_FULL_SHARE")) { double v = atof(e); if (v >= 0.0) t.req_full_share = v; }
     if (const char* e = getenv("FY_REQ_CHUNK")) { int v = atoi(e); if (v >= 64 && v <= 16384 && v % 64 == 0) t.req_chunk = v; }
+    if (const char* e = getenv("FY_RM1_NBR_CHUNK")) { int v = atoi(e); if (v >= 1 && v <= (1 << 20)) t.rm1_nbr_chunk = v; }
+    if (const char* e = getenv("FY_RM1_COL_CHUNK")) { int v = atoi(e); if (v >= 1 && v <= (1 << 20)) t.rm1_col_chunk = v; }
     if (const char* e = getenv("FY_UPD_LDS_KEYS")) { int v = atoi(e); if (v >= 0 && v <= fy::UPD_LDS_KEYS_MAX) t.upd_lds_keys = v; }
     if (const char* e = getenv("FY_ISIM_HEAVY")) t.isim_heavy = std::max(0, atoi(e));
     if (const char* e = getenv("FY_ISIM_GRAM")) t.isim_gram = atoi(e) != 0;

@@ -22,6 +22,7 @@
 #include <chrono>
 #include "fy_rm2.hpp"
 #include "fy_rm2_plan.hpp"
+#include "fy_rm1.hpp"
 #include "fy_rm2_request.hpp"
 
 namespace fy {
@@ -1543,6 +1544,8 @@ static void validate_params(const fy_rm2_params* p) {
     if (p->number_of_items <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "numberOfItems must be > 0 (got %d)", p->number_of_items);
     const bool dir = p->flags & FY_RM2_SMOOTHING_DIRICHLET, ad = p->flags & FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT;
     if (dir && ad) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "flags: FY_RM2_SMOOTHING_DIRICHLET and FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT are both set");
+    if (p->flags & ~(FY_RM2_NO_CACHE | FY_RM2_SMOOTHING_DIRICHLET | FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT | FY_RM2_ESTIMATOR_RM1))
+        FY_FAIL(FY_ERR_INVALID_ARGUMENT, "flags: unknown bits 0x%x", p->flags & ~15u);
     if (dir || ad) {
         if (!(std::isfinite(p->lambda) && p->lambda >= 0.0))
             FY_FAIL(FY_ERR_INVALID_ARGUMENT, "%s must be finite and >= 0 (got %g)", dir ? "mu" : "delta", p->lambda);
@@ -2865,6 +2868,39 @@ static PlanInput plan_input(const fy_rm2_job* J) {
     in.have_coll = J->have_coll;
     return in;
 }
+static void fill_request_view(fy_rm2_job* J, RequestView& V);
+
+// ---- the RM1 estimator (FY_RM2_ESTIMATOR_RM1): the side outputs of every job, then one fp64 pass over the rank's slots (fy_rm1.hip)
+static void score_rm1(fy_rm2_job* J, fy_result* R) {
+    Context* ctx = J->ctx;
+    const Prepared& P = J->P;
+    hipStream_t st = ctx->stream;
+    DevBuf<double> icoll_mine, d_total(ctx, 1);
+    if (J->S->sharded) icoll_mine.alloc(ctx, P.nI); else R->d_icoll.alloc(ctx, P.nI);
+    k_item_coll<<<grid_for(P.nI), 256, 0, st>>>(P.nI, J->stats.get(), J->S->sharded ? icoll_mine.get() : R->d_icoll.get(), d_total.get());
+    FY_KERNEL_CHECK();
+    for (int c = 0; c < P.K; c++)
+        if (P.csize[c] > 0) R->st.n_clusters_nonempty++;
+    RequestView V;
+    fill_request_view(J, V);
+    std::vector<int32_t> slots((size_t)std::max(0, J->slot_hi - J->slot_lo));
+    for (size_t k = 0; k < slots.size(); k++) slots[k] = J->slot_lo + (int32_t)k;
+    rm1_score_slots(V, slots, R);
+    R->rq = fy_rm2_request_stats{};      // (a full job's result carries no request statistics)
+    if (J->S->sharded) {
+        sharded_side_outputs(J, R, d_total.get());
+    } else {
+        R->d_user_id.alloc(ctx, P.nU);
+        R->d_user_sum.alloc(ctx, P.nU);
+        d2d(ctx, R->d_user_id.get(), P.uid.get(), P.nU);
+        d2d(ctx, R->d_user_sum.get(), P.usum.get(), P.nU);
+        R->d_item_id.alloc(ctx, P.nI);
+        d2d(ctx, R->d_item_id.get(), P.iid.get(), P.nI);
+    }
+    d2h(ctx, &R->total_sum, d_total.get(), 1);
+    sync(ctx);
+}
+
 fy_result* fy::rm2_score(fy_rm2_job* J) {
     Context* ctx = J->ctx;
     Prepared& P = J->P;
@@ -2906,8 +2942,9 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
     }
     const int32_t nU = P.nU, nI = P.nI;
     PlanInput in = plan_input(J);
-    if (J->S->smooth.general()) {
-        // The cooperative path (fy_rm2_coop.hpp) knows Jelinek-Mercer alone.  Whether a cluster would take it is host arithmetic: the
+    const bool rm1 = (prm.flags & FY_RM2_ESTIMATOR_RM1) != 0;
+    if (J->S->smooth.general() || rm1) {
+        // The cooperative path (fy_rm2_coop.hpp) knows RM2 with Jelinek-Mercer alone.  Whether a cluster would take it is host arithmetic: the
         // plan is made once ahead with a stand-in for the number of list rows, and such a job is refused before anything is queued.
         PlanInput dry = in;
         J->count_balanced = plan_count_balanced(dry);
@@ -2920,9 +2957,19 @@ fy_result* fy::rm2_score(fy_rm2_job* J) {
             would_coop = plan_job(dry).any_coop;
         } catch (const PlanError&) {      // (the job's own plan below reports it)
         }
+        if (would_coop && rm1)
+            FY_FAIL(FY_ERR_UNSUPPORTED, "fy_rm2_score: a cluster of this job would be scored cooperatively by all ranks, which supports the RM2 estimator "
+                                        "only (FY_RM2_ESTIMATOR_RM1: run without collectives)");
         if (would_coop)
             FY_FAIL(FY_ERR_UNSUPPORTED, "fy_rm2_score: a cluster of this job would be scored cooperatively by all ranks, which supports Jelinek-Mercer "
                                         "smoothing only (FY_RM2_SMOOTHING_DIRICHLET / FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT: run without collectives)");
+    }
+    if (rm1) {
+        score_rm1(J, R.get());
+        t_total.end(span_total);
+        sync(ctx);
+        R->st.ms_total = t_total.total_ms();
+        return R.release();
     }
     ScoreTune tune = ctx->tune;
     tune.seed_chunks = plan_seed(tune, prm.number_of_recommendations).seed_chunks;     // (0 = from the list length)
@@ -3038,6 +3085,10 @@ void fy::rm2_request_view(fy_rm2_job* J, RequestView& V) {
         if (J->prm.world == 1) rm2_set_global_stats(J, J->partial.get(), 1);
         else FY_FAIL(FY_ERR_STATE, "world > 1: call fy_rm2_set_global_stats before fy_rm2_score_users");
     }
+    fill_request_view(J, V);
+}
+
+static void fill_request_view(fy_rm2_job* J, RequestView& V) {
     V.ctx = J->ctx;
     V.prm = J->prm;
     V.P = &J->P;

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <limits>
 
+#include "fy_rm1.hpp"
 #include "fy_rm2_request.hpp"
 
 namespace fy {
@@ -237,6 +238,7 @@ struct ReqUser {
 fy_result* rm2_score_users(fy_rm2_job* J, const fy_rm2_request* rq) {
     RequestView V;
     rm2_request_view(J, V);
+    if (V.prm.flags & FY_RM2_ESTIMATOR_RM1) return rm1_score_users(V, rq);      // one fp64 pass of its own (fy_rm1.hip)
     Context* ctx = V.ctx;
     const Prepared& P = *V.P;
     const fy_rm2_params& prm = V.prm;

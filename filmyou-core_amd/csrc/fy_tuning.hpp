@@ -69,6 +69,9 @@ struct Tuning {
                                        // unrequested rows are dropped (0 = every touched cluster, >= 1 = never).  Not measured yet ("RM2 on
                                        // request"), so the default never falls back; ONE cluster that does costs the rank's whole full job
     int req_chunk = 8192;              // FY_REQ_CHUNK: columns (64-bit LDS accumulators) a workgroup of the slab build owns
+    // RM1 estimator (fy_rm1.hip); neither changes a bit of a result
+    int rm1_nbr_chunk = 512;           // FY_RM1_NBR_CHUNK: neighbours a workgroup of k_rm1_loglik takes (its four waves share the user's LDS bitmask)
+    int rm1_col_chunk = 1024;          // FY_RM1_COL_CHUNK: candidate columns a workgroup of k_rm1_score owns (a lane walks one column at a time)
     // ratings update (fy_ratings_update.hip)
     int upd_lds_keys = 4096;           // FY_UPD_LDS_KEYS: a batch of at most this many distinct keys is searched in LDS (32 KiB of keys beside the 32 KiB
                                        // user bitmap: two workgroups per CU), a larger one in global memory (0 = always); at most 8192

@@ -416,11 +416,17 @@ class RM2Job:
 
     Smoothing of the user language model (include/filmyou.h, FY_RM2_SMOOTHING_*): ``smoothing`` = ``jm`` (the default: the
     reference's Jelinek-Mercer, parameter ``lambda``), ``dirichlet`` (parameter ``mu``) or ``absoluteDiscounting`` (parameter
-    ``delta``), matched without regard to case.  ``mu`` / ``delta`` have no default: the chosen method's parameter must be set."""
+    ``delta``), matched without regard to case.  ``mu`` / ``delta`` have no default: the chosen method's parameter must be set.
+
+    Estimator: ``relevanceModel`` = ``rm2`` (the default, the reference's) or ``rm1`` (FY_RM2_ESTIMATOR_RM1: the paper's RM1 over the
+    same neighbourhoods and the same user model, one fp64 pass; include/filmyou.h), matched without regard to case; anything else
+    is a ValueError.  ``PreparedRM2.score_users`` and ``run(usersFile=)`` follow the job's estimator."""
 
     JOB_NAME = "RM2"
     # smoothing name (lower case) -> (flag bit of fy_rm2_params::flags, the Configuration key of the method's parameter)
     SMOOTHING = {"jm": (0, "lambda"), "dirichlet": (2, "mu"), "absolutediscounting": (4, "delta")}
+    # relevanceModel (lower case) -> flag bit: rm2 (the default, the reference's estimator) or rm1 (FY_RM2_ESTIMATOR_RM1)
+    RELEVANCE_MODEL = {"rm2": 0, "rm1": 8}
 
     def __init__(self, conf, ctx=None):
         self.conf = conf
@@ -440,6 +446,10 @@ class RM2Job:
         if conf.get(key) is None:
             raise ValueError("smoothing=%s needs %s" % (name, key))
         lam = float(conf.get(key))    # (jm) Double.valueOf(conf.get("lambda")), AbstractRM2Reducer.java:108
+        model = str(conf.get("relevanceModel", "rm2"))
+        if model.lower() not in self.RELEVANCE_MODEL:
+            raise ValueError("relevanceModel must be rm2 or rm1 (got %r)" % model)
+        flag |= self.RELEVANCE_MODEL[model.lower()]
         return _native.RM2Params(lam, n_items, conf.getInt("numberOfRecommendations", 1000),
                                  conf.getInt("filterUsers", 0), n_clusters, int(rank), int(world), flag,
                                  int(workspace_bytes))

@@ -210,6 +210,7 @@ inline double coverage(const fy_eval_errors& e) { return (double)e.estimated / (
 // The smoothing of the user language model (include/filmyou.h, FY_RM2_SMOOTHING_*) from the Configuration keys `smoothing` (jm --
 // the default, parameter `lambda` --, dirichlet with `mu`, absoluteDiscounting with `delta`; case does not matter) into
 // fy_rm2_params::flags and ::lambda.  mu / delta have no default; an unknown name or a missing parameter is std::invalid_argument.
+// Next to it the estimator: `relevanceModel` = rm2 (the default) or rm1 (FY_RM2_ESTIMATOR_RM1), refused the same way.
 inline void setSmoothing(const Configuration& conf, fy_rm2_params& p) {
     std::string name = conf.get("smoothing", "jm");
     for (char& ch : name) ch = (char)std::tolower((unsigned char)ch);
@@ -219,6 +220,11 @@ inline void setSmoothing(const Configuration& conf, fy_rm2_params& p) {
     else if (name != "jm") throw std::invalid_argument("smoothing must be jm, dirichlet or absoluteDiscounting (got " + conf.get("smoothing") + ")");
     if (!conf.has(key)) throw std::invalid_argument("smoothing=" + name + " needs " + key);
     p.lambda = std::stod(conf.get(key));
+    // relevanceModel = rm2 (the default, the reference's estimator) | rm1 (FY_RM2_ESTIMATOR_RM1); case does not matter
+    std::string model = conf.get("relevanceModel", "rm2");
+    for (char& ch : model) ch = (char)std::tolower((unsigned char)ch);
+    if (model == "rm1") p.flags |= FY_RM2_ESTIMATOR_RM1;
+    else if (model != "rm2") throw std::invalid_argument("relevanceModel must be rm2 or rm1 (got " + conf.get("relevanceModel") + ")");
 }
 
 // writePreference(context, userId, itemId, score, cluster)

@@ -68,6 +68,22 @@ public class NativeRM2Job extends AbstractJob {
         return out;
     }
 
+    /** The estimator (filmyou.h, FY_RM2_ESTIMATOR_RM1): relevanceModel = rm2 (default, the reference's) or rm1, case-insensitive.
+     *  The bit travels with the smoothing bits in the natives' smoothingFlags argument (fy_rm2_params::flags). */
+    public static final String RELEVANCE_MODEL_NAME = "relevanceModel";
+    private static final int ESTIMATOR_RM1 = 8;
+
+    private static int relevanceModel(final Configuration conf) {
+        final String name = conf.get(RELEVANCE_MODEL_NAME, "rm2");
+        if (name.equalsIgnoreCase("rm2")) {
+            return 0;
+        }
+        if (name.equalsIgnoreCase("rm1")) {
+            return ESTIMATOR_RM1;
+        }
+        throw new IllegalArgumentException("relevanceModel must be rm2 or rm1 (got " + name + ")");
+    }
+
     /** usersFile: one id per line; a line that is not an int is skipped (like the reference's "itemsFile line ignored") */
     public static final String USERS_FILE_NAME = "usersFile";
 
@@ -162,7 +178,7 @@ public class NativeRM2Job extends AbstractJob {
         }
         final ByteBuffer ids = usersFile != null ? readIds(usersFile) : null;
         final Object[] smoothing = smoothing(conf);
-        final int smoothingFlags = (Integer) smoothing[0];
+        final int smoothingFlags = (Integer) smoothing[0] | relevanceModel(conf);
         final double parameter = Double.valueOf(conf.get((String) smoothing[1]));
         final long h = usersFile != null
                 ? runUsers(parameter, smoothingFlags, conf.getInt(RMRecommenderDriver.numberOfItems, -1),

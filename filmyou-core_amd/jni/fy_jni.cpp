@@ -53,7 +53,7 @@ JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_run(JNIEnv* env,
     fy_rm2_params p;
     std::memset(&p, 0, sizeof p);
     p.lambda = lambda;                       // the chosen method's parameter: lambda, mu or delta
-    p.flags = (uint32_t)smoothingFlags;      // FY_RM2_SMOOTHING_* (0 = Jelinek-Mercer)
+    p.flags = (uint32_t)smoothingFlags;      // FY_RM2_SMOOTHING_* (0 = Jelinek-Mercer) | FY_RM2_ESTIMATOR_RM1 (relevanceModel=rm1)
     p.number_of_items = numberOfItems;
     p.number_of_recommendations = numberOfRecommendations;
     p.filter_users = filterUsers;
@@ -102,7 +102,7 @@ JNIEXPORT jlong JNICALL Java_es_udc_fi_dc_irlab_rm_NativeRM2Job_runUsers(JNIEnv*
     fy_rm2_params p;
     std::memset(&p, 0, sizeof p);
     p.lambda = lambda;                       // the chosen method's parameter: lambda, mu or delta
-    p.flags = (uint32_t)smoothingFlags;      // FY_RM2_SMOOTHING_* (0 = Jelinek-Mercer)
+    p.flags = (uint32_t)smoothingFlags;      // FY_RM2_SMOOTHING_* (0 = Jelinek-Mercer) | FY_RM2_ESTIMATOR_RM1 (relevanceModel=rm1)
     p.number_of_items = numberOfItems;
     p.number_of_recommendations = numberOfRecommendations;
     p.filter_users = filterUsers;

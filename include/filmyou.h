@@ -176,6 +176,39 @@ typedef struct {
  * FY_ERR_UNSUPPORTED from fy_rm2_score with either flag; the context stays usable. */
 #define FY_RM2_SMOOTHING_DIRICHLET 2u
 #define FY_RM2_SMOOTHING_ABSOLUTE_DISCOUNT 4u
+/* The estimator.  Parapar et al. 2013 define two relevance models; the reference ships RM2 (a product over the user's items of a sum
+ * over neighbours).  FY_RM2_ESTIMATOR_RM1 makes fy_rm2_score, fy_rm2_score_users and fy_rm2_run emit RM1 lists instead: with the user
+ * model c_vi above (the same table, all three methods -- the flag combines with either smoothing flag) and U_c users in the cluster,
+ *
+ *     score(u, i) = -ln U_c + ln  sum_{v in V_c, v != u}  c_vi * prod_{j in rated(u)} c_vj
+ *
+ * i.e. p(i|R_u) ~ sum_v p(v) p(i|v) prod_j p(j|v) with p(v) = 1 / U_c (the U_c of RM2's n ln U_c, not U_c - 1).  Everything an RM2
+ * job fixes stays: kept ratings are score > 0; s_v, n_v and p(i|C) with the counter quirk Q1; the routing (an unmapped user goes to
+ * cluster 0); the neighbourhood V_c \ {u}; the candidates of u are the items of its cluster it has not rated; a user without a
+ * candidate gets no list; filterUsers and numberOfRecommendations; the (float) cast, ties by ascending item id, users in the order of
+ * the unrestricted job, the cluster column; the side outputs, which are those of the raw ratings.  Consequences:
+ *   - numberOfItems plays no role (it is still validated);
+ *   - a kept rating with r' = 0 under absolute discounting is still a rated item: no candidate, one factor beta_v p_j;
+ *   - with beta_v = 0 (lambda = 0, mu = 0, delta = 0) a neighbour that has not rated every item of u has likelihood 0;
+ *   - if every neighbour's likelihood is 0, or U_c = 1, every row of u is -inf;
+ *   - a candidate none of the neighbours with positive likelihood gives mass to is -inf.
+ * The pass is fp64 in front of the (float) cast and never forms a likelihood unshifted: with L_uv = sum_j ln c_vj and
+ * m_u = max_v L_uv, score = -ln U_c + m_u + ln(sum_v exp(L_uv - m_u) c_vi) (csrc/fy_rm1.hip).  No
+ * floating-point atomics and a fixed summation order: a row's bits do not depend on the run, the batch, the FY_RM1_* chunk widths,
+ * or on whether it came from fy_rm2_score or fy_rm2_score_users.  Per batch of users the weights (B x U_c x 8 bytes) and the score
+ * rows (B x I_c x 4 bytes) are capped by workspace_bytes; one user whose own rows do not fit fails with FY_ERR_OUT_OF_MEMORY and is
+ * named.  Work: U_c x nnz_c row entries per product and cluster for a full job, nnz_c per requested user.
+ * Ranks: (rank, world) cut the slots as for the general smoothings (replicated and sharded prep both work); a job that would
+ * score a cluster cooperatively (collectives installed) answers FY_ERR_UNSUPPORTED from fy_rm2_score and the context stays usable.
+ * FY_REQ_FULL_SHARE has no meaning under RM1: there is one pass.  Without the flag nothing about any job changes; what a caching
+ * job keeps on the fy_ratings object does not depend on the flag.  Bits of flags outside the four FY_RM2_* are
+ * FY_ERR_INVALID_ARGUMENT.
+ * fy_result_stats of an RM1 result: users_scored, recs, pair_contribs = sum over the scored users u of (nnz_c - n_u) (entries of the
+ * neighbours' rows tested against the user's rated set: the first product), log_terms = sum over the scored users of nnz_c (entries
+ * of the cluster's columns gathered: the second product), cooc_launches / score_launches (= batches), ms_tables (e, ln p, a),
+ * ms_cooc (likelihoods and weights), ms_score, ms_topn, ms_total; fy_result_request_stats of a request: users_asked, users_known,
+ * clusters_touched, batches. */
+#define FY_RM2_ESTIMATOR_RM1 0x8u
 
 /* Stage 1 (jobs RM2-1/RM2-2 up to the exchange): score > 0 filter, CSR/CSC in HBM, cluster routing, user sums,
  * and this rank's PARTIAL per-item rating sums + partial floor-sum total.
