@@ -15,7 +15,7 @@ from ._native import build, LIB_PATH
 from .host import (BaselineRecommenderJob, ClusterAssignmentJob, Configuration, Context, FilmYouError, ItemRecommendations, ItemSimilarities, NMFDriver, PreparedItemSimilarity, PreparedRM2, Ratings, Recommendations, RM2Job,
                    RowSimilarityJob, SIMILARITY_COSINE, SIMILARITY_COOCCURRENCE, SIMILARITY_TANIMOTO_COEFFICIENT, SIMILARITY_LOGLIKELIHOOD,
                    SIMILARITY_CITY_BLOCK, SIMILARITY_EUCLIDEAN_DISTANCE, SIMILARITY_PEARSON_CORRELATION, ClusterRefinementJob, RMRecommenderDriver,
-                   SubClusterMappingJob, SubClusterMappings, read_id_file, write_similarity_pairs, Evaluation, Evaluator, EstimateErrors, PreferenceEstimates,
+                   SubClusterMappingJob, SubClusterMappings, read_id_file, write_similarity_pairs, Evaluation, Evaluator, EstimateErrors, PreferenceEstimates, PreferenceExplanations,
                    FY_ESTIMATE_OK, FY_ESTIMATE_UNKNOWN_USER, FY_ESTIMATE_UNKNOWN_ITEM, FY_ESTIMATE_OWN_PREFERENCE, FY_ESTIMATE_TOO_FEW,
                    FY_ESTIMATE_ZERO_NUMERATOR, FY_ESTIMATE_NOT_A_NUMBER)
 
@@ -23,5 +23,5 @@ __all__ = ["build", "BaselineRecommenderJob", "ClusterAssignmentJob", "ItemRecom
            "Recommendations", "RM2Job", "RowSimilarityJob", "SIMILARITY_COSINE", "SIMILARITY_COOCCURRENCE", "SIMILARITY_TANIMOTO_COEFFICIENT",
            "SIMILARITY_LOGLIKELIHOOD", "SIMILARITY_CITY_BLOCK", "SIMILARITY_EUCLIDEAN_DISTANCE", "SIMILARITY_PEARSON_CORRELATION", "_native",
            "ClusterRefinementJob", "RMRecommenderDriver", "SubClusterMappingJob", "SubClusterMappings", "read_id_file",
-           "write_similarity_pairs", "Evaluation", "Evaluator", "EstimateErrors", "PreferenceEstimates", "FY_ESTIMATE_OK", "FY_ESTIMATE_UNKNOWN_USER",
+           "write_similarity_pairs", "Evaluation", "Evaluator", "EstimateErrors", "PreferenceEstimates", "PreferenceExplanations", "FY_ESTIMATE_OK", "FY_ESTIMATE_UNKNOWN_USER",
            "FY_ESTIMATE_UNKNOWN_ITEM", "FY_ESTIMATE_OWN_PREFERENCE", "FY_ESTIMATE_TOO_FEW", "FY_ESTIMATE_ZERO_NUMERATOR", "FY_ESTIMATE_NOT_A_NUMBER"]

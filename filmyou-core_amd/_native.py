@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_estimate.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_eval.hpp"]
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -34,6 +34,7 @@ SYMBOLS = [
     "fy_refined_stats", "fy_refined_free",
     "fy_ratings_holdout", "fy_result_create_lists", "fy_eval_prepare", "fy_eval_lists", "fy_eval_destroy",
     "fy_itemcf_estimate_prepared", "fy_itemcf_estimate_ratings", "fy_result_itemcf_estimate_stats", "fy_eval_estimates",
+    "fy_itemcf_because_prepared", "fy_result_because_view", "fy_result_itemcf_because_stats",
 ]
 
 
@@ -230,6 +231,26 @@ class ItemCFEstimateStats(C.Structure):
         return d
 
 
+FY_BECAUSE_MAX = 64
+
+
+class ItemCFBecauseView(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("start", C.c_void_p), ("user", C.c_void_p), ("item", C.c_void_p), ("estimate", C.c_void_p),
+                ("status", C.c_void_p), ("contributors", C.c_void_p), ("pref", C.c_void_p)]
+
+
+class ItemCFBecauseStats(C.Structure):
+    _fields_ = [("pairs_asked", C.c_int64), ("pair_offset", C.c_int64), ("by_status", C.c_int64 * 8), ("users_known", C.c_int64),
+                ("targets", C.c_int64), ("rows", C.c_int64), ("contributors", C.c_int64), ("items_needed", C.c_int64),
+                ("rows_built", C.c_int64), ("rows_from_store", C.c_int64), ("rows_stored", C.c_int64), ("pair_contribs", C.c_int64),
+                ("batches", C.c_int64), ("row_entries_walked", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["by_status"] = list(self.by_status)
+        return d
+
+
 class EvalErrorParams(C.Structure):
     _fields_ = [("has_clamp", C.c_int32), ("reserved", C.c_int32), ("clamp_lo", C.c_double), ("clamp_hi", C.c_double)]
 
@@ -382,5 +403,8 @@ def load():
     L.fy_itemcf_estimate_ratings.argtypes = [vp, C.POINTER(ItemCFParams), vp, pvp]
     L.fy_result_itemcf_estimate_stats.argtypes = [vp, C.POINTER(ItemCFEstimateStats)]
     L.fy_eval_estimates.argtypes = [vp, vp, vp, C.POINTER(EvalErrorParams), C.POINTER(EvalErrors)]
+    L.fy_itemcf_because_prepared.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFPairs), i32, pvp]
+    L.fy_result_because_view.argtypes = [vp, C.POINTER(ItemCFBecauseView)]
+    L.fy_result_itemcf_because_stats.argtypes = [vp, C.POINTER(ItemCFBecauseStats)]
     _lib = L
     return L

@@ -509,6 +509,16 @@ int fy_itemcf_estimate_ratings(fy_itemsim_job* j, const fy_itemcf_params* p, con
     FY_CATCH
 }
 
+int fy_itemcf_because_prepared(fy_itemsim_job* j, const fy_itemcf_params* p, const fy_itemcf_pairs* pairs, int32_t how_many, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !p || !pairs) { set_error("job, parameters or pairs are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(j->ctx);
+    *out = fy::itemcf_because_prepared(j, p, pairs->n_pairs, pairs->users, pairs->items, pairs->location, how_many);
+    FY_CATCH
+}
+
 void fy_itemsim_job_drop_rows(fy_itemsim_job* j) {
     if (!j) return;
     if (j->ctx) (void)hipSetDevice(j->ctx->device);
@@ -675,6 +685,51 @@ int fy_result_itemcf_estimate_stats(fy_result* r, fy_itemcf_estimate_stats* out)
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     if (!r->has_itemcf_estimate_stats) { set_error("not a result of fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings"); return FY_ERR_STATE; }
     *out = r->est;
+    return FY_OK;
+}
+int fy_result_itemcf_because_stats(fy_result* r, fy_itemcf_because_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_itemcf_because_stats) { set_error("not a result of fy_itemcf_because_prepared"); return FY_ERR_STATE; }
+    *out = r->bec;
+    return FY_OK;
+}
+// the per-pair arrays and the per-row preference of an explanations result, on the host from the first call on
+static int because_to_host(fy_result* r) {
+    if (r->because_on_host) return FY_OK;
+    FY_TRY
+    const size_t np = (size_t)r->bp_n, n = (size_t)r->n;
+    std::vector<int32_t> start32(np + 1, 0);
+    r->h_bp_user.resize(np); r->h_bp_item.resize(np); r->h_bp_status.resize(np); r->h_bp_cnt.resize(np); r->h_bp_est.resize(np);
+    r->h_bp_start.assign(np + 1, 0);
+    r->h_pref.resize(n);
+    if (np > 0 && r->ctx) {
+        select_device(r->ctx);
+        fy::d2h(r->ctx, r->h_bp_user.data(), r->d_bp_user.get(), np);
+        fy::d2h(r->ctx, r->h_bp_item.data(), r->d_bp_item.get(), np);
+        fy::d2h(r->ctx, r->h_bp_status.data(), r->d_bp_status.get(), np);
+        fy::d2h(r->ctx, r->h_bp_cnt.data(), r->d_bp_cnt.get(), np);
+        fy::d2h(r->ctx, r->h_bp_est.data(), r->d_bp_est.get(), np);
+        fy::d2h(r->ctx, start32.data(), r->d_bp_start.get(), np + 1);
+        fy::d2h(r->ctx, r->h_pref.data(), r->d_pref.get(), n);
+        fy::sync(r->ctx);
+    }
+    for (size_t t = 0; t <= np; t++) r->h_bp_start[t] = start32[t];
+    r->because_on_host = true;
+    FY_CATCH
+}
+int fy_result_because_view(fy_result* r, fy_itemcf_because_view* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_itemcf_because_stats) { set_error("not a result of fy_itemcf_because_prepared"); return FY_ERR_STATE; }
+    const int rc = because_to_host(r);
+    if (rc != FY_OK) return rc;
+    out->n_pairs = r->bp_n;
+    out->start = r->h_bp_start.data();
+    out->user = r->h_bp_user.data();
+    out->item = r->h_bp_item.data();
+    out->estimate = r->h_bp_est.data();
+    out->status = r->h_bp_status.data();
+    out->contributors = r->h_bp_cnt.data();
+    out->pref = r->h_pref.data();
     return FY_OK;
 }
 void fy_result_free(fy_result* r) {

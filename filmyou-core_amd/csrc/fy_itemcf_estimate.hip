@@ -2,7 +2,8 @@
 // (fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings; include/filmyou.h).
 //
 // estimate(u, i) is the cell (u, i) of the list pass (k_icf_accumulate + k_icf_finalize, fy_itemcf.hip) before the top-N.  The list
-// pass pays a dense accumulator row over the catalogue per user; here the work is sized by the pairs asked for:
+// pass pays a dense accumulator row over the catalogue per user; here the work is sized by the pairs asked for (the steps up to the
+// targets are icf_pair_targets of fy_itemcf_pairs.hpp, shared with the explanations of fy_itemcf_because.hip):
 //   k_est_find_users     per pair: the user's slot (binary search), a flag per slot; scan + k_est_list_users: the known users once
 //                        each in slot order -- the slot list icfr_rows_for_users (fy_itemcf_request.hip) takes, as the list pass does
 //   icfr_rows_for_users  thresholds, the set J, the rows the job's store lacks: built and kept (shared with the list pass)
@@ -20,77 +21,13 @@
 #include <limits>
 #include <memory>
 
-#include "fy_itemcf_request.hpp"
+#include "fy_itemcf_pairs.hpp"
 
 namespace fy {
 namespace {
 
-constexpr uint64_t EST_NO_KEY = ~0ull;
 constexpr int EST_AGG = 10;      // status counts [0 .. 7], users with an OK pair [8], row entries walked [9]
 
-// pair t: the slot of its user (-1: nobody has the id) and that slot's flag
-__global__ void k_est_find_users(int64_t n, const int32_t* __restrict__ users, const int32_t* __restrict__ uid, int32_t nU,
-                                 const int32_t* __restrict__ du2slot, int32_t* __restrict__ pslot, int32_t* __restrict__ flag) {
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t raw = users[t];
-        int32_t lo = 0, hi = nU;
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (uid[mid] < raw) lo = mid + 1; else hi = mid;
-        }
-        int32_t s = -1;
-        if (lo < nU && uid[lo] == raw) {
-            s = du2slot[lo];
-            flag[s] = 1;                                         // (every writer stores the same word)
-        }
-        pslot[t] = s;
-    }
-}
-
-__global__ void k_est_list_users(int32_t nU, const int32_t* __restrict__ flag, const int32_t* __restrict__ pos, int32_t* __restrict__ list) {
-    for (int32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < nU; s += gridDim.x * blockDim.x)
-        if (flag[s]) list[pos[s]] = s;
-}
-
-// The row of every pair as far as it is known here, its sort key and its place.  pslot == nullptr: a job over no preferences.
-__global__ void k_est_keys(int64_t n, const int32_t* __restrict__ users, const int32_t* __restrict__ items, const int32_t* __restrict__ pslot,
-                           const int32_t* __restrict__ pos, const int32_t* __restrict__ iid, int32_t nI, const int32_t* __restrict__ pair_rank,
-                           uint64_t* __restrict__ keys, uint32_t* __restrict__ place, int32_t* __restrict__ o_user, int32_t* __restrict__ o_item,
-                           float* __restrict__ o_value, int32_t* __restrict__ o_aux) {
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t it = items[t];
-        const int32_t slot = pslot ? pslot[t] : -1;
-        const int32_t col = slot >= 0 ? icf_column(iid, nI, pair_rank, it) : -1;
-        o_user[t] = users[t];
-        o_item[t] = it;
-        o_value[t] = __builtin_nanf("");
-        o_aux[t] = slot < 0 ? FY_ESTIMATE_UNKNOWN_USER : col < 0 ? FY_ESTIMATE_UNKNOWN_ITEM : FY_ESTIMATE_OK;      // (OK: the estimate kernel writes the row)
-        if (keys) {
-            keys[t] = col >= 0 ? (((uint64_t)(uint32_t)pos[slot] << 32) | (uint32_t)col) : EST_NO_KEY;
-            place[t] = (uint32_t)t;
-        }
-    }
-}
-
-// sorted keys: head[t] = first entry of a target; n_valid[0] = entries in front of the all-ones keys
-__global__ void k_est_heads(int32_t n, const uint64_t* __restrict__ skeys, uint32_t* __restrict__ head, int32_t* __restrict__ n_valid) {
-    for (int32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        const bool valid = skeys[t] != EST_NO_KEY;
-        head[t] = valid && (t == 0 || skeys[t] != skeys[t - 1]);
-        if (valid && (t == n - 1 || skeys[t + 1] == EST_NO_KEY)) n_valid[0] = t + 1;
-    }
-}
-// tkey[m], tfirst[m] = key and first sorted entry of target m; tfirst[targets] = n_valid
-__global__ void k_est_targets(int32_t n_valid, const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ head,
-                              const uint32_t* __restrict__ head_incl, uint64_t* __restrict__ tkey, int32_t* __restrict__ tfirst) {
-    for (int32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_valid; t += gridDim.x * blockDim.x) {
-        if (head[t]) {
-            tkey[head_incl[t] - 1] = skeys[t];
-            tfirst[head_incl[t] - 1] = t;
-        }
-        if (t == n_valid - 1) tfirst[head_incl[t]] = n_valid;
-    }
-}
 // target m opens a chunk iff its distance from the first target of its user is a multiple of CH
 __global__ void k_est_chunk_heads(int32_t nT, const uint64_t* __restrict__ tkey, int32_t CH, uint32_t* __restrict__ chead) {
     for (int32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < nT; m += gridDim.x * blockDim.x) {
@@ -228,21 +165,6 @@ __global__ void __launch_bounds__(256) k_icf_estimate(EstArgs A) {
     }
 }
 
-// rows per status
-__global__ void k_est_count_status(int64_t n, const int32_t* __restrict__ aux, unsigned long long* __restrict__ agg) {
-    unsigned long long mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t s = aux[t] & 7;
-#pragma unroll
-        for (int q = 0; q < 8; q++) mine[q] += s == q;
-    }
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        unsigned long long v = mine[q];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&agg[q], v);
-    }
-}
 // the walk of all chunks; users with an OK pair: the first chunk of a user (its chunks are adjacent) that holds one
 __global__ void k_est_count_chunks(int32_t n_chunks, const int32_t* __restrict__ cstart, const uint64_t* __restrict__ tkey,
                                    const long long* __restrict__ walked, const int32_t* __restrict__ chunk_ok, unsigned long long* __restrict__ agg) {
@@ -309,16 +231,6 @@ fy_result* itemcf_estimate_prepared(fy_itemsim_job* J, const fy_itemcf_params* p
     SyncOnUnwind drain(st);      // behind the host ends of the queued copies (and the caller's id arrays); the buffers below are released before it drains
     const size_t sp_total = t_total.begin();
     size_t sp_tab = t_tables.begin();
-    DevBuf<int32_t> own_users, own_items;
-    const int32_t *d_users = users + off, *d_items = items + off;
-    if (location == FY_HOST) {
-        own_users.alloc(ctx, (size_t)n);
-        own_items.alloc(ctx, (size_t)n);
-        h2d(ctx, own_users.get(), users + off, (size_t)n);
-        h2d(ctx, own_items.get(), items + off, (size_t)n);
-        d_users = own_users.get();
-        d_items = own_items.get();
-    }
     DevBuf<unsigned long long> agg(ctx, EST_AGG);
     agg.zero();
     int32_t* o_user = Rs->d_key0.get();
@@ -326,101 +238,50 @@ fy_result* itemcf_estimate_prepared(fy_itemsim_job* J, const fy_itemcf_params* p
     float* o_value = Rs->d_value.get();
     int32_t* o_aux = Rs->d_aux.get();
 
-    // ---- the known users of the range once each, in slot order
-    int32_t n_known = 0;
-    DevBuf<int32_t> pslot, upos, list;
-    if (P.nnz > 0) {
-        DevBuf<int32_t> flag(ctx, (size_t)P.nU + 1);
-        pslot.alloc(ctx, (size_t)n);
-        upos.alloc(ctx, (size_t)P.nU + 1);
-        flag.zero();
-        k_est_find_users<<<grid_for(n), 256, 0, st>>>(n, d_users, P.uid.get(), P.nU, P.du2slot.get(), pslot.get(), flag.get());
+    // ---- the front half (fy_itemcf_pairs.hpp): known users, their rows in the store, keys, sort, targets
+    IcfPairTargets T;
+    icf_pair_targets(J, prm->max_prefs_per_user, n, users + off, items + off, location, o_user, o_item, o_value, o_aux, t_tables, sp_tab, t_cooc, T, "estimate");
+    es.users_known = T.n_known;
+    es.items_needed = T.built.items_needed;
+    es.rows_built = T.built.rows_built;
+    es.rows_from_store = T.built.rows_from_store;
+    if (T.n_known > 0) es.rows_stored = T.built.rows_stored;
+    es.pair_contribs = T.built.pair_contribs;
+    es.batches = T.built.batches;
+    const int32_t n_targets = T.n_targets;
+    int32_t n_chunks = 0;
+    if (n_targets > 0) {
+        const fy_itemsim_job::RowStore& store = J->store;
+        // ---- chunks
+        const int32_t CH = std::max(1, std::min(ctx->tune.icf_est_chunk, ICF_EST_CHUNK_MAX));
+        DevBuf<uint32_t> chead(ctx, (size_t)n_targets), cincl(ctx, (size_t)n_targets);
+        k_est_chunk_heads<<<grid_for(n_targets), 256, 0, st>>>(n_targets, T.tkey.get(), CH, chead.get());
         FY_KERNEL_CHECK();
-        exclusive_scan_i32(ctx, flag.get(), upos.get(), (size_t)P.nU + 1);
-        n_known = fetch(ctx, upos.get() + P.nU);
-        if (n_known < 0 || n_known > P.nU) FY_FAIL(FY_ERR_HIP, "estimate: %d known users of %d", n_known, P.nU);
-        if (n_known > 0) {
-            list.alloc(ctx, (size_t)n_known);
-            k_est_list_users<<<grid_for(P.nU), 256, 0, st>>>(P.nU, flag.get(), upos.get(), list.get());
-            FY_KERNEL_CHECK();
-        }
-    }
-    es.users_known = n_known;
-    int32_t n_targets = 0, n_chunks = 0;
-    if (n_known == 0) {
-        // nobody is known: every row is written by the key pass
-        k_est_keys<<<grid_for(n), 256, 0, st>>>(n, d_users, d_items, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, o_user, o_item, o_value, o_aux);
+        inclusive_scan_u32(ctx, chead.get(), cincl.get(), (size_t)n_targets);
+        n_chunks = (int32_t)fetch(ctx, cincl.get() + (n_targets - 1));
+        if (n_chunks < 1 || n_chunks > n_targets) FY_FAIL(FY_ERR_HIP, "estimate: %d chunks over %d targets", n_chunks, n_targets);
+        DevBuf<int32_t> cstart(ctx, (size_t)n_chunks + 1), chunk_ok(ctx, (size_t)n_chunks);
+        DevBuf<long long> walked(ctx, (size_t)n_chunks);
+        k_est_chunks<<<grid_for(n_targets), 256, 0, st>>>(n_targets, chead.get(), cincl.get(), cstart.get());
         FY_KERNEL_CHECK();
         t_tables.end(sp_tab);
+
+        // ---- the estimate kernel: one wave per (user, chunk)
+        const size_t sp_score = t_score.begin();
+        EstArgs A{};
+        A.rowptr = P.rowptr.get(); A.csr_idx = P.csr_idx.get(); A.csr_r = P.csr_r.get();
+        A.thr = T.thr.get(); A.list = T.list.get();
+        A.row_cnt = store.cnt.get(); A.col_other = store.other.get(); A.sim = store.sim.get();
+        A.K = K; A.boolean_data = prm->boolean_data; A.n_chunks = n_chunks; A.ld = (int32_t)round_up(CH, 2);
+        A.cstart = cstart.get(); A.tkey = T.tkey.get(); A.tfirst = T.tfirst.get(); A.splace = T.splace.get();
+        A.o_value = o_value; A.o_aux = o_aux; A.walked = walked.get(); A.chunk_ok = chunk_ok.get();
+        k_icf_estimate<<<(int)ceil_div((int64_t)n_chunks, (int64_t)4), 256, (size_t)4 * A.ld * 28, st>>>(A);
+        FY_KERNEL_CHECK();
+        t_score.end(sp_score);
+        k_est_count_chunks<<<grid_for(n_chunks), 256, 0, st>>>(n_chunks, cstart.get(), T.tkey.get(), walked.get(), chunk_ok.get(), agg.get());
+        FY_KERNEL_CHECK();
     } else {
-        // ---- thresholds, the set J, the rows the store lacks: built and kept
-        DevBuf<float> thr(ctx, (size_t)n_known + 1);
-        IcfrRows built;
-        icfr_rows_for_users(J, list.get(), 0, n_known, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
-        es.items_needed = built.items_needed;
-        es.rows_built = built.rows_built;
-        es.rows_from_store = built.rows_from_store;
-        es.rows_stored = built.rows_stored;
-        es.pair_contribs = built.pair_contribs;
-        es.batches = built.batches;
-        const fy_itemsim_job::RowStore& store = J->store;
-
-        // ---- pairs -> keys, sorted; targets; chunks
-        sp_tab = t_tables.begin();
-        const int32_t CH = std::max(1, std::min(ctx->tune.icf_est_chunk, ICF_EST_CHUNK_MAX));
-        DevBuf<uint64_t> keys(ctx, (size_t)n), skeys(ctx, (size_t)n);
-        DevBuf<uint32_t> place(ctx, (size_t)n), splace(ctx, (size_t)n), head(ctx, (size_t)n), head_incl(ctx, (size_t)n);
-        DevBuf<int32_t> n_valid(ctx, 1);
-        n_valid.zero();
-        k_est_keys<<<grid_for(n), 256, 0, st>>>(n, d_users, d_items, pslot.get(), upos.get(), P.iid.get(), P.nI, P.pair_rank.get(), keys.get(), place.get(),
-                                               o_user, o_item, o_value, o_aux);
-        FY_KERNEL_CHECK();
-        sort_pairs_u64_u32(ctx, keys.get(), skeys.get(), place.get(), splace.get(), (size_t)n);
-        k_est_heads<<<grid_for(n), 256, 0, st>>>(n, skeys.get(), head.get(), n_valid.get());
-        FY_KERNEL_CHECK();
-        inclusive_scan_u32(ctx, head.get(), head_incl.get(), (size_t)n);
-        int32_t h_valid = 0;
-        uint32_t h_targets = 0;
-        d2h(ctx, &h_valid, n_valid.get(), 1);
-        d2h(ctx, &h_targets, head_incl.get() + (n - 1), 1);
-        sync(ctx);
-        n_targets = (int32_t)h_targets;
-        if (h_valid < 0 || h_valid > n || n_targets < 0 || n_targets > h_valid || (n_targets == 0) != (h_valid == 0))
-            FY_FAIL(FY_ERR_HIP, "estimate: %d targets in %d valid pairs of %d", n_targets, h_valid, n);
-        if (n_targets > 0) {
-            DevBuf<uint64_t> tkey(ctx, (size_t)n_targets);
-            DevBuf<int32_t> tfirst(ctx, (size_t)n_targets + 1);
-            DevBuf<uint32_t> chead(ctx, (size_t)n_targets), cincl(ctx, (size_t)n_targets);
-            k_est_targets<<<grid_for(h_valid), 256, 0, st>>>(h_valid, skeys.get(), head.get(), head_incl.get(), tkey.get(), tfirst.get());
-            FY_KERNEL_CHECK();
-            k_est_chunk_heads<<<grid_for(n_targets), 256, 0, st>>>(n_targets, tkey.get(), CH, chead.get());
-            FY_KERNEL_CHECK();
-            inclusive_scan_u32(ctx, chead.get(), cincl.get(), (size_t)n_targets);
-            n_chunks = (int32_t)fetch(ctx, cincl.get() + (n_targets - 1));
-            if (n_chunks < 1 || n_chunks > n_targets) FY_FAIL(FY_ERR_HIP, "estimate: %d chunks over %d targets", n_chunks, n_targets);
-            DevBuf<int32_t> cstart(ctx, (size_t)n_chunks + 1), chunk_ok(ctx, (size_t)n_chunks);
-            DevBuf<long long> walked(ctx, (size_t)n_chunks);
-            k_est_chunks<<<grid_for(n_targets), 256, 0, st>>>(n_targets, chead.get(), cincl.get(), cstart.get());
-            FY_KERNEL_CHECK();
-            t_tables.end(sp_tab);
-
-            // ---- the estimate kernel: one wave per (user, chunk)
-            const size_t sp_score = t_score.begin();
-            EstArgs A{};
-            A.rowptr = P.rowptr.get(); A.csr_idx = P.csr_idx.get(); A.csr_r = P.csr_r.get();
-            A.thr = thr.get(); A.list = list.get();
-            A.row_cnt = store.cnt.get(); A.col_other = store.other.get(); A.sim = store.sim.get();
-            A.K = K; A.boolean_data = prm->boolean_data; A.n_chunks = n_chunks; A.ld = (int32_t)round_up(CH, 2);
-            A.cstart = cstart.get(); A.tkey = tkey.get(); A.tfirst = tfirst.get(); A.splace = splace.get();
-            A.o_value = o_value; A.o_aux = o_aux; A.walked = walked.get(); A.chunk_ok = chunk_ok.get();
-            k_icf_estimate<<<(int)ceil_div((int64_t)n_chunks, (int64_t)4), 256, (size_t)4 * A.ld * 28, st>>>(A);
-            FY_KERNEL_CHECK();
-            t_score.end(sp_score);
-            k_est_count_chunks<<<grid_for(n_chunks), 256, 0, st>>>(n_chunks, cstart.get(), tkey.get(), walked.get(), chunk_ok.get(), agg.get());
-            FY_KERNEL_CHECK();
-        } else {
-            t_tables.end(sp_tab);
-        }
+        t_tables.end(sp_tab);
     }
     k_est_count_status<<<grid_for(n), 256, 0, st>>>(n, o_aux, agg.get());
     FY_KERNEL_CHECK();

@@ -37,7 +37,8 @@ void icf_score_lists(Context*, const fy_itemcf_params*, const Prepared&, const I
                      const uint32_t* allow, int32_t lo, int32_t hi, const float* thr, fy_result* Rs, EventTimer& t_score, EventTimer& t_topn,
                      DevBuf<int32_t>& n_lists);
 
-// ---- the front half of a pass that reads a prepared job's rows: fy_itemcf_recommend_prepared and the estimates (fy_itemcf_estimate.hip)
+// ---- the front half of a pass that reads a prepared job's rows: fy_itemcf_recommend_prepared, the estimates (fy_itemcf_estimate.hip)
+// and the explanations (fy_itemcf_because.hip); what the two passes over named pairs share beyond it is fy_itemcf_pairs.hpp
 // what the job must be to serve either (world == 1, no minPrefsPerUser / maxPrefsPerUser of its own), and that its store fits
 void icfr_check_job(const fy_itemsim_job*);
 struct IcfrRows {
@@ -54,6 +55,9 @@ constexpr int ICF_EST_CHUNK_MAX = 512;   // FY_ICF_EST_CHUNK: targets a wave of 
 fy_result* itemcf_recommend_prepared(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_filter*);
 // users / items: the whole pair list, n raw ids each, host or device (location); the rank's range is cut inside
 fy_result* itemcf_estimate_prepared(fy_itemsim_job*, const fy_itemcf_params*, int64_t n, const int32_t* users, const int32_t* items, int location);
+// the contributing preferences of the same pairs, at most how_many listed per pair (fy_itemcf_because.hip)
+fy_result* itemcf_because_prepared(fy_itemsim_job*, const fy_itemcf_params*, int64_t n, const int32_t* users, const int32_t* items, int location,
+                                   int32_t how_many);
 void itemsim_job_drop_rows(fy_itemsim_job*);
 
 }  // namespace fy

@@ -7,7 +7,7 @@
 // result rows live in HBM until an accessor asks for them
 struct fy_result {
     fy::Context* ctx = nullptr;
-    int kind = 0;   // 0 = RM2, 1 = item-sim, 2 = item-CF lists, 3 = item pairs, 4 = item-CF estimates (one row per asked pair)
+    int kind = 0;   // 0 = RM2, 1 = item-sim, 2 = item-CF lists, 3 = item pairs, 4 = item-CF estimates (one row per asked pair), 5 = item-CF explanations
     int64_t n = 0;
     fy::DevBuf<int32_t> d_key0, d_key1, d_aux;
     fy::DevBuf<float> d_value;
@@ -23,6 +23,17 @@ struct fy_result {
     fy_itemcf_request_stats crq{};
     bool has_itemcf_estimate_stats = false;   // a result of fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings (kind 4)
     fy_itemcf_estimate_stats est{};
+    // a result of fy_itemcf_because_prepared (kind 5): rows = the listed contributors; per asked pair (bp_n of them) the ids, the
+    // estimate, its status, the count of contributors and the first row (bp_n + 1); per row the preference
+    bool has_itemcf_because_stats = false;
+    fy_itemcf_because_stats bec{};
+    int64_t bp_n = 0;
+    fy::DevBuf<int32_t> d_bp_user, d_bp_item, d_bp_status, d_bp_cnt, d_bp_start;
+    fy::DevBuf<float> d_bp_est, d_pref;
+    bool because_on_host = false;
+    std::vector<int32_t> h_bp_user, h_bp_item, h_bp_status, h_bp_cnt;
+    std::vector<int64_t> h_bp_start;
+    std::vector<float> h_bp_est, h_pref;
     // host mirrors, filled on first access
     bool rows_on_host = false, sums_on_host = false;
     std::vector<int32_t> h_key0, h_key1, h_aux, h_user_id, h_item_id;

@@ -407,6 +407,25 @@ def _pair_ids(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _itemcf_pairs(pairs):
+    """``(users, items)`` raw-id arrays (numpy, or int32 torch tensors on the context's GPU) -> (fy_itemcf_pairs, what must stay alive
+    while it is used)"""
+    users, items = pairs
+    if _is_torch_tensor(users):
+        import torch
+        assert users.is_cuda and items.is_cuda, "device tensors expected"
+        assert users.dtype == torch.int32 and items.dtype == torch.int32
+        users, items = users.contiguous(), items.contiguous()
+        torch.cuda.current_stream(users.device).synchronize()   # producer stream != the context's stream
+        n, ptrs, loc = users.numel(), (users.data_ptr(), items.data_ptr()), 1
+        assert n == items.numel()
+    else:
+        users, items = _pair_ids(users), _pair_ids(items)
+        n, ptrs, loc = len(users), (users.ctypes.data, items.ctypes.data), 0
+        assert n == len(items)
+    return _native.ItemCFPairs(n, ptrs[0] if n else None, ptrs[1] if n else None, loc), (users, items)
+
+
 class RM2Job:
     """Relevance Model 2 job (M/rm/RM2Job.java:54-272) on one MI355X (or one rank of several).
 
@@ -856,6 +875,48 @@ class PreferenceEstimates(_Result):
         return EstimateErrors(e.pairs, e.estimated, e.truth_not_finite, list(e.by_status), e.sum_abs, e.sum_sq, e.sum_err, e.ms)
 
 
+class PreferenceExplanations(_Result):
+    """What ``PreparedItemSimilarity.because`` returns.  ``rows()``: the listed contributors grouped by asked pair in the order asked,
+    best first -- ``pair`` (index of the asked pair inside this rank's range), ``user``, ``item`` (of the asked pair), ``because`` (the
+    contributing item), ``sim`` (float32, the job's row entry) and ``pref`` (float32; 1 with booleanData).  ``pairs()``: one entry per
+    asked pair -- ``user``, ``item``, ``estimate``, ``status`` (FY_ESTIMATE_*), ``contributors`` (all of them, listed or not) and
+    ``start`` (pairs + 1: the rows of pair t are start[t] .. start[t + 1]).  ``because_stats`` (fy_itemcf_because_stats) beside
+    ``stats``.  Nothing is computed on the host."""
+
+    def __init__(self, handle, ctx=None):
+        super().__init__(handle, ctx)
+        self.stats = self._stats()
+        self.size = self._lib.fy_result_size(handle)
+        self._rows = self._pairs = None
+        bs = _native.ItemCFBecauseStats()
+        _check(self._lib.fy_result_itemcf_because_stats(handle, C.byref(bs)))
+        self.because_stats = bs.as_dict()
+
+    def _view(self):
+        v = _native.ItemCFBecauseView()
+        _check(self._lib.fy_result_because_view(self._h, C.byref(v)))
+        return v
+
+    def pairs(self):
+        if self._pairs is None:
+            v = self._view()
+            n = v.n_pairs
+            start = _np(v.start, n + 1, np.int64)
+            self._pairs = {"user": _np(v.user, n, np.int32), "item": _np(v.item, n, np.int32), "estimate": _np(v.estimate, n, np.float32),
+                           "status": _np(v.status, n, np.int32), "contributors": _np(v.contributors, n, np.int32),
+                           "start": start if len(start) else np.zeros(1, dtype=np.int64)}
+        return self._pairs
+
+    def rows(self):
+        if self._rows is None:
+            L, h, n = self._lib, self._h, self.size
+            pair = _np(L.fy_result_aux(h), n, np.int32)
+            self._rows = {"pair": pair, "user": _np(L.fy_result_key0(h), n, np.int32), "item": self.pairs()["item"][pair],
+                          "because": _np(L.fy_result_key1(h), n, np.int32), "sim": _np(L.fy_result_value(h), n, np.float32),
+                          "pref": _np(self._view().pref, n, np.float32)}
+        return self._rows
+
+
 class Evaluator:
     """Ranking metrics of list results where they lie in HBM (fy_eval_*; include/filmyou.h states the definitions).
 
@@ -1139,24 +1200,30 @@ class PreparedItemSimilarity:
             if isinstance(pairs, Ratings):
                 _check(self._lib.fy_itemcf_estimate_ratings(self._h, C.byref(p), pairs._h, C.byref(res)))
             else:
-                users, items = pairs
-                if _is_torch_tensor(users):
-                    import torch
-                    assert users.is_cuda and items.is_cuda, "device tensors expected"
-                    assert users.dtype == torch.int32 and items.dtype == torch.int32
-                    users, items = users.contiguous(), items.contiguous()
-                    torch.cuda.current_stream(users.device).synchronize()   # producer stream != the context's stream
-                    n, ptrs, loc = users.numel(), (users.data_ptr(), items.data_ptr()), 1
-                    assert n == items.numel()
-                else:
-                    users, items = _pair_ids(users), _pair_ids(items)
-                    n, ptrs, loc = len(users), (users.ctypes.data, items.ctypes.data), 0
-                    assert n == len(items)
-                q = _native.ItemCFPairs(n, ptrs[0] if n else None, ptrs[1] if n else None, loc)
+                q, keep = _itemcf_pairs(pairs)
                 _check(self._lib.fy_itemcf_estimate_prepared(self._h, C.byref(p), C.byref(q), C.byref(res)))
+                del keep
         except FilmYouError as e:
             raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
         return PreferenceEstimates(res, self._ctx)
+
+    def because(self, pairs, howMany=5, maxPrefsPerUser=50, booleanData=False, rank=0, world=1):
+        """fy_itemcf_because_prepared: "because you liked ..." -- for every asked pair the kept preferences of the user whose
+        similarity rows hold the item, i.e. the terms of the sum ``estimate`` finishes for the same pair, the ``howMany`` (1 .. 64)
+        heaviest listed (weight pref * sim descending, equal weights by ascending item id, NaN last), with the pair's estimate, status
+        and count of contributors bit for bit ``estimate``'s.  ``pairs``: ``(users, items)`` raw-id arrays (numpy, or int32 torch
+        tensors on the context's GPU).  (rank, world) cut the pair list.  Rows built stay on the job like ``recommend``'s.  Returns
+        a ``PreferenceExplanations``."""
+        p = _native.ItemCFParams(0, int(maxPrefsPerUser), 1 if booleanData else 0, int(rank), int(world), 0)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            q, keep = _itemcf_pairs(pairs)
+            _check(self._lib.fy_itemcf_because_prepared(self._h, C.byref(p), C.byref(q), int(howMany), C.byref(res)))
+            del keep
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
+        return PreferenceExplanations(res, self._ctx)
 
     def drop_rows(self):
         """fy_itemsim_job_drop_rows: releases the similarity rows kept by ``recommend``; the job stays valid."""

@@ -770,6 +770,60 @@ class BaselineRecommenderJob {
         fy_result_itemcf_estimate_stats(res, &estimateStats);
         return res;
     }
+
+    // "Because you liked ...": Mahout's ItemBasedRecommender.recommendedBecause asked of the distributed job
+    // (fy_itemcf_because_prepared).  For every pair, in the order given, the kept preferences of the user whose similarity rows hold the
+    // item -- the terms of the sum estimatePairs finishes -- the howMany (1 .. FY_BECAUSE_MAX) heaviest listed: weight pref * sim
+    // descending, equal weights by ascending item id, NaN last.  estimate / status are estimatePairs' bit for bit; contributors counts
+    // all terms, listed or not.  The rows of pair t are start[t] .. start[t + 1].
+    struct Explanations {
+        std::vector<int32_t> user, item, status, contributors;      // per pair
+        std::vector<float> estimate;
+        std::vector<int64_t> start;                                 // pairs + 1
+        std::vector<int32_t> pair, because;                         // per row
+        std::vector<float> sim, pref;
+    };
+    fy_itemcf_because_stats becauseStats{};
+    Explanations recommendedBecause(PreparedItemSimilarity& prepared, const std::vector<int32_t>& users, const std::vector<int32_t>& items,
+                                    int32_t howMany, int32_t maxPrefs, bool boolean) {
+        if (!prepared.job()) throw std::runtime_error("BaselineRecommenderJob failed!: recommendedBecause on a closed prepared job");
+        if (users.size() != items.size()) throw std::invalid_argument("recommendedBecause: users and items differ in length");
+        fy_itemcf_params cp{};
+        cp.max_prefs_per_user = maxPrefs;
+        cp.boolean_data = boolean ? 1 : 0;
+        cp.world = 1;
+        fy_itemcf_pairs q{};
+        q.n_pairs = (int64_t)users.size();
+        q.users = users.empty() ? nullptr : users.data();
+        q.items = items.empty() ? nullptr : items.data();
+        q.location = FY_HOST;
+        fy_result* res = nullptr;
+        if (fy_itemcf_because_prepared(prepared.job(), &cp, &q, howMany, &res) != FY_OK)
+            throw std::runtime_error(std::string("BaselineRecommenderJob failed!: because: ") + fy_last_error());
+        fy_itemcf_because_view v{};
+        if (fy_result_because_view(res, &v) != FY_OK) {
+            fy_result_free(res);
+            throw std::runtime_error(std::string("BaselineRecommenderJob failed!: because: ") + fy_last_error());
+        }
+        Explanations e;
+        const int64_t np = v.n_pairs, n = fy_result_size(res);
+        e.user.assign(v.user, v.user + np);
+        e.item.assign(v.item, v.item + np);
+        e.status.assign(v.status, v.status + np);
+        e.contributors.assign(v.contributors, v.contributors + np);
+        e.estimate.assign(v.estimate, v.estimate + np);
+        e.start.assign(v.start, v.start + np + 1);
+        const int32_t *pair = fy_result_aux(res), *because = fy_result_key1(res);
+        const float* sim = fy_result_value(res);
+        e.pair.assign(pair, pair + n);
+        e.because.assign(because, because + n);
+        e.sim.assign(sim, sim + n);
+        e.pref.assign(v.pref, v.pref + n);
+        fy_result_stats(res, &stats);
+        fy_result_itemcf_because_stats(res, &becauseStats);
+        fy_result_free(res);
+        return e;
+    }
 };
 
 }  // namespace host

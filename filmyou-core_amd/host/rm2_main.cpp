@@ -141,6 +141,46 @@ static int main_estimate_pairs(char** a) {
     return 0;
 }
 
+// rm2_main --because <pairs.txt> <ratings.txt> <similarityClassname> <K> <maxPrefs> <howMany>
+//   : BaselineRecommenderJob::prepare on the ratings + recommendedBecause for the pairs ("user item" per line).
+//   Prints "pair user item because sim pref" per listed row, then "# pair user item estimate status contributors" per pair; one
+//   `because ...` line of counters on stderr.
+static int main_because(char** a) {
+    fy::host::Ratings r;
+    std::vector<int32_t> users, items;
+    FILE* f = fopen(a[1], "r");
+    if (!f) { perror(a[1]); return 2; }
+    int u, i; float s;
+    while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) r.add(u, i, s);
+    fclose(f);
+    f = fopen(a[0], "r");
+    if (!f) { perror(a[0]); return 2; }
+    while (fscanf(f, "%d %d", &u, &i) == 2) { users.push_back(u); items.push_back(i); }
+    fclose(f);
+    try {
+        fy::host::BaselineRecommenderJob job;
+        job.similarityClassname = a[2];
+        job.maxSimilaritiesPerItem = atoi(a[3]);
+        fy::host::PreparedItemSimilarity prepared = job.prepare(r);
+        const auto e = job.recommendedBecause(prepared, users, items, atoi(a[5]), atoi(a[4]), false);
+        for (size_t k = 0; k < e.pair.size(); k++) {
+            const int32_t t = e.pair[k];
+            printf("%d %d %d %d %.9g %.9g\n", t, e.user[t], e.item[t], e.because[k], e.sim[k], e.pref[k]);
+        }
+        for (size_t t = 0; t < e.user.size(); t++) printf("# %zu %d %d %.9g %d %d\n", t, e.user[t], e.item[t], e.estimate[t], e.status[t], e.contributors[t]);
+        const fy_itemcf_because_stats& b = job.becauseStats;
+        fprintf(stderr, "because pairs %lld rows %lld contributors %lld ok %lld unknown_user %lld unknown_item %lld own_preference %lld too_few %lld "
+                "zero_numerator %lld not_a_number %lld users_known %lld targets %lld rows_built %lld row_entries_walked %lld\n", (long long)b.pairs_asked,
+                (long long)b.rows, (long long)b.contributors, (long long)b.by_status[0], (long long)b.by_status[1], (long long)b.by_status[2],
+                (long long)b.by_status[3], (long long)b.by_status[4], (long long)b.by_status[5], (long long)b.by_status[6], (long long)b.users_known,
+                (long long)b.targets, (long long)b.rows_built, (long long)b.row_entries_walked);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     std::vector<std::pair<std::string, std::string>> extra;      // trailing key=value arguments
     while (argc > 1 && argv[argc - 1][0] != '-' && strchr(argv[argc - 1], '=') && !strchr(argv[argc - 1], '/')) {
@@ -152,6 +192,7 @@ int main(int argc, char** argv) {
     if (argc == 8 && strcmp(argv[1], "--recommend-users") == 0) return main_recommend_users(argv + 2);
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
     if (argc == 7 && strcmp(argv[1], "--estimate-pairs") == 0) return main_estimate_pairs(argv + 2);
+    if (argc == 8 && strcmp(argv[1], "--because") == 0) return main_because(argv + 2);
     bool rccl = false;
     // rm2_main --users <users.txt> <ratings.txt> ... : RM2Job::runUsers, lists for the ids of the usersFile alone
     const char* users_file = nullptr;

@@ -878,6 +878,74 @@ typedef struct {
 int fy_eval_estimates(fy_context*, fy_result* estimates, const fy_ratings* truth, const fy_eval_error_params* params_or_null,
                       fy_eval_errors* out);
 
+/* ------------------------------------------------------------------ item-based CF: named pairs explained by their contributing
+ * preferences (csrc/fy_itemcf_because.hip).  Mahout's ItemBasedRecommender.recommendedBecause(user, item,
+ * howMany) asked of the DISTRIBUTED job: the "because you liked ..." line under a recommendation.  The explanation of a pair (u, i)
+ * is the decomposition of the cell (u, i) of the list pass, the very cell fy_itemcf_estimate_prepared finishes for the same prepared
+ * job, the same max_prefs_per_user and boolean_data.  It is NOT Mahout's non-distributed recommendedBecause, which sees every
+ * preference and untruncated similarities; Mahout's source is not at hand, so the ranking is DEFINED here, not restated: PARITY
+ * UNPINNED like the rest of the package.
+ * Kept preferences of u: as everywhere, p >= the max_prefs_per_user-th largest value, ties at the cut kept.  A kept preference j is a
+ * CONTRIBUTOR of (u, i) iff its row in the job's store is non-empty and holds i.  A contributor carries
+ *     sim   the float of the store: bit for bit what fy_itemsim_rows returns for (j, i)
+ *     pref  the stored float, or 1.0f with boolean_data
+ * and its weight is (double) pref * (double) sim, the very term the numerator receives (the product of two floats is exact in fp64,
+ * so the order below involves no rounding).  Within a pair the contributors are ordered by descending weight, equal weights by
+ * ascending raw id of the contributing item, a NaN weight after every number (also by ascending id).  At most how_many are LISTED
+ * per pair, 1 <= how_many <= FY_BECAUSE_MAX.
+ * Per pair, whether or not rows are listed: `estimate` and `status` are exactly fy_itemcf_estimate_prepared's value and
+ * FY_ESTIMATE_* code for that pair, BIT FOR BIT (the additions run in the order of the user's preferences, __dmul_rn / __dadd_rn in
+ * fp64, with the same finish), and `contributors` counts all contributing preferences, listed or not (the estimate's cnt).  A pair
+ * with a known user and a known item lists its contributors whatever its status (FY_ESTIMATE_TOO_FEW, _ZERO_NUMERATOR,
+ * _NOT_A_NUMBER and _OWN_PREFERENCE pairs still have terms); FY_ESTIMATE_UNKNOWN_USER and _UNKNOWN_ITEM pairs list none.  Every
+ * asked pair is answered once, in the order asked; a pair asked twice is answered twice.
+ * The result is a kind of its own.  Rows are grouped by asked pair in the order asked: key0 = user, key1 = the contributing item
+ * (raw id), value = sim, aux = the index of the pair inside this rank's range.  fy_result_because_view gives host pointers owned by
+ * the result (valid until fy_result_free, like fy_result_key0): the rows of pair t are start[t] .. start[t + 1], per pair the ids as
+ * asked, estimate, status, contributors, and per row pref.  fy_eval_lists, fy_eval_estimates, fy_itemsim_pairs and
+ * fy_itemcf_recommend* refuse the kind with FY_ERR_INVALID_ARGUMENT.
+ * Arguments: the pairs as for fy_itemcf_estimate_prepared; (rank, world) of fy_itemcf_params cut the pair list into the same
+ * contiguous ranges; num_recommendations is ignored.  The failures are fy_itemcf_estimate_prepared's (a job prepared with world != 1
+ * or with min_prefs_per_user / max_prefs_per_user: FY_ERR_UNSUPPORTED; NULL arguments, max_prefs_per_user <= 0:
+ * FY_ERR_INVALID_ARGUMENT; more than 2^31 - 1 pairs, or pairs x how_many beyond 2^31 - 1: FY_ERR_UNSUPPORTED) plus how_many outside
+ * [1, FY_BECAUSE_MAX]: FY_ERR_INVALID_ARGUMENT.  Zero pairs, or a job over no preferences, build nothing.  The rows the call needs
+ * come from and stay in the job's row store, shared in both directions with fy_itemcf_recommend_prepared and the estimates; the
+ * store changes no bit of the answer.
+ * Work: equal pairs form one target and ONE WAVE per distinct target walks the user's kept rows, so row_entries_walked is paid per
+ * target.  Nothing is sized by the catalogue.
+ * fy_result_stats follows the estimates: recs = rows, users_scored = distinct users with at least one OK pair, ms_tables / ms_cooc /
+ * ms_score (the explanation kernel and the compaction) / ms_total; ms_prepare = ms_topn = 0. */
+#define FY_BECAUSE_MAX 64
+typedef struct {
+    int64_t n_pairs;
+    const int64_t* start;          /* n_pairs + 1: rows of pair t = start[t] .. start[t + 1] */
+    const int32_t* user;           /* per pair, as asked */
+    const int32_t* item;
+    const float* estimate;         /* per pair: NaN unless status is FY_ESTIMATE_OK */
+    const int32_t* status;         /* per pair: FY_ESTIMATE_* */
+    const int32_t* contributors;   /* per pair: all contributing preferences, listed or not */
+    const float* pref;             /* per row */
+} fy_itemcf_because_view;
+typedef struct {
+    int64_t pairs_asked;         /* pairs of this result (this rank's range of the pair list) */
+    int64_t pair_offset;         /* position of the first of them in the whole pair list */
+    int64_t by_status[8];        /* pairs per FY_ESTIMATE_* code */
+    int64_t users_known;         /* distinct users of the range with a kept preference */
+    int64_t targets;             /* distinct (known user, known item) pairs = waves of the explanation kernel */
+    int64_t rows;                /* rows listed */
+    int64_t contributors;        /* sum of `contributors` over the asked pairs */
+    int64_t items_needed;        /* these six as in fy_itemcf_estimate_stats */
+    int64_t rows_built;
+    int64_t rows_from_store;
+    int64_t rows_stored;
+    int64_t pair_contribs;
+    int64_t batches;
+    int64_t row_entries_walked;  /* sum over the distinct targets of the entries of the rows of the user's kept preferences */
+} fy_itemcf_because_stats;
+int fy_itemcf_because_prepared(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_pairs*, int32_t how_many, fy_result** out);
+int fy_result_because_view(fy_result*, fy_itemcf_because_view* out);             /* FY_ERR_STATE on any other result */
+int fy_result_itemcf_because_stats(fy_result*, fy_itemcf_because_stats* out);   /* FY_ERR_STATE on any other result */
+
 #ifdef __cplusplus
 }
 #endif
