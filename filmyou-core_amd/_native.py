@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_profiles.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -35,6 +35,7 @@ SYMBOLS = [
     "fy_ratings_holdout", "fy_result_create_lists", "fy_eval_prepare", "fy_eval_lists", "fy_eval_destroy",
     "fy_itemcf_estimate_prepared", "fy_itemcf_estimate_ratings", "fy_result_itemcf_estimate_stats", "fy_eval_estimates",
     "fy_itemcf_because_prepared", "fy_result_because_view", "fy_result_itemcf_because_stats",
+    "fy_itemcf_recommend_profiles", "fy_result_itemcf_profile_stats",
 ]
 
 
@@ -189,6 +190,25 @@ class ItemSimRequestStats(C.Structure):
 class ItemCFRequestStats(C.Structure):
     _fields_ = [("users_asked", C.c_int64), ("users_known", C.c_int64), ("items_needed", C.c_int64), ("rows_built", C.c_int64),
                 ("rows_from_store", C.c_int64), ("rows_stored", C.c_int64), ("pair_contribs", C.c_int64), ("batches", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+FY_PROFILE_WHOLE, FY_PROFILE_ON_RESIDENT = 0, 1
+
+
+class ItemCFProfiles(C.Structure):
+    _fields_ = [("n_profiles", C.c_int64), ("user", C.c_void_p), ("start", C.c_void_p), ("item", C.c_void_p), ("score", C.c_void_p),
+                ("remove", C.c_void_p), ("base", C.c_int32)]
+
+
+class ItemCFProfileStats(C.Structure):
+    _fields_ = [("profiles_asked", C.c_int64), ("profiles_mine", C.c_int64), ("profiles_scored", C.c_int64), ("profiles_empty", C.c_int64),
+                ("users_unknown", C.c_int64), ("entries", C.c_int64), ("entries_unknown_item", C.c_int64), ("entries_superseded", C.c_int64),
+                ("removes_hit", C.c_int64), ("removes_missed", C.c_int64), ("prefs_composed", C.c_int64), ("items_needed", C.c_int64),
+                ("rows_built", C.c_int64), ("rows_from_store", C.c_int64), ("rows_stored", C.c_int64), ("pair_contribs", C.c_int64),
+                ("batches", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -406,5 +426,7 @@ def load():
     L.fy_itemcf_because_prepared.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFPairs), i32, pvp]
     L.fy_result_because_view.argtypes = [vp, C.POINTER(ItemCFBecauseView)]
     L.fy_result_itemcf_because_stats.argtypes = [vp, C.POINTER(ItemCFBecauseStats)]
+    L.fy_itemcf_recommend_profiles.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFProfiles), C.POINTER(ItemCFFilter), pvp]
+    L.fy_result_itemcf_profile_stats.argtypes = [vp, C.POINTER(ItemCFProfileStats)]
     _lib = L
     return L

@@ -12,6 +12,7 @@
 #include "fy_rm2_request.hpp"
 #include "fy_itemsim_request.hpp"
 #include "fy_itemcf_request.hpp"
+#include "fy_itemcf_profiles.hpp"
 #include "fy_eval.hpp"
 
 namespace fy {
@@ -488,6 +489,17 @@ int fy_itemcf_recommend_prepared(fy_itemsim_job* j, const fy_itemcf_params* p, c
     FY_CATCH
 }
 
+int fy_itemcf_recommend_profiles(fy_itemsim_job* j, const fy_itemcf_params* p, const fy_itemcf_profiles* profiles, const fy_itemcf_filter* items_only,
+                                 fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !p || !profiles) { set_error("job, parameters or profiles are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(j->ctx);
+    *out = fy::itemcf_recommend_profiles(j, p, profiles, items_only);
+    FY_CATCH
+}
+
 int fy_itemcf_estimate_prepared(fy_itemsim_job* j, const fy_itemcf_params* p, const fy_itemcf_pairs* pairs, fy_result** out) {
     if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
     *out = nullptr;
@@ -679,6 +691,12 @@ int fy_result_itemcf_request_stats(fy_result* r, fy_itemcf_request_stats* out) {
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     if (!r->has_itemcf_request_stats) { set_error("not a result of fy_itemcf_recommend_prepared"); return FY_ERR_STATE; }
     *out = r->crq;
+    return FY_OK;
+}
+int fy_result_itemcf_profile_stats(fy_result* r, fy_itemcf_profile_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_itemcf_profile_stats) { set_error("not a result of fy_itemcf_recommend_profiles"); return FY_ERR_STATE; }
+    *out = r->cpf;
     return FY_OK;
 }
 int fy_result_itemcf_estimate_stats(fy_result* r, fy_itemcf_estimate_stats* out) {

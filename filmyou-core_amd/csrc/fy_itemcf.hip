@@ -272,21 +272,21 @@ void icf_allow_bitmap(Context* ctx, const Prepared& P, const fy_itemcf_filter* f
     FY_KERNEL_CHECK();
 }
 
-void icf_thresholds(Context* ctx, const Prepared& P, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr) {
+void icf_thresholds(Context* ctx, const IcfRowView& V, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr) {
     if (hi <= lo) return;
     hipStream_t st = ctx->stream;
     const int g = grid_for((int64_t)(hi - lo) * 64, 256);
-    if (list) k_icf_threshold<true><<<g, 256, 0, st>>>(lo, hi, list, P.rowptr.get(), P.csr_r.get(), max_prefs, thr);
-    else k_icf_threshold<false><<<g, 256, 0, st>>>(lo, hi, nullptr, P.rowptr.get(), P.csr_r.get(), max_prefs, thr);
+    if (list) k_icf_threshold<true><<<g, 256, 0, st>>>(lo, hi, list, V.rowptr, V.csr_r, max_prefs, thr);
+    else k_icf_threshold<false><<<g, 256, 0, st>>>(lo, hi, nullptr, V.rowptr, V.csr_r, max_prefs, thr);
     FY_KERNEL_CHECK();
 }
 
-void icf_score_lists(Context* ctx, const fy_itemcf_params* prm, const Prepared& P, const IcfSims& S_, const int32_t* list, const int32_t* list_du,
+void icf_score_lists(Context* ctx, const fy_itemcf_params* prm, const IcfRowView& V, const IcfSims& S_, const int32_t* list, const int32_t* list_du,
                      const uint32_t* allow, int32_t lo, int32_t hi, const float* thr, fy_result* Rs, EventTimer& t_score, EventTimer& t_topn,
                      DevBuf<int32_t>& n_lists) {
     hipStream_t st = ctx->stream;
     const bool by_list = list != nullptr, by_items = allow != nullptr;
-    const int32_t nI = P.nP, N = prm->num_recommendations, nmine = hi - lo;
+    const int32_t nI = V.n_cols, N = prm->num_recommendations, nmine = hi - lo;
     // ---- batches of users with dense accumulators
     const int64_t ld = round_up(nI, 256);
     const int64_t per_user = ld * (8 + 8 + 4 + 4);
@@ -310,7 +310,7 @@ void icf_score_lists(Context* ctx, const fy_itemcf_params* prm, const Prepared& 
         FY_HIP(hipMemsetAsync(num.get(), 0, (size_t)nb * ld * 8, st));
         FY_HIP(hipMemsetAsync(den.get(), 0, (size_t)nb * ld * 8, st));
         FY_HIP(hipMemsetAsync(cnt.get(), 0, (size_t)nb * ld * 4, st));
-        IcfArgs A{P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), thr, S_.row_start, S_.row_cnt, S_.col_other,
+        IcfArgs A{V.rowptr, V.csr_idx, V.csr_r, thr, S_.row_start, S_.row_cnt, S_.col_other,
                   S_.sim, lo, s0, nb, prm->boolean_data, ld, num.get(), den.get(), cnt.get(), list};
         const int g = grid_for((int64_t)nb * 64, 256, 256 * 32);
         if (by_list) k_icf_accumulate<true><<<g, 256, 0, st>>>(A);
@@ -322,8 +322,8 @@ void icf_score_lists(Context* ctx, const fy_itemcf_params* prm, const Prepared& 
         t_score.end(sp3);
         const size_t sp4 = t_topn.begin();
         // (the top-N kernels name row u's user through slot2du[slot0 + u]: with a list that is the list's own dense-index column)
-        launch_topn_rows(ctx, st, S.get(), ld, nI, nb, n_out.get() + (s0 - lo), pad_off.get() + (s0 - lo), P.rank_item_raw.get(),
-                         by_list ? list_du : P.slot2du.get(), P.uid.get(), s0, 0, p_user.get(), p_item.get(), p_score.get(), p_aux.get(),
+        launch_topn_rows(ctx, st, S.get(), ld, nI, nb, n_out.get() + (s0 - lo), pad_off.get() + (s0 - lo), V.rank_item_raw,
+                         by_list ? list_du : V.slot2du, V.uid, s0, 0, p_user.get(), p_item.get(), p_score.get(), p_aux.get(),
                          overflow.get(), any_overflow.get());
         t_topn.end(sp4);
     }
@@ -425,10 +425,11 @@ static fy_result* icf_run(Context* ctx, const fy_itemcf_params* prm, const fy_it
     }
     const int32_t nmine = hi - lo;
     DevBuf<float> thr(ctx, (size_t)nmine + 1);
-    icf_thresholds(ctx, P, by_list ? list.get() : nullptr, lo, hi, prm->max_prefs_per_user, thr.get());
+    const IcfRowView V = icf_rows_of(P);
+    icf_thresholds(ctx, V, by_list ? list.get() : nullptr, lo, hi, prm->max_prefs_per_user, thr.get());
     DevBuf<int32_t> n_lists;
     const IcfSims S_{row_start.get(), row_cnt.get(), col_other.get(), sims->d_value.get()};
-    icf_score_lists(ctx, prm, P, S_, by_list ? list.get() : nullptr, by_list ? list_du.get() : nullptr, by_items ? allow.get() : nullptr, lo, hi,
+    icf_score_lists(ctx, prm, V, S_, by_list ? list.get() : nullptr, by_list ? list_du.get() : nullptr, by_items ? allow.get() : nullptr, lo, hi,
                     thr.get(), Rs.get(), t_score, t_topn, n_lists);
     const int64_t n = Rs->n;
     t_total.end(sp0);

@@ -157,7 +157,7 @@ __attribute__((unused)) static void icf_pair_targets(fy_itemsim_job* J, int32_t 
     }
     // ---- thresholds, the set J, the rows the store lacks: built and kept
     T.thr.alloc(ctx, (size_t)n_known + 1);
-    icfr_rows_for_users(J, T.list.get(), 0, n_known, max_prefs, T.thr.get(), t_tables, sp_tab, t_cooc, T.built);
+    icfr_rows_for_users(J, icf_rows_of(P), T.list.get(), 0, n_known, max_prefs, T.thr.get(), t_tables, sp_tab, t_cooc, T.built);
 
     // ---- pairs -> keys, sorted; targets
     sp_tab = t_tables.begin();

@@ -29,13 +29,8 @@ namespace {
 __global__ void k_icfr_find_users(int64_t n, const int32_t* __restrict__ ids, const int32_t* __restrict__ uid, int32_t nU,
                                   const int32_t* __restrict__ du2slot, uint64_t* __restrict__ found) {
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t raw = ids[t];
-        int32_t lo = 0, hi = nU;
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (uid[mid] < raw) lo = mid + 1; else hi = mid;
-        }
-        found[t] = (lo < nU && uid[lo] == raw) ? (((uint64_t)(uint32_t)du2slot[lo] << 32) | (uint32_t)lo) : ~0ull;
+        const int32_t du = icf_find_user(uid, nU, ids[t]);
+        found[t] = du >= 0 ? (((uint64_t)(uint32_t)du2slot[du] << 32) | (uint32_t)du) : ~0ull;
     }
 }
 
@@ -111,7 +106,12 @@ void icfr_check_job(const fy_itemsim_job* J) {
         FY_FAIL(FY_ERR_UNSUPPORTED, "the similarity job was prepared with minPrefsPerUser / maxPrefsPerUser: its rows are no longer the users' preferences");
 }
 
-void icfr_rows_for_users(fy_itemsim_job* J, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
+void icfr_check_store(const fy_itemsim_job* J) {
+    if ((int64_t)J->P.nP * J->prm.max_similarities_per_item > (int64_t)std::numeric_limits<int32_t>::max())
+        FY_FAIL(FY_ERR_UNSUPPORTED, "the row store would exceed 2^31 entries");
+}
+
+void icfr_rows_for_users(fy_itemsim_job* J, const IcfRowView& V, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
                          size_t sp_tab, EventTimer& t_cooc, IcfrRows& rq) {
     Context* ctx = J->ctx;
     const Prepared& P = J->P;
@@ -120,7 +120,7 @@ void icfr_rows_for_users(fy_itemsim_job* J, const int32_t* list, int32_t lo, int
     std::vector<int32_t> h_missing;
     int32_t h_need = 0, h_build = 0;
     SyncOnUnwind drain(st);      // behind the host ends of the queued copies; the scratch buffers below go back to the allocator before it drains
-    icf_thresholds(ctx, P, list, lo, hi, max_prefs, thr);
+    icf_thresholds(ctx, V, list, lo, hi, max_prefs, thr);
 
     // ---- the row store of the job, on the first call: every buffer or none
     fy_itemsim_job::RowStore& store = J->store;
@@ -144,7 +144,7 @@ void icfr_rows_for_users(fy_itemsim_job* J, const int32_t* list, int32_t lo, int
     DevBuf<int32_t> missing(ctx, (size_t)nP + 1), pos(ctx, (size_t)nP + 1), n_needed(ctx, 1);
     need.zero();
     n_needed.zero();
-    k_icfr_mark_items<<<grid_for((int64_t)nmine * 64, 256), 256, 0, st>>>(lo, hi, list, P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), thr, nP, need.get());
+    k_icfr_mark_items<<<grid_for((int64_t)nmine * 64, 256), 256, 0, st>>>(lo, hi, list, V.rowptr, V.csr_idx, V.csr_r, thr, nP, need.get());
     FY_KERNEL_CHECK();
     k_icfr_split<<<grid_for((int64_t)nP + 1), 256, 0, st>>>(nP, need.get(), store.state.get(), missing.get(), n_needed.get());
     FY_KERNEL_CHECK();
@@ -190,7 +190,6 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
         FY_FAIL(FY_ERR_INVALID_ARGUMENT, "fy_itemcf_recommend_prepared needs the users to recommend for (has_users); lists for every user are fy_itemcf_recommend's");
     icf_check_arguments(prm, filt);
     icfr_check_job(J);
-    const int32_t K = J->prm.max_similarities_per_item, nP = P.nP;
     hipStream_t st = ctx->stream;
     std::unique_ptr<fy_result> Rs(new fy_result);
     Rs->ctx = ctx;
@@ -214,7 +213,7 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     };
     // Mahout's empty id set: nobody is asked for / nothing may be recommended
     if (P.nnz == 0 || filt->n_users == 0 || (filt->has_items && filt->n_items == 0)) return no_rows();
-    if ((int64_t)nP * K > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "the row store would exceed 2^31 entries");
+    icfr_check_store(J);
 
     EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx), t_topn(ctx);
     std::vector<uint64_t> found((size_t)filt->n_users);
@@ -269,7 +268,8 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     DevBuf<float> thr(ctx, (size_t)nmine + 1);
     // ---- thresholds, the set J, the rows the store lacks: built and kept
     IcfrRows built;
-    icfr_rows_for_users(J, list.get(), lo, hi, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
+    const IcfRowView V = icf_rows_of(P);
+    icfr_rows_for_users(J, V, list.get(), lo, hi, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
     rq.items_needed = built.items_needed;
     rq.rows_built = built.rows_built;
     rq.rows_from_store = built.rows_from_store;
@@ -281,7 +281,7 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     // ---- accumulate, finalize, top-N, compact: the filtered pass, reading the store
     DevBuf<int32_t> n_lists;
     const IcfSims S{store.start.get(), store.cnt.get(), store.other.get(), store.sim.get()};
-    icf_score_lists(ctx, prm, P, S, list.get(), list_du.get(), filt->has_items ? allow.get() : nullptr, lo, hi, thr.get(), Rs.get(), t_score, t_topn,
+    icf_score_lists(ctx, prm, V, S, list.get(), list_du.get(), filt->has_items ? allow.get() : nullptr, lo, hi, thr.get(), Rs.get(), t_score, t_topn,
                     n_lists);
     t_total.end(sp_total);
     const int64_t scored = (int64_t)fetch(ctx, n_lists.get());

@@ -15,6 +15,33 @@ __device__ __forceinline__ int32_t icf_column(const int32_t* __restrict__ iid, i
     return (lo < nI && iid[lo] == raw) ? pair_rank[lo] : -1;
 }
 
+// dense index of a raw user id among the nU ascending ids, -1 for an id nobody has
+__device__ __forceinline__ int32_t icf_find_user(const int32_t* __restrict__ uid, int32_t nU, int32_t raw) {
+    int32_t lo = 0, hi = nU;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (uid[mid] < raw) lo = mid + 1; else hi = mid;
+    }
+    return (lo < nU && uid[lo] == raw) ? lo : -1;
+}
+
+// The users' rows as the list pass reads them: row s = entries rowptr[s] .. rowptr[s + 1] of csr_idx (columns, ascending inside a row) /
+// csr_r (preferences); a row is named uid[slot2du[s]] in the result, and column c is the raw item rank_item_raw[c] of n_cols.  The
+// resident callers pass the job's own arrays (icf_rows_of); the profile pass (fy_itemcf_profiles.hip) passes the CSR it composed, with
+// the profiles' labels as uid.
+struct IcfRowView {
+    const int32_t* rowptr;
+    const int32_t* csr_idx;
+    const float* csr_r;
+    const int32_t* uid;
+    const int32_t* slot2du;
+    const int32_t* rank_item_raw;
+    int32_t n_cols;
+};
+inline IcfRowView icf_rows_of(const Prepared& P) {
+    return IcfRowView{P.rowptr.get(), P.csr_idx.get(), P.csr_r.get(), P.uid.get(), P.slot2du.get(), P.rank_item_raw.get(), P.nP};
+}
+
 // the similarity rows as k_icf_accumulate reads them: row j = entries row_start[j] .. + row_cnt[j] of col_other / sim
 struct IcfSims {
     const int32_t* row_start;
@@ -29,11 +56,11 @@ void icf_check_arguments(const fy_itemcf_params*, const fy_itemcf_filter*);
 // itemsFile: the allowed raw item ids -> bitmap over the columns
 void icf_allow_bitmap(Context*, const Prepared&, const fy_itemcf_filter*, DevBuf<uint32_t>& allow);
 // thr[k - lo] for the users lo .. hi of the slot list (list == nullptr: slots lo .. hi)
-void icf_thresholds(Context*, const Prepared&, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr);
+void icf_thresholds(Context*, const IcfRowView&, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr);
 // Batches of users with dense accumulators: accumulate, finalize, top-N, and the compaction of the lists into Rs (n, rows).
 // list / list_du == nullptr: the unrestricted pass over the slots lo .. hi; allow == nullptr: every item.  n_lists (the list pass
 // only) is left holding the number of users that received a list.
-void icf_score_lists(Context*, const fy_itemcf_params*, const Prepared&, const IcfSims&, const int32_t* list, const int32_t* list_du,
+void icf_score_lists(Context*, const fy_itemcf_params*, const IcfRowView&, const IcfSims&, const int32_t* list, const int32_t* list_du,
                      const uint32_t* allow, int32_t lo, int32_t hi, const float* thr, fy_result* Rs, EventTimer& t_score, EventTimer& t_topn,
                      DevBuf<int32_t>& n_lists);
 
@@ -44,15 +71,17 @@ void icfr_check_job(const fy_itemsim_job*);
 struct IcfrRows {
     int64_t items_needed = 0, rows_built = 0, rows_from_store = 0, rows_stored = 0, pair_contribs = 0, batches = 0;
 };
-// For the users lo .. hi of the slot list (device, ascending slots): thr[k - lo] (hi - lo + 1 floats of the caller), the set J of
+// For the rows lo .. hi of the list (device; slots of the job's own rows, or rows of a composed view): thr[k - lo] (hi - lo + 1 floats of the caller), the set J of
 // their kept preferences, J against the job's row store (allocated here on the first call), the missing rows built and kept.  The
 // caller has begun span sp_tab of t_tables (its own id -> slot work is inside it); it is ended here, in front of the row build,
 // whose spans go to t_cooc.  Synchronises.  When it returns, row j of every kept preference is in J->store.
-void icfr_rows_for_users(fy_itemsim_job* J, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
+void icfr_rows_for_users(fy_itemsim_job* J, const IcfRowView& V, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
                          size_t sp_tab, EventTimer& t_cooc, IcfrRows& out);
 
 constexpr int ICF_EST_CHUNK_MAX = 512;   // FY_ICF_EST_CHUNK: targets a wave of the estimate kernel holds in LDS (4 waves x 28 B x 512 = 56 KiB)
 fy_result* itemcf_recommend_prepared(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_filter*);
+// the 2^31-entry bound of the job's row store (FY_ERR_UNSUPPORTED), checked before the first row is asked for
+void icfr_check_store(const fy_itemsim_job*);
 // users / items: the whole pair list, n raw ids each, host or device (location); the rank's range is cut inside
 fy_result* itemcf_estimate_prepared(fy_itemsim_job*, const fy_itemcf_params*, int64_t n, const int32_t* users, const int32_t* items, int location);
 // the contributing preferences of the same pairs, at most how_many listed per pair (fy_itemcf_because.hip)

@@ -21,6 +21,8 @@ struct fy_result {
     fy_itemsim_request_stats irq{};
     bool has_itemcf_request_stats = false;    // a result of fy_itemcf_recommend_prepared
     fy_itemcf_request_stats crq{};
+    bool has_itemcf_profile_stats = false;    // a result of fy_itemcf_recommend_profiles
+    fy_itemcf_profile_stats cpf{};
     bool has_itemcf_estimate_stats = false;   // a result of fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings (kind 4)
     fy_itemcf_estimate_stats est{};
     // a result of fy_itemcf_because_prepared (kind 5): rows = the listed contributors; per asked pair (bp_n of them) the ids, the

@@ -407,6 +407,59 @@ def _pair_ids(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _profile_items(a):
+    """raw item ids of profile entries: an id outside int32 is outside the data -- it becomes -1, which has no column and is counted"""
+    a = np.asarray(a).reshape(-1)
+    if a.dtype != np.int32:
+        a = np.asarray(a, dtype=np.int64) if len(a) else np.zeros(0, dtype=np.int64)
+        a = np.where((a < -2 ** 31) | (a >= 2 ** 31), -1, a)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _itemcf_profiles(profiles, base, shift):
+    """``profiles`` of ``PreparedItemSimilarity.recommend_profiles`` -> (fy_itemcf_profiles, what must stay alive while it is used)"""
+    if base not in ("whole", "resident"):
+        raise ValueError("base must be 'whole' or 'resident'")
+    if isinstance(profiles, tuple) and len(profiles) in (4, 5) and isinstance(profiles[0], np.ndarray):      # the CSR arrays
+        labels, start, item, score = profiles[:4]
+        remove = profiles[4] if len(profiles) == 5 else None
+        start = np.ascontiguousarray(start, dtype=np.int64).reshape(-1)
+    else:
+        labels, lens, items, scores, removes = [], [], [], [], []
+        any_remove = False
+        for prof in profiles:
+            if len(prof) not in (3, 4):
+                raise ValueError("a profile is (label, items, scores) or (label, items, scores, remove)")
+            it = np.asarray(prof[1]).reshape(-1)
+            sc = np.asarray(prof[2], dtype=np.float32).reshape(-1)
+            rm = np.zeros(len(it), dtype=np.uint8) if len(prof) == 3 or prof[3] is None else (np.asarray(prof[3]).reshape(-1) != 0).astype(np.uint8)
+            if not len(it) == len(sc) == len(rm):
+                raise ValueError("items, scores and remove of a profile differ in length")
+            any_remove = any_remove or (len(prof) == 4 and prof[3] is not None)
+            labels.append(prof[0]); lens.append(len(it)); items.append(it); scores.append(sc); removes.append(rm)
+        start = np.zeros(len(labels) + 1, dtype=np.int64)
+        np.cumsum(lens, out=start[1:])
+        item = np.concatenate(items) if items else np.zeros(0, dtype=np.int64)
+        score = np.concatenate(scores) if scores else np.zeros(0, dtype=np.float32)
+        remove = np.concatenate(removes) if any_remove else None
+    labels = _pair_ids(labels)
+    item = _profile_items(item)
+    score = np.ascontiguousarray(score, dtype=np.float32).reshape(-1)
+    if shift != 0.0:
+        score = score + np.float32(shift)      # float32(score + shift): Ratings.shifted's arithmetic
+    if remove is not None:
+        remove = np.ascontiguousarray(np.asarray(remove).reshape(-1) != 0, dtype=np.uint8)
+    n = len(labels)
+    if len(start) != n + 1 and not (n == 0 and len(start) == 0):
+        raise ValueError("start must hold one offset more than there are profiles")
+    if len(item) != len(score) or (remove is not None and len(remove) != len(item)) or (n and int(start[-1]) > len(item)):
+        raise ValueError("item, score and remove must hold start[-1] entries each")
+    ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+    q = _native.ItemCFProfiles(n, ptr(labels), start.ctypes.data if len(start) else None, ptr(item), ptr(score), ptr(remove),
+                               _native.FY_PROFILE_ON_RESIDENT if base == "resident" else _native.FY_PROFILE_WHOLE)
+    return q, (labels, start, item, score, remove)
+
+
 def _itemcf_pairs(pairs):
     """``(users, items)`` raw-id arrays (numpy, or int32 torch tensors on the context's GPU) -> (fy_itemcf_pairs, what must stay alive
     while it is used)"""
@@ -710,7 +763,13 @@ class ItemRecommendations(_Result):
         self._rows = None
         # request=True (a result of fy_itemcf_recommend_prepared): what the request touched; None on any other result
         self.request_stats = None
-        if request:
+        # request="profiles" (a result of fy_itemcf_recommend_profiles): fy_itemcf_profile_stats; None on any other result
+        self.profile_stats = None
+        if request == "profiles":
+            ps = _native.ItemCFProfileStats()
+            _check(self._lib.fy_result_itemcf_profile_stats(handle, C.byref(ps)))
+            self.profile_stats = ps.as_dict()
+        elif request:
             rq = _native.ItemCFRequestStats()
             _check(self._lib.fy_result_itemcf_request_stats(handle, C.byref(rq)))
             self.request_stats = rq.as_dict()
@@ -1185,6 +1244,33 @@ class PreparedItemSimilarity:
         except FilmYouError as e:
             raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
         return ItemRecommendations(res, self._ctx, request=True)
+
+    def recommend_profiles(self, profiles, numRecommendations=100, maxPrefsPerUser=50, booleanData=False, itemsFile=None, base="whole",
+                           ratingShift=0.0, rank=0, world=1):
+        """fy_itemcf_recommend_profiles: the lists of ``recommend`` for preference vectors handed in -- an anonymous or new user's whole
+        profile (``base="whole"``), or a resident user's row of the prepared ratings with pending writes applied
+        (``base="resident"``: the label is the user id) -- on the standing job and its warm row store, without preparing again.  The
+        similarity rows stay as prepared.  ``profiles``: a sequence of ``(label, items, scores)`` / ``(label, items, scores,
+        remove)``, or the CSR arrays ``(labels, start, item, score[, remove])`` as a tuple of numpy arrays.  Per profile the last
+        entry of an item counts, a non-zero ``remove`` deletes the item, an item nobody rated in the prepared ratings is dropped
+        (include/filmyou.h states the rules).  ``ratingShift``: every given score becomes float32(score + shift) first, so a job
+        prepared with a ratingShift is fed raw scores.  Rows are grouped by profile in the order given, labelled ``label``; (rank,
+        world) cut the profile list.  Returns an ``ItemRecommendations`` with ``profile_stats`` beside ``stats``."""
+        if profiles is None:
+            raise ValueError("recommend_profiles() needs the profiles to recommend for")
+        q, keep = _itemcf_profiles(profiles, base, float(ratingShift))
+        items = _id_list(itemsFile)
+        p = _native.ItemCFParams(int(numRecommendations), int(maxPrefsPerUser), 1 if booleanData else 0, int(rank), int(world), 0)
+        f = _native.ItemCFFilter(0, int(items is not None), 0, None, 0 if items is None else len(items),
+                                 None if items is None or not len(items) else items.ctypes.data)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            _check(self._lib.fy_itemcf_recommend_profiles(self._h, C.byref(p), C.byref(q), C.byref(f), C.byref(res)))
+            del keep
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (BaselineRecommenderJob.JOB_NAME, e.message)) from e
+        return ItemRecommendations(res, self._ctx, request="profiles")
 
     def estimate(self, pairs, maxPrefsPerUser=50, booleanData=False, rank=0, world=1):
         """fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings: what would this user give this item -- the cell (user, item) of

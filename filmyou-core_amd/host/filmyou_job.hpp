@@ -737,6 +737,72 @@ class BaselineRecommenderJob {
         return 0;
     }
 
+    // "This visitor has no row yet" / "what if I rated this": the lists of recommendUsers for preference vectors handed in
+    // (fy_itemcf_recommend_profiles) on the standing prepared job and its warm row store; the similarity rows stay as prepared.
+    // Profile p holds the entries start[p] .. start[p + 1]; the last entry per item counts, a non-zero remove deletes the item.
+    // resident = false: whole profiles (the label only names the rows); true: applied on top of the prepared row of user label[p].
+    // Scores are taken as the job's ratings hold them: ratingShift is added here (fp32) as prepare() adds it to the ratings.
+    struct Profiles {
+        std::vector<int32_t> label;
+        std::vector<int64_t> start{0};
+        std::vector<int32_t> item;
+        std::vector<float> score;
+        std::vector<uint8_t> remove;
+        bool resident = false;
+        void begin(int32_t l) { label.push_back(l); start.push_back(start.back()); }      // then put / del into the profile begun last
+        void put(int32_t i, float s) { item.push_back(i); score.push_back(s); remove.push_back(0); start.back()++; }
+        void del(int32_t i) { item.push_back(i); score.push_back(0.0f); remove.push_back(1); start.back()++; }
+    };
+    fy_itemcf_profile_stats profileStats{};
+    int recommendProfiles(PreparedItemSimilarity& prepared, const Profiles& profiles, const RecommendationSink& sink) {
+        if (!prepared.job()) throw std::runtime_error("BaselineRecommenderJob failed!: recommendProfiles on a closed prepared job");
+        if (profiles.start.size() != profiles.label.size() + 1 || profiles.item.size() != profiles.score.size() ||
+            profiles.item.size() != profiles.remove.size() || (size_t)profiles.start.back() != profiles.item.size())
+            throw std::invalid_argument("recommendProfiles: the arrays of the profiles differ in length");
+        fy_result* res = nullptr;
+        int32_t* items = nullptr;
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("BaselineRecommenderJob failed!: ") + what + ": " + fy_last_error();
+            if (res) fy_result_free(res);
+            fy_buffer_free(items);
+            throw std::runtime_error(msg);
+        };
+        std::vector<float> shifted;
+        if (ratingShift != 0.0f) {
+            shifted = profiles.score;
+            for (float& v : shifted) v = v + ratingShift;
+        }
+        fy_itemcf_profiles q{};
+        q.n_profiles = (int64_t)profiles.label.size();
+        q.user = profiles.label.empty() ? nullptr : profiles.label.data();
+        q.start = profiles.start.data();
+        q.item = profiles.item.empty() ? nullptr : profiles.item.data();
+        q.score = profiles.item.empty() ? nullptr : (ratingShift != 0.0f ? shifted.data() : profiles.score.data());
+        q.remove = profiles.item.empty() ? nullptr : profiles.remove.data();
+        q.base = profiles.resident ? FY_PROFILE_ON_RESIDENT : FY_PROFILE_WHOLE;
+        fy_itemcf_filter f{};
+        if (!itemsFile.empty()) {
+            f.has_items = 1;
+            if (fy_idfile_read(itemsFile.c_str(), &f.n_items, &items) != FY_OK) fail("itemsFile");
+            f.items = items;
+        }
+        fy_itemcf_params cp{};
+        cp.num_recommendations = numRecommendations;
+        cp.max_prefs_per_user = maxPrefsPerUser;
+        cp.boolean_data = booleanData ? 1 : 0;
+        cp.world = 1;
+        if (fy_itemcf_recommend_profiles(prepared.job(), &cp, &q, &f, &res) != FY_OK) fail("recommend profiles");
+        const int64_t n = fy_result_size(res);
+        const int32_t *u = fy_result_key0(res), *i = fy_result_key1(res);
+        const float* s = fy_result_value(res);
+        for (int64_t k = 0; k < n; k++) sink(u[k], i[k], s[k]);
+        fy_result_stats(res, &stats);
+        fy_result_itemcf_profile_stats(res, &profileStats);
+        fy_result_free(res);
+        fy_buffer_free(items);
+        return 0;
+    }
+
     // "What would this user give this item": the cell (user, item) of the pass recommendUsers runs, before the top-N
     // (fy_itemcf_estimate_prepared; maxPrefsPerUser and booleanData are read at each call).  One row per pair in the order given:
     // the sink (may be empty) receives (user, item, estimate, FY_ESTIMATE_* status), the estimate is NaN unless the status is

@@ -89,6 +89,60 @@ static int main_recommend_users(char** a) {
     return 0;
 }
 
+// rm2_main --recommend-profiles <profiles.txt> --profile-base whole|resident <ratings.txt> <similarityClassname> <K> <N> <maxPrefs>
+//   : BaselineRecommenderJob::prepare on the ratings + recommendProfiles.  <profiles.txt>: "label item score" per line, in the style of
+//   the --estimate-pairs file; consecutive lines with one label form one profile (the same label again later begins another), their
+//   order is the order of the entries.  A score of "x" is the delete marker: "label item x" deletes the item from the profile.
+//   whole: each profile is a whole preference vector; resident: it is applied on top of the prepared row of user <label>.
+//   Prints "label item score" as --recommend-users does; one `profiles ...` line of counters on stderr.
+static int main_recommend_profiles(char** a) {
+    const char* base = a[2];
+    if (strcmp(a[1], "--profile-base") != 0 || (strcmp(base, "whole") != 0 && strcmp(base, "resident") != 0)) {
+        fprintf(stderr, "usage: --recommend-profiles FILE --profile-base whole|resident ratings similarityClassname K N maxPrefs\n"
+                        "  FILE: 'label item score' per line, consecutive lines with one label form one profile; 'label item x' deletes the item\n");
+        return 2;
+    }
+    fy::host::Ratings r;
+    FILE* f = fopen(a[3], "r");
+    if (!f) { perror(a[3]); return 2; }
+    int u, i; float s;
+    while (fscanf(f, "%d %d %f", &u, &i, &s) == 3) r.add(u, i, s);
+    fclose(f);
+    fy::host::BaselineRecommenderJob::Profiles profiles;
+    profiles.resident = strcmp(base, "resident") == 0;
+    f = fopen(a[0], "r");
+    if (!f) { perror(a[0]); return 2; }
+    char word[64];
+    bool any = false;
+    int last = 0;
+    while (fscanf(f, "%d %d %63s", &u, &i, word) == 3) {
+        if (!any || u != last) profiles.begin(u);
+        any = true;
+        last = u;
+        if (strcmp(word, "x") == 0) profiles.del(i); else profiles.put(i, strtof(word, nullptr));
+    }
+    fclose(f);
+    try {
+        fy::host::BaselineRecommenderJob job;
+        job.similarityClassname = a[4];
+        job.maxSimilaritiesPerItem = atoi(a[5]);
+        job.numRecommendations = atoi(a[6]);
+        job.maxPrefsPerUser = atoi(a[7]);
+        fy::host::PreparedItemSimilarity prepared = job.prepare(r);
+        job.recommendProfiles(prepared, profiles, [](int32_t user, int32_t item, float score) { printf("%d %d %.9g\n", user, item, score); });
+        const fy_itemcf_profile_stats& q = job.profileStats;
+        fprintf(stderr, "profiles asked %lld scored %lld empty %lld users_unknown %lld entries %lld unknown_item %lld superseded %lld removes_hit %lld "
+                "removes_missed %lld prefs_composed %lld items_needed %lld rows_built %lld\n", (long long)q.profiles_asked, (long long)q.profiles_scored,
+                (long long)q.profiles_empty, (long long)q.users_unknown, (long long)q.entries, (long long)q.entries_unknown_item,
+                (long long)q.entries_superseded, (long long)q.removes_hit, (long long)q.removes_missed, (long long)q.prefs_composed,
+                (long long)q.items_needed, (long long)q.rows_built);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // rm2_main --estimate-pairs <test.txt> <ratings.txt> <similarityClassname> <K> <maxPrefs>
 //   : BaselineRecommenderJob::prepare on the ratings + estimatePairs for the (user, item) of the test ratings ("user item score" per line)
 //   + estimateErrors against their scores.  <test.txt> = holdout:<fraction>:<seed> splits <ratings.txt> instead: prepared on the train side.
@@ -190,6 +244,7 @@ int main(int argc, char** argv) {
     }
     if (argc == 9 && strcmp(argv[1], "--files") == 0) return main_files(argv + 2);
     if (argc == 8 && strcmp(argv[1], "--recommend-users") == 0) return main_recommend_users(argv + 2);
+    if (argc == 10 && strcmp(argv[1], "--recommend-profiles") == 0) return main_recommend_profiles(argv + 2);
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
     if (argc == 7 && strcmp(argv[1], "--estimate-pairs") == 0) return main_estimate_pairs(argv + 2);
     if (argc == 8 && strcmp(argv[1], "--because") == 0) return main_because(argv + 2);

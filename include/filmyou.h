@@ -946,6 +946,77 @@ int fy_itemcf_because_prepared(fy_itemsim_job*, const fy_itemcf_params*, const f
 int fy_result_because_view(fy_result*, fy_itemcf_because_view* out);             /* FY_ERR_STATE on any other result */
 int fy_result_itemcf_because_stats(fy_result*, fy_itemcf_because_stats* out);   /* FY_ERR_STATE on any other result */
 
+/* ------------------------------------------------------------------ item-based CF: lists for given profiles and pending writes
+ * fy_itemcf_recommend_profiles (csrc/fy_itemcf_profiles.hip) runs the list pass of
+ * fy_itemcf_recommend_prepared over preference vectors the CALLER hands in instead of rows of the ratings the job was prepared on:
+ * an anonymous or brand-new user's whole profile (Mahout's PlusAnonymousUserDataModel), or a resident user's row with pending
+ * writes applied ("what if I rated this", or a write the job has not been prepared on yet).  The similarity rows stay as prepared:
+ * nothing of the job -- similarities, norms, popularity ranks, its own CSR -- follows the writes.  The job and its warm row store
+ * serve the call as they stand; no re-prepare.
+ * The profiles are HOST arrays in CSR form: profile p holds the entries start[p] .. start[p + 1] of item / score / remove.
+ * Composition, per profile:
+ *   1. The entries are applied in the order given and the LAST entry per item counts, whether it is a write or a delete
+ *      (remove[e] != 0; its score is ignored): fy_ratings_apply's rule 1.
+ *   2. An entry whose item has no column -- nobody rated it in the prepared ratings, or its id is negative -- is dropped and counted
+ *      (entries_unknown_item) before rule 1 sees it: such an item has no similarity row and can be neither a preference nor a
+ *      recommendation of this job.
+ *   3. FY_PROFILE_ON_RESIDENT: the entries are applied on top of the job's own row of `user[p]`, i.e. EVERY preference of that row
+ *      (before any max_prefs_per_user cut); an entry for an item of the row replaces or deletes it.  A user the job does not know
+ *      starts empty and is counted (users_unknown).  FY_PROFILE_WHOLE: the starting row is empty, whoever `user[p]` is.
+ *   4. Scores are taken as given, bit for bit, AS THE JOB'S RATINGS HOLD THEM: a job prepared on shifted ratings (fy_ratings_shifted)
+ *      wants shifted scores, and the shift is the caller's to apply.  A score <= 0 is a stored preference, not a delete.
+ *   5. The composed profile is ordered as a resident row is: ascending popularity-rank column.
+ * Then the list pass, unchanged: the max_prefs_per_user threshold on the COMPOSED profile with ties at the cut kept, the set J of the
+ * kept preferences, the missing similarity rows built and kept in the job's row store (shared in both directions with
+ * fy_itemcf_recommend_prepared, the estimates and the explanations), accumulate in preference order, finalize ((j, NaN) self entry,
+ * numerator == 0 skip, at least two contributing preferences -- one with boolean_data --, the allow-list), top-N.  A composed profile
+ * that equals a resident row therefore gets that user's list of fy_itemcf_recommend_prepared BIT FOR BIT.
+ * Result: the ordinary list kind (fy_eval_lists takes it).  Rows are grouped by profile IN THE ORDER GIVEN, best first; the user
+ * column holds user[p], a label that may repeat (two what-if variants of one user give two groups).  A profile that composes to
+ * nothing, or whose cells hold no prediction, gets no rows.  (rank, world) of fy_itemcf_params cut the PROFILE LIST into contiguous
+ * ranges [n rank / world, n (rank + 1) / world).  items_only: NULL, or a filter with has_items (the allow-list) and has_users == 0.
+ * Failures: everything fy_itemcf_recommend_prepared refuses (numRecommendations, maxPrefsPerUser, rank / world; a job prepared with
+ * world != 1 or with min / max_prefs_per_user: FY_ERR_UNSUPPORTED) with the same code; NULL user / start with n_profiles > 0, NULL
+ * item / score with entries, start[0] != 0 or start decreasing, base outside the enum, n_profiles < 0, has_users set in the filter:
+ * FY_ERR_INVALID_ARGUMENT; more than 2^31 - 1 profiles or entries, or more than 2^31 - 1 preferences to compose (this rank's entries
+ * plus the resident rows they are applied on): FY_ERR_UNSUPPORTED.  All of these are found on the host before any launch.  Zero
+ * profiles, or a job over no preferences, builds nothing and returns an empty result.  A failed call leaves the job and its row
+ * store usable.
+ * Work: sized by the request -- this rank's entries plus the resident rows of the users they name (one stable radix sort of that many
+ * 64-bit keys, a scan, a scatter) -- then exactly what fy_itemcf_recommend_prepared pays for as many users.
+ * fy_result_stats as for fy_itemcf_recommend_prepared (users_scored = profiles that received a list; ms_tables includes the ingest).
+ * Counters (all but profiles_asked over this rank's range of profiles):
+ *   profiles_asked        n_profiles
+ *   profiles_mine         profiles of this rank's range
+ *   profiles_scored       profiles that received a list
+ *   profiles_empty        profiles whose composed preference vector is empty
+ *   users_unknown         FY_PROFILE_ON_RESIDENT: profiles whose user the job does not know (0 with FY_PROFILE_WHOLE)
+ *   entries               entries of the profiles
+ *   entries_unknown_item  entries dropped by rule 2
+ *   entries_superseded    entries with a column that are not the last of their (profile, item)
+ *   removes_hit           last entries that are deletes of an item of the resident row
+ *   removes_missed        last entries that are deletes of an item the starting row does not hold (every one with FY_PROFILE_WHOLE)
+ *   prefs_composed        preferences of all composed profiles
+ *   items_needed .. batches   the six row-store fields of fy_itemcf_request_stats */
+enum { FY_PROFILE_WHOLE = 0, FY_PROFILE_ON_RESIDENT = 1 };
+typedef struct {
+    int64_t n_profiles;
+    const int32_t* user;     /* n_profiles: the label written to the result's user column; with ON_RESIDENT also the resident user id */
+    const int64_t* start;    /* n_profiles + 1 offsets into item / score / remove, non-decreasing from 0 */
+    const int32_t* item;     /* raw item ids */
+    const float*   score;    /* preferences as the job's ratings hold them (a ratingShift is the caller's to apply) */
+    const uint8_t* remove;   /* NULL: no deletes; else non-zero = delete this item from the profile */
+    int32_t base;            /* FY_PROFILE_WHOLE / FY_PROFILE_ON_RESIDENT */
+} fy_itemcf_profiles;        /* host arrays; they may be freed when the call returns */
+typedef struct {
+    int64_t profiles_asked, profiles_mine, profiles_scored, profiles_empty, users_unknown;
+    int64_t entries, entries_unknown_item, entries_superseded, removes_hit, removes_missed, prefs_composed;
+    int64_t items_needed, rows_built, rows_from_store, rows_stored, pair_contribs, batches;
+} fy_itemcf_profile_stats;
+int fy_itemcf_recommend_profiles(fy_itemsim_job*, const fy_itemcf_params*, const fy_itemcf_profiles*,
+                                 const fy_itemcf_filter* items_only /* may be NULL; has_users must be 0 */, fy_result** out);
+int fy_result_itemcf_profile_stats(fy_result*, fy_itemcf_profile_stats* out);   /* FY_ERR_STATE on any other result */
+
 #ifdef __cplusplus
 }
 #endif
