@@ -12,7 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_pairs.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
 HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_profiles.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]

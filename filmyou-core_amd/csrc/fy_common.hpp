@@ -214,6 +214,16 @@ inline int grid_for(int64_t n, int block = 256, int cap = 256 * 16) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
 }
 
+// a ascending over [lo, hi): the first index whose element is not less than key (UPPER: is greater than key), hi when there is none
+template <bool UPPER = false, class T, class K>
+__device__ __forceinline__ int32_t fy_lower_bound(const T* a, int32_t lo, int32_t hi, K key) {
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (UPPER ? a[mid] <= key : a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // 32-bit key that orders like the float (any sign, -0 < +0), and its inverse
 __device__ __forceinline__ uint32_t fy_order_key(float f) {
     const uint32_t b = __float_as_uint(f);

@@ -208,13 +208,8 @@ __global__ void k_icf_compact(int32_t n_users, int32_t top_n, const int32_t* __r
 __global__ void k_icf_mark_users(int64_t n, const int32_t* __restrict__ ids, const int32_t* __restrict__ uid, int32_t nU,
                                  const int32_t* __restrict__ du2slot, int32_t* __restrict__ flag) {
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t raw = ids[t];
-        int32_t lo = 0, hi = nU;
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (uid[mid] < raw) lo = mid + 1; else hi = mid;
-        }
-        if (lo < nU && uid[lo] == raw) flag[du2slot[lo]] = 1;
+        const int32_t du = icf_find_user(uid, nU, ids[t]);
+        if (du >= 0) flag[du2slot[du]] = 1;
     }
 }
 

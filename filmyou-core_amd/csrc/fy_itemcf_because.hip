@@ -2,13 +2,14 @@
 // similarity job (fy_itemcf_because_prepared; include/filmyou.h).
 //
 // The explanation of (u, i) is the decomposition of the cell (u, i) that k_icf_estimate (fy_itemcf_estimate.hip) finishes: the terms
-// pref * sim of the kept preferences j of u whose row holds i, the best how_many of them listed.  The front half is the estimates'
-// (icf_pair_targets, fy_itemcf_pairs.hpp): user slots, the rows of the kept preferences in the job's store, keys, sort, targets.
+// pref * sim of the kept preferences j of u whose row holds i, the best how_many of them listed.  Opening, front half (user slots,
+// the rows of the kept preferences in the job's store, keys, sort, targets) and closing are the estimates': fy_itemcf_pairs.hip.
 //   k_icf_because   ONE WAVE per distinct target.  The wave walks the user's kept preferences in CSR order; for each j with a
 //                   non-empty row the 64 lanes stride over the row's entries looking for column i.  A row holds a column at most
 //                   once, so at most one lane hits; the hit becomes wave-uniform by ballot / readlane.  num, den (fp64) and cnt are
 //                   wave-uniform and receive their additions in preference order exactly as k_icf_estimate's cells do: the rounded
-//                   product __dmul_rn(pref, sim), then the rounded sums -- so (estimate, status) are the estimates' bit for bit.
+//                   product __dmul_rn(pref, sim), then the rounded sums, then the one icf_estimate_finish -- so (estimate, status)
+//                   are the estimates' bit for bit.
 //                   The best how_many terms so far live ONE PER LANE in registers, sorted (NaN last, weight descending, raw id
 //                   ascending): an insert is one compare on every lane, a ballot whose population count is the position, and a
 //                   shift by one lane (__shfl_up).  No LDS, no atomics, no second walk; hence how_many <= 64.
@@ -18,7 +19,6 @@
 //                   grouped rows.
 // Nothing is sized by the catalogue.  Work model: fy_itemcf_because_stats.row_entries_walked (per target, not per chunk).
 #include <limits>
-#include <memory>
 
 #include "fy_itemcf_pairs.hpp"
 
@@ -27,15 +27,7 @@ namespace {
 
 constexpr int BEC_AGG = 11;      // status counts [0 .. 7], users with an OK pair [8], row entries walked [9], contributors over the asked pairs [10]
 
-struct BecArgs {
-    const int32_t* __restrict__ rowptr;
-    const int32_t* __restrict__ csr_idx;
-    const float* __restrict__ csr_r;
-    const float* __restrict__ thr;            // by position in the slot list
-    const int32_t* __restrict__ list;         // slot of the user at a position
-    const int32_t* __restrict__ row_cnt;      // the job's row store: row j = entries j * K .. + row_cnt[j]
-    const int32_t* __restrict__ col_other;
-    const float* __restrict__ sim;
+struct BecArgs : IcfPairArgs {                // (K .. splace: in both kernels' structs, at the offsets the kernels were tuned with)
     const int32_t* __restrict__ rank_item_raw;   // column -> raw item id
     int32_t K, boolean_data, n_targets, H;    // H = how_many
     const uint64_t* __restrict__ tkey;
@@ -114,16 +106,9 @@ __global__ void __launch_bounds__(256) k_icf_because(BecArgs A) {
             filled = min(filled + 1, A.H);
         }
     }
-    // ---- the finish of k_icf_estimate, the listed entries, and the answer at every asked place of the target
-    float v = __builtin_nanf("");
-    int32_t status;
-    if (own) status = FY_ESTIMATE_OWN_PREFERENCE;
-    else if (A.boolean_data ? cnt < 1 : cnt < 2) status = FY_ESTIMATE_TOO_FEW;
-    else if (!(num != 0.0)) status = FY_ESTIMATE_ZERO_NUMERATOR;
-    else {
-        v = A.boolean_data ? (float)num : (float)(num / den);
-        status = v == v ? FY_ESTIMATE_OK : FY_ESTIMATE_NOT_A_NUMBER;
-    }
+    // ---- the finish k_icf_estimate calls too, the listed entries, and the answer at every asked place of the target
+    float v;
+    const int32_t status = icf_estimate_finish(num, den, cnt, own != 0, A.boolean_data, v);
     if (lane < filled) {
         const size_t at = (size_t)m * A.H + lane;
         A.s_item[at] = e_id;
@@ -176,36 +161,20 @@ __global__ void k_bec_sum(int64_t n, const T* __restrict__ a, unsigned long long
 fy_result* itemcf_because_prepared(fy_itemsim_job* J, const fy_itemcf_params* prm, int64_t n_all_pairs, const int32_t* users, const int32_t* items,
                                    int location, int32_t how_many) {
     Context* ctx = J->ctx;
-    const Prepared& P = J->P;
+    const int32_t H = how_many;
     if (prm->max_prefs_per_user <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "maxPrefsPerUser must be > 0");
     if (how_many < 1 || how_many > FY_BECAUSE_MAX) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "howMany %d: 1 .. %d", how_many, FY_BECAUSE_MAX);
-    if (prm->world <= 0 || prm->rank < 0 || prm->rank >= prm->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", prm->rank, prm->world);
-    if (n_all_pairs < 0 || (n_all_pairs > 0 && (!users || !items))) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "users / items is NULL or n_pairs < 0");
-    if (location != FY_HOST && location != FY_DEVICE) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "location must be FY_HOST or FY_DEVICE");
-    if (n_all_pairs > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "%lld pairs: at most 2^31 - 1", (long long)n_all_pairs);
-    icfr_check_job(J);
-    const int32_t K = J->prm.max_similarities_per_item, nP = P.nP, H = how_many;
-    if ((int64_t)nP * K > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "the row store would exceed 2^31 entries");
-    // this rank's pairs: a contiguous range of the pair list
-    const int64_t off = n_all_pairs * prm->rank / prm->world;
-    const int32_t n = (int32_t)(n_all_pairs * (prm->rank + 1) / prm->world - off);
+    int64_t off;
+    int32_t n;
+    std::unique_ptr<fy_result> Rs = icf_pairs_open(J, prm, n_all_pairs, users, items, location, 5, off, n);
     if ((int64_t)n * H > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "%d pairs x howMany %d may exceed 2^31 - 1 rows", n, H);
     hipStream_t st = ctx->stream;
-    std::unique_ptr<fy_result> Rs(new fy_result);
-    Rs->ctx = ctx;
-    Rs->kind = 5;
-    Rs->n = 0;
     Rs->bp_n = n;
     Rs->has_itemcf_because_stats = true;
     fy_itemcf_because_stats& bs = Rs->bec;
     bs.pairs_asked = n;
     bs.pair_offset = off;
     bs.rows_stored = J->store.rows;
-    Rs->st.nnz = P.nnz;
-    Rs->st.n_users = P.nU;
-    Rs->st.n_items = P.nI;
-    Rs->d_user_id.alloc(ctx, 0);
-    Rs->d_item_id.alloc(ctx, 0);
     Rs->d_bp_user.alloc(ctx, (size_t)n);
     Rs->d_bp_item.alloc(ctx, (size_t)n);
     Rs->d_bp_est.alloc(ctx, (size_t)n);
@@ -213,46 +182,36 @@ fy_result* itemcf_because_prepared(fy_itemsim_job* J, const fy_itemcf_params* pr
     Rs->d_bp_cnt.alloc(ctx, (size_t)n);
     Rs->d_bp_start.alloc(ctx, (size_t)n + 1);
     if (n == 0) {
-        Rs->d_key0.alloc(ctx, 0);
-        Rs->d_key1.alloc(ctx, 0);
-        Rs->d_value.alloc(ctx, 0);
-        Rs->d_aux.alloc(ctx, 0);
         Rs->d_pref.alloc(ctx, 0);
         Rs->d_bp_start.zero();
         sync(ctx);
-        return Rs.release();
+        return icfr_no_rows(std::move(Rs));
     }
 
-    EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx);
+    IcfrTimers tm(ctx);
     unsigned long long h_agg[BEC_AGG] = {};
     SyncOnUnwind drain(st);      // behind the host ends of the queued copies (and the caller's id arrays); the buffers below are released before it drains
-    const size_t sp_total = t_total.begin();
-    size_t sp_tab = t_tables.begin();
+    const size_t sp_total = tm.total.begin();
+    size_t sp_tab = tm.tables.begin();
     DevBuf<unsigned long long> agg(ctx, BEC_AGG);
     agg.zero();
     DevBuf<int32_t> p_rows(ctx, (size_t)n + 1), p_target(ctx, (size_t)n);
     p_rows.zero();
     Rs->d_bp_cnt.zero();
 
-    // ---- the front half (fy_itemcf_pairs.hpp): known users, their rows in the store, keys, sort, targets
+    // ---- the front half (fy_itemcf_pairs.hip): known users, their rows in the store, keys, sort, targets
     IcfPairTargets T;
     icf_pair_targets(J, prm->max_prefs_per_user, n, users + off, items + off, location, Rs->d_bp_user.get(), Rs->d_bp_item.get(), Rs->d_bp_est.get(),
-                     Rs->d_bp_status.get(), t_tables, sp_tab, t_cooc, T, "because");
-    t_tables.end(sp_tab);
+                     Rs->d_bp_status.get(), tm, sp_tab, T, "because");
+    tm.tables.end(sp_tab);
     bs.users_known = T.n_known;
-    bs.items_needed = T.built.items_needed;
-    bs.rows_built = T.built.rows_built;
-    bs.rows_from_store = T.built.rows_from_store;
-    if (T.n_known > 0) bs.rows_stored = T.built.rows_stored;
-    bs.pair_contribs = T.built.pair_contribs;
-    bs.batches = T.built.batches;
+    icfr_report(bs, T.built, T.n_known > 0);
     const int32_t n_targets = T.n_targets;
     DevBuf<int32_t> s_item;
     DevBuf<float> s_sim, s_pref;
-    const size_t sp_score = t_score.begin();
+    const size_t sp_score = tm.score.begin();
     if (n_targets > 0) {
         // ---- the explanation kernel: one wave per target
-        const fy_itemsim_job::RowStore& store = J->store;
         s_item.alloc(ctx, (size_t)n_targets * H);
         s_sim.alloc(ctx, (size_t)n_targets * H);
         s_pref.alloc(ctx, (size_t)n_targets * H);
@@ -260,11 +219,8 @@ fy_result* itemcf_because_prepared(fy_itemsim_job* J, const fy_itemcf_params* pr
         DevBuf<int32_t> user_ok(ctx, (size_t)T.n_known);
         user_ok.zero();
         BecArgs A{};
-        A.rowptr = P.rowptr.get(); A.csr_idx = P.csr_idx.get(); A.csr_r = P.csr_r.get();
-        A.thr = T.thr.get(); A.list = T.list.get();
-        A.row_cnt = store.cnt.get(); A.col_other = store.other.get(); A.sim = store.sim.get(); A.rank_item_raw = P.rank_item_raw.get();
-        A.K = K; A.boolean_data = prm->boolean_data; A.n_targets = n_targets; A.H = H;
-        A.tkey = T.tkey.get(); A.tfirst = T.tfirst.get(); A.splace = T.splace.get();
+        icf_pair_args(A, J, T, prm->boolean_data);
+        A.rank_item_raw = J->P.rank_item_raw.get(); A.n_targets = n_targets; A.H = H;
         A.s_item = s_item.get(); A.s_sim = s_sim.get(); A.s_pref = s_pref.get();
         A.p_est = Rs->d_bp_est.get(); A.p_status = Rs->d_bp_status.get(); A.p_cnt = Rs->d_bp_cnt.get();
         A.p_rows = p_rows.get(); A.p_target = p_target.get(); A.walked = walked.get(); A.user_ok = user_ok.get();
@@ -282,7 +238,6 @@ fy_result* itemcf_because_prepared(fy_itemsim_job* J, const fy_itemcf_params* pr
     const int32_t rows = fetch(ctx, Rs->d_bp_start.get() + n);
     if (rows < 0 || (int64_t)rows > (int64_t)n * H || (n_targets == 0 && rows != 0)) FY_FAIL(FY_ERR_HIP, "because: %d rows for %d pairs x %d", rows, n, H);
     Rs->n = rows;
-    Rs->st.recs = rows;
     Rs->d_key0.alloc(ctx, (size_t)rows);
     Rs->d_key1.alloc(ctx, (size_t)rows);
     Rs->d_value.alloc(ctx, (size_t)rows);
@@ -294,25 +249,12 @@ fy_result* itemcf_because_prepared(fy_itemsim_job* J, const fy_itemcf_params* pr
                                                       s_pref.get(), Rs->d_key0.get(), Rs->d_key1.get(), Rs->d_value.get(), Rs->d_aux.get(), Rs->d_pref.get());
         FY_KERNEL_CHECK();
     }
-    t_score.end(sp_score);
-    k_est_count_status<<<grid_for(n), 256, 0, st>>>(n, Rs->d_bp_status.get(), agg.get());
-    FY_KERNEL_CHECK();
-    t_total.end(sp_total);
-    d2h(ctx, h_agg, agg.get(), BEC_AGG);
-    sync(ctx);
-    for (int q = 0; q < 8; q++) bs.by_status[q] = (int64_t)h_agg[q];
+    tm.score.end(sp_score);
+    icf_pairs_close(Rs.get(), n, Rs->d_bp_status.get(), agg, h_agg, bs.by_status, T.built, n_targets > 0 ? 1 : 0, tm, sp_total);
     bs.targets = n_targets;
     bs.rows = rows;
     bs.contributors = (int64_t)h_agg[10];
     bs.row_entries_walked = (int64_t)h_agg[9];
-    Rs->st.users_scored = (int64_t)h_agg[8];
-    Rs->st.pair_contribs = bs.pair_contribs;
-    Rs->st.cooc_launches = bs.batches;
-    Rs->st.score_launches = n_targets > 0 ? 1 : 0;
-    Rs->st.ms_tables = t_tables.total_ms();
-    Rs->st.ms_cooc = t_cooc.total_ms();
-    Rs->st.ms_score = t_score.total_ms();
-    Rs->st.ms_total = t_total.total_ms();
     return Rs.release();
 }
 

@@ -2,25 +2,17 @@
 // (fy_itemcf_estimate_prepared / fy_itemcf_estimate_ratings; include/filmyou.h).
 //
 // estimate(u, i) is the cell (u, i) of the list pass (k_icf_accumulate + k_icf_finalize, fy_itemcf.hip) before the top-N.  The list
-// pass pays a dense accumulator row over the catalogue per user; here the work is sized by the pairs asked for (the steps up to the
-// targets are icf_pair_targets of fy_itemcf_pairs.hpp, shared with the explanations of fy_itemcf_because.hip):
-//   k_est_find_users     per pair: the user's slot (binary search), a flag per slot; scan + k_est_list_users: the known users once
-//                        each in slot order -- the slot list icfr_rows_for_users (fy_itemcf_request.hip) takes, as the list pass does
-//   icfr_rows_for_users  thresholds, the set J, the rows the job's store lacks: built and kept (shared with the list pass)
-//   k_est_keys           per pair: (position of the user in the slot list << 32 | column of the item) and its place in the input;
-//                        an unknown user / item gets its row here and an all-ones key
-//   sort                 rocPRIM radix sort of (key, place): equal keys are one TARGET, a user's targets are adjacent, columns ascending
-//   heads, chunks        a user's targets are cut into chunks of at most CH (FY_ICF_EST_CHUNK)
+// pass pays a dense accumulator row over the catalogue per user; here the work is sized by the pairs asked for.  The opening, the
+// steps from the pairs to the TARGETS (the distinct (known user, known item) pairs, a user's adjacent, columns ascending) and the
+// closing are fy_itemcf_pairs.hip, shared with the explanations of fy_itemcf_because.hip; this file keeps
+//   chunks               a user's targets are cut into chunks of at most CH (FY_ICF_EST_CHUNK)
 //   k_icf_estimate       ONE WAVE per (user, chunk).  LDS per wave: the chunk's columns (ascending), fp64 num / den, int cnt, own flag.
 //                        The wave walks the user's kept preferences in CSR order; the 64 lanes stride over row j's entries, each lane
 //                        binary-searches its entry's column among the chunk's columns and, on a hit, adds to that target's cells
-//                        with plain LDS read-modify-writes.  Then the finish of k_icf_finalize and the scatter to every place of the key.
+//                        with plain LDS read-modify-writes.  Then icf_estimate_finish and the scatter to every place of the key.
 // Why the bits are the list pass's: a cell receives pd * s (rounded product, then rounded sum: the atomicAdd of a product there, the
 // explicit __dmul_rn / __dadd_rn here), |s| and 1 once per contributing preference, in the order of the user's preferences.  The
 // rows walked per (user, chunk) are the user's kept rows: the work model is fy_itemcf_estimate_stats.row_entries_walked.
-#include <limits>
-#include <memory>
-
 #include "fy_itemcf_pairs.hpp"
 
 namespace fy {
@@ -32,12 +24,7 @@ constexpr int EST_AGG = 10;      // status counts [0 .. 7], users with an OK pai
 __global__ void k_est_chunk_heads(int32_t nT, const uint64_t* __restrict__ tkey, int32_t CH, uint32_t* __restrict__ chead) {
     for (int32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < nT; m += gridDim.x * blockDim.x) {
         const uint64_t first_key = tkey[m] & 0xFFFFFFFF00000000ull;
-        int32_t lo = 0, hi = m;
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (tkey[mid] < first_key) lo = mid + 1; else hi = mid;
-        }
-        chead[m] = (m - lo) % CH == 0;
+        chead[m] = (m - fy_lower_bound(tkey, 0, m, first_key)) % CH == 0;
     }
 }
 __global__ void k_est_chunks(int32_t nT, const uint32_t* __restrict__ chead, const uint32_t* __restrict__ cincl, int32_t* __restrict__ cstart) {
@@ -47,15 +34,7 @@ __global__ void k_est_chunks(int32_t nT, const uint32_t* __restrict__ chead, con
     }
 }
 
-struct EstArgs {
-    const int32_t* __restrict__ rowptr;
-    const int32_t* __restrict__ csr_idx;
-    const float* __restrict__ csr_r;
-    const float* __restrict__ thr;          // by position in the slot list
-    const int32_t* __restrict__ list;       // slot of the user at a position
-    const int32_t* __restrict__ row_cnt;    // the job's row store: row j = entries j * K .. + row_cnt[j]
-    const int32_t* __restrict__ col_other;
-    const float* __restrict__ sim;
+struct EstArgs : IcfPairArgs {              // (K .. splace: in both kernels' structs, at the offsets the kernels were tuned with)
     int32_t K, boolean_data, n_chunks, ld;  // ld: targets a wave has room for (the chunk size rounded up to even)
     const int32_t* __restrict__ cstart;     // n_chunks + 1
     const uint64_t* __restrict__ tkey;
@@ -77,11 +56,7 @@ __device__ __forceinline__ void est_wave_sync() {
 
 // position of column c among the chunk's ascending columns, -1 when it is none of them
 __device__ __forceinline__ int32_t est_find(const int32_t* col, int32_t nt, int32_t c) {
-    int32_t lo = 0, hi = nt;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (col[mid] < c) lo = mid + 1; else hi = mid;
-    }
+    const int32_t lo = fy_lower_bound(col, 0, nt, c);
     return (lo < nt && col[lo] == c) ? lo : -1;
 }
 
@@ -137,20 +112,11 @@ __global__ void __launch_bounds__(256) k_icf_estimate(EstArgs A) {
         }
         est_wave_sync();
     }
-    // ---- the finish of k_icf_finalize, the status, and the row of every asked pair of the target
+    // ---- the finish (icf_estimate_finish, fy_itemcf_pairs.hpp) and the row of every asked pair of the target
     bool ok = false;
     for (int32_t i = lane; i < nt; i += 64) {
-        float v = __builtin_nanf("");
-        int32_t status;
-        const int32_t n = cnt[i];
-        const double nm = num[i];
-        if (own[i]) status = FY_ESTIMATE_OWN_PREFERENCE;
-        else if (A.boolean_data ? n < 1 : n < 2) status = FY_ESTIMATE_TOO_FEW;
-        else if (!(nm != 0.0)) status = FY_ESTIMATE_ZERO_NUMERATOR;
-        else {
-            v = A.boolean_data ? (float)nm : (float)(nm / den[i]);
-            status = v == v ? FY_ESTIMATE_OK : FY_ESTIMATE_NOT_A_NUMBER;
-        }
+        float v;
+        const int32_t status = icf_estimate_finish(num[i], den[i], cnt[i], own[i] != 0, A.boolean_data, v);
         ok |= status == FY_ESTIMATE_OK;
         for (int32_t q = A.tfirst[m0 + i]; q < A.tfirst[m0 + i + 1]; q++) {
             const uint32_t at = A.splace[q];
@@ -192,66 +158,41 @@ __global__ void k_est_count_chunks(int32_t n_chunks, const int32_t* __restrict__
 fy_result* itemcf_estimate_prepared(fy_itemsim_job* J, const fy_itemcf_params* prm, int64_t n_all_pairs, const int32_t* users, const int32_t* items,
                                     int location) {
     Context* ctx = J->ctx;
-    const Prepared& P = J->P;
     if (prm->max_prefs_per_user <= 0) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "maxPrefsPerUser must be > 0");
-    if (prm->world <= 0 || prm->rank < 0 || prm->rank >= prm->world) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "rank %d of world %d", prm->rank, prm->world);
-    if (n_all_pairs < 0 || (n_all_pairs > 0 && (!users || !items))) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "users / items is NULL or n_pairs < 0");
-    if (location != FY_HOST && location != FY_DEVICE) FY_FAIL(FY_ERR_INVALID_ARGUMENT, "location must be FY_HOST or FY_DEVICE");
-    if (n_all_pairs > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "%lld pairs: at most 2^31 - 1", (long long)n_all_pairs);
-    icfr_check_job(J);
-    const int32_t K = J->prm.max_similarities_per_item, nP = P.nP;
-    if ((int64_t)nP * K > (int64_t)std::numeric_limits<int32_t>::max()) FY_FAIL(FY_ERR_UNSUPPORTED, "the row store would exceed 2^31 entries");
-    // this rank's pairs: a contiguous range of the pair list
-    const int64_t off = n_all_pairs * prm->rank / prm->world;
-    const int32_t n = (int32_t)(n_all_pairs * (prm->rank + 1) / prm->world - off);
+    int64_t off;
+    int32_t n;
+    std::unique_ptr<fy_result> Rs = icf_pairs_open(J, prm, n_all_pairs, users, items, location, 4, off, n);
     hipStream_t st = ctx->stream;
-    std::unique_ptr<fy_result> Rs(new fy_result);
-    Rs->ctx = ctx;
-    Rs->kind = 4;
     Rs->n = n;
     Rs->has_itemcf_estimate_stats = true;
     fy_itemcf_estimate_stats& es = Rs->est;
     es.pairs_asked = n;
     es.pair_offset = off;
     es.rows_stored = J->store.rows;
-    Rs->st.nnz = P.nnz;
-    Rs->st.n_users = P.nU;
-    Rs->st.n_items = P.nI;
-    Rs->st.recs = n;
-    Rs->d_user_id.alloc(ctx, 0);
-    Rs->d_item_id.alloc(ctx, 0);
     Rs->d_key0.alloc(ctx, (size_t)n);
     Rs->d_key1.alloc(ctx, (size_t)n);
     Rs->d_value.alloc(ctx, (size_t)n);
     Rs->d_aux.alloc(ctx, (size_t)n);
     if (n == 0) return Rs.release();
 
-    EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx);
+    IcfrTimers tm(ctx);
     unsigned long long h_agg[EST_AGG] = {};
     SyncOnUnwind drain(st);      // behind the host ends of the queued copies (and the caller's id arrays); the buffers below are released before it drains
-    const size_t sp_total = t_total.begin();
-    size_t sp_tab = t_tables.begin();
+    const size_t sp_total = tm.total.begin();
+    size_t sp_tab = tm.tables.begin();
     DevBuf<unsigned long long> agg(ctx, EST_AGG);
     agg.zero();
-    int32_t* o_user = Rs->d_key0.get();
-    int32_t* o_item = Rs->d_key1.get();
     float* o_value = Rs->d_value.get();
     int32_t* o_aux = Rs->d_aux.get();
 
-    // ---- the front half (fy_itemcf_pairs.hpp): known users, their rows in the store, keys, sort, targets
+    // ---- the front half (fy_itemcf_pairs.hip): known users, their rows in the store, keys, sort, targets
     IcfPairTargets T;
-    icf_pair_targets(J, prm->max_prefs_per_user, n, users + off, items + off, location, o_user, o_item, o_value, o_aux, t_tables, sp_tab, t_cooc, T, "estimate");
+    icf_pair_targets(J, prm->max_prefs_per_user, n, users + off, items + off, location, Rs->d_key0.get(), Rs->d_key1.get(), o_value, o_aux, tm, sp_tab, T, "estimate");
     es.users_known = T.n_known;
-    es.items_needed = T.built.items_needed;
-    es.rows_built = T.built.rows_built;
-    es.rows_from_store = T.built.rows_from_store;
-    if (T.n_known > 0) es.rows_stored = T.built.rows_stored;
-    es.pair_contribs = T.built.pair_contribs;
-    es.batches = T.built.batches;
+    icfr_report(es, T.built, T.n_known > 0);
     const int32_t n_targets = T.n_targets;
     int32_t n_chunks = 0;
     if (n_targets > 0) {
-        const fy_itemsim_job::RowStore& store = J->store;
         // ---- chunks
         const int32_t CH = std::max(1, std::min(ctx->tune.icf_est_chunk, ICF_EST_CHUNK_MAX));
         DevBuf<uint32_t> chead(ctx, (size_t)n_targets), cincl(ctx, (size_t)n_targets);
@@ -264,42 +205,26 @@ fy_result* itemcf_estimate_prepared(fy_itemsim_job* J, const fy_itemcf_params* p
         DevBuf<long long> walked(ctx, (size_t)n_chunks);
         k_est_chunks<<<grid_for(n_targets), 256, 0, st>>>(n_targets, chead.get(), cincl.get(), cstart.get());
         FY_KERNEL_CHECK();
-        t_tables.end(sp_tab);
+        tm.tables.end(sp_tab);
 
         // ---- the estimate kernel: one wave per (user, chunk)
-        const size_t sp_score = t_score.begin();
+        const size_t sp_score = tm.score.begin();
         EstArgs A{};
-        A.rowptr = P.rowptr.get(); A.csr_idx = P.csr_idx.get(); A.csr_r = P.csr_r.get();
-        A.thr = T.thr.get(); A.list = T.list.get();
-        A.row_cnt = store.cnt.get(); A.col_other = store.other.get(); A.sim = store.sim.get();
-        A.K = K; A.boolean_data = prm->boolean_data; A.n_chunks = n_chunks; A.ld = (int32_t)round_up(CH, 2);
-        A.cstart = cstart.get(); A.tkey = T.tkey.get(); A.tfirst = T.tfirst.get(); A.splace = T.splace.get();
+        icf_pair_args(A, J, T, prm->boolean_data);
+        A.n_chunks = n_chunks; A.ld = (int32_t)round_up(CH, 2); A.cstart = cstart.get();
         A.o_value = o_value; A.o_aux = o_aux; A.walked = walked.get(); A.chunk_ok = chunk_ok.get();
         k_icf_estimate<<<(int)ceil_div((int64_t)n_chunks, (int64_t)4), 256, (size_t)4 * A.ld * 28, st>>>(A);
         FY_KERNEL_CHECK();
-        t_score.end(sp_score);
+        tm.score.end(sp_score);
         k_est_count_chunks<<<grid_for(n_chunks), 256, 0, st>>>(n_chunks, cstart.get(), T.tkey.get(), walked.get(), chunk_ok.get(), agg.get());
         FY_KERNEL_CHECK();
     } else {
-        t_tables.end(sp_tab);
+        tm.tables.end(sp_tab);
     }
-    k_est_count_status<<<grid_for(n), 256, 0, st>>>(n, o_aux, agg.get());
-    FY_KERNEL_CHECK();
-    t_total.end(sp_total);
-    d2h(ctx, h_agg, agg.get(), EST_AGG);
-    sync(ctx);
-    for (int q = 0; q < 8; q++) es.by_status[q] = (int64_t)h_agg[q];
+    icf_pairs_close(Rs.get(), n, o_aux, agg, h_agg, es.by_status, T.built, (int64_t)tm.score.count(), tm, sp_total);
     es.targets = n_targets;
     es.chunks = n_chunks;
     es.row_entries_walked = (int64_t)h_agg[9];
-    Rs->st.users_scored = (int64_t)h_agg[8];
-    Rs->st.pair_contribs = es.pair_contribs;
-    Rs->st.cooc_launches = es.batches;
-    Rs->st.score_launches = (int64_t)t_score.count();
-    Rs->st.ms_tables = t_tables.total_ms();
-    Rs->st.ms_cooc = t_cooc.total_ms();
-    Rs->st.ms_score = t_score.total_ms();
-    Rs->st.ms_total = t_total.total_ms();
     return Rs.release();
 }
 

@@ -2,7 +2,7 @@
 //
 // DESIGN.md section 2i.  The list pass of fy_itemcf_request.hip reads a user's preferences through an IcfRowView; here the view is a
 // small CSR composed from the caller's profiles instead of the job's own CSR, and everything behind it -- thresholds, the set J, the
-// row store, accumulate, finalize, top-N -- is that pass unchanged.  The ingest is sized by the request: T = the entries of this
+// row store, accumulate, finalize, top-N, the result and its statistics -- is that pass unchanged (the icfr_* frame of fy_itemcf_request.hip).  The ingest is sized by the request: T = the entries of this
 // rank's profiles + (FY_PROFILE_ON_RESIDENT) the resident rows of the users they name.
 //   k_prof_residents   label -> slot by icf_find_user (the search of k_icfr_find_users), the length of the resident row; scan -> roff
 //   k_prof_keys        key = profile << cb | column over the T elements, resident entries IN FRONT of the profile's own entries (raw
@@ -10,12 +10,11 @@
 //   sort_pairs_u64_u32 stable, cb + bits(n) key bits: a run of one key keeps resident-then-given order, its last element counts
 //   k_prof_runs        keep = last of its run and no delete; the counters (superseded, deletes that hit / missed the resident row)
 //   exclusive_scan_i32 place of every kept element = the composed CSR's entry (sorted by profile, then ascending column)
-//   k_prof_rowptr      rowptr[p] = place of the first element whose key is >= p << cb (binary search); empty profiles counted
+//   k_prof_rowptr      rowptr[p] = place of the first element whose key is >= p << cb (fy_lower_bound); empty profiles counted
 //   k_prof_scatter     column and preference (the resident row's float or the given one, bit for bit) to their place
 // All stores are plain vector stores; the counters are a handful of wave-aggregated atomics.
 #include <algorithm>
 #include <limits>
-#include <memory>
 
 #include "fy_itemcf_profiles.hpp"
 
@@ -32,12 +31,7 @@ inline int bits_for(int64_t v) {      // bits needed to hold the values 0 .. v
 
 // the p in [0, n) with off[p] <= t < off[p + 1] (off ascending from 0, t < off[n])
 __device__ __forceinline__ int32_t prof_owner(const int32_t* __restrict__ off, int32_t n, int32_t t) {
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (off[mid] <= t) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
+    return fy_lower_bound<true>(off, 0, n, t) - 1;
 }
 
 __device__ __forceinline__ void prof_count(unsigned long long* __restrict__ counters, int which, bool mine) {      // whole waves call it
@@ -125,12 +119,7 @@ __global__ void k_prof_runs(ProfIn A, const uint64_t* __restrict__ skeys, const 
                     const int32_t s = A.slot ? A.slot[p] : -1;
                     if (s >= 0) {      // is the column in the resident row (ascending columns)?
                         const int32_t col = (int32_t)(key & col_mask);
-                        int32_t lo = A.rowptr[s], hi = A.rowptr[s + 1];
-                        const int32_t end = hi;
-                        while (lo < hi) {
-                            const int32_t mid = (lo + hi) >> 1;
-                            if (A.csr_idx[mid] < col) lo = mid + 1; else hi = mid;
-                        }
+                        const int32_t end = A.rowptr[s + 1], lo = fy_lower_bound(A.csr_idx, A.rowptr[s], end, col);
                         hit = lo < end && A.csr_idx[lo] == col;
                     }
                     kind = hit ? 1 : 2;
@@ -146,15 +135,6 @@ __global__ void k_prof_runs(ProfIn A, const uint64_t* __restrict__ skeys, const 
     }
 }
 
-__device__ __forceinline__ int32_t prof_lower(const uint64_t* __restrict__ skeys, int32_t T, uint64_t want) {
-    int32_t lo = 0, hi = T;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (skeys[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // rowptr[p], p <= n: the place of the first kept element of profile p (place[T] = all kept elements)
 __global__ void k_prof_rowptr(int32_t n, int32_t T, int cb, const uint64_t* __restrict__ skeys, const int32_t* __restrict__ place,
                               int32_t* __restrict__ rowptr, unsigned long long* __restrict__ counters) {
@@ -162,9 +142,9 @@ __global__ void k_prof_rowptr(int32_t n, int32_t T, int cb, const uint64_t* __re
     for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n_up; p += (int64_t)gridDim.x * blockDim.x) {
         bool empty = false;
         if (p <= n) {
-            const int32_t a = place[prof_lower(skeys, T, (uint64_t)p << cb)];
+            const int32_t a = place[fy_lower_bound(skeys, 0, T, (uint64_t)p << cb)];
             rowptr[p] = a;
-            if (p < n) empty = place[prof_lower(skeys, T, (uint64_t)(p + 1) << cb)] == a;
+            if (p < n) empty = place[fy_lower_bound(skeys, 0, T, (uint64_t)(p + 1) << cb)] == a;
         }
         prof_count(counters, PC_EMPTY, empty);
     }
@@ -218,26 +198,12 @@ fy_result* itemcf_recommend_profiles(fy_itemsim_job* J, const fy_itemcf_params* 
 
     const bool by_items = filt && filt->has_items;
     hipStream_t st = ctx->stream;
-    std::unique_ptr<fy_result> Rs(new fy_result);
-    Rs->ctx = ctx;
-    Rs->kind = 2;
+    std::unique_ptr<fy_result> Rs = icfr_new_result(J, 2);
     Rs->has_itemcf_profile_stats = true;
     fy_itemcf_profile_stats& ps = Rs->cpf;
     ps.profiles_asked = n_all;
     ps.rows_stored = J->store.rows;
-    Rs->st.nnz = P.nnz;
-    Rs->st.n_users = P.nU;
-    Rs->st.n_items = P.nI;
-    Rs->d_user_id.alloc(ctx, 0);
-    Rs->d_item_id.alloc(ctx, 0);
-    auto no_rows = [&]() {
-        Rs->d_key0.alloc(ctx, 0);
-        Rs->d_key1.alloc(ctx, 0);
-        Rs->d_value.alloc(ctx, 0);
-        Rs->d_aux.alloc(ctx, 0);
-        return Rs.release();
-    };
-    if (P.nnz == 0 || n_all == 0 || (by_items && filt->n_items == 0)) return no_rows();
+    if (P.nnz == 0 || n_all == 0 || (by_items && filt->n_items == 0)) return icfr_no_rows(std::move(Rs));
     icfr_check_store(J);
 
     // ---- this rank's profiles: a contiguous range of the list given
@@ -251,17 +217,17 @@ fy_result* itemcf_recommend_profiles(fy_itemsim_job* J, const fy_itemcf_params* 
     const int32_t E = (int32_t)(pf->start[phi] - e0);
     ps.profiles_mine = n;
     ps.entries = E;
-    if (n == 0) return no_rows();
+    if (n == 0) return icfr_no_rows(std::move(Rs));
     const bool resident = pf->base == FY_PROFILE_ON_RESIDENT;
 
-    EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx), t_topn(ctx);
+    IcfrTimers tm(ctx);
     std::vector<int32_t> h_start((size_t)n + 1);
     for (int32_t p = 0; p <= n; p++) h_start[(size_t)p] = (int32_t)(pf->start[plo + p] - e0);
     unsigned long long h_c[PC_N] = {};
     int32_t h_composed = 0;
     SyncOnUnwind drain(st);      // behind the host ends of the queued copies (and the caller's arrays); the buffers below are released first
-    const size_t sp_total = t_total.begin();
-    const size_t sp_tab = t_tables.begin();
+    const size_t sp_total = tm.total.begin();
+    const size_t sp_tab = tm.tables.begin();
 
     // ---- the profiles in HBM
     DevBuf<int32_t> labels(ctx, (size_t)n), start(ctx, (size_t)n + 1), item(ctx, (size_t)E);
@@ -338,14 +304,7 @@ fy_result* itemcf_recommend_profiles(fy_itemsim_job* J, const fy_itemcf_params* 
     ps.removes_missed = (int64_t)h_c[PC_REMOVES_MISSED];
     ps.profiles_empty = T > 0 ? (int64_t)h_c[PC_EMPTY] : n;
     ps.prefs_composed = h_composed;
-    if (h_composed == 0) {      // every profile is empty: nothing is built, nobody gets a list
-        t_tables.end(sp_tab);
-        t_total.end(sp_total);
-        sync(ctx);
-        Rs->st.ms_tables = t_tables.total_ms();
-        Rs->st.ms_total = t_total.total_ms();
-        return no_rows();
-    }
+    if (h_composed == 0) return icfr_nobody(std::move(Rs), tm, sp_tab, sp_total);      // every profile is empty: nothing is built, nobody gets a list
     k_prof_identity<<<grid_for(n), 256, 0, st>>>(n, list.get());
     FY_KERNEL_CHECK();
     DevBuf<uint32_t> allow;
@@ -355,31 +314,9 @@ fy_result* itemcf_recommend_profiles(fy_itemsim_job* J, const fy_itemcf_params* 
     const IcfRowView V{c_rowptr.get(), c_idx.get(), c_r.get(), labels.get(), list.get(), P.rank_item_raw.get(), P.nP};
     DevBuf<float> thr(ctx, (size_t)n + 1);
     IcfrRows built;
-    icfr_rows_for_users(J, V, list.get(), 0, n, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
-    ps.items_needed = built.items_needed;
-    ps.rows_built = built.rows_built;
-    ps.rows_from_store = built.rows_from_store;
-    ps.rows_stored = built.rows_stored;
-    ps.pair_contribs = built.pair_contribs;
-    ps.batches = built.batches;
-    fy_itemsim_job::RowStore& store = J->store;
-    DevBuf<int32_t> n_lists;
-    const IcfSims S{store.start.get(), store.cnt.get(), store.other.get(), store.sim.get()};
-    icf_score_lists(ctx, prm, V, S, list.get(), list.get(), by_items ? allow.get() : nullptr, 0, n, thr.get(), Rs.get(), t_score, t_topn, n_lists);
-    t_total.end(sp_total);
-    const int64_t scored = (int64_t)fetch(ctx, n_lists.get());
-    sync(ctx);
-    ps.profiles_scored = scored;
-    Rs->st.recs = Rs->n;
-    Rs->st.users_scored = scored;
-    Rs->st.pair_contribs = ps.pair_contribs;
-    Rs->st.cooc_launches = ps.batches;
-    Rs->st.score_launches = (int64_t)t_score.count();
-    Rs->st.ms_tables = t_tables.total_ms();
-    Rs->st.ms_cooc = t_cooc.total_ms();
-    Rs->st.ms_score = t_score.total_ms();
-    Rs->st.ms_topn = t_topn.total_ms();
-    Rs->st.ms_total = t_total.total_ms();
+    icfr_rows_for_users(J, V, list.get(), 0, n, prm->max_prefs_per_user, thr.get(), tm, sp_tab, built);
+    icfr_report(ps, built, true);
+    ps.profiles_scored = icfr_lists_from_store(J, prm, V, list.get(), list.get(), by_items ? allow.get() : nullptr, 0, n, thr.get(), built, Rs.get(), tm, sp_total);
     return Rs.release();
 }
 

@@ -14,11 +14,12 @@
 //   accumulate .. compact   icf_score_lists of the filtered pass with row_start[j] = j * K and row_cnt read from the store
 // The per-cell order of additions is the order of the user's preferences, as in the filtered pass, so the result is the filtered
 // pass's bit for bit when it is fed the rows fy_itemsim_rows returns; the store changes where a row comes from, never its bits.
-// The steps from the thresholds to k_icfr_fill_store are icfr_rows_for_users, which the estimates for named pairs
-// (fy_itemcf_estimate.hip) call too: a row built for either pass serves the other.
+// The steps from the thresholds to k_icfr_fill_store are icfr_rows_for_users, which the profile pass (fy_itemcf_profiles.hip) and the
+// passes over named pairs (fy_itemcf_pairs.hip) call too: a row built for any pass serves the others.  The frame every such pass
+// shares is here as well: the result (icfr_new_result, icfr_no_rows, icfr_nobody), the list pass over the store
+// (icfr_lists_from_store) and the fy_stats (icfr_finish_stats).
 #include <algorithm>
 #include <limits>
-#include <memory>
 
 #include "fy_itemcf_request.hpp"
 
@@ -111,8 +112,8 @@ void icfr_check_store(const fy_itemsim_job* J) {
         FY_FAIL(FY_ERR_UNSUPPORTED, "the row store would exceed 2^31 entries");
 }
 
-void icfr_rows_for_users(fy_itemsim_job* J, const IcfRowView& V, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, EventTimer& t_tables,
-                         size_t sp_tab, EventTimer& t_cooc, IcfrRows& rq) {
+void icfr_rows_for_users(fy_itemsim_job* J, const IcfRowView& V, const int32_t* list, int32_t lo, int32_t hi, int32_t max_prefs, float* thr, IcfrTimers& tm,
+                         size_t sp_tab, IcfrRows& rq) {
     Context* ctx = J->ctx;
     const Prepared& P = J->P;
     const int32_t K = J->prm.max_similarities_per_item, nP = P.nP, nmine = hi - lo;
@@ -163,24 +164,80 @@ void icfr_rows_for_users(fy_itemsim_job* J, const IcfRowView& V, const int32_t* 
         h_missing.resize((size_t)n_build);
         d2h(ctx, h_missing.data(), rows.get(), (size_t)n_build);
     }
-    t_tables.end(sp_tab);
+    tm.tables.end(sp_tab);
 
     // ---- build the missing rows and keep them
     if (n_build > 0) {
         DevBuf<int32_t> cnt(ctx, (size_t)n_build), other(ctx, (size_t)n_build * K);
         DevBuf<float> sim(ctx, (size_t)n_build * K);
-        rq.batches = itemsim_build_rank_rows(J, rows.get(), n_build, cnt.get(), other.get(), sim.get(), t_cooc, t_cooc);
-        const size_t sp_f = t_cooc.begin();
+        rq.batches = itemsim_build_rank_rows(J, rows.get(), n_build, cnt.get(), other.get(), sim.get(), tm.cooc, tm.cooc);
+        const size_t sp_f = tm.cooc.begin();
         k_icfr_fill_store<<<grid_for(n_build * 64, 256), 256, 0, st>>>((int32_t)n_build, K, nP, rows.get(), cnt.get(), other.get(), sim.get(), P.iid.get(),
                                                                       P.nI, P.pair_rank.get(), store.state.get(), store.cnt.get(), store.other.get(),
                                                                       store.sim.get());
         FY_KERNEL_CHECK();
-        t_cooc.end(sp_f);
+        tm.cooc.end(sp_f);
         store.rows += n_build;
         sync(ctx);      // the list of the built rows is on the host
         for (int32_t r : h_missing) rq.pair_contribs += J->walk[(size_t)r];
     }
     rq.rows_stored = store.rows;
+}
+
+std::unique_ptr<fy_result> icfr_new_result(const fy_itemsim_job* J, int kind) {
+    std::unique_ptr<fy_result> Rs(new fy_result);
+    Rs->ctx = J->ctx;
+    Rs->kind = kind;
+    Rs->st.nnz = J->P.nnz;
+    Rs->st.n_users = J->P.nU;
+    Rs->st.n_items = J->P.nI;
+    Rs->d_user_id.alloc(J->ctx, 0);
+    Rs->d_item_id.alloc(J->ctx, 0);
+    return Rs;
+}
+
+fy_result* icfr_no_rows(std::unique_ptr<fy_result> Rs) {
+    Rs->d_key0.alloc(Rs->ctx, 0);
+    Rs->d_key1.alloc(Rs->ctx, 0);
+    Rs->d_value.alloc(Rs->ctx, 0);
+    Rs->d_aux.alloc(Rs->ctx, 0);
+    return Rs.release();
+}
+
+void icfr_finish_stats(fy_result* Rs, const IcfrRows& built, int64_t users_scored, int64_t score_launches, IcfrTimers& tm) {
+    Rs->st.recs = Rs->n;
+    Rs->st.users_scored = users_scored;
+    Rs->st.pair_contribs = built.pair_contribs;
+    Rs->st.cooc_launches = built.batches;
+    Rs->st.score_launches = score_launches;
+    Rs->st.ms_tables = tm.tables.total_ms();
+    Rs->st.ms_cooc = tm.cooc.total_ms();
+    Rs->st.ms_score = tm.score.total_ms();
+    Rs->st.ms_topn = tm.topn.total_ms();
+    Rs->st.ms_total = tm.total.total_ms();
+}
+
+fy_result* icfr_nobody(std::unique_ptr<fy_result> Rs, IcfrTimers& tm, size_t sp_tab, size_t sp_total) {
+    tm.tables.end(sp_tab);
+    tm.total.end(sp_total);
+    sync(Rs->ctx);
+    icfr_finish_stats(Rs.get(), IcfrRows{}, 0, 0, tm);
+    return icfr_no_rows(std::move(Rs));
+}
+
+int64_t icfr_lists_from_store(fy_itemsim_job* J, const fy_itemcf_params* prm, const IcfRowView& V, const int32_t* list, const int32_t* list_du,
+                              const uint32_t* allow, int32_t lo, int32_t hi, const float* thr, const IcfrRows& built, fy_result* Rs, IcfrTimers& tm,
+                              size_t sp_total) {
+    Context* ctx = J->ctx;
+    const fy_itemsim_job::RowStore& store = J->store;
+    DevBuf<int32_t> n_lists;
+    const IcfSims S{store.start.get(), store.cnt.get(), store.other.get(), store.sim.get()};
+    icf_score_lists(ctx, prm, V, S, list, list_du, allow, lo, hi, thr, Rs, tm.score, tm.topn, n_lists);
+    tm.total.end(sp_total);
+    const int64_t scored = (int64_t)fetch(ctx, n_lists.get());
+    sync(ctx);
+    icfr_finish_stats(Rs, built, scored, (int64_t)tm.score.count(), tm);
+    return scored;
 }
 
 fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* prm, const fy_itemcf_filter* filt) {
@@ -191,39 +248,24 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     icf_check_arguments(prm, filt);
     icfr_check_job(J);
     hipStream_t st = ctx->stream;
-    std::unique_ptr<fy_result> Rs(new fy_result);
-    Rs->ctx = ctx;
-    Rs->kind = 2;
+    std::unique_ptr<fy_result> Rs = icfr_new_result(J, 2);
     Rs->has_itemcf_request_stats = true;
     fy_itemcf_request_stats& rq = Rs->crq;
     rq.users_asked = filt->n_users;
     rq.rows_stored = J->store.rows;
-    Rs->st.nnz = P.nnz;
-    Rs->st.n_users = P.nU;
-    Rs->st.n_items = P.nI;
-    Rs->d_user_id.alloc(ctx, 0);
-    Rs->d_item_id.alloc(ctx, 0);
-    // a result without rows (where there are lists, icf_score_lists allocates the four columns)
-    auto no_rows = [&]() {
-        Rs->d_key0.alloc(ctx, 0);
-        Rs->d_key1.alloc(ctx, 0);
-        Rs->d_value.alloc(ctx, 0);
-        Rs->d_aux.alloc(ctx, 0);
-        return Rs.release();
-    };
     // Mahout's empty id set: nobody is asked for / nothing may be recommended
-    if (P.nnz == 0 || filt->n_users == 0 || (filt->has_items && filt->n_items == 0)) return no_rows();
+    if (P.nnz == 0 || filt->n_users == 0 || (filt->has_items && filt->n_items == 0)) return icfr_no_rows(std::move(Rs));
     icfr_check_store(J);
 
-    EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx), t_topn(ctx);
+    IcfrTimers tm(ctx);
     std::vector<uint64_t> found((size_t)filt->n_users);
     std::vector<int32_t> slots, dus;
     // behind the host ends of the queued copies (and the caller's id arrays).  The scratch buffers below are declared after it and so
     // go back to the allocator BEFORE a failure drains the stream, as in icf_run: the allocator hands blocks out again on this same
     // stream only, and no later call queues work before this one has unwound.
     SyncOnUnwind drain(st);
-    const size_t sp_total = t_total.begin();
-    const size_t sp_tab = t_tables.begin();
+    const size_t sp_total = tm.total.begin();
+    const size_t sp_tab = tm.tables.begin();
     // ---- the request: known users once each, in slot order -- the list of the filtered pass
     {
         DevBuf<int32_t> ids(ctx, (size_t)filt->n_users);
@@ -246,14 +288,7 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     }
     const int32_t nmine = hi - lo;
     rq.users_known = nmine;
-    if (nmine == 0) {
-        t_tables.end(sp_tab);
-        t_total.end(sp_total);
-        sync(ctx);
-        Rs->st.ms_tables = t_tables.total_ms();
-        Rs->st.ms_total = t_total.total_ms();
-        return no_rows();
-    }
+    if (nmine == 0) return icfr_nobody(std::move(Rs), tm, sp_tab, sp_total);
     slots.resize((size_t)n_all);
     dus.resize((size_t)n_all);
     for (int32_t k = 0; k < n_all; k++) {
@@ -269,33 +304,11 @@ fy_result* itemcf_recommend_prepared(fy_itemsim_job* J, const fy_itemcf_params* 
     // ---- thresholds, the set J, the rows the store lacks: built and kept
     IcfrRows built;
     const IcfRowView V = icf_rows_of(P);
-    icfr_rows_for_users(J, V, list.get(), lo, hi, prm->max_prefs_per_user, thr.get(), t_tables, sp_tab, t_cooc, built);
-    rq.items_needed = built.items_needed;
-    rq.rows_built = built.rows_built;
-    rq.rows_from_store = built.rows_from_store;
-    rq.rows_stored = built.rows_stored;
-    rq.pair_contribs = built.pair_contribs;
-    rq.batches = built.batches;
-    fy_itemsim_job::RowStore& store = J->store;
+    icfr_rows_for_users(J, V, list.get(), lo, hi, prm->max_prefs_per_user, thr.get(), tm, sp_tab, built);
+    icfr_report(rq, built, true);
 
     // ---- accumulate, finalize, top-N, compact: the filtered pass, reading the store
-    DevBuf<int32_t> n_lists;
-    const IcfSims S{store.start.get(), store.cnt.get(), store.other.get(), store.sim.get()};
-    icf_score_lists(ctx, prm, V, S, list.get(), list_du.get(), filt->has_items ? allow.get() : nullptr, lo, hi, thr.get(), Rs.get(), t_score, t_topn,
-                    n_lists);
-    t_total.end(sp_total);
-    const int64_t scored = (int64_t)fetch(ctx, n_lists.get());
-    sync(ctx);
-    Rs->st.recs = Rs->n;
-    Rs->st.users_scored = scored;
-    Rs->st.pair_contribs = rq.pair_contribs;
-    Rs->st.cooc_launches = rq.batches;
-    Rs->st.score_launches = (int64_t)t_score.count();
-    Rs->st.ms_tables = t_tables.total_ms();
-    Rs->st.ms_cooc = t_cooc.total_ms();
-    Rs->st.ms_score = t_score.total_ms();
-    Rs->st.ms_topn = t_topn.total_ms();
-    Rs->st.ms_total = t_total.total_ms();
+    icfr_lists_from_store(J, prm, V, list.get(), list_du.get(), filt->has_items ? allow.get() : nullptr, lo, hi, thr.get(), built, Rs.get(), tm, sp_total);
     return Rs.release();
 }
 

@@ -2,7 +2,7 @@
 """Times explanations of named pairs (PreparedItemSimilarity.because) beside the estimates of the same pairs
 (PreparedItemSimilarity.estimate) on the same warm row store:
 `python tools/because_bench.py [--shape ml25m] [--measure SIMILARITY_COSINE] [--fraction 0.1] [--reps 5] [--k 100] [--max-prefs 50]
- [--how-many 5] [--out profiles/because/ml25m.json]`.
+ [--how-many 5] [--out profiles/because/ml25m.json] [--dump DIR]`.
 
 The ratings are generated in HBM and split once (Ratings.holdout(fraction, seed 1)); ONE job is prepared on the train side.  Three
 requests, their pairs resident in HBM:
@@ -12,7 +12,9 @@ requests, their pairs resident in HBM:
 Each request is first answered once by both calls (the rows it needs are then in the store, both kernels have run), then `reps`
 rounds alternate because / estimate.  Reported per request and call: median and min .. max over the rounds of the library's own
 HIP-event times (ms_total, ms_tables, ms_score), the because / estimate ratio of the ms_total and ms_score medians, and
-row_entries_walked of both.  Nothing is compared for correctness here: tests/test_because_gpu.py does that."""
+row_entries_walked of both.  Nothing is compared for correctness here: tests/test_because_gpu.py does that.
+`--dump DIR`: the arrays and the integer statistics of the first result of every
+request and call as files (tools/_dump.py), to compare two builds of the library byte for byte."""
 import argparse
 import importlib
 import json
@@ -23,6 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _dump import Dump  # noqa: E402
 
 
 def summary(ms):
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--max-prefs", type=int, default=50)
     ap.add_argument("--how-many", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dump", default="")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -54,6 +58,7 @@ def main():
     R.close()
     tu, ti, _ = test.to_host()
     test_users = np.unique(tu).astype(np.int32)
+    dump = Dump(a.dump)
     prepared = P.BaselineRecommenderJob(ctx).prepare(train, maxSimilaritiesPerItem=a.k, similarityClassname=a.measure)
 
     def list_pairs(users, n):
@@ -81,6 +86,7 @@ def main():
         for keep in [False] + [True] * a.reps:                  # one round to fill the store and warm both kernels, then the rounds that count
             for call, fn in calls.items():
                 res = fn()
+                dump("%s.%s" % (name, call), res, res.because_stats if call == "because" else res.estimate_stats)
                 if keep:
                     for k in ("ms_total", "ms_tables", "ms_score"):
                         series.setdefault("%s.%s" % (call, k), []).append(float(res.stats[k]))

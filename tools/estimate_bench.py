@@ -2,7 +2,7 @@
 """Times estimated preferences for the pairs of a hold-out (PreparedItemSimilarity.estimate + PreferenceEstimates.errors) beside the
 list pass of the same users on the same job:
 `python tools/estimate_bench.py [--shape ml25m] [--measure SIMILARITY_COSINE] [--fraction 0.1] [--reps 5] [--k 100] [--n 10]
- [--max-prefs 50] [--out profiles/estimate/ml25m.json]`.
+ [--max-prefs 50] [--out profiles/estimate/ml25m.json] [--dump DIR]`.
 
 The ratings are generated in HBM and split once (Ratings.holdout(fraction, seed 1)).  After one warm-up of every leg, `reps` rounds
 run the legs in one process, each round on a NEW prepared job of the train side:
@@ -13,7 +13,9 @@ run the legs in one process, each round on a NEW prepared job of the train side:
 Reported per leg: median and spread (max - min) over the rounds of the library's own HIP-event times (ms_total, ms_score, and for the
 list pass ms_score + ms_topn), pairs per second of the warm estimate, its statistics (row_entries_walked among them) and MAE / RMSE.
 The expectation -- the warm estimate's ms_score does not exceed the list pass's ms_score + ms_topn by more than the larger spread --
-is evaluated and printed, never enforced.  Nothing is compared for correctness here: tests/test_estimate_gpu.py does that."""
+is evaluated and printed, never enforced.  Nothing is compared for correctness here: tests/test_estimate_gpu.py does that.
+`--dump DIR`: the arrays and the integer statistics of the first result of every
+leg as files (tools/_dump.py), to compare two builds of the library byte for byte."""
 import argparse
 import importlib
 import json
@@ -24,6 +26,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _dump import Dump  # noqa: E402
 
 
 def summary(ms):
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--max-prefs", type=int, default=50)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dump", default="")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -58,6 +62,7 @@ def main():
            "reps": a.reps, "k": a.k, "n": a.n, "max_prefs": a.max_prefs, "train": train.nnz, "test": test.nnz, "test_users": len(test_users)}
     series = {}
     info = {}
+    dump = Dump(a.dump)
 
     def note(name, value):
         series.setdefault(name, []).append(float(value))
@@ -68,6 +73,9 @@ def main():
         warm = prepared.estimate(test, maxPrefsPerUser=a.max_prefs)
         err = warm.errors(test)
         rec = prepared.recommend(test_users, numRecommendations=a.n, maxPrefsPerUser=a.max_prefs)
+        dump("cold", cold, cold.estimate_stats)
+        dump("warm", warm, warm.estimate_stats)
+        dump("recommend", rec, rec.request_stats)
         if keep:
             for leg, res in (("cold", cold), ("warm", warm)):
                 for k in ("ms_total", "ms_tables", "ms_cooc", "ms_score"):

@@ -2,7 +2,7 @@
 """Times item-based recommendations for named users from a prepared similarity job (BaselineRecommenderJob.prepare +
 PreparedItemSimilarity.recommend) beside what such a request costs after a write without it:
 `python tools/itemcf_request_bench.py [--shape ml25m] [--measure SIMILARITY_COSINE,SIMILARITY_LOGLIKELIHOOD] [--sizes 1,100,10000]
- [--reps 5] [--k 100] [--n 100] [--max-prefs 50] [--out profiles/itemcf_request/ml25m.json]`.
+ [--reps 5] [--k 100] [--n 100] [--max-prefs 50] [--out profiles/itemcf_request/ml25m.json] [--dump DIR]`.
 
 The ratings are put into HBM once.  Per measure and request size, after one warm-up of every leg, `reps` rounds ALTERNATE the legs
 in one run:
@@ -17,7 +17,9 @@ chunk walks all of it).  The conditions, each against other legs OF THE SAME RUN
 of the two spreads, are evaluated and printed, never enforced:
   B < A for the 1-user request with SIMILARITY_LOGLIKELIHOOD;
   C < B.recommend for both measures at every size.
-Nothing is compared for correctness here: tests/test_itemcf_request_gpu.py does that."""
+Nothing is compared for correctness here: tests/test_itemcf_request_gpu.py does that.
+`--dump DIR`: the arrays and the integer statistics of the first result of every
+leg as files (tools/_dump.py), to compare two builds of the library byte for byte."""
 import argparse
 import importlib
 import json
@@ -28,6 +30,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _dump import Dump  # noqa: E402
 
 
 def summary(ms):
@@ -65,6 +68,7 @@ def main():
     ap.add_argument("--max-prefs", type=int, default=50)
     ap.add_argument("--seed", type=int, default=20261019)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dump", default="")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -83,6 +87,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     sizes = [min(int(x), len(all_users) // 2) for x in a.sizes.split(",")]
     kw = dict(numRecommendations=a.n, maxPrefsPerUser=a.max_prefs)
+    dump = Dump(a.dump)
     out = {"shape": a.shape, "facts": {k: facts[k] for k in ("n_users", "n_items", "nnz")}, "reps": a.reps, "k": a.k, "n": a.n,
            "max_prefs": a.max_prefs, "measures": {}}
 
@@ -116,6 +121,7 @@ def main():
                 t["B.prepare"], prepared = timed(lambda: job.prepare(R, maxSimilaritiesPerItem=a.k, similarityClassname=measure))
                 for leg, users in (("B.recommend", first), ("C", first), ("D", other)):
                     t[leg], rec = timed(lambda: prepared.recommend(users, **kw))
+                    dump("%s.users_%d.%s" % (measure, n, leg), rec, rec.request_stats)
                     info[leg] = dict(rec.request_stats, recs=rec.stats["recs"], users_scored=rec.stats["users_scored"],
                                      lib_ms_tables=rec.stats["ms_tables"], lib_ms_cooc=rec.stats["ms_cooc"], lib_ms_score=rec.stats["ms_score"],
                                      lib_ms_topn=rec.stats["ms_topn"], lib_ms_total=rec.stats["ms_total"])

@@ -2,7 +2,7 @@
 """Times item-based lists for given profiles on a standing prepared job (PreparedItemSimilarity.recommend_profiles) beside what a
 request right after a write costs without it:
 `python tools/profile_bench.py [--shape ml25m] [--measure SIMILARITY_COSINE] [--sizes 1,100,10000] [--whole 1,1000] [--reps 5] [--k 100]
- [--n 100] [--max-prefs 50] [--out profiles/profiles/ml25m.json]`.
+ [--n 100] [--max-prefs 50] [--out profiles/profiles/ml25m.json] [--dump DIR]`.
 
 The ratings are put into HBM once and one job is prepared on them (the STANDING job).  Per request size n -- n random users with one
 new rating each (score 5, an item the user has not rated) -- after one warm-up of every leg, `reps` rounds alternate the legs in one
@@ -17,7 +17,9 @@ run:
 `ms` is the HIP-event time of the whole call(s): two events recorded on the context's stream around them, every call ends
 synchronised.  Reported per leg: median and min..max over the rounds, and the call's own statistics.  Note that A answers from
 similarities that follow the write, B / C from the similarities as prepared: they are different answers by design
-(include/filmyou.h).  Nothing is compared for correctness here: tests/test_profiles_gpu.py does that."""
+(include/filmyou.h).  Nothing is compared for correctness here: tests/test_profiles_gpu.py does that.
+`--dump DIR`: the arrays and the integer statistics of the first result of every
+leg as files (tools/_dump.py), to compare two builds of the library byte for byte."""
 import argparse
 import importlib
 import json
@@ -28,6 +30,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _dump import Dump  # noqa: E402
 
 
 def summary(ms):
@@ -57,6 +60,7 @@ def main():
     ap.add_argument("--max-prefs", type=int, default=50)
     ap.add_argument("--seed", type=int, default=20261021)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dump", default="")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -72,6 +76,7 @@ def main():
     stream = torch.cuda.ExternalStream(int(ctx.stream), device=torch.device("cuda", 0))
     rng = np.random.default_rng(a.seed)
     kw = dict(numRecommendations=a.n, maxPrefsPerUser=a.max_prefs)
+    dump = Dump(a.dump)
     job = P.BaselineRecommenderJob(ctx)
     standing = job.prepare(R, maxSimilaritiesPerItem=a.k, similarityClassname=a.measure)
     out = {"shape": a.shape, "facts": {k: facts[k] for k in ("n_users", "n_items", "nnz")}, "measure": a.measure, "reps": a.reps, "k": a.k, "n": a.n,
@@ -87,6 +92,7 @@ def main():
         return e0.elapsed_time(e1), res
 
     def note(info, leg, rec, stats):
+        dump("%s.%s" % (dump_as, leg), rec, stats)
         info[leg] = dict(stats, recs=rec.stats["recs"], users_scored=rec.stats["users_scored"], lib_ms_tables=rec.stats["ms_tables"],
                          lib_ms_cooc=rec.stats["ms_cooc"], lib_ms_score=rec.stats["ms_score"], lib_ms_topn=rec.stats["ms_topn"])
         rec.close()
@@ -106,7 +112,7 @@ def main():
         scores = np.full(n, 5.0, dtype=np.float32)
         start = np.arange(n + 1, dtype=np.int64)
         profiles = (users, start, items, scores)
-        info = {}
+        info, dump_as = {}, "users_%d" % n
 
         def one_round():
             t = {}
@@ -146,7 +152,7 @@ def main():
         items = np.concatenate([rng.choice(all_items, size=20, replace=False) for _ in range(m)]).astype(np.int32)
         scores = (rng.integers(1, 11, size=20 * m) / 2.0).astype(np.float32)
         profiles = (np.arange(m, dtype=np.int32) + int(all_users.max()) + 1, start, items, scores)
-        info = {}
+        info, dump_as = {}, "whole_%d" % m
 
         def whole_round():
             t = {}
