@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_pairs.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_profiles.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm2_profiles.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_pairs.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm2_profiles.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_profiles.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -36,6 +36,7 @@ SYMBOLS = [
     "fy_itemcf_estimate_prepared", "fy_itemcf_estimate_ratings", "fy_result_itemcf_estimate_stats", "fy_eval_estimates",
     "fy_itemcf_because_prepared", "fy_result_because_view", "fy_result_itemcf_because_stats",
     "fy_itemcf_recommend_profiles", "fy_result_itemcf_profile_stats",
+    "fy_rm2_score_profiles", "fy_result_rm2_profile_stats",
 ]
 
 
@@ -209,6 +210,22 @@ class ItemCFProfileStats(C.Structure):
                 ("removes_hit", C.c_int64), ("removes_missed", C.c_int64), ("prefs_composed", C.c_int64), ("items_needed", C.c_int64),
                 ("rows_built", C.c_int64), ("rows_from_store", C.c_int64), ("rows_stored", C.c_int64), ("pair_contribs", C.c_int64),
                 ("batches", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RM2Profiles(C.Structure):
+    _fields_ = [("n_profiles", C.c_int64), ("user", C.c_void_p), ("start", C.c_void_p), ("item", C.c_void_p), ("score", C.c_void_p),
+                ("remove", C.c_void_p), ("cluster", C.c_void_p), ("base", C.c_int32), ("rank", C.c_int32), ("world", C.c_int32)]
+
+
+class RM2ProfileStats(C.Structure):
+    _fields_ = [("profiles_asked", C.c_int64), ("profiles_mine", C.c_int64), ("profiles_scored", C.c_int64), ("profiles_empty", C.c_int64),
+                ("users_unknown", C.c_int64), ("users_filtered", C.c_int64), ("entries", C.c_int64), ("entries_unknown_item", C.c_int64),
+                ("entries_nonpositive", C.c_int64), ("entries_superseded", C.c_int64), ("removes_hit", C.c_int64),
+                ("removes_missed", C.c_int64), ("items_composed", C.c_int64), ("clusters_touched", C.c_int64), ("batches", C.c_int64),
+                ("slab_rows", C.c_int64), ("slab_bytes_peak", C.c_int64), ("slab_pair_contribs", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -428,5 +445,7 @@ def load():
     L.fy_result_itemcf_because_stats.argtypes = [vp, C.POINTER(ItemCFBecauseStats)]
     L.fy_itemcf_recommend_profiles.argtypes = [vp, C.POINTER(ItemCFParams), C.POINTER(ItemCFProfiles), C.POINTER(ItemCFFilter), pvp]
     L.fy_result_itemcf_profile_stats.argtypes = [vp, C.POINTER(ItemCFProfileStats)]
+    L.fy_rm2_score_profiles.argtypes = [vp, C.POINTER(RM2Profiles), pvp]
+    L.fy_result_rm2_profile_stats.argtypes = [vp, C.POINTER(RM2ProfileStats)]
     _lib = L
     return L

@@ -10,6 +10,7 @@
 #include "fy_rm2.hpp"
 #include "fy_ratings_update.hpp"
 #include "fy_rm2_request.hpp"
+#include "fy_rm2_profiles.hpp"
 #include "fy_itemsim_request.hpp"
 #include "fy_itemcf_request.hpp"
 #include "fy_itemcf_profiles.hpp"
@@ -335,6 +336,16 @@ int fy_rm2_score_users(fy_rm2_job* j, const fy_rm2_request* rq, fy_result** out)
     FY_TRY
     select_device(job_context(j));
     *out = fy::rm2_score_users(j, rq);
+    FY_CATCH
+}
+
+int fy_rm2_score_profiles(fy_rm2_job* j, const fy_rm2_profiles* profiles, fy_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!j || !profiles) { set_error("job or profiles is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(job_context(j));
+    *out = fy::rm2_score_profiles(j, profiles);
     FY_CATCH
 }
 
@@ -679,6 +690,12 @@ int fy_result_request_stats(fy_result* r, fy_rm2_request_stats* out) {
     if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
     if (!r->has_request_stats) { set_error("not a result of fy_rm2_score_users"); return FY_ERR_STATE; }
     *out = r->rq;
+    return FY_OK;
+}
+int fy_result_rm2_profile_stats(fy_result* r, fy_rm2_profile_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!r->has_rm2_profile_stats) { set_error("not a result of fy_rm2_score_profiles"); return FY_ERR_STATE; }
+    *out = r->rpf;
     return FY_OK;
 }
 int fy_result_itemsim_request_stats(fy_result* r, fy_itemsim_request_stats* out) {

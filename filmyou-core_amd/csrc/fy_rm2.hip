@@ -3088,6 +3088,11 @@ void fy::rm2_request_view(fy_rm2_job* J, RequestView& V) {
     fill_request_view(J, V);
 }
 
+void fy::rm2_job_peek(const fy_rm2_job* J, fy_rm2_params* prm, bool* have_coll) {
+    *prm = J->prm;
+    *have_coll = J->have_coll;
+}
+
 static void fill_request_view(fy_rm2_job* J, RequestView& V) {
     V.ctx = J->ctx;
     V.prm = J->prm;

@@ -17,6 +17,8 @@ struct fy_result {
     fy_stats st{};
     bool has_request_stats = false;   // a result of fy_rm2_score_users
     fy_rm2_request_stats rq{};
+    bool has_rm2_profile_stats = false;       // a result of fy_rm2_score_profiles
+    fy_rm2_profile_stats rpf{};
     bool has_itemsim_request_stats = false;   // a result of fy_itemsim_rows
     fy_itemsim_request_stats irq{};
     bool has_itemcf_request_stats = false;    // a result of fy_itemcf_recommend_prepared

@@ -56,24 +56,6 @@ __global__ void k_req_chunk_offsets(int32_t nU, int32_t CH, int32_t stride, cons
     }
 }
 
-struct SlabArgs {
-    const int32_t* __restrict__ J;          // [nJ] rows of the slab: item index inside the cluster (rank order)
-    int32_t nJ, Ic, CH, nch, pbase, stride;
-    int64_t ld;
-    const int32_t* __restrict__ rank_pair;
-    const int32_t* __restrict__ pair_start;
-    const int32_t* __restrict__ csc_slot;
-    const float* __restrict__ csc_r;
-    const int32_t* __restrict__ choff;
-    const int32_t* __restrict__ csr_idx;
-    const float* __restrict__ csr_r;
-    const double* __restrict__ usum_slot;
-    const double* __restrict__ b_rank;
-    double* __restrict__ slab;
-    const float* __restrict__ fx_rank;      // general smoothing: the row's bound is fx_rank[3 pos] * rmax (null: b_j)
-    double rmax;
-};
-
 // Workgroup = (row j of the slab, column chunk).  The accumulators hold round(x_vj x_vi 2^k) with k per row from b_j = sum_v x_vj, an
 // upper bound of every entry of the row (x_vi <= 1): b_j 2^k < 2^62, so no sum overflows and a contribution resolves 2^-61 of b_j.
 __global__ __launch_bounds__(SLAB_THREADS) void k_req_slab(SlabArgs A) {
@@ -145,8 +127,7 @@ __global__ __launch_bounds__(SCORE_COLS) void k_req_score(ScoreReqArgs A) {
             const int32_t j = A.csr_idx[f];
             const double x = (double)A.csr_r[f] / s;
             const double p = A.p_rank[j];
-            double e = (1.0 - A.lambda) * (A.b_rank[j] - x) + A.lambda * A.users_minus_1 * p;      // = sum_{v != u} c_vj
-            if (!(e > 0.0)) e = 0.0;
+            double e = fy_req_e(A.lambda, A.b_rank[j], x, A.users_minus_1, p);      // = sum_{v != u} c_vj
             if (A.general)
                 e = fy_e_general(A.b_rank[j], p, (double)A.csr_r[f], s, (double)A.G.deg_slot[slot], A.G.beta_slot[slot], A.G.s2_cluster[A.cluster],
                                  A.G.bt_scale, A.G.bt_by_n);
@@ -162,13 +143,12 @@ __global__ __launch_bounds__(SCORE_COLS) void k_req_score(ScoreReqArgs A) {
                 rated |= sh_j[k] == i;
                 const int32_t r = sh_row[k];
                 const double g = r >= 0 ? A.slab[(int64_t)r * A.ld + i] : __longlong_as_double(0x7FF8000000000000ll);
-                acc += log(w2 * g + sh_q[k] * b_i + a_i * sh_e[k]);
+                acc += fy_req_log_term(w2, g, sh_q[k], b_i, a_i, sh_e[k]);
             }
         __syncthreads();
     }
     const double n = (double)(f1 - f0);
-    const double pvpi = (n - 1.0) * A.ln_items - n * A.ln_users;      // AbstractRM2Reducer.java:327-329
-    A.S[(int64_t)u * A.ldS + i] = live && !rated ? (float)(acc + pvpi) : __uint_as_float(0x7FC00000u);
+    A.S[(int64_t)u * A.ldS + i] = live && !rated ? fy_req_row_value(acc, n, A.ln_items, A.ln_users) : __uint_as_float(0x7FC00000u);
 }
 
 // rows of the full job's result -> the request's result (one wave per user)
@@ -187,17 +167,9 @@ __global__ void k_req_copy_rows(int32_t n, const int32_t* __restrict__ desc /* 3
     }
 }
 
-// What the first request builds from the ratings and the clustering alone, kept with the cached static part of the job (a later job
-// over the same ratings and clustering finds it): host mirrors of the structure the request is planned from and the chunk offsets of
-// every user's row for the slab kernel's column chunks.  p(i|C) depends on the job's statistics and is computed per request.
-struct RequestState {
-    int32_t CH = 0, stride = 0;
-    std::vector<int32_t> uid, du2slot, rowptr, csr_idx;
-    std::vector<long long> walk;
-    DevBuf<int32_t> choff;
-};
+}  // namespace
 
-RequestState& ensure_state(const RequestView& V) {
+RequestState& rm2_request_state(const RequestView& V) {
     Context* ctx = V.ctx;
     const Prepared& P = *V.P;
     const int32_t CH = ctx->tune.req_chunk;
@@ -228,6 +200,21 @@ RequestState& ensure_state(const RequestView& V) {
     *V.state = fresh;
     return *fresh;
 }
+
+void rm2_request_p(const RequestView& V, double* p_rank) {
+    const Prepared& P = *V.P;
+    k_req_p<<<req_grid(P.nP), 256, 0, V.ctx->stream>>>(P.nP, P.nI, P.rank_pair.get(), P.pair_di.get(), V.stats, p_rank);
+    FY_KERNEL_CHECK();
+}
+
+void rm2_launch_req_slab(hipStream_t st, const SlabArgs& SA, const char* who) {
+    if ((int64_t)SA.nJ * SA.nch > 0x7FFFFFFFll) FY_FAIL(FY_ERR_UNSUPPORTED, "%s: %d slab rows x %d chunks exceed the launch grid", who, SA.nJ, SA.nch);
+    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_req_slab), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    k_req_slab<<<(unsigned)((int64_t)SA.nJ * SA.nch), SLAB_THREADS, (size_t)SA.CH * sizeof(unsigned long long), st>>>(SA);
+    FY_KERNEL_CHECK();
+}
+
+namespace {
 
 struct ReqUser {
     int32_t slot, du, cluster, n_out, out_off;
@@ -262,10 +249,9 @@ fy_result* rm2_score_users(fy_rm2_job* J, const fy_rm2_request* rq) {
     EventTimer t_total(ctx), t_tables(ctx), t_cooc(ctx), t_score(ctx), t_topn(ctx);
     const size_t sp_total = t_total.begin();
     const size_t sp_tables = t_tables.begin();
-    RequestState& S = ensure_state(V);
+    RequestState& S = rm2_request_state(V);
     DevBuf<double> p_rank(ctx, (size_t)P.nP);
-    k_req_p<<<req_grid(P.nP), 256, 0, st>>>(P.nP, P.nI, P.rank_pair.get(), P.pair_di.get(), V.stats, p_rank.get());
-    FY_KERNEL_CHECK();
+    rm2_request_p(V, p_rank.get());
 
     // ---- the request: known users of this rank's share, once each, in the order of the unrestricted job (slot order)
     std::vector<std::pair<int32_t, int32_t>> known;      // (slot, dense user index)
@@ -333,7 +319,6 @@ fy_result* rm2_score_users(fy_rm2_job* J, const fy_rm2_request* rq) {
     const int64_t ws = prm.workspace_bytes > 0 ? prm.workspace_bytes : ctx->tune.workspace_default;
     const double share = ctx->tune.req_full_share;
     const double lambda = prm.lambda;
-    FY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_req_slab), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     std::vector<int32_t> full_users;       // positions in `users` of the users of full-pass clusters
     std::vector<int32_t> stamp;            // item index -> slab row of the batch being planned (-1: none)
     DevBuf<int32_t> overflow, any_overflow(ctx, 1);
@@ -389,12 +374,10 @@ fy_result* rm2_score_users(fy_rm2_job* J, const fy_rm2_request* rq) {
             h2d(ctx, d_plan.get(), h.data(), h.size());
             DevBuf<double> slab(ctx, (size_t)nJ * (size_t)ld);
             const size_t sp_c = t_cooc.begin();
-            if ((int64_t)nJ * nch > 0x7FFFFFFFll) FY_FAIL(FY_ERR_UNSUPPORTED, "fy_rm2_score_users: %d slab rows x %d chunks exceed the launch grid", nJ, nch);
             SlabArgs SA{d_plan.get(), nJ, Ic, CH, nch, pbase, S.stride, ld, P.rank_pair.get(), P.pair_start.get(), P.csc_slot.get(), P.csc_r.get(),
                         S.choff.get(), P.csr_idx.get(), P.csr_r.get(), V.usum_slot, V.b_rank, slab.get(),
                         V.general ? V.fx_rank : nullptr, V.general ? (double)V.fx_bounds[3 * (size_t)c + 2] : 0.0};
-            k_req_slab<<<(unsigned)((int64_t)nJ * nch), SLAB_THREADS, (size_t)CH * sizeof(unsigned long long), st>>>(SA);
-            FY_KERNEL_CHECK();
+            rm2_launch_req_slab(st, SA, "fy_rm2_score_users");
             t_cooc.end(sp_c);
             R->st.cooc_launches++;
             // ---- scoring + top-N in groups of users whose float rows fit 256 MB

@@ -308,6 +308,9 @@ class Recommendations(_Result):
         # fy_rm2_score_users only: what the request touched (None on the result of a full job)
         rq = _native.RM2RequestStats()
         self.request_stats = rq.as_dict() if L.fy_result_request_stats(handle, C.byref(rq)) == 0 else None
+        # fy_rm2_score_profiles only: fy_rm2_profile_stats (None on any other result)
+        ps = _native.RM2ProfileStats()
+        self.profile_stats = ps.as_dict() if L.fy_result_rm2_profile_stats(handle, C.byref(ps)) == 0 else None
 
     def rows(self):
         if self._rows is None:
@@ -458,6 +461,26 @@ def _itemcf_profiles(profiles, base, shift):
     q = _native.ItemCFProfiles(n, ptr(labels), start.ctypes.data if len(start) else None, ptr(item), ptr(score), ptr(remove),
                                _native.FY_PROFILE_ON_RESIDENT if base == "resident" else _native.FY_PROFILE_WHOLE)
     return q, (labels, start, item, score, remove)
+
+
+def _rm2_profiles(profiles, base, clusters, rank, world):
+    """``profiles`` of ``PreparedRM2.score_profiles`` (the two forms ``recommend_profiles`` takes) -> (fy_rm2_profiles, what must stay
+    alive while it is used).  ``clusters``: one cluster for all profiles or one per profile; required with base="whole"."""
+    q, keep = _itemcf_profiles(profiles, base, 0.0)
+    n = q.n_profiles
+    cl = None
+    if clusters is not None:
+        cl = np.asarray(clusters).reshape(-1)
+        if cl.size == 1 and n != 1:
+            cl = np.repeat(cl, n)
+        cl = _pair_ids(cl)
+        if len(cl) != n:
+            raise ValueError("clusters must hold one cluster, or one per profile")
+    elif base == "whole" and n > 0:
+        raise ValueError("base='whole' needs clusters=: the cluster every profile is scored in")
+    r = _native.RM2Profiles(n, q.user, q.start, q.item, q.score, q.remove, cl.ctypes.data if cl is not None and len(cl) else None, q.base,
+                            int(rank), int(world))
+    return r, (keep, cl)
 
 
 def _itemcf_pairs(pairs):
@@ -738,6 +761,25 @@ class PreparedRM2:
             _check(self._lib.fy_rm2_score_users(self._h, C.byref(rq), C.byref(res)))
         except FilmYouError as e:
             raise RuntimeError("%s failed!: %s" % (RM2Job.JOB_NAME, e.message)) from e
+        return Recommendations(res, self._ctx)
+
+    def score_profiles(self, profiles, base="whole", clusters=None, rank=0, world=1):
+        """fy_rm2_score_profiles: RM2 lists for item sets handed in -- an anonymous or new visitor's whole profile scored as one
+        more member of a cluster (base="whole", ``clusters`` = one cluster or one per profile), or a resident user's row with
+        pending writes applied (base="resident": the label is the user id, the cluster is that user's).  Only the SET of items
+        matters; a score that is not > 0 removes the item, like a delete.  ``profiles``: a sequence of (label, items, scores) or
+        (label, items, scores, remove) with the writes in order, or the CSR arrays (labels, start, item, score[, remove]).  The job
+        stays as prepared and valid.  (rank, world) cut the profile list.  Returns a ``Recommendations`` with ``profile_stats``."""
+        if profiles is None:
+            raise ValueError("score_profiles() needs the profiles to score")
+        q, keep = _rm2_profiles(profiles, base, clusters, rank, world)
+        res = C.c_void_p()
+        try:
+            self._ctx.sync_tuning()
+            _check(self._lib.fy_rm2_score_profiles(self._h, C.byref(q), C.byref(res)))
+        except FilmYouError as e:
+            raise RuntimeError("%s failed!: %s" % (RM2Job.JOB_NAME, e.message)) from e
+        del keep
         return Recommendations(res, self._ctx)
 
     def close(self):

@@ -395,6 +395,70 @@ class RM2Job {
         return 0;
     }
 
+    // RM2 for item sets handed in (fy_rm2_score_profiles): an anonymous or new visitor's whole profile scored as one more member of
+    // a cluster (resident = false: cluster[p] names it), or a resident user's row with pending writes applied (resident = true: the
+    // label is the user id, the cluster is that user's).  Profile p holds the entries start[p] .. start[p + 1], applied in order; the
+    // last entry per item counts; a non-zero remove, or a score that is not > 0, removes the item.  The job stays as prepared: one
+    // GPU, context, ratings, prepare, the call.  Rows reach the sink grouped by profile in the order given, the label in the user
+    // column.  profileStats holds the counters.
+    struct Profiles {
+        std::vector<int32_t> label, cluster;
+        std::vector<int64_t> start{0};
+        std::vector<int32_t> item;
+        std::vector<float> score;
+        std::vector<uint8_t> remove;
+        bool resident = false;
+        void begin(int32_t l, int32_t c = 0) { label.push_back(l); cluster.push_back(c); start.push_back(start.back()); }      // then put / del
+        void put(int32_t i, float s) { item.push_back(i); score.push_back(s); remove.push_back(0); start.back()++; }
+        void del(int32_t i) { item.push_back(i); score.push_back(0.0f); remove.push_back(1); start.back()++; }
+    };
+    fy_rm2_profile_stats profileStats{};
+    int scoreProfiles(const Ratings& r, const Clustering& c, const Profiles& profiles, const PreferenceSink& sink, int device = 0) {
+        if (profiles.start.size() != profiles.label.size() + 1 || profiles.cluster.size() != profiles.label.size() ||
+            profiles.item.size() != profiles.score.size() || profiles.item.size() != profiles.remove.size() ||
+            (size_t)profiles.start.back() != profiles.item.size())
+            throw std::invalid_argument("scoreProfiles: the arrays of the profiles differ in length");
+        fy_rm2_params p = params();
+        fy_context* ctx = nullptr;
+        fy_ratings* rt = nullptr;
+        fy_rm2_job* job = nullptr;
+        fy_result* res = nullptr;
+        auto fail = [&](const char* what) {
+            const std::string msg = std::string("RM2 failed!: ") + what + ": " + fy_last_error();
+            if (job) fy_rm2_job_destroy(job);
+            if (rt) fy_ratings_destroy(rt);
+            if (ctx) fy_context_destroy(ctx);
+            throw std::runtime_error(msg);
+        };
+        std::vector<int32_t> cc = counts(c, p.number_of_clusters);
+        if (fy_context_create(device, &ctx) != FY_OK) fail("context");
+        if (fy_ratings_create(ctx, (int64_t)r.user.size(), r.user.data(), r.item.data(), r.score.data(), FY_HOST, &rt) != FY_OK) fail("ratings");
+        if (fy_rm2_prepare(ctx, &p, rt, (int64_t)c.user.size(), c.user.data(), c.cluster.data(), cc.empty() ? nullptr : cc.data(), &job) != FY_OK) fail("prepare");
+        fy_rm2_profiles q{};
+        q.n_profiles = (int64_t)profiles.label.size();
+        q.user = profiles.label.empty() ? nullptr : profiles.label.data();
+        q.start = profiles.start.data();
+        q.item = profiles.item.empty() ? nullptr : profiles.item.data();
+        q.score = profiles.item.empty() ? nullptr : profiles.score.data();
+        q.remove = profiles.item.empty() ? nullptr : profiles.remove.data();
+        q.cluster = profiles.cluster.empty() ? nullptr : profiles.cluster.data();
+        q.base = profiles.resident ? FY_PROFILE_ON_RESIDENT : FY_PROFILE_WHOLE;
+        q.rank = 0;
+        q.world = 1;
+        if (fy_rm2_score_profiles(job, &q, &res) != FY_OK) fail("score_profiles");
+        const int64_t n = fy_result_size(res);
+        const int32_t *u = fy_result_key0(res), *i = fy_result_key1(res), *cl = fy_result_aux(res);
+        const float* s = fy_result_value(res);
+        for (int64_t k = 0; k < n; k++) sink(u[k], i[k], s[k], cl[k]);
+        fy_result_stats(res, &stats);
+        fy_result_rm2_profile_stats(res, &profileStats);
+        fy_result_free(res);
+        fy_rm2_job_destroy(job);
+        fy_ratings_destroy(rt);
+        fy_context_destroy(ctx);
+        return 0;
+    }
+
     // RM2Job.run on the reference's own files (M/rm/RM2Job.java:76-100 with useCassandraInput / Output = false): ratings from
     // <mapred.input.dir>, <directory>/<clustering>, <directory>/<clusteringCount>; writes <directory>/rm2/userSum,
     // <directory>/rm2/itemColl (MapFile) and the recommendations under <mapred.output.dir>.  Files: fy_seqfile_* (layout

@@ -248,10 +248,28 @@ int main(int argc, char** argv) {
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
     if (argc == 7 && strcmp(argv[1], "--estimate-pairs") == 0) return main_estimate_pairs(argv + 2);
     if (argc == 8 && strcmp(argv[1], "--because") == 0) return main_because(argv + 2);
+    // rm2_main --score-profiles <profiles.txt> --profile-base whole|resident [--profile-cluster C] <ratings.txt> ... : RM2Job::scoreProfiles.
+    //   <profiles.txt> in the format of --recommend-profiles: "label item score" per line, consecutive lines with one label form one
+    //   profile, "label item x" deletes the item.  whole: every profile is scored in cluster C (default 0) as one more member of it;
+    //   resident: the entries go on top of the prepared row of user <label>.  One `profiles ...` line of counters on stderr.
+    const char* profiles_file = nullptr;
+    const char* profile_base = nullptr;
+    int profile_cluster = 0;
+    if (argc >= 11 && strcmp(argv[1], "--score-profiles") == 0 && strcmp(argv[3], "--profile-base") == 0) {
+        profiles_file = argv[2];
+        profile_base = argv[4];
+        argv += 4; argc -= 4;
+        if (argc == 9 && strcmp(argv[1], "--profile-cluster") == 0) { profile_cluster = atoi(argv[2]); argv += 2; argc -= 2; }
+        if (argc != 7 || (strcmp(profile_base, "whole") != 0 && strcmp(profile_base, "resident") != 0)) {
+            fprintf(stderr, "usage: --score-profiles FILE --profile-base whole|resident [--profile-cluster C] ratings clustering lambda numberOfItems "
+                            "numberOfClusters numberOfRecommendations\n");
+            return 2;
+        }
+    }
     bool rccl = false;
     // rm2_main --users <users.txt> <ratings.txt> ... : RM2Job::runUsers, lists for the ids of the usersFile alone
     const char* users_file = nullptr;
-    if (argc == 9 && strcmp(argv[1], "--users") == 0) { users_file = argv[2]; argv += 2; argc -= 2; }
+    if (argc == 9 && !profiles_file && strcmp(argv[1], "--users") == 0) { users_file = argv[2]; argv += 2; argc -= 2; }
     if (argc == 8 && strcmp(argv[1], "--rccl") == 0) { rccl = true; argv++; argc--; }
     // rm2_main --writes <writes.txt> <ratings.txt> ... : fy::host::applyWrites first ("user item score remove" per line, in order), the job on the result
     const char* writes_file = nullptr;
@@ -300,7 +318,30 @@ int main(int argc, char** argv) {
         if (users_file) conf.set("usersFile", users_file);      // (the job copies its configuration)
         fy::host::RM2Job job(conf);
         auto sink = [](int32_t user, int32_t item, float score, int32_t cluster) { printf("%d %d %.9g %d\n", user, item, score, cluster); };
-        if (users_file) {
+        if (profiles_file) {
+            fy::host::RM2Job::Profiles profiles;
+            profiles.resident = strcmp(profile_base, "resident") == 0;
+            f = fopen(profiles_file, "r");
+            if (!f) { perror(profiles_file); return 2; }
+            char word[64];
+            bool any = false;
+            int last = 0;
+            while (fscanf(f, "%d %d %63s", &u, &i, word) == 3) {
+                if (!any || u != last) profiles.begin(u, profile_cluster);
+                any = true;
+                last = u;
+                if (strcmp(word, "x") == 0) profiles.del(i); else profiles.put(i, strtof(word, nullptr));
+            }
+            fclose(f);
+            job.scoreProfiles(r, c, profiles, sink);
+            const fy_rm2_profile_stats& q = job.profileStats;
+            fprintf(stderr, "profiles asked %lld scored %lld empty %lld users_unknown %lld users_filtered %lld entries %lld unknown_item %lld nonpositive %lld "
+                    "superseded %lld removes_hit %lld removes_missed %lld items_composed %lld clusters_touched %lld slab_rows %lld\n",
+                    (long long)q.profiles_asked, (long long)q.profiles_scored, (long long)q.profiles_empty, (long long)q.users_unknown,
+                    (long long)q.users_filtered, (long long)q.entries, (long long)q.entries_unknown_item, (long long)q.entries_nonpositive,
+                    (long long)q.entries_superseded, (long long)q.removes_hit, (long long)q.removes_missed, (long long)q.items_composed,
+                    (long long)q.clusters_touched, (long long)q.slab_rows);
+        } else if (users_file) {
             job.runUsers(r, c, {}, sink);
             fprintf(stderr, "request users_known %lld clusters_touched %lld slab_rows %lld full_pass_clusters %lld\n", (long long)job.requestStats.users_known,
                     (long long)job.requestStats.clusters_touched, (long long)job.requestStats.slab_rows, (long long)job.requestStats.full_pass_clusters);

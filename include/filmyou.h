@@ -1017,6 +1017,81 @@ int fy_itemcf_recommend_profiles(fy_itemsim_job*, const fy_itemcf_params*, const
                                  const fy_itemcf_filter* items_only /* may be NULL; has_users must be 0 */, fy_result** out);
 int fy_result_itemcf_profile_stats(fy_result*, fy_itemcf_profile_stats* out);   /* FY_ERR_STATE on any other result */
 
+/* ------------------------------------------------------------------ RM2 on request: lists for given profiles and pending writes
+ * fy_rm2_score_profiles (csrc/fy_rm2_profiles.hip) scores item sets the CALLER hands in on a prepared RM2 job
+ * whose global statistics are in place (as fy_rm2_score_users): an anonymous or brand-new visitor's whole profile, or a resident
+ * user's row with pending writes applied.  Nothing of the job follows the writes: s_v, p(i|C), b, G, the clustering and U_c stay as
+ * prepared.  The call may be made any number of times, before or after fy_rm2_score / fy_rm2_score_users, and leaves the job as it
+ * was.  A user's own rating VALUES never enter that user's scores, only the SET of rated items does, so a pending write changes
+ * which rows G[j][.] are summed, which columns are masked, and the user's own subtracted term.
+ * The profiles are HOST arrays in CSR form, exactly like fy_itemcf_profiles (user = label, start, item, score, remove, base), plus
+ *   cluster      n_profiles: the cluster a FY_PROFILE_WHOLE profile is scored in; ignored with FY_PROFILE_ON_RESIDENT (may be NULL)
+ *   rank, world  cut the PROFILE LIST into contiguous ranges [n rank / world, n (rank + 1) / world)
+ * Composition, per profile:
+ *   1. The entries are applied in the order given and the LAST entry per item counts, whether it is a write or a delete
+ *      (remove[e] != 0; its score is ignored).
+ *   2. An entry whose item has no column in the profile's cluster -- nobody of that cluster rated it in the prepared ratings, the
+ *      job does not know the id, or the id is negative -- is dropped and counted (entries_unknown_item) before rule 1 sees it.
+ *   3. A last entry whose score is not > 0 (zero, negative, NaN) is not a kept rating: the `score > 0` filter of the prep.  It
+ *      removes the item, like a delete, and is counted (entries_nonpositive).
+ *   4. FY_PROFILE_ON_RESIDENT: the entries go on top of the job's own row of user[p], and the cluster is that user's.  A user the
+ *      job does not know, or one that is not in this job's share, gets no list (users_unknown); a user with id < filterUsers gets
+ *      no list (users_filtered).  The entries of such a profile are counted in `entries` and not looked at any further.
+ *   5. FY_PROFILE_WHOLE: the starting row is empty, the cluster is cluster[p], filterUsers is not applied.
+ *   6. The composed profile is ordered as a resident row is: ascending cluster-local column (rank order).
+ * An empty composed profile gets no list (profiles_empty); so does a profile with no candidate left (n' >= I_c).
+ * Scoring (Jelinek-Mercer), for every candidate i of I_c outside the profile, n' = |profile|:
+ *   ON_RESIDENT  score = (n' - 1) ln M - n' ln U_c + sum_{j in profile} ln sum_{v in c, v != u} c_vi c_vj; with x_u. the PREPARED
+ *                row of u (0 where it holds nothing) the inner sum is (1-l)^2 (G[j][i] - x_uj x_ui) + q_j (b_i - x_ui) + a_i e_uj,
+ *                e_uj = (1-l)(b_j - x_uj) + l (U_c - 1) p_j, q_j = l (1-l) p_j, a_i = l p_i, every difference clamped at 0.  Where u
+ *                is the ONLY rater of i or of j in the cluster, G - x_uj x_ui and the matching b - x are exactly 0 (ln 0 = -inf at
+ *                lambda = 0, as the full job gives).
+ *   WHOLE        the profile is the (U_c + 1)-th member of its cluster: all U_c residents are neighbours, there is no own term:
+ *                (n' - 1) ln M - n' ln(U_c + 1) + sum_j ln[(1-l)^2 G[j][i] + q_j b_i + a_i ((1-l) b_j + l U_c p_j)].
+ * List length min(numberOfRecommendations, I_c - n'), the (float) cast, ties by ascending item id; the top-N kernels and the list
+ * length limit of fy_rm2_score_users apply.
+ * Result: the ordinary list kind (fy_eval_lists takes it).  Rows are grouped by profile IN THE ORDER GIVEN, best first; the user
+ * column holds the label, which may repeat; the cluster column holds the cluster scored in.
+ * Bit-level promises: an ON_RESIDENT profile whose composed item set equals the resident row gets that user's rows of
+ * fy_rm2_score_users BIT FOR BIT; a profile's rows do not depend on the other profiles of the call, their order, workspace_bytes,
+ * FY_REQ_CHUNK or (rank, world).
+ * Failures, leaving the job usable.  FY_ERR_INVALID_ARGUMENT: NULL user / start with profiles, NULL item / score with entries,
+ * start[0] != 0 or start decreasing, base outside the enum, n_profiles < 0, rank / world out of range, WHOLE with cluster == NULL
+ * or a cluster[p] outside [0, numberOfClusters) or naming an empty cluster.  FY_ERR_UNSUPPORTED: a job with FY_RM2_ESTIMATOR_RM1; a
+ * job with Dirichlet-prior or absolute-discounting smoothing (deliberately out of scope: the own-term algebra above is the
+ * Jelinek-Mercer one); a job with collectives installed or prepared with world != 1; more than 2^31 - 1 profiles, entries or
+ * elements to compose.  These are found on the host before any launch.  FY_ERR_OUT_OF_MEMORY: one profile whose own slab rows
+ * exceed workspace_bytes (found when the batches are planned, before any slab is built; the message names the profile's position
+ * and label).  Zero profiles, or a job over no ratings, gives an empty result.
+ * fy_result_stats as for fy_rm2_score_users (users_scored = profiles_scored; ms_tables includes the ingest).  Counters (all but
+ * profiles_asked over this rank's range):
+ *   profiles_asked / _mine / _scored / _empty   asked; of this rank's range; that received a list; that composed to nothing
+ *   users_unknown, users_filtered               rule 4
+ *   entries                                     entries of the profiles
+ *   entries_unknown_item, entries_nonpositive   rules 2 and 3
+ *   entries_superseded                          entries with a column that are not the last of their (profile, item)
+ *   removes_hit / removes_missed                last entries that are deletes of an item the resident row holds / does not hold
+ *   items_composed                              items of all composed profiles
+ *   clusters_touched .. slab_pair_contribs      as in fy_rm2_request_stats, over the profiles that received a list */
+typedef struct {
+    int64_t n_profiles;
+    const int32_t* user;     /* n_profiles: the label of the result's user column; with ON_RESIDENT also the resident user id */
+    const int64_t* start;    /* n_profiles + 1 offsets into item / score / remove, non-decreasing from 0 */
+    const int32_t* item;     /* raw item ids */
+    const float*   score;    /* only score > 0 matters: the values never enter the scores */
+    const uint8_t* remove;   /* NULL: no deletes; else non-zero = delete this item from the profile */
+    const int32_t* cluster;  /* n_profiles with FY_PROFILE_WHOLE; ignored (may be NULL) with FY_PROFILE_ON_RESIDENT */
+    int32_t base;            /* FY_PROFILE_WHOLE / FY_PROFILE_ON_RESIDENT */
+    int32_t rank, world;     /* the range of the profile list this call serves; 0, 1 = all of it */
+} fy_rm2_profiles;           /* host arrays; they may be freed when the call returns */
+typedef struct {
+    int64_t profiles_asked, profiles_mine, profiles_scored, profiles_empty, users_unknown, users_filtered;
+    int64_t entries, entries_unknown_item, entries_nonpositive, entries_superseded, removes_hit, removes_missed, items_composed;
+    int64_t clusters_touched, batches, slab_rows, slab_bytes_peak, slab_pair_contribs;
+} fy_rm2_profile_stats;
+int fy_rm2_score_profiles(fy_rm2_job*, const fy_rm2_profiles*, fy_result** out);
+int fy_result_rm2_profile_stats(fy_result*, fy_rm2_profile_stats* out);   /* FY_ERR_STATE on any other result */
+
 #ifdef __cplusplus
 }
 #endif
