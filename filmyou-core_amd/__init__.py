@@ -17,11 +17,13 @@ from .host import (BaselineRecommenderJob, ClusterAssignmentJob, Configuration, 
                    SIMILARITY_CITY_BLOCK, SIMILARITY_EUCLIDEAN_DISTANCE, SIMILARITY_PEARSON_CORRELATION, ClusterRefinementJob, RMRecommenderDriver,
                    SubClusterMappingJob, SubClusterMappings, read_id_file, write_similarity_pairs, Evaluation, Evaluator, EstimateErrors, PreferenceEstimates, PreferenceExplanations,
                    FY_ESTIMATE_OK, FY_ESTIMATE_UNKNOWN_USER, FY_ESTIMATE_UNKNOWN_ITEM, FY_ESTIMATE_OWN_PREFERENCE, FY_ESTIMATE_TOO_FEW,
-                   FY_ESTIMATE_ZERO_NUMERATOR, FY_ESTIMATE_NOT_A_NUMBER)
+                   FY_ESTIMATE_ZERO_NUMERATOR, FY_ESTIMATE_NOT_A_NUMBER, FoldIn, FoldInAssignment)
+from ._native import FY_FOLDIN_OK, FY_FOLDIN_EMPTY, FY_FOLDIN_NO_CLUSTER, FY_FOLDIN_EMPTY_IN_PARENT
 
 __all__ = ["build", "BaselineRecommenderJob", "ClusterAssignmentJob", "ItemRecommendations", "NMFDriver", "LIB_PATH", "Configuration", "Context", "FilmYouError", "ItemSimilarities", "PreparedItemSimilarity", "PreparedRM2", "Ratings",
            "Recommendations", "RM2Job", "RowSimilarityJob", "SIMILARITY_COSINE", "SIMILARITY_COOCCURRENCE", "SIMILARITY_TANIMOTO_COEFFICIENT",
            "SIMILARITY_LOGLIKELIHOOD", "SIMILARITY_CITY_BLOCK", "SIMILARITY_EUCLIDEAN_DISTANCE", "SIMILARITY_PEARSON_CORRELATION", "_native",
            "ClusterRefinementJob", "RMRecommenderDriver", "SubClusterMappingJob", "SubClusterMappings", "read_id_file",
            "write_similarity_pairs", "Evaluation", "Evaluator", "EstimateErrors", "PreferenceEstimates", "PreferenceExplanations", "FY_ESTIMATE_OK", "FY_ESTIMATE_UNKNOWN_USER",
-           "FY_ESTIMATE_UNKNOWN_ITEM", "FY_ESTIMATE_OWN_PREFERENCE", "FY_ESTIMATE_TOO_FEW", "FY_ESTIMATE_ZERO_NUMERATOR", "FY_ESTIMATE_NOT_A_NUMBER"]
+           "FY_ESTIMATE_UNKNOWN_ITEM", "FY_ESTIMATE_OWN_PREFERENCE", "FY_ESTIMATE_TOO_FEW", "FY_ESTIMATE_ZERO_NUMERATOR", "FY_ESTIMATE_NOT_A_NUMBER",
+           "FoldIn", "FoldInAssignment", "FY_FOLDIN_OK", "FY_FOLDIN_EMPTY", "FY_FOLDIN_NO_CLUSTER", "FY_FOLDIN_EMPTY_IN_PARENT"]

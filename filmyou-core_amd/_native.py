@@ -12,8 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfilmyou_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "filmyou.h")
-SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm2_profiles.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_pairs.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
-HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm2_profiles.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_profiles.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
+SOURCES = ["fy_api.hip", "fy_prep.hip", "fy_rm2.hip", "fy_rm2_request.hip", "fy_rm2_profiles.hip", "fy_rm1.hip", "fy_ratings_update.hip", "fy_itemsim.hip", "fy_itemsim_request.hip", "fy_itemcf.hip", "fy_itemcf_request.hip", "fy_itemcf_profiles.hip", "fy_itemcf_pairs.hip", "fy_itemcf_estimate.hip", "fy_itemcf_because.hip", "fy_eval.hip", "fy_cluster.hip", "fy_nmf.hip", "fy_foldin.hip", "fy_refine.hip", "fy_rccl.hip", "fy_seqfile.cpp"]
+HEADERS = ["fy_common.hpp", "fy_tuning.hpp", "fy_rm2_plan.hpp", "fy_rm2_tables.hpp", "fy_partition.hpp", "fy_prep.hpp", "fy_cooc.hpp", "fy_cooc_tables.hpp", "fy_rm2.hpp", "fy_rm2_kernels.hpp", "fy_rm2_launch.hpp", "fy_rm2_coop.hpp", "fy_rm2_request.hpp", "fy_rm2_profiles.hpp", "fy_rm1.hpp", "fy_ratings_update.hpp", "fy_refine.hpp", "fy_nmf_kernels.hpp", "fy_foldin.hpp", "fy_itemsim_plan.hpp", "fy_itemsim_kernels.hpp", "fy_itemsim_request.hpp", "fy_itemcf_request.hpp", "fy_itemcf_profiles.hpp", "fy_itemcf_pairs.hpp", "fy_eval.hpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-ldl"]
 
@@ -37,6 +37,9 @@ SYMBOLS = [
     "fy_itemcf_because_prepared", "fy_result_because_view", "fy_result_itemcf_because_stats",
     "fy_itemcf_recommend_profiles", "fy_result_itemcf_profile_stats",
     "fy_rm2_score_profiles", "fy_result_rm2_profile_stats",
+    "fy_foldin_create", "fy_foldin_add_level", "fy_foldin_assign", "fy_foldin_result_n", "fy_foldin_result_assignment",
+    "fy_foldin_result_factors", "fy_foldin_result_sub_size", "fy_foldin_result_sub_factors", "fy_foldin_result_stats",
+    "fy_foldin_result_free", "fy_foldin_destroy",
 ]
 
 
@@ -226,6 +229,26 @@ class RM2ProfileStats(C.Structure):
                 ("entries_nonpositive", C.c_int64), ("entries_superseded", C.c_int64), ("removes_hit", C.c_int64),
                 ("removes_missed", C.c_int64), ("items_composed", C.c_int64), ("clusters_touched", C.c_int64), ("batches", C.c_int64),
                 ("slab_rows", C.c_int64), ("slab_bytes_peak", C.c_int64), ("slab_pair_contribs", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+FY_FOLDIN_OK, FY_FOLDIN_EMPTY, FY_FOLDIN_NO_CLUSTER, FY_FOLDIN_EMPTY_IN_PARENT = 0, 1, 2, 3
+
+
+class FoldInParams(C.Structure):
+    _fields_ = [("number_of_items", C.c_int32), ("number_of_clusters", C.c_int32), ("ppc", C.c_int32),
+                ("normalization_frequency", C.c_int32)]
+
+
+class FoldInStats(C.Structure):
+    _fields_ = [("profiles_asked", C.c_int64), ("profiles_mine", C.c_int64), ("profiles_assigned", C.c_int64), ("profiles_empty", C.c_int64),
+                ("profiles_no_cluster", C.c_int64), ("profiles_empty_in_parent", C.c_int64), ("entries", C.c_int64),
+                ("entries_out_of_range", C.c_int64), ("entries_superseded", C.c_int64), ("entries_removed", C.c_int64),
+                ("entries_nonpositive", C.c_int64), ("items_composed", C.c_int64), ("items_in_parent", C.c_int64), ("collisions", C.c_int64),
+                ("launches", C.c_int64), ("ms_ingest", C.c_double), ("ms_level1", C.c_double), ("ms_level2", C.c_double),
+                ("ms_total", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -447,5 +470,19 @@ def load():
     L.fy_result_itemcf_profile_stats.argtypes = [vp, C.POINTER(ItemCFProfileStats)]
     L.fy_rm2_score_profiles.argtypes = [vp, C.POINTER(RM2Profiles), pvp]
     L.fy_result_rm2_profile_stats.argtypes = [vp, C.POINTER(RM2ProfileStats)]
+    L.fy_foldin_create.argtypes = [vp, C.POINTER(FoldInParams), vp, C.c_int, vp, i64, pvp]
+    L.fy_foldin_add_level.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i64]
+    L.fy_foldin_assign.argtypes = [vp, C.POINTER(ItemCFProfiles), i32, i32, vp, i32, i32, pvp]
+    for name in ("fy_foldin_result_n", "fy_foldin_result_sub_size"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = i64
+    L.fy_foldin_result_assignment.argtypes = [vp, vp, vp, vp, vp]
+    L.fy_foldin_result_factors.argtypes = [vp, vp]
+    L.fy_foldin_result_sub_factors.argtypes = [vp, vp, vp]
+    L.fy_foldin_result_stats.argtypes = [vp, C.POINTER(FoldInStats)]
+    L.fy_foldin_result_free.argtypes = [vp]
+    L.fy_foldin_result_free.restype = None
+    L.fy_foldin_destroy.argtypes = [vp]
+    L.fy_foldin_destroy.restype = None
     _lib = L
     return L

@@ -15,6 +15,7 @@
 #include "fy_itemcf_request.hpp"
 #include "fy_itemcf_profiles.hpp"
 #include "fy_eval.hpp"
+#include "fy_foldin.hpp"
 
 namespace fy {
 static thread_local char g_err[512] = "";
@@ -773,6 +774,85 @@ void fy_result_free(fy_result* r) {
     if (ctx) (void)hipSetDevice(ctx->device);
     delete r;
     if (ctx) (void)hipStreamSynchronize(ctx->stream);
+}
+
+// ---- fold-in (fy_foldin.hip)
+int fy_foldin_create(fy_context* c, const fy_foldin_params* p, const double* W, int location, const int32_t* count, int64_t n_count, fy_foldin** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!p) { set_error("params is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (p->number_of_items <= 0 || p->number_of_clusters <= 0) { set_error("numberOfItems / numberOfClusters must be > 0"); return FY_ERR_INVALID_ARGUMENT; }
+    if (p->number_of_clusters > 256) { set_error("numberOfClusters %d exceeds the kernel limit 256", p->number_of_clusters); return FY_ERR_UNSUPPORTED; }
+    if (!W) { set_error("W is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    if (location != FY_HOST && location != FY_DEVICE) { set_error("location must be FY_HOST or FY_DEVICE"); return FY_ERR_INVALID_ARGUMENT; }
+    if (n_count < 0 || (n_count > 0 && !count)) { set_error("count is NULL with n_count > 0, or n_count < 0"); return FY_ERR_INVALID_ARGUMENT; }
+    if (!c) { set_error("context is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    FY_HIP(hipSetDevice(c->c.device));
+    *out = fy::foldin_create(&c->c, p, W, location, count, n_count);
+    FY_CATCH
+}
+int fy_foldin_add_level(fy_foldin* f, int32_t n_parents, const int32_t* items_in_cluster, const int32_t* sub_clusters, const int32_t* item_raw,
+                        const double* W_ragged, int32_t stride, const int32_t* count, int64_t n_count) {
+    if (!f) { set_error("the fold-in model is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(f->ctx);
+    fy::foldin_add_level(f, n_parents, items_in_cluster, sub_clusters, item_raw, W_ragged, stride, count, n_count);
+    FY_CATCH
+}
+int fy_foldin_assign(fy_foldin* f, const fy_itemcf_profiles* profiles, int32_t iterations, int32_t first_iteration, const double* h0, int32_t rank,
+                     int32_t world, fy_foldin_result** out) {
+    if (!out) { set_error("out is NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!f || !profiles) { set_error("the fold-in model or the profiles are NULL"); return FY_ERR_INVALID_ARGUMENT; }
+    FY_TRY
+    select_device(f->ctx);
+    *out = fy::foldin_assign(f, profiles, iterations, first_iteration, h0, rank, world);
+    FY_CATCH
+}
+int64_t fy_foldin_result_n(const fy_foldin_result* r) { return r ? (int64_t)r->label.size() : 0; }
+int64_t fy_foldin_result_sub_size(const fy_foldin_result* r) { return r ? r->sub_off.back() : 0; }
+int fy_foldin_result_assignment(const fy_foldin_result* r, int32_t* label, int32_t* cluster, int32_t* parent, int32_t* status) {
+    if (!r || (!r->label.empty() && (!label || !cluster || !parent || !status))) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    const size_t b = r->label.size() * sizeof(int32_t);
+    if (b) { memcpy(label, r->label.data(), b); memcpy(cluster, r->cluster.data(), b); memcpy(parent, r->parent.data(), b); memcpy(status, r->status.data(), b); }
+    return FY_OK;
+}
+int fy_foldin_result_factors(fy_foldin_result* r, double* H) {
+    if (!r || (!r->label.empty() && !H)) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    if (r->label.empty()) return FY_OK;
+    FY_TRY
+    select_device(r->ctx);
+    fy::d2h(r->ctx, H, r->H.get(), r->label.size() * (size_t)r->k);
+    fy::sync(r->ctx);
+    FY_CATCH
+}
+int fy_foldin_result_sub_factors(fy_foldin_result* r, int64_t* offset, double* H) {
+    if (!r || !offset || (r->sub_off.back() > 0 && !H)) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    memcpy(offset, r->sub_off.data(), r->sub_off.size() * sizeof(int64_t));
+    if (r->sub_off.back() == 0) return FY_OK;
+    FY_TRY
+    select_device(r->ctx);
+    fy::d2h(r->ctx, H, r->H1.get(), (size_t)r->sub_off.back());
+    fy::sync(r->ctx);
+    FY_CATCH
+}
+int fy_foldin_result_stats(const fy_foldin_result* r, fy_foldin_stats* out) {
+    if (!r || !out) { set_error("NULL argument"); return FY_ERR_INVALID_ARGUMENT; }
+    *out = r->stats;
+    return FY_OK;
+}
+void fy_foldin_result_free(fy_foldin_result* r) {
+    if (!r) return;
+    fy::Context* ctx = r->ctx;
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+    delete r;
+}
+void fy_foldin_destroy(fy_foldin* f) {
+    if (!f) return;
+    fy::Context* ctx = f->ctx;
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+    delete f;
 }
 
 }  // extern "C"

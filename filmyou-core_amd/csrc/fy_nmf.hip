@@ -14,13 +14,21 @@
 #include <vector>
 
 #include "fy_common.hpp"
+#include "fy_nmf_kernels.hpp"      // NMF_MAX_K, NMF_GRAM_BLOCKS, NMF_CHUNK, nmf_update_row: shared with fy_foldin.hip
 #include "fy_prep.hpp"
 #include "fy_rm2.hpp"
 
 namespace fy {
 
+// The limits this file's kernels and the tests' edge inputs are built around.  The fold-in shares them through fy_nmf_kernels.hpp:
+// the two statements of each value are held together here.
+namespace nmf_limits {
 constexpr int NMF_MAX_K = 256;
 constexpr int NMF_GRAM_BLOCKS = 256;
+constexpr int NMF_CHUNK = 512;
+}  // namespace nmf_limits
+static_assert(nmf_limits::NMF_MAX_K == NMF_MAX_K && nmf_limits::NMF_GRAM_BLOCKS == NMF_GRAM_BLOCKS && nmf_limits::NMF_CHUNK == NMF_CHUNK,
+              "fy_nmf_kernels.hpp and fy_nmf.hip disagree on a limit");
 
 // keys (row << 32 | col) of the kept ratings (score > 0, VectorByItemHDFSMapper.java:37-40); dropped ones sort to the end
 __global__ void k_nmf_keys(int64_t n, const int32_t* __restrict__ user, const int32_t* __restrict__ item, const float* __restrict__ score,
@@ -67,7 +75,6 @@ __global__ void k_nmf_check_rows(int32_t n_rows, const int32_t* __restrict__ row
 // NMF_CHUNK entries (the most popular item of ML-25M shape has ~10^5 raters: one wave walking it alone took 50 ms), one
 // wave per chunk writes a partial k-vector (lanes over the k columns, four entries in flight), then the row's partials are
 // added in chunk order.
-constexpr int NMF_CHUNK = 512;
 __global__ void k_nmf_chunk_counts(int32_t n_rows, const int32_t* __restrict__ rowptr, int32_t* __restrict__ cnt) {
     for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= n_rows; r += gridDim.x * blockDim.x)
         cnt[r] = r < n_rows ? (rowptr[r + 1] - rowptr[r] + NMF_CHUNK - 1) / NMF_CHUNK : 0;
@@ -144,13 +151,17 @@ __global__ void k_nmf_gram_sum(int32_t k, int32_t n_part, const double* __restri
     }
 }
 
-__device__ __forceinline__ double fy_clampinf(double v) { return isinf(v) ? (v > 0 ? DBL_MAX : -DBL_MAX) : v; }
+void nmf_gram(Context* ctx, int32_t n_rows, int32_t k, const double* M, double* part, double* C) {
+    k_nmf_gram_partial<<<NMF_GRAM_BLOCKS, 256, 0, ctx->stream>>>(n_rows, k, M, part);
+    FY_KERNEL_CHECK();
+    k_nmf_gram_sum<<<grid_for((int64_t)k * k), 256, 0, ctx->stream>>>(k, NMF_GRAM_BLOCKS, part, C);
+    FY_KERNEL_CHECK();
+}
 
 // out[r][c] = m_c * x_c / (y_c + eps),  y = C m.   mode 0: HComputationReducer; 1: PPCHComputationReducer (+ optional L1
-// normalisation); 2: WComputationMapper (infinities clamped)
+// normalisation); 2: WComputationMapper (infinities clamped).  The row body is nmf_update_row (fy_nmf_kernels.hpp).
 __global__ void k_nmf_update(int32_t n_rows, int32_t k, const double* __restrict__ M, const double* __restrict__ X,
                              const double* __restrict__ C_, int mode, int normalize, double* __restrict__ out) {
-    const double eps = 1e-12;   // MatrixComputationJob.java:41
     const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
     // the k x k matrix in LDS (k <= 64: 32 KiB), padded rows against bank conflicts; larger k reads it through L2
     __shared__ double shC[64 * 65];
@@ -162,46 +173,17 @@ __global__ void k_nmf_update(int32_t n_rows, int32_t k, const double* __restrict
     const double* __restrict__ C = in_lds ? shC : C_;
     const int ldc = in_lds ? 65 : k;
     for (int32_t r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n_rows; r += gridDim.x * wpb) {
-        const double* __restrict__ m = M + (int64_t)r * k;
-        double y[NMF_MAX_K / 64], x[NMF_MAX_K / 64], mv[NMF_MAX_K / 64];
-        double d = 0.0, e = 0.0;
+        double x[NMF_MAX_K / 64], res[NMF_MAX_K / 64];
 #pragma unroll
         for (int q = 0; q < NMF_MAX_K / 64; q++) {
             const int c = lane + 64 * q;
-            y[q] = 0.0; x[q] = 0.0; mv[q] = 0.0;
-            if (c < k) {
-                double s = 0.0;
-                for (int a = 0; a < k; a++) s += C[(int64_t)c * ldc + a] * m[a];
-                y[q] = s;
-                x[q] = X[(int64_t)r * k + c];
-                mv[q] = m[c];
-                d += mv[q] * y[q];
-                e += mv[q] * x[q];
-            }
+            x[q] = c < k ? X[(int64_t)r * k + c] : 0.0;
         }
-        if (mode == 1) {
-            for (int o = 32; o > 0; o >>= 1) { d += __shfl_xor(d, o, 64); e += __shfl_xor(e, o, 64); }
-        }
-        double res[NMF_MAX_K / 64], l1 = 0.0;
+        nmf_update_row(k, lane, M + (int64_t)r * k, x, C, ldc, mode, normalize, res);
 #pragma unroll
         for (int q = 0; q < NMF_MAX_K / 64; q++) {
             const int c = lane + 64 * q;
-            res[q] = 0.0;
-            if (c < k) {
-                double xx = x[q], yy = y[q];
-                if (mode == 1) { xx = fy_clampinf(xx + d); yy = fy_clampinf(yy + e); }
-                else if (mode == 2) { xx = fy_clampinf(xx); yy = fy_clampinf(yy); }
-                res[q] = mv[q] * (xx / (yy + eps));
-                l1 += fabs(res[q]);
-            }
-        }
-        if (normalize) {
-            for (int o = 32; o > 0; o >>= 1) l1 += __shfl_xor(l1, o, 64);
-        }
-#pragma unroll
-        for (int q = 0; q < NMF_MAX_K / 64; q++) {
-            const int c = lane + 64 * q;
-            if (c < k) out[(int64_t)r * k + c] = normalize ? res[q] / l1 : res[q];
+            if (c < k) out[(int64_t)r * k + c] = res[q];
         }
     }
 }
@@ -287,10 +269,7 @@ void nmf_factorize(Context* ctx, const fy_nmf_params* prm, const fy_ratings* R, 
         FY_KERNEL_CHECK();
         k_nmf_spmm_reduce<<<grid_for((int64_t)nU * k), 256, 0, s>>>(nU, k, cu.ptr.get(), spart.get(), XH.get());
         FY_KERNEL_CHECK();
-        k_nmf_gram_partial<<<NMF_GRAM_BLOCKS, 256, 0, s>>>(nI, k, w, part.get());
-        FY_KERNEL_CHECK();
-        k_nmf_gram_sum<<<grid_for((int64_t)k * k), 256, 0, s>>>(k, NMF_GRAM_BLOCKS, part.get(), C.get());
-        FY_KERNEL_CHECK();
+        nmf_gram(ctx, nI, k, w, part.get(), C.get());
         const int normalize = prm->ppc && f != 0 && (it % f == 0);   // Java %: f = -1 (the key left unset) normalises every iteration
         k_nmf_update<<<grid_for((int64_t)nU * 64, 256), 256, 0, s>>>(nU, k, h, XH.get(), C.get(), prm->ppc ? 1 : 0, normalize, h2);
         FY_KERNEL_CHECK();
@@ -299,10 +278,7 @@ void nmf_factorize(Context* ctx, const fy_nmf_params* prm, const fy_ratings* R, 
         FY_KERNEL_CHECK();
         k_nmf_spmm_reduce<<<grid_for((int64_t)nI * k), 256, 0, s>>>(nI, k, ci.ptr.get(), spart.get(), XW.get());
         FY_KERNEL_CHECK();
-        k_nmf_gram_partial<<<NMF_GRAM_BLOCKS, 256, 0, s>>>(nU, k, h, part.get());
-        FY_KERNEL_CHECK();
-        k_nmf_gram_sum<<<grid_for((int64_t)k * k), 256, 0, s>>>(k, NMF_GRAM_BLOCKS, part.get(), C.get());
-        FY_KERNEL_CHECK();
+        nmf_gram(ctx, nU, k, h, part.get(), C.get());
         k_nmf_update<<<grid_for((int64_t)nI * 64, 256), 256, 0, s>>>(nI, k, w, XW.get(), C.get(), 2, 0, w2);
         FY_KERNEL_CHECK();
         std::swap(h, h2);

@@ -1609,6 +1609,123 @@ class ClusterRefinementJob:
                 r.close()
 
 
+class FoldInAssignment:
+    """What ``FoldIn.assign`` returns, for this rank's profiles in the order given: ``labels``, ``clusters`` (-1 unless the status is
+    FY_FOLDIN_OK), ``parents`` (the top-level argmax; -1 with EMPTY and NO_CLUSTER), ``status`` (FY_FOLDIN_*), ``foldin_stats``
+    (fy_foldin_stats as a dict); ``factors()`` downloads the top-level rows (n x k), ``sub_factors()`` the second-level rows as a list
+    with one array of k_c values per profile (empty where level 2 did not run)."""
+
+    def __init__(self, handle, k, ctx):
+        lib = self._lib = _native.load()
+        self._h, self._k = handle, int(k)
+        self._ctx = ctx   # the factor rows are downloaded through the context's stream: keep it alive
+        n = lib.fy_foldin_result_n(handle)
+        self.labels, self.clusters, self.parents, self.status = (np.zeros(n, np.int32) for _ in range(4))
+        _check(lib.fy_foldin_result_assignment(handle, self.labels.ctypes.data, self.clusters.ctypes.data, self.parents.ctypes.data,
+                                               self.status.ctypes.data))
+        st = _native.FoldInStats()
+        _check(lib.fy_foldin_result_stats(handle, C.byref(st)))
+        self.foldin_stats = st.as_dict()
+
+    def factors(self):
+        H = np.zeros((len(self.labels), self._k))
+        _check(self._lib.fy_foldin_result_factors(self._h, H.ctypes.data))
+        return H
+
+    def sub_factors(self):
+        off = np.zeros(len(self.labels) + 1, np.int64)
+        H = np.zeros(self._lib.fy_foldin_result_sub_size(self._h))
+        _check(self._lib.fy_foldin_result_sub_factors(self._h, off.ctypes.data, H.ctypes.data if len(H) else None))
+        return [H[off[p]:off[p + 1]] for p in range(len(self.labels))]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._ctx._h:      # a result must not outlive its context's stream
+                self._lib.fy_foldin_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FoldIn:
+    """Fold-in of given profiles on standing factors (fy_foldin_*): the item factors ``W`` (numberOfItems x k, row r
+    = item id r + 1; numpy or a CUDA float64 torch tensor) of the last PPC (``ppc=True``) / NMF run are held fixed, the reference's H
+    update runs for the given rows alone and the cluster is the argmax -- the ``clusters=`` of ``PreparedRM2.score_profiles(base="whole")``
+    for a visitor nobody has seen, without a factorisation and without a prepare.  ``counts``: a `clusteringCount`; a cluster without
+    resident users cannot win.  ``add_level`` adds the refined level of ``ClusterRefinementJob``.  Only whole profiles are taken: a
+    resident row with pending writes is composed by the caller (``Ratings.to_host``)."""
+
+    def __init__(self, ctx, W, ppc=True, normalizationFrequency=-1, counts=None):
+        self._ctx, self._lib = ctx, _native.load()
+        self._h = C.c_void_p()
+        device = hasattr(W, "is_cuda") and W.is_cuda
+        if device:
+            import torch
+            assert W.dtype == torch.float64 and W.is_contiguous() and W.dim() == 2
+            torch.cuda.current_stream(W.device).synchronize()
+            ptr = W.data_ptr()
+        else:
+            W = np.ascontiguousarray(W, dtype=np.float64)
+            if W.ndim != 2:
+                raise ValueError("W must be a (numberOfItems x numberOfClusters) matrix")
+            ptr = W.ctypes.data
+        self.number_of_items, self.k = int(W.shape[0]), int(W.shape[1])
+        p = _native.FoldInParams(self.number_of_items, self.k, 1 if ppc else 0, int(normalizationFrequency))
+        cnt = None if counts is None else _i32(counts)
+        _check(self._lib.fy_foldin_create(ctx._h, C.byref(p), ptr, 1 if device else 0, cnt.ctypes.data if cnt is not None and len(cnt) else None,
+                                          len(cnt) if cnt is not None else 0, C.byref(self._h)))
+
+    def add_level(self, mappings, factors_W, stride, counts=None):
+        """mappings: the ``SubClusterMappings`` of the parent clustering; factors_W: one (itemsInCluster x subClusters) array per parent
+        (or the ``(H_c, W_c)`` pairs of ``ClusterRefinementJob(...).factors``); stride = ceil(numberOfUsers / numberOfClusters);
+        counts: the refined `clusteringCount`."""
+        Ws = [np.ascontiguousarray(w[1] if isinstance(w, tuple) else w, dtype=np.float64) for w in factors_W]
+        if len(Ws) != len(mappings.items_in_cluster):
+            raise ValueError("factors_W must hold one matrix per parent cluster")
+        for c, w in enumerate(Ws):
+            if w.ndim != 2 or (w.shape[0] != mappings.items_in_cluster[c] and w.size):
+                raise ValueError("W of parent cluster %d must be itemsInCluster x subClusters" % c)
+        m_c = _i32(mappings.items_in_cluster)
+        k_c = _i32([w.shape[1] for w in Ws])
+        flat = np.concatenate([w.ravel() for w in Ws]) if Ws else np.zeros(0)
+        item = _i32(mappings.item)
+        cnt = None if counts is None else _i32(counts)
+        _check(self._lib.fy_foldin_add_level(self._h, len(Ws), m_c.ctypes.data, k_c.ctypes.data, item.ctypes.data if len(item) else None,
+                                             flat.ctypes.data if len(flat) else None, int(stride),
+                                             cnt.ctypes.data if cnt is not None and len(cnt) else None, len(cnt) if cnt is not None else 0))
+        return self
+
+    def assign(self, profiles, iterations=10, first_iteration=1, h0=None, rank=0, world=1):
+        """profiles: the two forms ``recommend_profiles`` takes.  h0: (profiles x k) starting rows of ALL profiles given (top level);
+        None = uniform 1 / k.  Returns a ``FoldInAssignment`` for this rank's range of the list."""
+        q, keep = _itemcf_profiles(profiles, "whole", 0.0)
+        if h0 is not None:
+            h0 = np.ascontiguousarray(h0, dtype=np.float64)
+            if h0.shape != (q.n_profiles, self.k):
+                raise ValueError("h0 must be profiles x k")
+        out = C.c_void_p()
+        _check(self._lib.fy_foldin_assign(self._h, C.byref(q), int(iterations), int(first_iteration),
+                                          h0.ctypes.data if h0 is not None and h0.size else None, int(rank), int(world), C.byref(out)))
+        del keep
+        return FoldInAssignment(out, self.k, self._ctx)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._ctx._h:      # the model's HBM goes with its context
+                self._lib.fy_foldin_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class RMRecommenderDriver:
     """The reference's production entry point in one call (M/rmrecommender/RMRecommenderDriver.java:164-206):
 
@@ -1631,6 +1748,7 @@ class RMRecommenderDriver:
         self.conf = conf
         self.ctx = ctx
         self.stats = {}
+        self.fold_in = None
 
     def _stage_conf(self, **over):
         c = Configuration(self.conf)
@@ -1641,10 +1759,12 @@ class RMRecommenderDriver:
             c.setInt(k, v)
         return c
 
-    def run(self, ratings, H=None, W=None, clustering=None, clustering_count=None, seed=0):
+    def run(self, ratings, H=None, W=None, clustering=None, clustering_count=None, seed=0, keep_model=False):
         """H / W: the initial matrices of the top-level PPC run (numberOfUsers x numberOfClusters, numberOfItems x
         numberOfClusters); None = uniform in (0, 1] from ``seed`` (the reference draws unpinned random matrices).  ``seed`` also
-        seeds the sub-runs' matrices."""
+        seeds the sub-runs' matrices.  ``keep_model=True`` (numberOfIterations > 0 only) leaves ``self.fold_in``, a ``FoldIn`` over
+        the run's final W and ``counts`` -- after refinement also over the parents' item lists and W_c: the mapping job then runs
+        once more for the item lists, and the refinement keeps its factors.  The default changes nothing the driver does."""
         conf = self._stage_conf()
         n_users, n_items, K = (conf.getInt(k, -1) for k in ("numberOfUsers", "numberOfItems", "numberOfClusters"))
         if min(n_users, n_items, K) <= 0:
@@ -1666,10 +1786,17 @@ class RMRecommenderDriver:
                 H, W = ppc.run(r, H, W)
                 self.stats["ppc"] = ppc.stats
                 users, clusters, counts = ClusterAssignmentJob(ctx).run(H, first_user=1)
-                if conf.getInt("usersPerSubCluster", -1) > 0:
+                refined = conf.getInt("usersPerSubCluster", -1) > 0
+                if refined:
+                    parents = (users, clusters)
                     refine = ClusterRefinementJob(conf, ctx, ppc=True)
-                    users, clusters, counts = refine.run(r, (users, clusters), seed=seed)
+                    users, clusters, counts = refine.run(r, parents, seed=seed, keep_factors=bool(keep_model))
                     self.stats["refine"] = refine.stats
+                if keep_model:
+                    f = conf.getInt("normalizationFrequency", -1)
+                    self.fold_in = FoldIn(ctx, W, ppc=True, normalizationFrequency=f, counts=None if refined else counts)
+                    if refined:
+                        self.fold_in.add_level(SubClusterMappingJob(conf, ctx).run(r, parents), refine.factors, -(-n_users // K), counts=counts)
             else:
                 users, clusters = _clustering_arrays(clustering)
                 counts = None if clustering_count is None else _i32(clustering_count)

@@ -956,5 +956,83 @@ class BaselineRecommenderJob {
     }
 };
 
+// Fold-in of given profiles on standing factors (fy_foldin_*; include/filmyou.h): the cluster of a visitor nobody has seen, from the item
+// factors W of the last PPC / NMF run, without a factorisation and without a prepare.  Owns its context and model (move-only).  Only
+// whole profiles are taken: a resident row with pending writes is composed by the caller.
+class FoldIn {
+   public:
+    using Profiles = BaselineRecommenderJob::Profiles;      // label, start, item, score, remove
+    struct Assignment {
+        std::vector<int32_t> label, cluster, parent, status;      // status: FY_FOLDIN_*
+        std::vector<double> factors;                                // profiles x k, the top-level rows
+        std::vector<int64_t> subOffset;                             // profiles + 1 into subFactors
+        std::vector<double> subFactors;                             // the second-level rows, ragged
+        fy_foldin_stats stats{};
+    };
+
+    // W: numberOfItems x k, row r = item id r + 1; counts: a `clusteringCount` (empty = every column may win)
+    FoldIn(const std::vector<double>& W, int32_t numberOfItems, int32_t k, bool ppc = true, int32_t normalizationFrequency = -1,
+           const std::vector<int32_t>& counts = {}, int device = 0) : k_(k) {
+        if ((int64_t)W.size() != (int64_t)numberOfItems * k) throw std::invalid_argument("W must hold numberOfItems x k values");
+        if (fy_context_create(device, &ctx_) != FY_OK) throw std::runtime_error(std::string("FoldIn failed!: ") + fy_last_error());
+        const fy_foldin_params p{numberOfItems, k, ppc ? 1 : 0, normalizationFrequency};
+        if (fy_foldin_create(ctx_, &p, W.data(), FY_HOST, counts.empty() ? nullptr : counts.data(), (int64_t)counts.size(), &model_) != FY_OK) {
+            const std::string msg = fy_last_error();
+            close();
+            throw std::runtime_error("FoldIn failed!: " + msg);
+        }
+    }
+    FoldIn(const FoldIn&) = delete;
+    FoldIn& operator=(const FoldIn&) = delete;
+    FoldIn(FoldIn&& o) noexcept : ctx_(o.ctx_), model_(o.model_), k_(o.k_) { o.ctx_ = nullptr; o.model_ = nullptr; }
+    ~FoldIn() { close(); }
+
+    // the refined level: per parent its item count, sub-cluster count, ascending raw item ids and W_c, in the layout of
+    // fy_submap_items / fy_refined_factors; counts: the refined `clusteringCount`
+    void addLevel(const std::vector<int32_t>& itemsInCluster, const std::vector<int32_t>& subClusters, const std::vector<int32_t>& itemRaw,
+                  const std::vector<double>& Wragged, int32_t stride, const std::vector<int32_t>& counts = {}) {
+        if (itemsInCluster.size() != subClusters.size()) throw std::invalid_argument("itemsInCluster and subClusters differ in length");
+        if (fy_foldin_add_level(model_, (int32_t)subClusters.size(), itemsInCluster.data(), subClusters.data(), itemRaw.data(), Wragged.data(), stride,
+                                counts.empty() ? nullptr : counts.data(), (int64_t)counts.size()) != FY_OK)
+            throw std::runtime_error(std::string("FoldIn failed!: ") + fy_last_error());
+    }
+
+    // h0: profiles x k starting rows (top level) or empty = uniform 1 / k
+    Assignment assign(const Profiles& profiles, int32_t iterations = 10, int32_t firstIteration = 1, const std::vector<double>& h0 = {}, int32_t rank = 0,
+                      int32_t world = 1) {
+        if (!h0.empty() && h0.size() != profiles.label.size() * (size_t)k_) throw std::invalid_argument("h0 must hold profiles x k values");
+        const fy_itemcf_profiles q{(int64_t)profiles.label.size(), profiles.label.data(), profiles.start.data(), profiles.item.data(), profiles.score.data(),
+                                   profiles.remove.data(), FY_PROFILE_WHOLE};
+        fy_foldin_result* res = nullptr;
+        if (fy_foldin_assign(model_, &q, iterations, firstIteration, h0.empty() ? nullptr : h0.data(), rank, world, &res) != FY_OK)
+            throw std::runtime_error(std::string("FoldIn failed!: ") + fy_last_error());
+        Assignment a;
+        const size_t n = (size_t)fy_foldin_result_n(res);
+        a.label.resize(n); a.cluster.resize(n); a.parent.resize(n); a.status.resize(n);
+        a.factors.resize(n * (size_t)k_);
+        a.subOffset.resize(n + 1);
+        a.subFactors.resize((size_t)fy_foldin_result_sub_size(res));
+        int rc = fy_foldin_result_assignment(res, a.label.data(), a.cluster.data(), a.parent.data(), a.status.data());
+        if (rc == FY_OK) rc = fy_foldin_result_factors(res, a.factors.data());
+        if (rc == FY_OK) rc = fy_foldin_result_sub_factors(res, a.subOffset.data(), a.subFactors.data());
+        if (rc == FY_OK) rc = fy_foldin_result_stats(res, &a.stats);
+        fy_foldin_result_free(res);
+        if (rc != FY_OK) throw std::runtime_error(std::string("FoldIn failed!: ") + fy_last_error());
+        return a;
+    }
+    int32_t k() const { return k_; }
+    void close() {
+        if (model_) fy_foldin_destroy(model_);
+        if (ctx_) fy_context_destroy(ctx_);
+        model_ = nullptr;
+        ctx_ = nullptr;
+    }
+
+   private:
+    fy_context* ctx_ = nullptr;
+    fy_foldin* model_ = nullptr;
+    int32_t k_ = 0;
+};
+
 }  // namespace host
 }  // namespace fy

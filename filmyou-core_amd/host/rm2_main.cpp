@@ -143,6 +143,53 @@ static int main_recommend_profiles(char** a) {
     return 0;
 }
 
+// rm2_main --fold-in <profiles.txt> <W.txt> <k> <iterations> <ppc> <normalizationFrequency>
+//   : FoldIn::assign, the cluster of every profile from the standing item factors.  <profiles.txt> in the format of --recommend-profiles;
+//   <W.txt>: one row of k values per line, row r = item id r + 1.  Prints "label cluster status" followed by the k values of the
+//   profile's factor row (%.17g); one `foldin ...` line of counters on stderr.
+static int main_fold_in(char** a) {
+    const int k = atoi(a[2]);
+    if (k <= 0) { fprintf(stderr, "usage: --fold-in PROFILES W.txt k iterations ppc normalizationFrequency\n"); return 2; }
+    std::vector<double> W;
+    FILE* f = fopen(a[1], "r");
+    if (!f) { perror(a[1]); return 2; }
+    double v;
+    while (fscanf(f, "%lf", &v) == 1) W.push_back(v);
+    fclose(f);
+    if (W.empty() || W.size() % (size_t)k != 0) { fprintf(stderr, "%s: %zu values are not rows of %d\n", a[1], W.size(), k); return 2; }
+    fy::host::FoldIn::Profiles profiles;
+    f = fopen(a[0], "r");
+    if (!f) { perror(a[0]); return 2; }
+    char word[64];
+    bool any = false;
+    int u, i, last = 0;
+    while (fscanf(f, "%d %d %63s", &u, &i, word) == 3) {
+        if (!any || u != last) profiles.begin(u);
+        any = true;
+        last = u;
+        if (strcmp(word, "x") == 0) profiles.del(i); else profiles.put(i, strtof(word, nullptr));
+    }
+    fclose(f);
+    try {
+        fy::host::FoldIn fold(W, (int32_t)(W.size() / (size_t)k), k, atoi(a[4]) != 0, atoi(a[5]));
+        const fy::host::FoldIn::Assignment r = fold.assign(profiles, atoi(a[3]));
+        for (size_t p = 0; p < r.label.size(); p++) {
+            printf("%d %d %d", r.label[p], r.cluster[p], r.status[p]);
+            for (int c = 0; c < k; c++) printf(" %.17g", r.factors[p * (size_t)k + c]);
+            printf("\n");
+        }
+        const fy_foldin_stats& q = r.stats;
+        fprintf(stderr, "foldin asked %lld assigned %lld empty %lld no_cluster %lld entries %lld out_of_range %lld superseded %lld removed %lld "
+                "nonpositive %lld items_composed %lld launches %lld\n", (long long)q.profiles_asked, (long long)q.profiles_assigned, (long long)q.profiles_empty,
+                (long long)q.profiles_no_cluster, (long long)q.entries, (long long)q.entries_out_of_range, (long long)q.entries_superseded,
+                (long long)q.entries_removed, (long long)q.entries_nonpositive, (long long)q.items_composed, (long long)q.launches);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // rm2_main --estimate-pairs <test.txt> <ratings.txt> <similarityClassname> <K> <maxPrefs>
 //   : BaselineRecommenderJob::prepare on the ratings + estimatePairs for the (user, item) of the test ratings ("user item score" per line)
 //   + estimateErrors against their scores.  <test.txt> = holdout:<fraction>:<seed> splits <ratings.txt> instead: prepared on the train side.
@@ -247,6 +294,7 @@ int main(int argc, char** argv) {
     if (argc == 10 && strcmp(argv[1], "--recommend-profiles") == 0) return main_recommend_profiles(argv + 2);
     if (argc == 6 && strcmp(argv[1], "--similar-items") == 0) return main_similar_items(argv + 2);
     if (argc == 7 && strcmp(argv[1], "--estimate-pairs") == 0) return main_estimate_pairs(argv + 2);
+    if (argc == 8 && strcmp(argv[1], "--fold-in") == 0) return main_fold_in(argv + 2);
     if (argc == 8 && strcmp(argv[1], "--because") == 0) return main_because(argv + 2);
     // rm2_main --score-profiles <profiles.txt> --profile-base whole|resident [--profile-cluster C] <ratings.txt> ... : RM2Job::scoreProfiles.
     //   <profiles.txt> in the format of --recommend-profiles: "label item score" per line, consecutive lines with one label form one

@@ -1092,6 +1092,93 @@ typedef struct {
 int fy_rm2_score_profiles(fy_rm2_job*, const fy_rm2_profiles*, fy_result** out);
 int fy_result_rm2_profile_stats(fy_result*, fy_rm2_profile_stats* out);   /* FY_ERR_STATE on any other result */
 
+/* ------------------------------------------------------------------ fold-in: assign given profiles to clusters from the standing factors
+ * (csrc/fy_foldin.hip).  fy_rm2_score_profiles scores a FY_PROFILE_WHOLE profile "as one more member of the
+ * cluster named in `cluster`"; this is the call that produces that cluster without a new factorisation and without a prepare.  The
+ * item factors W of the last PPC / NMF run are held FIXED, the reference's own H update (HComputationReducer.java:57-75 /
+ * PPCHComputationReducer.java:61-96) runs for the given rows alone, and the cluster is the argmax (FindClusterMapper.java:37-45; with a
+ * refined level FindSubClusterMapper.java:46-76 on the parent's factors).  All of it in fp64 with eps = 1e-12, as fy_nmf_factorize.
+ *
+ * Model.  fy_foldin_create puts W (number_of_items x k doubles, row r = item id r + 1; FY_HOST or FY_DEVICE) into HBM and forms
+ * C = W^T W exactly as the H half of fy_nmf_factorize forms it (same kernels, same summation order: the same bits).  The model is
+ * created once and serves any number of fy_foldin_assign calls.  count_or_null (HOST, n_count ints: a `clusteringCount`) builds a mask of
+ * ALLOWED columns: column j may win the argmax only when j < n_count and count[j] > 0 -- fy_rm2_score_profiles refuses an empty
+ * cluster.  The mask touches the argmax alone, never the iterations.  NULL: every column is allowed.
+ * fy_foldin_add_level adds the refined level of fy_cluster_refine (once): one block per parent cluster c = top-level column c, n_parents
+ * = k.  HOST arrays in the layout of fy_submap_counts / fy_submap_items / fy_refined_layout / fy_refined_factors: items_in_cluster
+ * (m_c), sub_clusters (k_c <= 256; 0 for a parent without users), item_raw (the parents' item lists one after the other, raw ids
+ * ASCENDING inside a parent; row = position), W_ragged (the m_c x k_c matrices one after the other), stride = ceil(numberOfUsers /
+ * numberOfClusters).  count_or_null (the refined, long `clusteringCount`): sub-cluster j of parent c is allowed when c * stride + j <
+ * n_count and count[c * stride + j] > 0, and top-level column c is allowed when any of its k_c sub-clusters is (this REPLACES the mask
+ * of fy_foldin_create); NULL: the sub-clusters are unmasked and the top-level mask stays as it is.
+ *
+ * Profiles: the HOST CSR of fy_itemcf_profiles (user = label, start, item, score, remove).  Only WHOLE profiles are taken (base must be
+ * FY_PROFILE_WHOLE): a resident user's row with pending writes is composed by the caller (Ratings.to_host / fy_ratings_copy_out plus the
+ * writes).  Composition, per profile, counted like the other profile calls:
+ *   1. an entry whose item id is outside [1, number_of_items] is dropped and counted (entries_out_of_range) before rule 2 sees it;
+ *   2. the entries are applied in the order given and the LAST entry per item counts (entries_superseded: the others);
+ *   3. a last entry that is a delete (remove[e] != 0) removes the item (entries_removed);
+ *   4. a last entry whose score is not > 0 (zero, negative, NaN) removes the item (entries_nonpositive): the factorisation's
+ *      kept-rating rule;
+ *   5. the composed profile is in ascending item id, the order of the factorisation's rows.
+ * Assignment, per profile with composed entries (item_i, a_i):
+ *   x      = sum_i a_i W[item_i - 1][:]   in entry order: chunks of 512 entries each summed from 0.0, the chunk sums added from 0.0
+ *            (the order fy_nmf_factorize sums a user's row in);
+ *   h      = h0[p][:] (h0: HOST, n_profiles x k, rows of ALL profiles of the list; top level only) or uniform 1 / k;
+ *   `iterations` times:  y = C h;  NMF: h_c <- h_c x_c / (y_c + eps);  PPC: d = h.y, e = h.x, h_c <- h_c clamp(x_c + d) /
+ *            (clamp(y_c + e) + eps) (clamp: +-infinity -> +-DBL_MAX), then h <- h / |h|_1 when normalization_frequency != 0 and
+ *            it % normalization_frequency == 0 (C remainder; -1 normalises always), it = first_iteration, first_iteration + 1, ...;
+ *   parent = first index of the strictly largest ALLOWED value of h (NaN never wins).
+ * h0 = the row's H, first_iteration = 1 and one iteration give the row fy_nmf_factorize would give it in its first iteration from the
+ * same W, BIT FOR BIT.  With a refined level every profile then runs on the block of its parent c, over its entries whose item has a
+ * row in parent c (same summation order over those entries), from uniform 1 / k_c, and cluster = c * stride + argmax; an argmax >=
+ * stride is kept and counted (collisions): the reference's quirk, as fy_cluster_refine documents it.  Without one cluster = parent.
+ * Status per profile: FY_FOLDIN_OK; FY_FOLDIN_EMPTY (composed to nothing); FY_FOLDIN_NO_CLUSTER (no allowed column holds a value >
+ * -infinity, at either level); FY_FOLDIN_EMPTY_IN_PARENT (none of its items has a row in the parent: `parent` is still reported).
+ * cluster = -1 unless the status is OK; parent = -1 with EMPTY and NO_CLUSTER.  The factor rows are kept whatever the status: top
+ * level n x k; second level ragged, offset[p] .. offset[p + 1] = the k_c values of profile p (none where level 2 did not run).
+ * (rank, world) cut the PROFILE LIST into contiguous ranges [n rank / world, n (rank + 1) / world); the result holds this rank's
+ * profiles in the order given.  A profile's outputs do not depend on the other profiles, their order, or the cut.
+ * Failures, all found on the host before any launch, leaving the model usable.  FY_ERR_INVALID_ARGUMENT: NULL context / params / W /
+ * out, number_of_items or number_of_clusters <= 0, location outside the enum, count NULL with n_count > 0 or n_count < 0;
+ * fy_foldin_add_level: n_parents != k, NULL arrays, negative m_c / k_c, stride <= 0, an item list that is not strictly ascending;
+ * fy_foldin_assign: NULL model / profiles / out, base other than FY_PROFILE_WHOLE, n_profiles < 0, NULL user / start with profiles,
+ * NULL item / score with entries, start[0] != 0 or start decreasing, iterations or first_iteration < 0, rank / world out of range.
+ * FY_ERR_UNSUPPORTED: number_of_clusters or a k_c above 256 (the factorisation's limit), more than 2^31 - 1 profiles or entries, a
+ * refined cluster id beyond 2^31 - 1.  FY_ERR_STATE: a second fy_foldin_add_level.
+ * Counters (all but profiles_asked over this rank's range): profiles_asked / _mine; entries and the four rules' counters;
+ * items_composed; profiles_assigned / _empty / _no_cluster / _empty_in_parent (the four statuses); items_in_parent (entries that
+ * entered a level-2 sum); collisions; launches (kernel and rocPRIM launches); HIP-event milliseconds per phase. */
+enum { FY_FOLDIN_OK = 0, FY_FOLDIN_EMPTY = 1, FY_FOLDIN_NO_CLUSTER = 2, FY_FOLDIN_EMPTY_IN_PARENT = 3 };
+typedef struct {
+    int32_t number_of_items;           /* "numberOfItems": rows of W */
+    int32_t number_of_clusters;        /* "numberOfClusters" = k (<= 256) */
+    int32_t ppc;                       /* 0 = NMFDriver's H update, 1 = PPCDriver's */
+    int32_t normalization_frequency;   /* as in fy_nmf_params */
+} fy_foldin_params;
+typedef struct {
+    int64_t profiles_asked, profiles_mine, profiles_assigned, profiles_empty, profiles_no_cluster, profiles_empty_in_parent;
+    int64_t entries, entries_out_of_range, entries_superseded, entries_removed, entries_nonpositive, items_composed;
+    int64_t items_in_parent, collisions, launches;
+    double ms_ingest, ms_level1, ms_level2, ms_total;
+} fy_foldin_stats;
+typedef struct fy_foldin fy_foldin;
+typedef struct fy_foldin_result fy_foldin_result;
+int fy_foldin_create(fy_context*, const fy_foldin_params*, const double* W, int location, const int32_t* count_or_null, int64_t n_count,
+                     fy_foldin** out);
+int fy_foldin_add_level(fy_foldin*, int32_t n_parents, const int32_t* items_in_cluster, const int32_t* sub_clusters, const int32_t* item_raw,
+                        const double* W_ragged, int32_t stride, const int32_t* count_or_null, int64_t n_count);
+int fy_foldin_assign(fy_foldin*, const fy_itemcf_profiles* profiles, int32_t iterations, int32_t first_iteration, const double* h0_or_null,
+                     int32_t rank, int32_t world, fy_foldin_result** out);
+int64_t fy_foldin_result_n(const fy_foldin_result*);                                /* this rank's profiles */
+int fy_foldin_result_assignment(const fy_foldin_result*, int32_t* label, int32_t* cluster, int32_t* parent, int32_t* status);   /* n ints each */
+int fy_foldin_result_factors(fy_foldin_result*, double* H);                         /* n x k doubles: the top-level rows */
+int64_t fy_foldin_result_sub_size(const fy_foldin_result*);                         /* doubles of all second-level rows */
+int fy_foldin_result_sub_factors(fy_foldin_result*, int64_t* offset, double* H);    /* n + 1 offsets, sub_size doubles (H may be NULL when 0) */
+int fy_foldin_result_stats(const fy_foldin_result*, fy_foldin_stats* out);
+void fy_foldin_result_free(fy_foldin_result*);
+void fy_foldin_destroy(fy_foldin*);
+
 #ifdef __cplusplus
 }
 #endif
